@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Benchmark of the `pt` hot path on MI355X (BASELINE.json metric: Msamples/s, whole node, 1080p Cornell box 1024 spp).
 
-    python bench.py                                   # N = 1: configs[1] (C2) timed, then C3 and C4 once each, CPU baseline
-    python bench.py --gpus 1 --steps 20 --warmup 5    # what the driver runs
+    python bench.py --gpus 1 --steps 20 --warmup 5    # the headline alone: configs[1] (C2) timed, one JSON line
+    python bench.py --full                            # N = 1: the headline, then C3, C4 and the other legs once each, CPU baseline
     python bench.py --config c3|c4                    # another BASELINE configuration as the timed workload
+    python bench.py --dump-outputs DIR                # also writes the film of the timed run as DIR/film.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 ONE STEP = ONE RENDER OF THE NAMED WORKLOAD'S SAMPLE BATCH: 1024 samples per pixel of the 1920x1080 frame, i.e. 16 passes
@@ -19,6 +20,13 @@ with its own sampler seed (N independent sample sets; the metric name says so). 
 SAMPLES of every pixel instead of the pixels (akr_pt_config.sample_begin / sample_count: rank r renders samples
 [r S / N, (r + 1) S / N) of all pixels -- perfectly balanced at any resolution; exact only for the index-based samplers, so it
 is a secondary leg (extra_configs.c2_sobol_sample_split) next to the BASELINE configuration, which uses the independent sampler).
+
+A plain run measures the headline and nothing else. --full adds what is measured or checked next to it (extra_configs: the
+other configurations, frame sizes, samplers, schedules and arithmetic tiers, the reference's own workload, the textured room,
+the instanced forest; the CPU baseline). --dump-outputs DIR writes, before the line is printed, what the timed render hands its
+caller: the film of rank 0 after the last step, f32[7, H, W] in the reference layout (rgb | splat | weight planes), as
+DIR/film.npy. The inputs are fixed (scene file, sampler seed 0), so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -587,9 +595,11 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4"], help="the timed workload (BASELINE.json configs[1..3])")
-    ap.add_argument("--also", default=None, help="comma list of further configs measured once each after the timed one, reported under "
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the secondary legs (extra_configs) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the film of the timed run (rank 0, after the last step) as DIR/film.npy")
+    ap.add_argument("--also", default=None, help="with --full: comma list of further configs measured once each after the timed one, reported under "
                                                    "extra_configs (default at N = 1 with --config c2: c3,c4; 'none' to skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--leg", default=None, help="run ONE secondary leg alone and print its JSON (what tools/pmc_bench.sh profiles): reference_default, "
                                                 "forest_100k_kept, forest_10k_kept, forest_10k_flattened, textured_exhaustive_interpreter, textured_exhaustive_per_scene, "
                                                 "textured_bvh_interpreter, textured_bvh_per_scene")
@@ -609,11 +619,13 @@ def main():
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only for smoke-testing the "
                          "multi-rank path on a box with fewer GPUs than ranks: all ranks then share device 0)")
     ap.add_argument("--comm-deadline", type=float, default=120.0, help="seconds akr_comm_create + the first akr_film_reduce may take before the run falls back to --reduce torch")
-    ap.add_argument("--legs-deadline", type=float, default=900.0, help="seconds the secondary legs (extra_configs, CPU baseline) may take after the "
+    ap.add_argument("--legs-deadline", type=float, default=900.0, help="with --full: seconds the secondary legs (extra_configs, CPU baseline) may take after the "
                                                                         "headline is measured; past it rank 0 prints the headline line without them")
     args = ap.parse_args()
     if args.full_graph:
         args.config = "c3"
+    if args.also not in (None, "none") and not args.full:
+        ap.error("--also names secondary legs: they run with --full only")
     if args.split == "samples" and args.sampler == "independent":
         ap.error("--split samples needs an index-based sampler (--sampler sobol | pmj02bn): the independent sampler's per-pixel PCG stream is sequential")
 
@@ -732,6 +744,9 @@ def main():
         if world == 1 and sinfo.get("warmup_launch_ms"):
             out["value_1024spp_launch"] = W * H * SPP_PER_STEP / (sinfo["warmup_launch_ms"] * 1e-3) / 1e6
             out["config"]["value_1024spp_launch_is"] = "Msamples/s of a 16-pass (1024 spp) launch: mean HIP-event time of the warm-up launches"
+        if args.dump_outputs:  # the film the timed render leaves to its caller (before a secondary leg reuses the tensor)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "film.npy"), film_t.view(7, H, W).cpu().numpy())
     extra = {}
     printed = []
     import threading
@@ -774,7 +789,7 @@ def main():
     #  c2_weak                N > 1: every rank renders the whole 1080p frame with its own sampler seed (N independent sample sets)
     #  c2_sobol_sample_split  the 1080p frame with the sobol sampler, the SAMPLES of every pixel over the ranks (at N = 1: the same
     #                         frame on one GPU, the number the split's speed-up is measured against)
-    if args.also != "none" and key == "c2" and args.split == "tiles" and args.sampler == "independent":
+    if args.full and args.also != "none" and key == "c2" and args.split == "tiles" and args.sampler == "independent":
         legs = (("c5_strong", "c5", "strong", "tiles", "independent"),) + ((("c2_weak", "c2", "weak", "tiles", "independent"),) if world > 1 else ())
         legs += (("c2_sobol_sample_split", "c2", "strong", "samples", "sobol"),)
         for name, k2, scal2, split2, smp2 in legs:
@@ -802,7 +817,7 @@ def main():
     if rank == 0:
         also = args.also
         if also is None:
-            also = "c3,c4" if (args.gpus == 1 and key == "c2") else "none"
+            also = "c3,c4" if (args.full and args.gpus == 1 and key == "c2") else "none"
         for k2 in [k for k in also.split(",") if k and k != "none" and k != key]:
             try:
                 e2, d2, si2 = run_config(ctx, k2, 1, 0 if k2 == "c4" else 1, 0, 1, "strong", film_t, torch, dist, args.backend, dev, keep_scene=(k2 == "c4"))
@@ -869,7 +884,7 @@ def main():
                              "C2 shards 0.8e-3 .. 1.3e-3, C1 2e-3 .. 9e-3 -- flipped comparisons, see tests/test_gpu_relaxed.py)")
             add_leg("arithmetic_tiers", tiers)
             _SCENES.clear()
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             try:
                 base = cpu_baseline(key, *host_threads())
             except Exception as ex:  # noqa: BLE001

@@ -72,6 +72,14 @@ def test_sample_split_needs_an_index_based_sampler():
     assert r.returncode != 0 and "index-based sampler" in r.stderr
 
 
+def test_secondary_legs_need_full():
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--also", "c3"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 def test_native_communicator_fallbacks(monkeypatch):
     """make_native_comm with the library and torch.distributed faked: a communicator that works is used on the context it was made
     on; one whose creation raises, whose first reduce never returns, or whose unique id cannot be made gives (None, a FRESH context,

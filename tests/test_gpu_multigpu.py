@@ -164,7 +164,7 @@ def test_bench_control_flow_with_eight_ranks_on_one_gpu(root):
     port = 29900 + (os.getpid() % 90)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--steps", "1", "--warmup", "0"]
+           os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--steps", "1", "--warmup", "0", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -16,7 +16,7 @@ python tools/inst_extreme_check.py 400 0 oracle 2>&1 | tail -1 > $OUT/inst_extre
 bash tools/pmc_all.sh > $OUT/pmc_all.txt 2>&1
 cp gpurun_out/pmc_all/r6_pmc_*.json $OUT/
 mkdir -p profiles_tmp && cp $OUT/r6_pmc_*.json profiles/   # (on the box: bench.py reads the summaries from profiles/)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof -o r6 -- python bench.py --steps 20 --warmup 5 --also none --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cp $(find $OUT/prof -name '*kernel_stats.csv' | head -1) $OUT/r6_bench_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/prof profiles_tmp
