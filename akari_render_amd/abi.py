@@ -100,6 +100,13 @@ class ImageDesc(C.Structure):
                 ("address", C.c_uint32), ("_pad", C.c_uint32), ("texels", C.c_void_p)]
 
 
+class EnvironmentDesc(C.Structure):
+    """akr_environment_desc: an equirectangular RGBA32F image (width x height, row 0 = v = 0) or a constant colour (width = height = 0),
+    times strength, turned by a row-major rotation (environment -> world)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_uint32), ("_pad", C.c_uint32), ("texels", C.POINTER(C.c_float)),
+                ("color", C.c_float * 3), ("strength", C.c_float), ("rotation", C.c_float * 9), ("_pad2", C.c_uint32)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("c2w", C.c_float * 16), ("fov", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -424,6 +431,42 @@ class ImageData:
 
 
 @dataclass
+class EnvironmentData:
+    """The environment light of a scene: `image` (H, W, 3 or 4) float32 linear RGB, row 0 = v = 0, or `color` (r, g, b); times
+    `strength`; `rotation` (3, 3) environment -> world; `filter` TEX_FILTER_NEAREST / TEX_FILTER_LINEAR for an image."""
+    image: Optional[np.ndarray] = None
+    color: Optional[tuple] = None
+    strength: float = 1.0
+    rotation: Optional[np.ndarray] = None
+    filter: int = TEX_FILTER_LINEAR
+
+    def to_desc(self):
+        """Returns (EnvironmentDesc, keepalive)."""
+        d = EnvironmentDesc()
+        keep = None
+        if (self.image is None) == (self.color is None):
+            raise ValueError("EnvironmentData: exactly one of image and color")
+        if self.image is not None:
+            im = np.asarray(self.image, dtype=np.float32)
+            if im.ndim != 3 or im.shape[2] not in (3, 4):
+                raise ValueError("EnvironmentData.image must be (H, W, 3) or (H, W, 4)")
+            if im.shape[2] == 3:
+                im = np.concatenate([im, np.ones(im.shape[:2] + (1,), np.float32)], axis=2)
+            keep = np.ascontiguousarray(im, dtype=np.float32)
+            d.height, d.width = int(keep.shape[0]), int(keep.shape[1])
+            d.texels = keep.ctypes.data_as(C.POINTER(C.c_float))
+            d.filter = int(self.filter)
+        else:
+            for c in range(3):
+                d.color[c] = float(self.color[c])
+        d.strength = float(self.strength)
+        rot = np.eye(3, dtype=np.float32) if self.rotation is None else np.asarray(self.rotation, dtype=np.float32).reshape(3, 3)
+        for k in range(9):
+            d.rotation[k] = float(rot.reshape(-1)[k])
+        return d, keep
+
+
+@dataclass
 class CameraData:
     c2w: np.ndarray  # (16,) f32 column-major
     fov: float  # radians
@@ -441,6 +484,7 @@ class SceneData:
     instance_names: List[str] = field(default_factory=list)
     material_names: List[str] = field(default_factory=list)
     images: List["ImageData"] = field(default_factory=list)
+    environment: Optional[EnvironmentData] = None  # set by capi.Scene through akr_scene_set_environment (not part of akr_scene_desc)
 
     def n_triangles(self) -> int:
         return sum(self.meshes[i.mesh].indices.shape[0] for i in self.instances)

@@ -21,7 +21,9 @@ ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED
 (ARRAY_WOOP, ARRAY_TRI_GID, ARRAY_SHADE, ARRAY_INSTANCES, ARRAY_MATERIALS, ARRAY_BVH_NODES, ARRAY_LIGHT_ENTRIES,
  ARRAY_LIGHT_PDF, ARRAY_AREA_ENTRIES, ARRAY_AREA_PDF, ARRAY_INST_TRI_OFFSET, ARRAY_R2C, ARRAY_C2W,
  ARRAY_TEX_NODES, ARRAY_TEX_IMAGES, ARRAY_TEX_TEXELS, ARRAY_MAT_INPUTS,
- ARRAY_INST_LEAVES, ARRAY_MESH_TRIS, ARRAY_MESH_POS, ARRAY_MESH_META, ARRAY_MESH_NORMALS) = range(22)
+ ARRAY_INST_LEAVES, ARRAY_MESH_TRIS, ARRAY_MESH_POS, ARRAY_MESH_META, ARRAY_MESH_NORMALS,
+ ARRAY_ENV_MARGINAL_ENTRIES, ARRAY_ENV_MARGINAL_PDF, ARRAY_ENV_CONDITIONAL_ENTRIES, ARRAY_ENV_CONDITIONAL_PDF, ARRAY_ENV_TEXELS) = range(27)
+ENV_LIGHT_INSTANCE = 0xFFFFFFFF  # akr_scene_get_light's instance of the environment light
 
 # every symbol include/akari_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
@@ -39,6 +41,7 @@ EXPORTS = [
     "akr_device_count", "akr_comm_unique_id", "akr_comm_create", "akr_comm_wrap", "akr_comm_destroy", "akr_film_reduce",
     "akr_pt_kernel_info", "akr_scene_spec_source", "akr_host_spec_compile", "akr_host_spec_compile_text",
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
+    "akr_scene_set_environment", "akr_scene_get_environment",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -47,6 +50,7 @@ TEST_EXPORTS = [
     "akr_probe_surface_interaction", "akr_probe_material_inputs", "akr_host_decode_png", "akr_host_decode_jpeg",
     "akr_host_decode_exr", "akr_host_decode_tiff", "akr_host_decode_dds", "akr_host_pmj02bn_tables",
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
+    "akr_probe_env_sample", "akr_probe_env_pdf",
 ]
 
 
@@ -83,7 +87,8 @@ def lib() -> C.CDLL:
     L.akr_struct_size.restype = C.c_uint32
     L.akr_struct_size.argtypes = [C.c_int32]
     for sid, cls in enumerate((abi.MeshDesc, abi.InstanceDesc, abi.MaterialDesc, abi.CameraDesc, abi.SceneDesc, abi.PtConfig, abi.PtStats, abi.SceneInfo,
-                               abi.KernelInfo, abi.AovConfig, abi.GptConfig, abi.McmcConfig, abi.McmcResult, abi.McmcPartial), start=1):
+                               abi.KernelInfo, abi.AovConfig, abi.GptConfig, abi.McmcConfig, abi.McmcResult, abi.McmcPartial,
+                               abi.EnvironmentDesc), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -104,6 +109,10 @@ def lib() -> C.CDLL:
     proto("akr_scene_set_resolution", vp, u32, u32)
     proto("akr_scene_get_info", vp, C.POINTER(abi.SceneInfo))
     proto("akr_scene_get_light", vp, u32, up, fp, fp)
+    proto("akr_scene_set_environment", vp, C.POINTER(abi.EnvironmentDesc))
+    proto("akr_scene_get_environment", vp, C.POINTER(abi.EnvironmentDesc))
+    proto("akr_probe_env_sample", vp, vp, u32, fp, fp)
+    proto("akr_probe_env_pdf", vp, vp, u32, fp, fp)
     proto("akr_scene_get_ggx_table", vp, fp)
     proto("akr_scene_get_desc_counts", vp, up, up, up)
     proto("akr_scene_get_mesh", vp, u32, C.POINTER(abi.MeshDesc))
@@ -246,6 +255,9 @@ class Scene:
                 desc.camera.width, desc.camera.height = width, height
             check(lib().akr_scene_create(ch, C.byref(desc), C.byref(self.h)))
             del keep
+            env = getattr(source, "environment", None)
+            if env is not None:
+                self._set_environment_data(env)
 
     def close(self):
         if self.h:
@@ -271,11 +283,12 @@ class Scene:
         check(lib().akr_scene_spec_source(self.h, buf, n.value + 1, C.byref(n)))
         return buf.value.decode()
 
-    def spec_compile(self, bvh: bool = False, pmj: bool = False, stage: bool = True, defer: bool = False, min_waves: int = 3, arch: str = "gfx950", inst: bool = False) -> int:
+    def spec_compile(self, bvh: bool = False, pmj: bool = False, stage: bool = True, defer: bool = False, min_waves: int = 3, arch: str = "gfx950", inst: bool = False,
+                     env: bool = False) -> int:
         """akr_host_spec_compile: hiprtc-compiles the scene's per-scene kernel (no device needed); returns the code object's size."""
         nbytes = C.c_uint64()
         log = C.create_string_buffer(4096)
-        flags = (1 if bvh else 0) | (2 if pmj else 0) | (4 if stage else 0) | (8 if defer else 0) | (16 if inst else 0)
+        flags = (1 if bvh else 0) | (2 if pmj else 0) | (4 if stage else 0) | (8 if defer else 0) | (16 if inst else 0) | (32 if env else 0)
         check(lib().akr_host_spec_compile(self.h, flags, min_waves, arch.encode(), C.byref(nbytes), log, 4096))
         return nbytes.value
 
@@ -286,6 +299,49 @@ class Scene:
         out, alpha, em = np.zeros((n, 64), np.uint32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
         check(lib().akr_probe_material_folded_host(self.h, material, n, _fp(uv), out.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(alpha), _fp(em)))
         return out, alpha, em
+
+    def _set_environment_data(self, env: Optional[abi.EnvironmentData]):
+        if env is None:
+            check(lib().akr_scene_set_environment(self.h, None))
+            return
+        d, keep = env.to_desc()
+        check(lib().akr_scene_set_environment(self.h, C.byref(d)))
+        del keep
+
+    def set_environment(self, image=None, color=None, strength: float = 1.0, rotation=None, filter: int = abi.TEX_FILTER_LINEAR):
+        """akr_scene_set_environment: an equirectangular image ((H, W, 3 | 4) float32, row 0 = v = 0) or a constant colour, times
+        strength, turned by `rotation` (3 x 3, environment -> world). Both None: removes the environment."""
+        if image is None and color is None:
+            self._set_environment_data(None)
+        else:
+            self._set_environment_data(abi.EnvironmentData(image=image, color=color, strength=strength, rotation=rotation, filter=filter))
+
+    def environment(self) -> Optional[abi.EnvironmentData]:
+        """akr_scene_get_environment: the environment as the scene holds it (None without one)."""
+        d = abi.EnvironmentDesc()
+        check(lib().akr_scene_get_environment(self.h, C.byref(d)))
+        if d.strength == 0.0:
+            return None
+        rot = np.array(list(d.rotation), dtype=np.float32).reshape(3, 3)
+        if d.width:
+            n = d.width * d.height * 4
+            im = np.ctypeslib.as_array(d.texels, shape=(n,)).astype(np.float32, copy=True).reshape(d.height, d.width, 4)
+            return abi.EnvironmentData(image=im, strength=float(d.strength), rotation=rot, filter=int(d.filter))
+        return abi.EnvironmentData(color=tuple(float(c) for c in d.color), strength=float(d.strength), rotation=rot)
+
+    def probe_env_sample(self, u: np.ndarray) -> np.ndarray:
+        """akr_probe_env_sample (test hook): (n, 2) uniform points -> (n, 5) wi.xyz, pdf, valid."""
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((u.shape[0], 5), np.float32)
+        check(lib().akr_probe_env_sample(self.ctx.h, self.h, u.shape[0], _fp(u), _fp(out)))
+        return out
+
+    def probe_env_pdf(self, d: np.ndarray) -> np.ndarray:
+        """akr_probe_env_pdf (test hook): (n, 3) directions -> (n, 4) pdf, radiance.rgb."""
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((d.shape[0], 4), np.float32)
+        check(lib().akr_probe_env_pdf(self.ctx.h, self.h, d.shape[0], _fp(d), _fp(out)))
+        return out
 
     def set_resolution(self, w: int, h: int):
         check(lib().akr_scene_set_resolution(self.h, w, h))
@@ -372,7 +428,7 @@ class Scene:
         c = abi.CameraDesc()
         check(lib().akr_scene_get_camera(self.h, C.byref(c)))
         cam = abi.CameraData(np.array(list(c.c2w), dtype=np.float32), float(c.fov), c.width, c.height)
-        return abi.SceneData(meshes, instances, materials, cam, images=images)
+        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment())
 
 
 def set_option(name: str, value: int) -> None:

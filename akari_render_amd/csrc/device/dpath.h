@@ -3,6 +3,7 @@
 // Everything here follows crates/akari_integrator/src/pt.rs:95-323,329-900 (shift_mapping = None), camera/mod.rs,
 // film.rs, sampler/mod.rs, light/{mod,area}.rs of the reference; file:line cited per function.
 #pragma once
+#include "denv.h"
 #include "dinst_trav.h"
 #include "drng.h"
 #include "../kernels.h"
@@ -251,9 +252,11 @@ struct LightSample {
     uint32_t ex1;
     bool valid;
 };
-// LightAggregate::sample_direct (light/mod.rs:115-132) + AreaLight::sample_direct (light/area.rs:51-107)
-template <bool TEX, bool INST = false>
-AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_select, vec2 u_sample) {
+// LightAggregate::sample_direct (light/mod.rs:115-132) + AreaLight::sample_direct (light/area.rs:51-107).
+// ENV: the scene has an environment light, the last entry of the light table (denv.h); a choice of it draws its direction from the
+// environment's tables with the u_sample a triangle would use -- no dimension more -- and its shadow ray is an unbounded one.
+template <bool TEX, bool INST = false, bool ENV = false>
+AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_select, vec2 u_sample, uint32_t color = 0) {
     LightSample s;
     s.li = mk3(0, 0, 0);
     s.wi = mk3(0, 0, 0);
@@ -265,6 +268,20 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
     if (sc.n_lights == 0) return s;
     float light_choice_pdf, u_sel2, pdf_prim, u_unused;
     uint32_t light = alias_sample_and_remap(sc.light_alias, sc.n_lights, u_select, light_choice_pdf, u_sel2);
+    if (ENV && light == sc.env->light) {
+        const DEnv& env = *sc.env;
+        vec3 wi;
+        float pdf;
+        const bool ok = env_sample(env, u_sample, wi, pdf);
+        s.li = env_eval(env, color, wi);
+        s.ro = offset_ray_origin(pn_p, face_forward(pn_n, wi));
+        s.tmax = 1e20f;  // closest-ray convention (dinst_trav.h)
+        s.ex1 = kInvalid;
+        s.wi = wi;
+        s.valid = ok;
+        s.pdf = pdf * light_choice_pdf;
+        return s;
+    }
     const LightRec L = sc.lights[light];
     uint32_t prim = alias_sample_and_remap(sc.area_alias + L.tri_offset, L.n_tris, u_sel2, pdf_prim, u_unused);
     uint32_t gid = L.first_gid + prim;
@@ -451,7 +468,7 @@ AKR_D void shifted_pixel(const PtParams& p, uint32_t px, uint32_t py, uint32_t& 
 // FD: 1 / 0 = force_diffuse known at compile time (the reference's JIT also specialises the kernel on it: the branch
 // at pt.rs:268 is taken while tracing the kernel, so a force_diffuse kernel contains no Principled code); -1 = read
 // p.force_diffuse at run time.
-template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h)
+template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h)
 AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found, bool occluded, uint32_t pix_in, uint32_t sx_in, uint32_t sy_in,
                      uint32_t* park = nullptr) {
     const bool force_diffuse = FD < 0 ? (p.force_diffuse != 0) : (FD != 0);
@@ -502,7 +519,17 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
             if (PARK == 1) { park_put(park, PK_DEFER + 0, r.d_gid); park_put(park, PK_DEFER + 1, f2u(r.d_u)); park_put(park, PK_DEFER + 2, f2u(r.d_v)); }
         }
         if (!found) {
-            terminated = true;  // pt.rs:381-396 (hit_envmap adds zero)
+            terminated = true;  // pt.rs:381-396
+            if (ENV && (!p.indirect_only || r.depth > 1)) {
+                // hit_envmap: the environment's radiance, MIS-weighted against its light sample as handle_surface_light weighs an
+                // emitter. `base` is not captured (the reference leaves the loop before its depth-0 capture): directly visible
+                // radiance above clamp_indirect is clamped.
+                const DEnv& env = *sc.env;
+                const vec3 le = env_eval(env, p.color, r.rd);
+                float w = 1.0f;
+                if (r.depth != 0 && p.use_nee) w = mis_weight(r.prev_bsdf_pdf, sc.light_pdf[env.light] * env_pdf(env, r.rd));
+                if (p.debug_depth < 0 || r.depth == (uint32_t)p.debug_depth) r.radiance = r.radiance + r.beta * (le * w);
+            }
         } else {
             SurfacePoint si = surface_interaction_any<INST>(sc, hit.gid, mk2(hit.u, hit.v));
             vec3 wo = -r.rd;
@@ -533,7 +560,7 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
                 LightSample dl;
                 dl.valid = false;
                 if (p.use_nee && (!p.indirect_only || r.depth > 1))
-                    dl = sample_direct<TEX, INST>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z));
+                    dl = sample_direct<TEX, INST, ENV>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z), p.color);
                 vec3 u_bsdf = next_3d<PMJ>(p, r.smp);
                 // sample_surface_and_shade_direct, pt.rs:297-323
                 ShadePoint sp;

@@ -55,6 +55,16 @@ struct DInst {
     uint32_t on, n_instances;
 };
 
+// The environment light of a scene (host/scene_env.cpp, device/denv.h): one record in HBM, read by the ENV kernels only. Its tables
+// stay in HBM too (they are not part of the LDS staging plan).
+struct DEnv {
+    const float4* __restrict__ texels;          // w x h, row 0 = v = 0, strength applied, the pipeline's RGB space
+    const AliasPacked* __restrict__ marginal;   // h entries: rows
+    const AliasPacked* __restrict__ conditional;  // h x w entries: the columns of each row (j relative to the row)
+    float rot[9];                               // world -> environment (R^T), row-major
+    uint32_t w, h, filter, light;               // light: the environment's entry in the light table (the last one)
+};
+
 struct DScene {
     const float4* __restrict__ woop;        // 3 float4 per triangle (exhaustive path) or 4 (BVH path: + global id)
     const uint32_t* __restrict__ tri_gid;   // traversal order -> global id (host-side tests; the BVH path reads the id from the record)
@@ -67,13 +77,15 @@ struct DScene {
     const float* __restrict__ light_pdf;
     const uint32_t* __restrict__ light_inst;        // light id -> instance
     const uint32_t* __restrict__ light_tri_offset;  // light id -> first entry in area_entries / area_pdf
-    const uint32_t* __restrict__ light_n_tris;
+    // The environment light, or nullptr: a scene with one runs the ENV kernels. (It has the slot of the per-light triangle counts, which
+    // no kernel reads -- LightRec carries them: the record keeps its layout, and with it the code of every kernel compiled before.)
+    const DEnv* __restrict__ env;
     const AliasEntry* __restrict__ area_entries;
     const float* __restrict__ area_pdf;
     const uint32_t* __restrict__ inst_tri_offset;   // instance -> first global triangle id
     const AliasPacked* __restrict__ light_alias;    // light_entries + light_pdf, packed
     const AliasPacked* __restrict__ area_alias;     // area_entries + area_pdf, packed
-    const LightRec* __restrict__ lights;            // light_tri_offset + light_n_tris + light_inst (+ inst_tri_offset), packed
+    const LightRec* __restrict__ lights;            // light_tri_offset + per-light triangle counts + light_inst (+ inst_tri_offset), packed
     const uint4* __restrict__ bvh_nodes;            // nullptr on the exhaustive path
     uint32_t n_tris, n_lights, n_nodes, has_alpha;
     uint32_t bvh_stack_depth;                       // BVH path: traversal stack entries per lane in LDS = depth of this scene's tree

@@ -40,7 +40,8 @@ namespace akr {
 // ABSENT: lobes the scene cannot have (dbsdf.h AB_*). The precompiled kernels know 0 and AB_SIMPLE (PtParams.simple_scene: scenes without
 // textures); a per-scene kernel gets the mask of its scene.
 // INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h); BVH kernels without STAGE / DEFER only.
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false>
+// ENV: the scene has an environment light (device/denv.h); kernels without DEFER / SIMPLE only.
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false>
 AKR_D void pt_pass_body(const PtParams& p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];  // BVH: kBvhStackDepth x 256 words; else: staged tables
     TraceCtx tc;
@@ -225,8 +226,8 @@ AKR_D void pt_pass_body(const PtParams& p) {
             }
             if (STRAG > 0 && r.carry) {
                 // still tracing: nothing to resolve or shade yet
-            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST>(q, r, hit, found, occluded, 0, 0, 0, park);
-            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST>(q, r, hit, found, occluded, pix, sx, sy);
+            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV>(q, r, hit, found, occluded, 0, 0, 0, park);
+            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV>(q, r, hit, found, occluded, pix, sx, sy);
         }
     }
     flush_counters(p, r, tc.cnt, BVH);

@@ -3,6 +3,7 @@
 // Every entry point catches C++ exceptions and HIP errors and turns them into an akr_status plus a thread-local message; nothing
 // throws or aborts across the boundary.
 #pragma once
+#include <atomic>
 #include <mutex>
 #include <hip/hip_runtime.h>
 
@@ -145,6 +146,8 @@ struct akr_scene {
     DevBuf woop, tri_gid, shade, normals, inst, materials, ggx_table, light_entries, light_pdf, light_inst, light_tri_offset,
         light_n_tris, area_entries, area_pdf, inst_tri_offset, bvh_nodes, tex_nodes, tex_images, tex_texels, tex_mat_inputs;
     DevBuf in2_tlas_leaves, in2_mesh_tris, in2_mesh_pos, in2_mesh_meta, in2_mesh_normals, in2_inst_mats, in2_share_bits;  // meshes + instances (scene_inst.cpp)
+    DevBuf env_texels, env_marginal, env_conditional, env_rec;  // the environment light (scene_env.cpp; DScene.env points at env_rec)
+    std::atomic<int> sessions{0};  // pt / aov / gpt / mcmc_opt sessions that hold the scene (akr_scene_set_environment is refused meanwhile)
     std::vector<float> ggx_host;
     // materials / node lists / raw inputs re-compiled for a non-default colour pipeline (akr_pt_config.color), by pipeline
     struct ColorSet {
@@ -216,6 +219,7 @@ struct akr_pt_session {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double kernel_ms = 0.0;
     PtParams params;
+    bool holds_scene = false;  // counted in scene->sessions (pt_begin)
     void fold_events(bool all) {  // all: the stream has been synchronised
         size_t keep = 0;
         for (size_t i = 0; i < pending.size(); i++) {
@@ -232,6 +236,7 @@ struct akr_pt_session {
         pending.resize(keep);
     }
     ~akr_pt_session() {
+        if (holds_scene) scene->sessions--;
         for (hipStream_t st : wf_streams) (void)hipStreamDestroy(st);
         for (hipEvent_t ev : wf_join) (void)hipEventDestroy(ev);
         if (wf_fork) (void)hipEventDestroy(wf_fork);

@@ -143,6 +143,27 @@ AKR_TEST_API int32_t akr_probe_intersect(akr_context* ctx, akr_scene* scene, uin
         }
     });
 }
+// the environment light's sampler (device/denv.h): n points u -> wi, pdf, valid; n directions -> pdf, radiance (default colour pipeline)
+static int32_t probe_env(akr_context* ctx, akr_scene* scene, uint32_t mode, uint32_t n, const float* in, float* out, const char* name) {
+    if (!ctx || !scene || !in || !out) return fail(AKR_ERR_INVALID_ARGUMENT, std::string(name) + ": NULL argument");
+    if (scene->ctx != ctx || !scene->cs.env.on) return fail(AKR_ERR_INVALID_ARGUMENT, std::string(name) + ": the scene has no environment light on this context");
+    return guarded([&] {
+        ctx->bind();
+        const size_t n_in = (mode == 0 ? 2ull : 3ull) * n, n_out = (mode == 0 ? 5ull : 4ull) * n;
+        DevBuf din, dout;
+        din.upload(std::vector<float>(in, in + n_in));
+        dout.alloc(n_out * 4);
+        if (n) HIP_CHECK(launch_probe_env(probe_params(scene), mode, n, din.as<float>(), dout.as<float>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) HIP_CHECK(hipMemcpy(out, dout.p, n_out * 4, hipMemcpyDeviceToHost));
+    });
+}
+AKR_TEST_API int32_t akr_probe_env_sample(akr_context* ctx, akr_scene* scene, uint32_t n, const float* u2, float* out5) {
+    return probe_env(ctx, scene, 0, n, u2, out5, "akr_probe_env_sample");
+}
+AKR_TEST_API int32_t akr_probe_env_pdf(akr_context* ctx, akr_scene* scene, uint32_t n, const float* dirs3, float* out4) {
+    return probe_env(ctx, scene, 1, n, dirs3, out4, "akr_probe_env_pdf");
+}
 AKR_TEST_API int32_t akr_probe_surface_interaction(akr_context* ctx, akr_scene* scene, uint32_t n, const uint32_t* inst_prim, const float* bary,
                                               float* out) {
     if (!ctx || !scene || !inst_prim || !bary || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_surface_interaction: NULL argument");

@@ -97,7 +97,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
             if (m.kind == MAT_GLASS) simple = false;
             if (m.kind == MAT_PRINCIPLED && ((m.flags & (MF_COAT | MF_EVAL_DIEL | MF_NORMAL_MAP)) != 0 || m.transmission != 0.0f || m.coat_weight != 0.0f)) simple = false;
         }
-        p.simple_scene = (simple && se->simple_kernels_option) ? 1u : 0u;
+        p.simple_scene = (simple && se->simple_kernels_option && !cs.env.on) ? 1u : 0u;  // (no SIMPLE kernels with an environment light)
     }
     {   // hits on "expensive" materials on even iterations only (pt_kernels.hip: DEFER): pays when SOME materials are expensive and
         // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
@@ -116,7 +116,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         bool want = n_dear > 0 && 2 * n_dear <= n_surface;
         uint32_t mask = 1u;  // iterations with (iteration & mask) != 0 put those hits off
         if (se->defer_metal_option >= 0) { mask = (uint32_t)se->defer_metal_option; want = mask != 0; }  // akr_option_set("defer_metal"): measurements / tests
-        p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on) ? mask : 0u;
+        p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on && !cs.env.on) ? mask : 0u;  // (nor DEFER ones)
         p.defer_flags = flags;
     }
     p.wf_sort = se->wf_sort ? 1u : 0u;
@@ -520,6 +520,8 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
             // The relaxed arithmetic tier (pt_kernels_relaxed.hip): the precompiled megakernels of flattened scenes. Everything else --
             // kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
             se->arith_relaxed = t.arith == 1 && for_pt_kernel && !scene->cs.instanced.on && !se->wavefront;
+            if (se->arith_relaxed && scene->cs.env.on)
+                throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
             if (!for_pt_kernel) se->spec_status = "not a pt session";
             else if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
             else if (se->wavefront) se->spec_status = "wavefront schedule";
@@ -543,6 +545,7 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
                 rq.pmj = se->params.sampler != 0;
                 rq.stage = se->params.stage_total != 0;
                 rq.defer = se->params.defer_metal != 0;
+                rq.env = scene->cs.env.on;
                 rq.min_waves = se->spec_waves;
                 se->spec = ctx->spec_cache.get(scene->spec_header, rq, ctx->props.gcnArchName, may_compile);
                 se->spec_status = se->spec->status;
@@ -555,6 +558,8 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
         }
         se->sched_trial = schedule_trial_eligible(se.get(), for_pt_kernel) ? 1 : 0;
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        scene->sessions++;
+        se->holds_scene = true;
         *out = se.release();
     });
 }

@@ -31,9 +31,90 @@ static void ensure_ggx_table(akr_scene* s) {
     s->ggx_table.upload(s->ggx_host);
 }
 
+// the light tables (and the environment's record and tables) on the device, and their pointers in s->dscene: at scene creation and after
+// akr_scene_set_environment
+static void upload_lights(akr_scene* s) {
+    const CompiledScene& cs = s->cs;
+    s->light_entries.upload(cs.light_entries);
+    s->light_pdf.upload(cs.light_pdf);
+    s->light_inst.upload(cs.light_inst);
+    s->light_tri_offset.upload(cs.light_tri_offset);
+    s->light_n_tris.upload(cs.light_n_tris);
+    {  // the light tables once more, packed so that each level of light sampling is ONE gather (device/dgeom.h, dscene.h)
+        auto pack = [](const std::vector<AliasEntry>& e, const std::vector<float>& pdf, size_t first, size_t n, std::vector<AliasPacked>& out) {
+            for (size_t i = 0; i < n; i++) out.push_back(AliasPacked{e[first + i].j, e[first + i].t, pdf[first + i], pdf[first + e[first + i].j]});
+        };
+        std::vector<AliasPacked> la, aa;
+        std::vector<LightRec> lr;
+        pack(cs.light_entries, cs.light_pdf, 0, cs.n_lights, la);
+        for (uint32_t l = 0; l < cs.n_lights; l++) {
+            if (cs.light_inst[l] == 0xffffffffu) {  // the environment (no triangles)
+                lr.push_back(LightRec{cs.light_tri_offset[l], 0u, 0u, 0xffffffffu});
+                continue;
+            }
+            pack(cs.area_entries, cs.area_pdf, cs.light_tri_offset[l], cs.light_n_tris[l], aa);
+            lr.push_back(LightRec{cs.light_tri_offset[l], cs.light_n_tris[l], cs.inst_tri_offset[cs.light_inst[l]], cs.light_inst[l]});
+        }
+        s->light_alias.upload(la);
+        s->area_alias.upload(aa);
+        s->lights.upload(lr);
+        if (cs.env.on) {
+            std::vector<AliasPacked> marg, cond;
+            pack(cs.env.marginal_entries, cs.env.marginal_pdf, 0, cs.env.h, marg);
+            for (uint32_t y = 0; y < cs.env.h; y++) {
+                const size_t first = (size_t)y * cs.env.w;
+                for (uint32_t x = 0; x < cs.env.w; x++) {  // j is relative to the row
+                    const AliasEntry& e = cs.env.conditional_entries[first + x];
+                    cond.push_back(AliasPacked{e.j, e.t, cs.env.conditional_pdf[first + x], cs.env.conditional_pdf[first + e.j]});
+                }
+            }
+            s->env_texels.upload(cs.env.texels);
+            s->env_marginal.upload(marg);
+            s->env_conditional.upload(cond);
+            DEnv rec;
+            std::memset(&rec, 0, sizeof rec);
+            rec.texels = s->env_texels.as<float4>();
+            rec.marginal = s->env_marginal.as<AliasPacked>();
+            rec.conditional = s->env_conditional.as<AliasPacked>();
+            for (int k = 0; k < 9; k++) rec.rot[k] = cs.env.rot_t[k];
+            rec.w = cs.env.w;
+            rec.h = cs.env.h;
+            rec.filter = cs.env.filter;
+            rec.light = cs.n_lights - 1;
+            s->env_rec.alloc(sizeof rec);
+            HIP_CHECK(hipMemcpy(s->env_rec.p, &rec, sizeof rec, hipMemcpyHostToDevice));
+        } else {
+            s->env_texels.release();
+            s->env_marginal.release();
+            s->env_conditional.release();
+            s->env_rec.release();
+        }
+    }
+    DScene& d = s->dscene;
+    d.light_entries = s->light_entries.as<AliasEntry>();
+    d.light_pdf = s->light_pdf.as<float>();
+    d.light_inst = s->light_inst.as<uint32_t>();
+    d.light_tri_offset = s->light_tri_offset.as<uint32_t>();
+    d.light_alias = s->light_alias.as<AliasPacked>();
+    d.area_alias = s->area_alias.as<AliasPacked>();
+    d.lights = s->lights.as<LightRec>();
+    d.n_lights = cs.n_lights;
+    d.env = cs.env.on ? s->env_rec.as<DEnv>() : nullptr;
+}
+static void count_device_bytes(akr_scene* s) {
+    s->device_bytes = 0;
+    for (const DevBuf* b : {&s->woop, &s->tri_gid, &s->shade, &s->normals, &s->inst, &s->materials, &s->ggx_table, &s->light_entries,
+                            &s->light_pdf, &s->light_inst, &s->light_tri_offset, &s->light_n_tris, &s->area_entries, &s->area_pdf,
+                            &s->inst_tri_offset, &s->light_alias, &s->area_alias, &s->lights, &s->bvh_nodes, &s->tex_nodes, &s->tex_images, &s->tex_texels, &s->tex_mat_inputs,
+                            &s->in2_tlas_leaves, &s->in2_mesh_tris, &s->in2_mesh_pos, &s->in2_mesh_meta, &s->in2_mesh_normals, &s->in2_inst_mats, &s->in2_share_bits,
+                            &s->env_texels, &s->env_marginal, &s->env_conditional, &s->env_rec})
+        s->device_bytes += b->bytes;
+}
+
 void akr_api::scene_finish(akr_scene* s) {
     akr_context* ctx = s->ctx;
     compile_scene(s->flat, s->cs);
+    compile_environment(s->flat, s->cs);
     CompiledScene& cs = s->cs;
     camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity);
     if (!ctx) {  // host-only scene: inspectable, not renderable
@@ -48,29 +129,9 @@ void akr_api::scene_finish(akr_scene* s) {
     s->normals.upload(cs.normals);
     s->inst.upload(cs.inst);
     s->materials.upload(cs.materials);
-    s->light_entries.upload(cs.light_entries);
-    s->light_pdf.upload(cs.light_pdf);
-    s->light_inst.upload(cs.light_inst);
-    s->light_tri_offset.upload(cs.light_tri_offset);
-    s->light_n_tris.upload(cs.light_n_tris);
     s->area_entries.upload(cs.area_entries);
     s->area_pdf.upload(cs.area_pdf);
     s->inst_tri_offset.upload(cs.inst_tri_offset);
-    {  // the light tables once more, packed so that each level of light sampling is ONE gather (device/dgeom.h, dscene.h)
-        auto pack = [](const std::vector<AliasEntry>& e, const std::vector<float>& pdf, size_t first, size_t n, std::vector<AliasPacked>& out) {
-            for (size_t i = 0; i < n; i++) out.push_back(AliasPacked{e[first + i].j, e[first + i].t, pdf[first + i], pdf[first + e[first + i].j]});
-        };
-        std::vector<AliasPacked> la, aa;
-        std::vector<LightRec> lr;
-        pack(cs.light_entries, cs.light_pdf, 0, cs.n_lights, la);
-        for (uint32_t l = 0; l < cs.n_lights; l++) {
-            pack(cs.area_entries, cs.area_pdf, cs.light_tri_offset[l], cs.light_n_tris[l], aa);
-            lr.push_back(LightRec{cs.light_tri_offset[l], cs.light_n_tris[l], cs.inst_tri_offset[cs.light_inst[l]], cs.light_inst[l]});
-        }
-        s->light_alias.upload(la);
-        s->area_alias.upload(aa);
-        s->lights.upload(lr);
-    }
     s->bvh_nodes.upload(cs.instanced.on ? cs.instanced.nodes : cs.bvh_nodes);
     if (cs.instanced.on) {
         s->in2_tlas_leaves.upload(cs.instanced.tlas_leaves);
@@ -96,20 +157,12 @@ void akr_api::scene_finish(akr_scene* s) {
     d.inst = s->inst.as<float4>();
     d.materials = s->materials.as<DMaterial>();
     d.ggx_table = s->ggx_table.as<float>();
-    d.light_entries = s->light_entries.as<AliasEntry>();
-    d.light_pdf = s->light_pdf.as<float>();
-    d.light_inst = s->light_inst.as<uint32_t>();
-    d.light_tri_offset = s->light_tri_offset.as<uint32_t>();
-    d.light_n_tris = s->light_n_tris.as<uint32_t>();
     d.area_entries = s->area_entries.as<AliasEntry>();
     d.area_pdf = s->area_pdf.as<float>();
     d.inst_tri_offset = s->inst_tri_offset.as<uint32_t>();
-    d.light_alias = s->light_alias.as<AliasPacked>();
-    d.area_alias = s->area_alias.as<AliasPacked>();
-    d.lights = s->lights.as<LightRec>();
+    upload_lights(s);  // light tables, environment
     d.bvh_nodes = s->bvh_nodes.as<uint4>();
     d.n_tris = cs.n_tris;
-    d.n_lights = cs.n_lights;
     d.n_nodes = (uint32_t)((cs.instanced.on ? cs.instanced.nodes.size() : cs.bvh_nodes.size()) / kBvhNodeWords);
     d.has_alpha = cs.has_alpha ? 1u : 0u;
     d.bvh_stack_depth = std::max(1u, std::min(cs.bvh_depth, kBvhStackDepth));  // one pending group per tree level at most (disect.h)
@@ -142,12 +195,7 @@ void akr_api::scene_finish(akr_scene* s) {
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         d.in2.share_bits = s->in2_share_bits.as<uint32_t>();
     }
-    s->device_bytes = 0;
-    for (const DevBuf* b : {&s->woop, &s->tri_gid, &s->shade, &s->normals, &s->inst, &s->materials, &s->ggx_table, &s->light_entries,
-                            &s->light_pdf, &s->light_inst, &s->light_tri_offset, &s->light_n_tris, &s->area_entries, &s->area_pdf,
-                            &s->inst_tri_offset, &s->light_alias, &s->area_alias, &s->lights, &s->bvh_nodes, &s->tex_nodes, &s->tex_images, &s->tex_texels, &s->tex_mat_inputs,
-                            &s->in2_tlas_leaves, &s->in2_mesh_tris, &s->in2_mesh_pos, &s->in2_mesh_meta, &s->in2_mesh_normals, &s->in2_inst_mats, &s->in2_share_bits})
-        s->device_bytes += b->bytes;
+    count_device_bytes(s);
 }
 
 // the arrays scene_finish uploads, in bytes (the packed light tables repeat the alias tables: 16 B per entry)
@@ -157,6 +205,7 @@ static uint64_t compiled_scene_bytes(const CompiledScene& cs) {
                  b(cs.light_inst) + b(cs.light_tri_offset) + b(cs.light_n_tris) + b(cs.area_entries) + b(cs.area_pdf) + b(cs.inst_tri_offset) +
                  16ull * (cs.light_entries.size() + cs.area_entries.size() + cs.n_lights) + b(cs.bvh_nodes) + b(cs.tex_nodes) + b(cs.images) + b(cs.texels) +
                  b(cs.mat_inputs);
+    n += b(cs.env.texels) + 16ull * (cs.env.marginal_entries.size() + cs.env.conditional_entries.size()) + (cs.env.on ? sizeof(DEnv) : 0u);
     const CompiledScene::Instanced& is = cs.instanced;
     return n + b(is.nodes) + b(is.tlas_leaves) + b(is.mesh_tris) + b(is.mesh_pos) + b(is.mesh_meta) + b(is.mesh_normals) + b(is.inst_mats) + (is.on ? std::max<uint64_t>(((uint64_t)cs.n_tris + 31u) / 32u, 1u) * 4u : 0u);
 }
@@ -218,6 +267,40 @@ AKR_API int32_t akr_scene_get_info(const akr_scene* s, akr_scene_info* info) {
     info->node_stride_bytes = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 0u : kBvhNodeWords * 4u;
     info->tri_bytes = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 48u : kBvhTriWords * 4u;
     info->bvh_depth = s->cs.bvh_depth;
+    return AKR_OK;
+}
+AKR_API int32_t akr_scene_set_environment(akr_scene* s, const akr_environment_desc* desc) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_environment: scene is NULL");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_set_environment: a session holds the scene (end it first)");
+        HostEnvironment env;
+        if (desc) env = environment_from_desc(*desc);
+        std::swap(s->flat.env, env);
+        try {
+            compile_environment(s->flat, s->cs);
+        } catch (...) {
+            std::swap(s->flat.env, env);  // (compile_environment refuses before it changes anything)
+            throw;
+        }
+        if (s->ctx) {
+            s->ctx->bind();
+            upload_lights(s);
+            count_device_bytes(s);
+        }
+    });
+}
+AKR_API int32_t akr_scene_get_environment(const akr_scene* s, akr_environment_desc* out) {
+    if (!s || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_environment: NULL argument");
+    const HostEnvironment& e = s->flat.env;
+    std::memset(out, 0, sizeof *out);
+    for (int k = 0; k < 9; k++) out->rotation[k] = e.rotation[k];
+    if (!e.set) return AKR_OK;
+    out->width = e.width;
+    out->height = e.height;
+    out->filter = e.filter;
+    out->texels = e.texels.empty() ? nullptr : e.texels.data();
+    for (int c = 0; c < 3; c++) out->color[c] = e.color[c];
+    out->strength = e.strength;
     return AKR_OK;
 }
 AKR_API int32_t akr_scene_get_light(const akr_scene* s, uint32_t light, uint32_t* instance, float* power, float* pdf) {
@@ -326,6 +409,11 @@ AKR_API int32_t akr_scene_get_array(const akr_scene* s, int32_t which, const voi
         case AKR_ARRAY_MESH_POS: set(cs.instanced.mesh_pos.data(), cs.instanced.mesh_pos.size() * 4); break;
         case AKR_ARRAY_MESH_META: set(cs.instanced.mesh_meta.data(), cs.instanced.mesh_meta.size() * 4); break;
         case AKR_ARRAY_MESH_NORMALS: set(cs.instanced.mesh_normals.data(), cs.instanced.mesh_normals.size() * 4); break;
+        case AKR_ARRAY_ENV_MARGINAL_ENTRIES: set(cs.env.marginal_entries.data(), cs.env.marginal_entries.size() * sizeof(AliasEntry)); break;
+        case AKR_ARRAY_ENV_MARGINAL_PDF: set(cs.env.marginal_pdf.data(), cs.env.marginal_pdf.size() * 4); break;
+        case AKR_ARRAY_ENV_CONDITIONAL_ENTRIES: set(cs.env.conditional_entries.data(), cs.env.conditional_entries.size() * sizeof(AliasEntry)); break;
+        case AKR_ARRAY_ENV_CONDITIONAL_PDF: set(cs.env.conditional_pdf.data(), cs.env.conditional_pdf.size() * 4); break;
+        case AKR_ARRAY_ENV_TEXELS: set(cs.env.texels.data(), cs.env.texels.size() * 4); break;
         default: return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: unknown array id");
     }
     return AKR_OK;
@@ -361,7 +449,7 @@ AKR_API int32_t akr_host_spec_compile(akr_scene* scene, uint32_t flags, uint32_t
         }
         if (header.empty()) throw Unsupported("unsupported: the scene has no per-scene code (no texture-fed material, or too many shader kinds)");
         SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u;
+        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u;
         rq.min_waves = (int)min_waves;
         std::vector<char> code;
         std::string text;
@@ -376,7 +464,7 @@ AKR_API int32_t akr_host_spec_compile_text(const char* spec_header, uint32_t fla
     if (!spec_header || !arch || !out_path) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_spec_compile_text: NULL argument");
     return guarded([&] {
         SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u;
+        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u;
         rq.min_waves = (int)min_waves;
         std::vector<char> code;
         std::string log;

@@ -35,6 +35,16 @@ struct HostGraph {
     uint32_t input[AKR_IN_COUNT];
     HostGraph() { for (uint32_t& i : input) i = AKR_NODE_NONE; }
 };
+// The environment light as given (akr_environment_desc / scene.json "environment"): decoded linear texels, no strength applied.
+struct HostEnvironment {
+    bool set = false;                // false: none (also after a strength of 0 or an all-black image)
+    uint32_t width = 0, height = 0;  // 0 x 0: the constant `color`
+    uint32_t filter = 0;             // akr_tex_filter
+    std::vector<float> texels;       // RGBA32F, row 0 = v = 0
+    float color[3] = {0, 0, 0};
+    float strength = 0.0f;
+    float rotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // environment -> world, row-major
+};
 // Owning copy of an akr_scene_desc.
 struct FlatScene {
     std::vector<HostMesh> meshes;
@@ -44,6 +54,7 @@ struct FlatScene {
     std::vector<float> ggx_table;  // 4096 or empty
     std::vector<HostImage> images;
     std::vector<HostGraph> graphs;  // empty, or one per material
+    HostEnvironment env;
     static FlatScene from_desc(const akr_scene_desc& d);
 };
 
@@ -101,6 +112,16 @@ struct CompiledScene {
         uint32_t tlas_nodes = 0, tlas_depth = 0, blas_depth = 0, n_mesh_tris = 0;
         uint32_t n_padding_classes = 0;    // per-mesh trees built: one per (mesh, padding class of its instances), scene_inst.cpp
     } instanced;
+    // the environment light (scene_env.cpp): what device/denv.h reads, and its place in the light table (the last entry)
+    struct Environment {
+        bool on = false;
+        uint32_t w = 0, h = 0, filter = 0;
+        std::vector<float> texels;                      // RGBA32F, strength applied (a constant colour: kEnvConstW x kEnvConstH texels)
+        std::vector<AliasEntry> marginal_entries, conditional_entries;  // rows; the columns of each row (j relative to the row)
+        std::vector<float> marginal_pdf, conditional_pdf;
+        float rot_t[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // world -> environment (R^T), row-major
+        float power = 0.0f;                             // selection weight 4 pi R^2 Lbar
+    } env;
     bool has_textures = false;
     bool has_alpha = false;
     bool needs_ggx_table = false;
@@ -214,6 +235,11 @@ bool tuning_set(const char* name, int value);    // false: unknown name
 bool tuning_get(const char* name, int* value);
 
 void compile_scene(const FlatScene& flat, CompiledScene& out);
+// scene_env.cpp: the environment light of `flat` into `out` (tables, light-table entry); replaces the one `out` has. After compile_scene.
+constexpr uint32_t kEnvConstW = 32, kEnvConstH = 16;  // the image a constant colour is stored as
+void compile_environment(const FlatScene& flat, CompiledScene& out);
+// an akr_environment_desc checked and copied (throws std::invalid_argument); the result's `set` is false for "no environment"
+HostEnvironment environment_from_desc(const akr_environment_desc& d);
 float triangle_emission_power(const CompiledScene& out, const TexScene& host_tex, uint32_t material, uint32_t prim, vec2 uv0, vec2 uv1, vec2 uv2, float area);
 bool instance_may_emit(const CompiledScene& out, const std::vector<akr_material_desc>& descs, const HostInstance& in);
 // scene_inst.cpp: does this scene take the two-level route, and its geometry + light tables if so (materials and the instance table

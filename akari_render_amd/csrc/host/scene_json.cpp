@@ -488,6 +488,55 @@ FlatScene load_scene_json(const std::string& path) {
         std::memcpy(h.transform, t.m, sizeof h.transform);
         flat.instances.push_back(std::move(h));
     }
+    if (scene.has("environment") && !scene.at("environment").is_null()) {
+        // optional environment light: {"strength", exactly one of "color" / "image" (the Image schema of a tex_image node), "transform"}
+        const JsonValue& ej = scene.at("environment");
+        akr_environment_desc d;
+        std::memset(&d, 0, sizeof d);
+        d.strength = ej.has("strength") ? ej.at("strength").as_f32() : 1.0f;
+        d.rotation[0] = d.rotation[4] = d.rotation[8] = 1.0f;
+        const bool has_color = ej.has("color") && !ej.at("color").is_null(), has_image = ej.has("image") && !ej.at("image").is_null();
+        if (has_color == has_image) throw std::runtime_error("environment: exactly one of \"color\" and \"image\" must be given");
+        std::vector<float> texels;
+        if (has_color) {
+            for (int c = 0; c < 3; c++) d.color[c] = ej.at("color").at(c).as_f32();
+        } else {
+            const JsonValue& im = ej.at("image");
+            const std::string cs = im.has("colorspace") ? im.at("colorspace").as_string() : std::string("none");
+            if (cs != "srgb" && cs != "none") throw std::runtime_error("unsupported: image colour space '" + cs + "'");
+            // the reader of image textures, so that every decoder and colourspace rule is the same; the image is not a texture of the scene
+            const size_t n_before = flat.images.size();
+            std::map<std::string, uint32_t> no_index;
+            GraphBuilder gb{scene, bufs, flat, no_index, HostGraph(), {}};
+            const uint32_t idx = gb.image(im);
+            HostImage hi = std::move(flat.images[idx]);
+            flat.images.resize(n_before);
+            if (hi.width == 0 || hi.height == 0) throw std::runtime_error("environment: zero-size image");
+            texels.resize(4ull * hi.width * hi.height);
+            for (size_t t = 0; t < (size_t)hi.width * hi.height; t++) {
+                float v[4];
+                if (hi.format == AKR_IMAGE_RGBA8) {
+                    const uint32_t p = hi.words[t];
+                    for (int c = 0; c < 4; c++) v[c] = unorm8((p >> (8 * c)) & 0xffu);
+                } else {
+                    for (int c = 0; c < 4; c++) v[c] = u2f(hi.words[4 * t + c]);
+                }
+                if (cs == "srgb")  // as an image node does (dtex.h node_image)
+                    for (int c = 0; c < 3; c++) v[c] = srgb_to_linear1(v[c]);
+                for (int c = 0; c < 4; c++) texels[4 * t + c] = v[c];
+            }
+            d.width = hi.width;
+            d.height = hi.height;
+            d.filter = hi.filter;
+            d.texels = texels.data();
+        }
+        if (ej.has("transform") && !ej.at("transform").is_null()) {  // an instance's transform; only its rotation is used
+            M4 t = load_transform(ej.at("transform"), false);
+            for (int row = 0; row < 3; row++)
+                for (int col = 0; col < 3; col++) d.rotation[3 * row + col] = t.m[col * 4 + row];
+        }
+        flat.env = environment_from_desc(d);
+    }
     if (!scene.has("camera")) throw std::runtime_error("scene has no camera");
     const JsonValue& cam = scene.at("camera");
     if (cam.at("type").as_string() != "perspective") throw std::runtime_error("unsupported camera type");

@@ -232,6 +232,9 @@ inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds
 PtParams pt_pass_layout(const PtParams& p, size_t& lds_bytes, uint32_t& blocks);
 hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_inst_kernels.hip: once per kept scene (DInst::share_bits)
 hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream);  // pt_inst_kernels.hip: scenes kept as meshes + instances
+hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream);   // pt_env_kernels.hip: scenes with an environment light (device/denv.h)
+hipError_t launch_pt_pass_inst_env(const PtParams& p, hipStream_t stream);  // pt_inst_env_kernels.hip: kept scenes with an environment light
+hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
 // spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled instantiation, or nullptr
 hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn = nullptr);
 hipError_t launch_gpt_sample(const PtParams& p, const GptParams& g, hipStream_t stream);
@@ -241,6 +244,7 @@ hipError_t launch_gpt_recon(const GptParams& g, uint32_t W, uint32_t H, const fl
 hipError_t launch_aov(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream);
 hipError_t launch_wf_init(const PtParams& p, const WfBuffers& wf, hipStream_t stream);
 hipError_t launch_wf_shade(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);
+hipError_t launch_wf_shade_env(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);  // wf_env_kernels.hip: scenes with an environment light
 uint32_t wf_trace_blocks_per_cu(const PtParams& p);
 hipError_t launch_wf_trace(const PtParams& p, const WfBuffers& wf, uint32_t q_in, uint32_t n_blocks, hipStream_t stream);
 // wf_sort.hip: key-value radix sort of a ray queue (24-bit keys)

@@ -1,0 +1,73 @@
+// pt_env_kernels.hip -- k_pt_pass for flattened scenes with an environment light (device/denv.h; ENV = true), in a translation unit of
+// their own so that the library's build compiles them beside pt_kernels.hip. The launch paths are those of launch_pt_pass (pt_launch.h)
+// without DEFER and SIMPLE: BVH or exhaustive x force_diffuse x textures x sampler family x staged tables (BVH path; the exhaustive path
+// always stages). Kept scenes run k_pt_pass_inst<.., ENV> (pt_inst_env_kernels.hip), the wavefront schedule k_wf_shade<.., ENV>
+// (wf_env_kernels.hip).
+#include <algorithm>
+#define AKR_PT_LAUNCH_KERNEL_ONLY 1
+#include "pt_launch.h"
+
+namespace akr {
+
+hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream) {
+    size_t lds;
+    uint32_t blocks;
+    const PtParams q = pt_pass_layout(p, lds, blocks);
+    if (blocks == 0) return hipSuccess;
+    const bool fd = p.force_diffuse != 0, tex = p.sc.tex.nodes != nullptr, pmj = p.sampler != 0;
+    const bool bvh = p.sc.bvh_nodes != nullptr, stage = p.stage_total != 0;
+    if (!bvh && !stage) return hipErrorInvalidValue;  // (the exhaustive kernels read their tables from LDS: the host guarantees the fit)
+#define AKR_ENV4(B, F, T, S)                                                                                                             \
+    {                                                                                                                                  \
+        if (pmj) {                                                                                                                     \
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)(k_pt_pass<B, F, T, true, S, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipLaunchKernelGGL((k_pt_pass<B, F, T, true, S, false, false, true>), dim3(blocks), dim3(256), lds, stream, q);          \
+        } else {                                                                                                                       \
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)(k_pt_pass<B, F, T, false, S, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipLaunchKernelGGL((k_pt_pass<B, F, T, false, S, false, false, true>), dim3(blocks), dim3(256), lds, stream, q);         \
+        }                                                                                                                              \
+    }
+#define AKR_ENV3(B, F, T)                            \
+    {                                               \
+        if (!B || stage) AKR_ENV4(B, F, T, true)    \
+        else AKR_ENV4(B, F, T, false)               \
+    }
+    if (bvh) {
+        if (tex) { if (fd) AKR_ENV3(true, true, true) else AKR_ENV3(true, false, true) }
+        else { if (fd) AKR_ENV3(true, true, false) else AKR_ENV3(true, false, false) }
+    } else {
+        if (tex) { if (fd) AKR_ENV4(false, true, true, true) else AKR_ENV4(false, false, true, true) }
+        else { if (fd) AKR_ENV4(false, true, false, true) else AKR_ENV4(false, false, false, true) }
+    }
+#undef AKR_ENV3
+#undef AKR_ENV4
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------- test hook
+// mode 0: in = u (2 floats / item) -> out = wi.xyz, pdf, valid (5 floats); mode 1: in = direction (3 floats) -> out = pdf, radiance.rgb (4 floats)
+__global__ void k_probe_env(const DEnv* __restrict__ env_p, uint32_t color, uint32_t mode, uint32_t n, const float* __restrict__ in, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DEnv& env = *env_p;
+    if (mode == 0) {
+        vec3 wi;
+        float pdf;
+        const bool ok = env_sample(env, mk2(in[2 * (size_t)i], in[2 * (size_t)i + 1]), wi, pdf);
+        float* o = out + 5 * (size_t)i;
+        o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = pdf; o[4] = ok ? 1.0f : 0.0f;
+    } else {
+        const vec3 d = mk3(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]);
+        const vec3 le = env_eval(env, color, d);
+        float* o = out + 4 * (size_t)i;
+        o[0] = env_pdf(env, d); o[1] = le.x; o[2] = le.y; o[3] = le.z;
+    }
+}
+hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream) {
+    if (!p.sc.env || mode > 1) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_probe_env, dim3((n + 255) / 256), dim3(256), 0, stream, p.sc.env, p.color, mode, n, in, out);
+    return hipGetLastError();
+}
+
+}  // namespace akr

@@ -1,0 +1,21 @@
+// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances (pt_inst_kernels.hip). A header
+// so that the instantiations of scenes with an environment light (pt_inst_env_kernels.hip, ENV = true) are compiled in a translation unit of
+// their own: those of pt_inst_kernels.hip, and their code, are the ones of a library without environments.
+#pragma once
+#include "device/pt_pass.h"
+
+#ifndef AKR_PT_MIN_WAVES_INST
+#define AKR_PT_MIN_WAVES_INST AKR_PT_MIN_WAVES_BVH
+#endif
+#ifndef AKR_PT_MIN_WAVES_INST_TEX
+#define AKR_PT_MIN_WAVES_INST_TEX AKR_PT_MIN_WAVES_BVH_TEX
+#endif
+
+namespace akr {
+
+template <bool FD, bool TEX, bool PMJ, bool ENV = false>
+__global__ __launch_bounds__(256, TEX ? AKR_PT_MIN_WAVES_INST_TEX : AKR_PT_MIN_WAVES_INST) void k_pt_pass_inst(const PtParams p) {
+    pt_pass_body<true, FD, TEX, PMJ, false, false, 0u, true, ENV>(p);
+}
+
+}  // namespace akr

@@ -1,21 +1,9 @@
 // pt_inst_kernels.hip -- k_pt_pass for scenes kept as meshes + instances (host/scene_inst.cpp): the same persistent-lane path
 // tracer over the two-level traversal of device/dinst_trav.h. BVH kernels without staged tables, deferral or absent-lobe masks:
-// force_diffuse x textures x sampler family.
-#include "device/pt_pass.h"
-
-#ifndef AKR_PT_MIN_WAVES_INST
-#define AKR_PT_MIN_WAVES_INST AKR_PT_MIN_WAVES_BVH
-#endif
-#ifndef AKR_PT_MIN_WAVES_INST_TEX
-#define AKR_PT_MIN_WAVES_INST_TEX AKR_PT_MIN_WAVES_BVH_TEX
-#endif
+// force_diffuse x textures x sampler family (those of scenes with an environment light: pt_inst_env_kernels.hip).
+#include "pt_inst_kernel.h"
 
 namespace akr {
-
-template <bool FD, bool TEX, bool PMJ>
-__global__ __launch_bounds__(256, TEX ? AKR_PT_MIN_WAVES_INST_TEX : AKR_PT_MIN_WAVES_INST) void k_pt_pass_inst(const PtParams p) {
-    pt_pass_body<true, FD, TEX, PMJ, false, false, 0u, true>(p);
-}
 
 // One thread per instance-triangle, once per scene: the bit of an odd triangle that takes its even neighbour's plane row (dinst.h
 // share_plane_row) -- what the flattening compiler decides per instance-triangle and resolve_pending used to decide at every candidate.
@@ -47,6 +35,7 @@ hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream) {
     uint32_t blocks;
     const PtParams q = pt_pass_layout(p, lds, blocks);
     if (blocks == 0) return hipSuccess;
+    if (p.sc.env) return launch_pt_pass_inst_env(p, stream);  // an environment light: pt_inst_env_kernels.hip
     const bool fd = p.force_diffuse != 0, tex = p.sc.tex.nodes != nullptr, pmj = p.sampler != 0;
 #define AKR_LAUNCH_INST(F, T, S)                                                                                                          \
     {                                                                                                                                   \

@@ -1,16 +1,18 @@
 // pt_launch.h -- k_pt_pass, the LDS plan of its launches and the launcher that picks the instantiation. Included by the two translation
 // units that instantiate the kernel: pt_kernels.hip (the AKR-F32 contract: the default, and the verifier) and pt_kernels_relaxed.hip
-// (the relaxed arithmetic tier, device/dmath.h AKR_ARITH_RELAXED; there everything below lives in namespace akr_rx).
+// (the relaxed arithmetic tier, device/dmath.h AKR_ARITH_RELAXED; there everything below lives in namespace akr_rx). pt_env_kernels.hip
+// includes it with AKR_PT_LAUNCH_KERNEL_ONLY for the kernel template alone: the instantiations of scenes with an environment light.
 #pragma once
 #include <algorithm>
 #include "device/pt_pass.h"
 
 namespace akr {
 
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, bool SIMPLE = false>
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, bool SIMPLE = false, bool ENV = false>
 __global__ __launch_bounds__(256, pt_pass_min_waves(BVH, FD, TEX)) void k_pt_pass(const PtParams p) {
-    pt_pass_body<BVH, FD, TEX, PMJ, STAGE, DEFER, SIMPLE ? AB_SIMPLE : 0u>(p);
+    pt_pass_body<BVH, FD, TEX, PMJ, STAGE, DEFER, SIMPLE ? AB_SIMPLE : 0u, false, ENV>(p);
 }
+#if !AKR_PT_LAUNCH_KERNEL_ONLY
 
 // Dynamic LDS of a k_pt_pass launch and where its blocks start: [traversal stacks][staged tables][triangle records (WALK 1)][node
 // tile][park columns][carry columns][blue-noise columns (pmj02bn)][graph values]. Shared by the precompiled kernels, the per-scene
@@ -54,6 +56,11 @@ hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t s
     if (p.sc.in2.on && !spec_fn) return launch_pt_pass_inst(p, stream);  // meshes + instances: pt_inst_kernels.hip (a per-scene kernel wraps the same body: below)
 #else
     if (p.sc.in2.on) return hipErrorInvalidValue;  // (the host never sends a kept scene to the relaxed tier: api_pt.cpp)
+#endif
+#if !AKR_ARITH_RELAXED
+    if (p.sc.env && !spec_fn) return launch_pt_pass_env(p, stream);  // an environment light: pt_env_kernels.hip (and pt_inst_kernels.hip for kept scenes)
+#else
+    if (p.sc.env) return hipErrorInvalidValue;  // (the host refuses the relaxed tier on such a scene: api_pt.cpp)
 #endif
     size_t lds;
     uint32_t blocks;
@@ -108,4 +115,5 @@ hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t s
 #undef AKR_LAUNCH
     return hipGetLastError();
 }
+#endif  // !AKR_PT_LAUNCH_KERNEL_ONLY
 }  // namespace akr

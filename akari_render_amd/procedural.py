@@ -114,13 +114,33 @@ def sponza_like(target_tris: int = 10_000_000, seed: int = 1234, width: int = 19
     return abi.SceneData([hall, light], insts, mats, cam)
 
 
+def sky_image(width: int = 512, height: int = 256, sun_dir=(0.35, 0.6, -0.5), sun_radius_deg: float = 5.0, sun_radiance: float = 1000.0,
+              zenith=(0.35, 0.55, 1.2), horizon=(1.1, 1.15, 1.25), ground=(0.12, 0.1, 0.08)) -> np.ndarray:
+    """An analytic equirectangular sky ((height, width, 3) float32, row 0 = v = 0 = straight down; the environment mapping of
+    include/akari_hip.h): a zenith-to-horizon gradient above the horizon, a dim ground below it and a sun disc of `sun_radius_deg`
+    around `sun_dir` (environment frame, y up) with radiance `sun_radiance`."""
+    u = (np.arange(width, dtype=np.float64) + 0.5) / width
+    v = (np.arange(height, dtype=np.float64) + 0.5) / height
+    phi, lat = (u[None, :] - 0.5) * 2 * np.pi, (v[:, None] - 0.5) * np.pi
+    e = np.stack([np.cos(lat) * np.cos(phi), np.sin(lat) * np.ones_like(phi), np.cos(lat) * np.sin(phi)], -1)
+    up = np.clip(e[..., 1], 0.0, 1.0)[..., None]
+    img = np.where(e[..., 1:2] >= 0.0, np.asarray(horizon) + (np.asarray(zenith) - np.asarray(horizon)) * np.sqrt(up), np.asarray(ground))
+    s = np.asarray(sun_dir, dtype=np.float64)
+    s = s / np.linalg.norm(s)
+    sun = (e @ s) >= np.cos(np.deg2rad(sun_radius_deg))
+    img[sun] = sun_radiance * np.array([1.0, 0.95, 0.85])
+    return img.astype(np.float32)
+
+
 def instanced_forest(n_instances: int = 1000, tris_per_mesh: int = 100_000, seed: int = 77, width: int = 1920, height: int = 1080,
-                     n_meshes: int = 2, n_lanterns: int = 4) -> abi.SceneData:
+                     n_meshes: int = 2, n_lanterns: int = 4, sky=None) -> abi.SceneData:
     """A field of `n_instances` copies of `n_meshes` "plants" (closed, lumpy, fluted blobs of ~`tris_per_mesh` triangles each, with
     smooth corner normals, uvs and two material slots) on a displaced ground, under a sky-light quad. Transforms: a rotation about
     a tilted axis, non-uniform scale, every fifth copy mirrored; the first `n_lanterns` copies carry an emissive material in slot 1.
     The kind of scene the reference's accel is built for (mesh.rs:259-348: one `push_mesh` per instance) and a flattening scene
-    compiler cannot hold: 1000 x 100 k = 100 M instance-triangles. A pure function of its arguments."""
+    compiler cannot hold: 1000 x 100 k = 100 M instance-triangles. A pure function of its arguments.
+    sky: None (the sky-light quad) or a dict of sky_image() arguments ({} for its defaults): the quad is left out and the scene is lit
+    by that image as its environment light instead (importance-sampled like any light)."""
     rng = np.random.default_rng(seed)
     meshes = []
     for mi in range(n_meshes):
@@ -153,8 +173,10 @@ def instanced_forest(n_instances: int = 1000, tris_per_mesh: int = 100_000, seed
     gp, gi = _grid(64, 64, lambda u, v: np.stack([extent * (u - 0.5) * 1.3, 0.15 * np.sin(9 * u) * np.cos(7 * v), extent * (v - 0.5) * 1.3], 1), flip=True)
     ground = abi.MeshData(vertices=gp, indices=gi)
     lq = np.array([[-1, 0, -1], [1, 0, -1], [1, 0, 1], [-1, 0, 1]], dtype=np.float32) * np.float32(0.35 * extent) + np.array([0, 0.55 * extent, 0], dtype=np.float32)
-    sky = abi.MeshData(vertices=lq, indices=np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32))
-    meshes += [ground, sky]
+    if sky is None:
+        meshes += [ground, abi.MeshData(vertices=lq, indices=np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32))]
+    else:
+        meshes += [ground]
     mats = [
         abi.MaterialData(base_color=(0.45, 0.4, 0.3), roughness=0.9, ior=1.45, specular_ior_level=0.5),     # 0 ground
         abi.MaterialData(base_color=(0.8, 0.8, 0.8), ior=1.0, specular_ior_level=0.0, emission_color=(6.0, 6.5, 8.0), emission_strength=1.0),  # 1 sky
@@ -165,7 +187,9 @@ def instanced_forest(n_instances: int = 1000, tris_per_mesh: int = 100_000, seed
         abi.MaterialData(base_color=(0.5, 0.5, 0.5), ior=1.0, specular_ior_level=0.0, emission_color=(9.0, 5.0, 2.0), emission_strength=1.0),  # 6 lantern
     ]
     eye = np.eye(4, dtype=np.float32)
-    insts = [abi.InstanceData(n_meshes, [0], eye.T.reshape(16).copy()), abi.InstanceData(n_meshes + 1, [1], eye.T.reshape(16).copy())]
+    insts = [abi.InstanceData(n_meshes, [0], eye.T.reshape(16).copy())]
+    if sky is None:
+        insts.append(abi.InstanceData(n_meshes + 1, [1], eye.T.reshape(16).copy()))
     for kk in range(n_instances):
         gx, gz = kk % side, kk // side
         ax = np.array([0.25 * (rng.random() - 0.5), 1.0, 0.25 * (rng.random() - 0.5)])
@@ -184,4 +208,5 @@ def instanced_forest(n_instances: int = 1000, tris_per_mesh: int = 100_000, seed
     ca = -0.45
     c2w = np.array([[1, 0, 0, 0], [0, np.cos(ca), -np.sin(ca), 0.32 * extent], [0, np.sin(ca), np.cos(ca), 0.62 * extent], [0, 0, 0, 1]], dtype=np.float32)
     cam = abi.CameraData(c2w=c2w.T.reshape(16).copy(), fov=0.9, width=width, height=height)
-    return abi.SceneData(meshes, insts, mats, cam)
+    env = None if sky is None else abi.EnvironmentData(image=sky_image(**sky), filter=abi.TEX_FILTER_LINEAR)
+    return abi.SceneData(meshes, insts, mats, cam, environment=env)

@@ -287,6 +287,26 @@ typedef struct {
 AKR_API int32_t akr_scene_get_info(const akr_scene *scene, akr_scene_info *info);
 /* Light `light` of LightAggregate (light/mod.rs:87-98): owning instance, total power, selection pdf. */
 AKR_API int32_t akr_scene_get_light(const akr_scene *scene, uint32_t light, uint32_t *instance, float *power, float *pdf);
+/* Environment light of a scene (pt integrator): an equirectangular image or a constant colour, times `strength`, turned by `rotation`.
+ * A world direction d looks up e = R^-1 d at u = 0.5 + atan2(e.z, e.x) / 2pi, v = 0.5 + atan2(e.y, hypot(e.x, e.z)) / pi (Blender's
+ * equirectangular World after the exporter's axis change); row 0 of the texels is v = 0, u wraps, v clamps. Texels are linear RGB in the
+ * scene's RGB colour space. It is the last entry of the light list (akr_scene_get_light: instance 0xFFFFFFFF) and is importance-sampled
+ * by next-event estimation. gpt, mcmc_opt and the relaxed arithmetic tier refuse a scene with one (AKR_ERR_UNSUPPORTED). */
+typedef struct {
+    uint32_t width, height;   /* texels; width = height = 0: the constant `color` */
+    uint32_t filter;          /* akr_tex_filter: nearest or bilinear lookup */
+    uint32_t _pad;
+    const float *texels;      /* RGBA32F, 4 * width * height floats, row 0 = v = 0 (owned by the caller / by the scene in a get) */
+    float color[3];           /* the constant colour (width = 0) */
+    float strength;           /* 0, or an all-black image: no environment */
+    float rotation[9];        /* R, row-major: environment -> world; must be a rotation (tolerance 1e-4) */
+    uint32_t _pad2;
+} akr_environment_desc;
+/* Sets (or, desc = NULL, removes) the scene's environment. Refused while a session holds the scene. */
+AKR_API int32_t akr_scene_set_environment(akr_scene *scene, const akr_environment_desc *desc);
+/* The environment as decoded (texels owned by the scene); width = height = 0 and strength = 0 when there is none. A constant
+ * colour comes back as width = height = 0 with its colour. */
+AKR_API int32_t akr_scene_get_environment(const akr_scene *scene, akr_environment_desc *out);
 /* The folded ggx_dielectric_s table in use (4096 floats), for comparison with a golden copy. */
 AKR_API int32_t akr_scene_get_ggx_table(const akr_scene *scene, float *dst4096);
 /* Host-side copy of the flattened description akr_scene_load produced (for loader tests):
@@ -328,7 +348,13 @@ typedef enum {
                                     bit of a record's last word says that some instance gives the triangle its even neighbour's plane row) */
     AKR_ARRAY_MESH_POS = 19,     /* u32[mesh triangles] mesh order -> position in MESH_TRIS */
     AKR_ARRAY_MESH_META = 20,    /* u32[mesh triangles] material slot | flags << 30 */
-    AKR_ARRAY_MESH_NORMALS = 21  /* f32[24 * mesh triangles] corner normals / tangents (empty if no mesh has any) */
+    AKR_ARRAY_MESH_NORMALS = 21, /* f32[24 * mesh triangles] corner normals / tangents (empty if no mesh has any) */
+    /* the environment's sampling tables (empty without one): alias tables over its rows and, per row, over its columns */
+    AKR_ARRAY_ENV_MARGINAL_ENTRIES = 22,    /* {u32 j, f32 t}[env height] */
+    AKR_ARRAY_ENV_MARGINAL_PDF = 23,        /* f32[env height] */
+    AKR_ARRAY_ENV_CONDITIONAL_ENTRIES = 24, /* {u32 j, f32 t}[env height * env width], row by row */
+    AKR_ARRAY_ENV_CONDITIONAL_PDF = 25,     /* f32[env height * env width] */
+    AKR_ARRAY_ENV_TEXELS = 26               /* f32[4 * env width * env height]: what the kernels look up (strength applied) */
 } akr_array_id;
 AKR_API int32_t akr_scene_get_array(const akr_scene *scene, int32_t which, const void **ptr, uint64_t *bytes);
 
@@ -613,7 +639,7 @@ AKR_API const char *akr_version(void);
 typedef enum {
     AKR_STRUCT_MESH_DESC = 1, AKR_STRUCT_INSTANCE_DESC, AKR_STRUCT_MATERIAL_DESC, AKR_STRUCT_CAMERA_DESC, AKR_STRUCT_SCENE_DESC,
     AKR_STRUCT_PT_CONFIG, AKR_STRUCT_PT_STATS, AKR_STRUCT_SCENE_INFO, AKR_STRUCT_KERNEL_INFO, AKR_STRUCT_AOV_CONFIG, AKR_STRUCT_GPT_CONFIG,
-    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL
+    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;

@@ -65,6 +65,13 @@ AKR_TEST_API int32_t akr_probe_intersect(akr_context *ctx, akr_scene *scene, uin
 AKR_TEST_API int32_t akr_probe_surface_interaction(akr_context *ctx, akr_scene *scene, uint32_t n, const uint32_t *inst_prim,
                                               const float *bary, float *out);
 
+/* The environment light's sampler on the device (csrc/device/denv.h), for a scene with one:
+ *   akr_probe_env_sample  u2 (2 floats / item) -> wi.xyz, pdf, valid (5 floats / item): env_sample
+ *   akr_probe_env_pdf     directions (3 floats / item) -> pdf, radiance.rgb (4 floats / item): env_pdf, env_eval */
+AKR_TEST_API int32_t akr_probe_env_sample(akr_context *ctx, akr_scene *scene, uint32_t n, const float *u2, float *out5);
+
+AKR_TEST_API int32_t akr_probe_env_pdf(akr_context *ctx, akr_scene *scene, uint32_t n, const float *dirs3, float *out4);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);
