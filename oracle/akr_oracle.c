@@ -11,6 +11,7 @@
  *   microfacet.rs (see or_bsdf.h); further down, each with its own citation block: svm/eval.rs + image sampling (or_tex.h),
  *   akari_integrator/src/aov.rs, gpt.rs (+ the shift-mapping branches of pt.rs:329-900), mcmc_opt.rs (+ mcmc.rs,
  *   sampler/mcmc.rs, util/distribution.rs:92-115), sampler/mod.rs:329-700 (pmj02bn; the two tables are handed in by the tests).
+ *   The environment light has no reference counterpart (hit_envmap returns zero): or_env.h restates DESIGN.md 4.8.
  *
  * Parity status: the reference cannot be built or run here (no Rust toolchain; LuisaCompute is an
  * un-vendored path dependency) and its tests hold no numeric fixtures for this path, so
@@ -29,6 +30,7 @@
 #include "or_bsdf.h"
 #include "or_tex.h"
 #include "or_geom.h"
+#include "or_env.h"
 #include "or_math.h"
 #include "or_rng.h"
 #include <pthread.h>
@@ -79,6 +81,7 @@ typedef struct {
     struct or_bvh *bvh;          /* optional, checker-side only (or_accel.h); NULL = the exhaustive loop below */
     uint32_t color;              /* ColorPipeline of the render in progress (OR_COLOR_*), set by the render entry points; 0 during
                                   * scene creation: the light tables come from the sRGB pipeline (load.rs:316-319) */
+    or_env *env;                 /* the environment light (or_env.h) or NULL; it is light n_lights - 1 */
 } or_scene;
 
 typedef struct { v3 o, d; float t_min, t_max; uint32_t ex0_inst, ex0_prim, ex1_inst, ex1_prim; } or_ray;
@@ -417,6 +420,20 @@ static or_light_sample or_sample_direct(const or_scene *sc, v3 pn_p, v3 pn_n, fl
     if (sc->n_lights == 0) return s;
     float light_choice_pdf, u_sel2, pdf_prim, u_unused;
     uint32_t light_idx = or_alias_sample_and_remap(&sc->light_dist, u_select, &light_choice_pdf, &u_sel2);
+    if (sc->env && light_idx == sc->n_lights - 1) { /* the environment (4.8 NEE): u_sample picks the direction; unbounded shadow ray */
+        v3 wi;
+        float pdf;
+        int ok = or_env_sample(sc->env, u_sample, &wi, &pdf);
+        s.li = or_env_eval(sc->env, sc->color, wi);
+        s.shadow_ray.o = or_offset_ray_origin(pn_p, or_face_forward(pn_n, wi));
+        s.shadow_ray.d = wi; s.shadow_ray.t_min = 0.0f; s.shadow_ray.t_max = 1e20f;
+        s.shadow_ray.ex0_inst = OR_INVALID; s.shadow_ray.ex0_prim = OR_INVALID;
+        s.shadow_ray.ex1_inst = OR_INVALID; s.shadow_ray.ex1_prim = OR_INVALID;
+        s.wi = wi;
+        s.valid = ok;
+        s.pdf = pdf * light_choice_pdf;
+        return s;
+    }
     uint32_t inst_id = sc->light_inst[light_idx];
     uint32_t prim_id = or_alias_sample_and_remap(&sc->instances[inst_id].area_sampler, u_sel2, &pdf_prim, &u_unused);
     v2 bary = or_uniform_sample_triangle(u_sample);
@@ -617,6 +634,7 @@ OR_EXPORT void or_scene_destroy(or_scene *sc) {
     free(sc->meshes); free(sc->instances); free(sc->materials);
     free(sc->woop); free(sc->tri_inst); free(sc->tri_prim);
     free(sc->light_inst); free(sc->light_power);
+    or_env_free(sc->env);
     or_scene_free_bvh(sc);
     free(sc);
 }
@@ -768,7 +786,16 @@ static v3 or_radiance(const or_scene *sc, const or_pt_config *cfg, or_ray ray, o
     for (;;) {
         uint32_t h_inst = 0, h_prim = 0; v2 h_bary = V2(0, 0);
         st->n_closest++;
-        if (!or_trace(sc, &ray, 0, &h_inst, &h_prim, &h_bary, st)) break; /* pt.rs:381-396: envmap adds 0 */
+        if (!or_trace(sc, &ray, 0, &h_inst, &h_prim, &h_bary, st)) { /* pt.rs:381-396 */
+            if (sc->env && (!indirect_only || depth > 1)) {
+                /* the environment (4.8 Miss), weighted as an emitter; `base` is not captured: directly visible texels are clamped */
+                v3 le = or_env_eval(sc->env, sc->color, ray.d);
+                float w = 1.0f;
+                if (depth != 0 && use_nee) w = or_mis_weight(prev_bsdf_pdf, sc->light_dist.pdf[sc->n_lights - 1] * or_env_pdf(sc->env, ray.d));
+                ADD_RADIANCE(v3scale(le, w));
+            }
+            break;
+        }
         or_si si = or_surface_interaction(sc, h_inst, h_prim, h_bary);
         v3 wo = v3neg(ray.d);
         { /* handle_surface_light, pt.rs:230-258 */
@@ -1362,6 +1389,7 @@ static int or_gpt_sources(int32_t cp, int32_t o, uint32_t r, uint32_t out[3]) {
  * otherwise written with the reconstructed image, splat_scale = 1). aux (optional, reconstruction != none):
  * [primal 3N | Gx 3(W+1)(H+1) | Gy 3(W+1)(H+1)] = the accumulated sums of gpt.rs:441-455 (divide by spp for the mean). */
 OR_EXPORT int or_gpt_render(const or_scene *sc, const or_gpt_config *g, float *film, float *aux, uint32_t n_threads) {
+    if (sc->env) return -5; /* no environment in gpt (refused) */
     ((or_scene *)sc)->color = g->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H, NG = (uint64_t)(W + 1) * (H + 1);
@@ -1594,6 +1622,7 @@ static or_mcmc_eval or_mcmc_evaluate(const or_scene *sc, const or_mcmc_config *c
 /* out: film (7N floats; the direct pass fills rgb + weight, the chains the splat channels), result[4] = {b (normalisation),
  * acceptance rate, splat scale as f32 bits, contribution as f32 bits} (doubles / reinterpreted), chain_states (10 u32 each). */
 OR_EXPORT int or_mcmc_render(const or_scene *sc, const or_mcmc_config *c, float *film, double *result, uint32_t *chain_states, uint32_t n_threads) {
+    if (sc->env) return -5; /* no environment in mcmc_opt (refused) */
     ((or_scene *)sc)->color = c->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H;
@@ -1883,6 +1912,89 @@ OR_EXPORT void or_bsdf_probe_many(const or_material_desc *m, const float *table,
 OR_EXPORT void or_bsdf_eval_many(const or_material_desc *m, const float *table, const float *wo_, uint32_t n, const float *wi, float *out) {
     for (uint32_t i = 0; i < n; i++) or_bsdf_probe(m, table, 0, wo_, wi + 3 * i, out + 4 * i);
 }
+/* ---------------------------------- the environment light (or_env.h) -------------- */
+/* Sets (desc = NULL: removes) the scene's environment: the last entry of the light table, weight 4 pi R^2 Lbar. Returns 0, or -1 for a
+ * description akr_scene_set_environment refuses (the scene is left as it was). */
+OR_EXPORT int or_scene_set_environment(or_scene *sc, const or_environment_desc *d) {
+    or_env *e = 0;
+    if (d) {
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint32_t i = 0; i < sc->n_instances; i++) { /* world bounds over every triangle corner */
+            const or_instance *in = &sc->instances[i];
+            const or_mesh_desc *g = &sc->meshes[in->mesh].d;
+            for (uint32_t k = 0; k < 3 * g->n_triangles; k++) {
+                v3 p = xf_point(&in->xf, ld3(g->vertices, g->indices[k]));
+                lo[0] = or_min(lo[0], p.x); lo[1] = or_min(lo[1], p.y); lo[2] = or_min(lo[2], p.z);
+                hi[0] = or_max(hi[0], p.x); hi[1] = or_max(hi[1], p.y); hi[2] = or_max(hi[2], p.z);
+            }
+        }
+        if (or_env_create(d, lo, hi, &e) != 0) return -1;
+    }
+    if (sc->n_lights > 0) or_alias_free(&sc->light_dist);
+    if (sc->env) { sc->n_lights--; or_env_free(sc->env); sc->env = 0; }
+    if (e) {
+        sc->env = e;
+        sc->light_inst[sc->n_lights] = OR_INVALID;
+        sc->light_power[sc->n_lights] = e->power;
+        sc->n_lights++;
+    }
+    if (sc->n_lights > 0) or_alias_build(&sc->light_dist, sc->light_power, sc->n_lights);
+    return 0;
+}
+/* The environment's size and tables, for comparison with the library's (akr_scene_get_array): returns 0 without one. dims = w, h, filter.
+ * Any output pointer may be NULL; entries as {j, t} pairs, row by row for the conditional tables. */
+OR_EXPORT int or_scene_env_tables(const or_scene *sc, uint32_t *dims, float *texels, or_alias_entry *marginal, float *marginal_pdf,
+                                  or_alias_entry *conditional, float *conditional_pdf) {
+    const or_env *e = sc->env;
+    if (!e) return 0;
+    if (dims) { dims[0] = e->w; dims[1] = e->h; dims[2] = e->filter; }
+    if (texels) memcpy(texels, e->texels, 16 * (size_t)e->w * e->h);
+    if (marginal) memcpy(marginal, e->marginal.table, sizeof(or_alias_entry) * e->h);
+    if (marginal_pdf) memcpy(marginal_pdf, e->marginal.pdf, 4 * (size_t)e->h);
+    for (uint32_t y = 0; y < e->h; y++) {
+        if (conditional) memcpy(conditional + (size_t)y * e->w, e->conditional[y].table, sizeof(or_alias_entry) * e->w);
+        if (conditional_pdf) memcpy(conditional_pdf + (size_t)y * e->w, e->conditional[y].pdf, 4 * (size_t)e->w);
+    }
+    return 1;
+}
+/* known-answer entry points in the style of or_tex_sample_many (the probes akr_probe_env_sample / akr_probe_env_pdf restate):
+ * u2 (2 / item) -> wi.xyz, pdf, valid (5 / item); directions (3 / item) -> pdf, radiance.rgb under the scene's pipeline (4 / item) */
+OR_EXPORT int or_env_sample_many(const or_scene *sc, uint32_t n, const float *u2, float *out5) {
+    if (!sc->env) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        v3 wi; float pdf;
+        int ok = or_env_sample(sc->env, V2(u2[2 * i], u2[2 * i + 1]), &wi, &pdf);
+        float r[5] = {wi.x, wi.y, wi.z, pdf, ok ? 1.0f : 0.0f};
+        memcpy(out5 + 5 * (size_t)i, r, sizeof r);
+    }
+    return 0;
+}
+OR_EXPORT int or_env_pdf_many(const or_scene *sc, uint32_t n, const float *dirs, float *out4) {
+    if (!sc->env) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        v3 d = V3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+        v3 c = or_env_eval(sc->env, sc->color, d);
+        float r[4] = {or_env_pdf(sc->env, d), c.x, c.y, c.z};
+        memcpy(out4 + 4 * (size_t)i, r, sizeof r);
+    }
+    return 0;
+}
+/* the environment-frame (u, v) and sin(theta) of world directions (3 / item -> 3 / item) */
+OR_EXPORT int or_env_uv_many(const or_scene *sc, uint32_t n, const float *dirs, float *out3) {
+    if (!sc->env) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        float st;
+        v2 uv = or_env_uv(or_env_local(sc->env, V3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2])), &st);
+        out3[3 * i] = uv.x; out3[3 * i + 1] = uv.y; out3[3 * i + 2] = st;
+    }
+    return 0;
+}
+OR_EXPORT void or_kat_atan2_many(uint32_t n, const float *y, const float *x, float *out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = or_atan2f(y[i], x[i]);
+}
+OR_EXPORT float or_kat_atan2(float y, float x) { return or_atan2f(y, x); }
+OR_EXPORT uint32_t or_sizeof_environment_desc(void) { return (uint32_t)sizeof(or_environment_desc); }
+
 OR_EXPORT uint32_t or_sizeof_material(void) { return (uint32_t)sizeof(or_material_desc); }
 OR_EXPORT uint32_t or_sizeof_config(void) { return (uint32_t)sizeof(or_pt_config); }
 OR_EXPORT uint32_t or_sizeof_scene_desc(void) { return (uint32_t)sizeof(or_scene_desc); }

@@ -79,6 +79,18 @@ typedef struct {
     const or_material_graph *material_graphs; /* n_materials entries or NULL */
 } or_scene_desc;
 
+/* The environment light: layout-identical to akr_environment_desc. width = height = 0: the constant `color`. */
+typedef struct {
+    uint32_t width, height;
+    uint32_t filter;         /* OR_TEX_NEAREST / OR_TEX_LINEAR */
+    uint32_t _pad;
+    const float *texels;     /* RGBA32F, row 0 = v = 0 */
+    float color[3];
+    float strength;
+    float rotation[9];       /* environment -> world, row-major */
+    uint32_t _pad2;
+} or_environment_desc;
+
 enum { OR_FILTER_BOX = 0, OR_FILTER_GAUSSIAN = 1 };
 enum { OR_SAMPLER_INDEPENDENT = 0 };
 typedef struct {

@@ -110,8 +110,19 @@ def lib() -> C.CDLL:
     L.or_set_pmj_tables.argtypes = [up, C.POINTER(C.c_uint16)]
     L.or_aov_render.restype = i32
     L.or_aov_render.argtypes = [vp, C.POINTER(abi.AovConfig), fp, u32, u64p]
-    for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config"):
+    L.or_scene_set_environment.restype = i32
+    L.or_scene_set_environment.argtypes = [vp, C.POINTER(abi.EnvironmentDesc)]
+    L.or_scene_env_tables.restype = i32
+    L.or_scene_env_tables.argtypes = [vp, up, fp, vp, fp, vp, fp]
+    for n in ("or_env_sample_many", "or_env_pdf_many", "or_env_uv_many"):
+        getattr(L, n).restype = i32
+        getattr(L, n).argtypes = [vp, u32, fp, fp]
+    L.or_kat_atan2.restype = f32
+    L.or_kat_atan2.argtypes = [f32, f32]
+    L.or_kat_atan2_many.argtypes = [u32, fp, fp, fp]
+    for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config", "or_sizeof_environment_desc"):
         getattr(L, n).restype = u32
+    assert L.or_sizeof_environment_desc() == C.sizeof(abi.EnvironmentDesc)
     assert L.or_sizeof_material() == C.sizeof(abi.MaterialDesc)
     assert L.or_sizeof_config() == C.sizeof(abi.PtConfig)
     assert L.or_sizeof_scene_desc() == C.sizeof(abi.SceneDesc)
@@ -139,6 +150,56 @@ class OracleScene:
             lib().or_set_share_plane_rows(1)
         self.width, self.height = scene.camera.width, scene.camera.height
         self.n_bvh_nodes = lib().or_scene_build_bvh(self.h) if bvh else 0
+        if getattr(scene, "environment", None) is not None:
+            self.set_environment(scene.environment)
+
+    def set_environment(self, env: abi.EnvironmentData | None) -> None:
+        """or_scene_set_environment; None removes it. A description the library would refuse raises ValueError."""
+        if env is None:
+            rc = lib().or_scene_set_environment(self.h, None)
+        else:
+            d, keep = env.to_desc()
+            rc = lib().or_scene_set_environment(self.h, C.byref(d))
+            del keep
+        if rc != 0:
+            raise ValueError("or_scene_set_environment refused the environment")
+
+    def env_tables(self):
+        """The environment's tables as the oracle built them, or None: dict of texels (H, W, 4), marginal / conditional alias entries
+        ({j, t} records) and pdfs, filter."""
+        dims = np.zeros(3, dtype=np.uint32)
+        up = C.POINTER(C.c_uint32)
+        if not lib().or_scene_env_tables(self.h, dims.ctypes.data_as(up), None, None, None, None, None):
+            return None
+        w, h = int(dims[0]), int(dims[1])
+        alias = np.dtype([("j", np.uint32), ("t", np.float32)])
+        tex = np.zeros((h, w, 4), np.float32)
+        me, mp = np.zeros(h, alias), np.zeros(h, np.float32)
+        ce, cp = np.zeros(h * w, alias), np.zeros(h * w, np.float32)
+        lib().or_scene_env_tables(self.h, dims.ctypes.data_as(up), _fp(tex), me.ctypes.data, _fp(mp), ce.ctypes.data, _fp(cp))
+        return {"texels": tex, "marginal_entries": me, "marginal_pdf": mp, "conditional_entries": ce, "conditional_pdf": cp, "filter": int(dims[2])}
+
+    def env_sample_many(self, u2) -> np.ndarray:
+        """or_env_sample_many: u (n, 2) -> (n, 5) wi.xyz, pdf, valid."""
+        u = np.ascontiguousarray(u2, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((u.shape[0], 5), np.float32)
+        assert lib().or_env_sample_many(self.h, u.shape[0], _fp(u), _fp(out)) == 0, "the scene has no environment"
+        return out
+
+    def env_pdf_many(self, dirs, color: int = 0) -> np.ndarray:
+        """or_env_pdf_many: directions (n, 3) -> (n, 4) pdf, radiance.rgb (under the ColorPipeline bits `color`)."""
+        lib().or_scene_set_color(self.h, color)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((d.shape[0], 4), np.float32)
+        assert lib().or_env_pdf_many(self.h, d.shape[0], _fp(d), _fp(out)) == 0, "the scene has no environment"
+        return out
+
+    def env_uv_many(self, dirs) -> np.ndarray:
+        """or_env_uv_many: world directions (n, 3) -> (n, 3) u, v, sin(theta) of the environment frame."""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((d.shape[0], 3), np.float32)
+        assert lib().or_env_uv_many(self.h, d.shape[0], _fp(d), _fp(out)) == 0, "the scene has no environment"
+        return out
 
     def intersect_many(self, rays: np.ndarray, any_hit: bool = False, n_threads: int = 0):
         """rays (n, 8) = o, d, tmin, tmax -> (hit/inst/prim u32 (n, 3), t/u/v f32 (n, 3)); through or_trace."""
@@ -255,6 +316,15 @@ class OracleScene:
         rc = lib().or_pt_render(self.h, C.byref(cfg), _fp(film), sp, n_threads, C.byref(st))
         assert rc == 0
         return film, {k: getattr(st, k) for k, _ in OrStats._fields_}
+
+
+def atan2_many(y, x) -> np.ndarray:
+    """or_kat_atan2 (the f32 atan2 of DESIGN.md 4.8) elementwise."""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    out = np.zeros(y.shape[0], np.float32)
+    lib().or_kat_atan2_many(y.shape[0], _fp(y), _fp(x), _fp(out))
+    return out
 
 
 def resolve(film: np.ndarray, width: int, height: int, splat_scale: float = 1.0) -> np.ndarray:

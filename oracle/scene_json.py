@@ -54,7 +54,14 @@ def _axis_angle(axis, angle) -> np.ndarray:
 
 
 def _matmul(a, b):
-    return (a.astype(f32) @ b.astype(f32)).astype(f32)
+    """glam Mat4 * Mat4 in f32, each entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3 un-fused (numpy's f32 matmul leaves the order and
+    the fusing to BLAS: a turn about two or three axes then came out an ulp away from the library's reader)."""
+    a, b = a.astype(f32), b.astype(f32)
+    r = np.zeros((4, 4), dtype=f32)
+    for i in range(4):
+        for j in range(4):
+            r[i, j] = ((a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j]) + a[i, 3] * b[3, j]
+    return r
 
 
 def load_transform(t: dict, is_camera: bool) -> np.ndarray:
@@ -649,7 +656,51 @@ def load_scene(path: str, width: int = 0, height: int = 0) -> SceneData:
         width=int(width or cd["sensor_width"]),
         height=int(height or cd["sensor_height"]),
     )
-    return SceneData(meshes, instances, materials, camera, None, inst_ids, mat_ids, images)
+    env = _load_environment(scene["environment"], bufs) if scene.get("environment") is not None else None
+    return SceneData(meshes, instances, materials, camera, None, inst_ids, mat_ids, images, environment=env)
+
+
+def _srgb_to_linear(v: np.ndarray) -> np.ndarray:
+    """s <= 0.04045 ? s / 12.92 : pow((s + 0.055) / 1.055, 2.4), f32, with the oracle's pow (the AKR-F32 one)."""
+    from oracle import pyoracle
+
+    pw = pyoracle.lib().or_kat_pow
+    flat = np.asarray(v, dtype=f32).reshape(-1)
+    out = np.empty_like(flat)
+    memo = {}
+    for i, s in enumerate(flat):
+        k = s.tobytes()
+        if k not in memo:
+            memo[k] = s / f32(12.92) if s <= f32(0.04045) else f32(pw(float((s + f32(0.055)) / f32(1.055)), 2.4))
+        out[i] = memo[k]
+    return out.reshape(np.shape(v))
+
+
+def _load_environment(ej: dict, bufs: "_Buffers") -> abi.EnvironmentData:
+    """The top-level "environment" (DESIGN.md 4.8): strength, exactly one of color / image (the Image schema of a tex_image node, read
+    by this module's own decoders), and an instance-style transform of which the rotation is used (the oracle refuses anything else)."""
+    strength = float(f32(ej.get("strength", 1.0)))
+    has_color, has_image = ej.get("color") is not None, ej.get("image") is not None
+    if has_color == has_image:
+        raise ValueError('environment: exactly one of "color" and "image" must be given')
+    rot = np.eye(3, dtype=f32)
+    if ej.get("transform") is not None:
+        rot = np.ascontiguousarray(load_transform(ej["transform"], False)[:3, :3], dtype=f32)
+    if has_color:
+        return abi.EnvironmentData(color=tuple(float(f32(c)) for c in ej["color"][:3]), strength=strength, rotation=rot)
+    im = ej["image"]
+    cs = im.get("colorspace", "none")
+    if cs not in ("srgb", "none"):
+        raise NotImplementedError(f"image colour space '{cs}'")
+    images: list = []
+    data = images[_Graph({}, bufs, images, {}).image(im)]  # not a texture of the scene: a list of its own
+    tex = data.texels
+    texf = tex.astype(f32) / f32(255.0) if tex.dtype == np.uint8 else np.array(tex, dtype=f32)  # unorm8 = byte / 255
+    if texf.shape[0] == 0 or texf.shape[1] == 0:
+        raise ValueError("environment: zero-size image")
+    if cs == "srgb":  # as an image node converts (svm/texture/mod.rs:44-51)
+        texf[:, :, :3] = _srgb_to_linear(texf[:, :, :3])
+    return abi.EnvironmentData(image=texf, strength=strength, rotation=rot, filter=data.filter)
 
 
 def load_method(path_or_text: str) -> dict:

@@ -1,7 +1,10 @@
 """Randomised parity soak: random small scenes (random triangle soups + a few quads, random materials drawn from edge values,
 random emitters, cameras, samplers, configs, colour pipelines; a third of them with random images and random shader-graph DAGs
 feeding random inputs), the HIP path tracer against the oracle, film accumulators and
-counters bit for bit. Prints the seeds that differ. python tools/soak.py [n_cases] [first_seed] [tex] [big] [aov | gpt | mcmc | shard | wavefront [carry] | inst]   (needs a GPU; uses oracle/)"""
+counters bit for bit. Prints the seeds that differ. "env": every scene also gets a random environment light (constant colour or an
+image of 1-40 x 1-20 texels with occasional black rows and HDR spikes, a random rotation, strength and filter); it combines with the
+schedules and with aov / shard.
+python tools/soak.py [n_cases] [first_seed] [tex] [big] [env] [aov | gpt | mcmc | shard | wavefront [carry] | inst]   (needs a GPU; uses oracle/)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -166,6 +169,27 @@ def rand_scene(seed, textures=None, big=False, inst=False):
     return sd, cfg
 
 
+def rand_environment(rng):
+    """a random environment light"""
+    ax = rng.normal(size=3)
+    ax /= np.linalg.norm(ax)
+    a = rng.uniform(0, 6.28) if rng.random() < 0.8 else 0.0
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    rot = (np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)).astype(np.float32)
+    strength = float(rng.choice([0.25, 1.0, 1.0, 2.5, 8.0]))
+    if rng.random() < 0.25:
+        return abi.EnvironmentData(color=tuple(float(x) for x in rng.random(3)), strength=strength, rotation=rot)
+    h, w = int(rng.integers(1, 21)), int(rng.integers(1, 41))
+    img = (rng.random((h, w, 4)) * rng.choice([0.2, 1.0, 3.0])).astype(np.float32)
+    img[:, :, 3] = 1.0
+    if rng.random() < 0.4:  # black rows (the marginal never picks them)
+        img[rng.random(h) < 0.3, :, :3] = 0.0
+    if rng.random() < 0.4:  # HDR spikes, some above the clamp of 1000
+        for _ in range(int(rng.integers(1, 4))):
+            img[int(rng.integers(0, h)), int(rng.integers(0, w)), :3] = float(rng.choice([50.0, 1500.0, 2e4]))
+    return abi.EnvironmentData(image=img, strength=strength, rotation=rot, filter=int(rng.integers(0, 2)))
+
+
 def run_pt(ctx, scene, sd, cfg, rng):
     w, h = sd.camera.width, sd.camera.height
     film = capi.Film(ctx, w, h)
@@ -268,9 +292,11 @@ def main():
     ctx = capi.Context(0)
     pyoracle.set_pmj_tables(*capi.host_pmj02bn_tables())
     bad, refused, t0 = [], 0, time.time()
-    kinds = {"exhaustive": 0, "bvh": 0, "kept": 0, "textured": 0}
+    kinds = {"exhaustive": 0, "bvh": 0, "kept": 0, "textured": 0, "env": 0}
     for seed in range(first, first + n):
         sd, cfg = rand_scene(seed, textures, "big" in opts, "inst" in opts)
+        if "env" in opts:
+            sd.environment = rand_environment(np.random.default_rng(seed + 11))
         if runner in (run_gpt, run_mcmc):
             cfg.sampler_type = abi.SAMPLER_INDEPENDENT  # gpt: independent sampler only
         sd.ggx_table = table
@@ -283,6 +309,7 @@ def main():
             continue
         kinds[("exhaustive", "bvh", "kept")[scene.info().uses_bvh]] += 1
         kinds["textured"] += int(bool(sd.images))
+        kinds["env"] += int(scene.environment() is not None)
         try:
             nd, same_counts, info = runner(ctx, scene, sd, cfg, np.random.default_rng(seed + 7))
         except capi.AkariError as e:
