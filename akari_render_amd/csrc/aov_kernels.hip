@@ -2,6 +2,7 @@
 // the value of one closure / geometry attribute at the first hit, accumulated into the film like a radiance sample. Shares
 // the camera, sampler, intersectors, hit reconstruction and material records of the path tracer (device/*.h).
 #include "device/dpath.h"
+#include "launch.h"
 
 namespace akr {
 
@@ -93,21 +94,9 @@ hipError_t launch_aov(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t re
     const bool bvh = p.sc.bvh_nodes != nullptr, tex = p.sc.tex.nodes != nullptr;
     size_t lds;
     const PtParams q = with_tex_slots(p, bvh ? p.sc.bvh_stack_depth * 256 * 4 : p.stage_total, lds);
-#define AKR_AOV(B, T)                                                                                                  \
-    {                                                                                                                \
-        if (p.sampler) hipLaunchKernelGGL((k_aov<B, T, true>), dim3(blocks), dim3(256), lds, stream, q, spp, aov, remap); \
-        else hipLaunchKernelGGL((k_aov<B, T, false>), dim3(blocks), dim3(256), lds, stream, q, spp, aov, remap);      \
-    }
-#define AKR_AOV_INST(T)                                                                                                          \
-    {                                                                                                                            \
-        if (p.sampler) hipLaunchKernelGGL((k_aov<true, T, true, true>), dim3(blocks), dim3(256), lds, stream, q, spp, aov, remap); \
-        else hipLaunchKernelGGL((k_aov<true, T, false, true>), dim3(blocks), dim3(256), lds, stream, q, spp, aov, remap);      \
-    }
-    if (p.sc.in2.on) { if (tex) AKR_AOV_INST(true) else AKR_AOV_INST(false) }  // meshes + instances (aov.rs:57-173 over the reference's two-level accel)
-    else if (bvh) { if (tex) AKR_AOV(true, true) else AKR_AOV(true, false) }
-    else { if (tex) AKR_AOV(false, true) else AKR_AOV(false, false) }
-#undef AKR_AOV
-#undef AKR_AOV_INST
+    // meshes + instances (aov.rs:57-173 over the reference's two-level accel): the BVH kernel with INST, whatever bvh_nodes says
+    dispatch_bools([&](auto B, auto T, auto P, auto I) { launch_kernel(k_aov<B() || I(), T(), P(), I()>, blocks, lds, stream, q, spp, aov, remap); },
+                   bvh, tex, p.sampler != 0, p.sc.in2.on != 0);
     return hipGetLastError();
 }
 

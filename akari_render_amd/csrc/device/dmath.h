@@ -24,8 +24,8 @@ typedef unsigned long size_t;
 #define AKR_D __device__ __forceinline__
 
 // The arithmetic tier of a translation unit. 0 (everything but pt_kernels_relaxed.hip): the AKR-F32 contract above, bit for bit the
-// oracle's. 1 = RELAXED (option `arith`): the same algorithm to the tolerance north_star states (relRMSE < 1e-3
-// against the oracle, tests/test_gpu_relaxed.py) instead of to the bit -- v_rcp_f32 / v_sqrt_f32 / v_rsq_f32 (1 ulp) for the IEEE
+// oracle's. 1 = RELAXED (option `arith`): the same algorithm, unbiased but not the oracle's to the bit (DESIGN.md 4.7 says how
+// close at fixed seed; tests/test_gpu_relaxed.py) -- v_rcp_f32 / v_sqrt_f32 / v_rsq_f32 (1 ulp) for the IEEE
 // division and square root (11 and 16 instructions each under the contract), the hardware's sin / cos / log2 / exp2, and the
 // compiler's contraction of a * b + c (that translation unit is built with -ffp-contract=fast, without correctly rounded
 // divide / sqrt and with denormals flushed). Device code only: anything a relaxed translation unit compiles for the host keeps the contract.

@@ -9,6 +9,7 @@
 // whatever the hardware does. Here k_gpt_sample writes what a pixel splats onto itself (`own`) and what it splats for each
 // neighbour (`shifted[i]`) to per-pixel slots and k_gpt_update gathers them in a fixed order -- no atomics, reproducible.
 #include "device/dradiance.h"
+#include "launch.h"
 
 namespace akr {
 
@@ -246,16 +247,8 @@ hipError_t launch_gpt_sample(const PtParams& p, const GptParams& g, hipStream_t 
     const bool bvh = p.sc.bvh_nodes != nullptr, tex = p.sc.tex.nodes != nullptr;
     size_t lds;
     const PtParams q = with_tex_slots(p, bvh ? p.sc.bvh_stack_depth * 256 * 4 : p.stage_total, lds);
-    if (p.sc.in2.on) {  // meshes + instances (gpt.rs:381-640 traces through the same two-level accel the path tracer does)
-        if (tex) hipLaunchKernelGGL((k_gpt_sample<true, true, true>), dim3(blocks), dim3(256), lds, stream, q, g);
-        else hipLaunchKernelGGL((k_gpt_sample<true, false, true>), dim3(blocks), dim3(256), lds, stream, q, g);
-    } else if (bvh) {
-        if (tex) hipLaunchKernelGGL((k_gpt_sample<true, true>), dim3(blocks), dim3(256), lds, stream, q, g);
-        else hipLaunchKernelGGL((k_gpt_sample<true, false>), dim3(blocks), dim3(256), lds, stream, q, g);
-    } else {
-        if (tex) hipLaunchKernelGGL((k_gpt_sample<false, true>), dim3(blocks), dim3(256), lds, stream, q, g);
-        else hipLaunchKernelGGL((k_gpt_sample<false, false>), dim3(blocks), dim3(256), lds, stream, q, g);
-    }
+    // meshes + instances (gpt.rs:381-640 traces through the same two-level accel the path tracer does): the BVH kernel with INST, whatever bvh_nodes says
+    dispatch_bools([&](auto B, auto T, auto I) { launch_kernel(k_gpt_sample<B() || I(), T(), I()>, blocks, lds, stream, q, g); }, bvh, tex, p.sc.in2.on != 0);
     return hipGetLastError();
 }
 hipError_t launch_gpt_update(const GptParams& g, uint32_t W, uint32_t H, float* film, hipStream_t stream) {

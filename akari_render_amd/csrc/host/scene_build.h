@@ -220,7 +220,7 @@ struct TuningOptions {
                           // default while its records fit a budget), 0 never, 1 whenever a mesh has more than one instance
     int rebraid = 1;  // kept scenes: (instance, subtree) pairs of the top-level tree per instance, on average (partial re-braiding); 1 = off
     int arith = 0;    // arithmetic tier of the pt megakernel: 0 = the AKR-F32 contract (bit-exact with the oracle), 1 = relaxed (pt_kernels_relaxed.hip:
-                      // films within north_star's relRMSE < 1e-3 of the oracle, not identical to it)
+                      // films not identical to the oracle's; how close at fixed seed: DESIGN.md 4.7)
     int pad_percent = 100;  // test hook: the padding of the acceleration structures' boxes (flat part and needle part) in percent of what the compiler derives --
                             // tests/test_bvh_conservative.py shows with it how far the derived padding is from the first lost hit
     int wf_groups = 0;  // wavefront schedule: slot groups whose init / trace / shade chains run side by side on streams of their own (1 = one chain, 0 = the library decides)

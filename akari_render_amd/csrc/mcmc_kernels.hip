@@ -8,6 +8,7 @@
 // deterministic (tests compare the chain states with the oracle bit for bit), the order in which different chains' splats
 // reach a pixel is not, here or there.
 #include "device/dradiance.h"
+#include "launch.h"
 
 namespace akr {
 
@@ -267,29 +268,28 @@ __global__ __launch_bounds__(256, 2) void k_mcmc_advance(const PtParams p_in, co
     }
 }
 
-#define AKR_MCMC_LAUNCH(KERNEL, COUNT, ...)                                                                         \
-    {                                                                                                             \
-        uint32_t blocks = ((COUNT) + 255u) / 256u;                                                                \
-        if (blocks == 0) return hipSuccess;                                                                       \
-        const bool bvh = p_in.sc.bvh_nodes != nullptr, tex = p_in.sc.tex.nodes != nullptr;                        \
-        size_t lds;                                                                                               \
-        const PtParams p = with_tex_slots(p_in, bvh ? p_in.sc.bvh_stack_depth * 256 * 4 : p_in.stage_total, lds);           \
-        if (p_in.sc.in2.on) { /* meshes + instances (mcmc_opt.rs:686-746 over the reference's two-level accel) */   \
-            if (tex) hipLaunchKernelGGL((KERNEL<true, true, true>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<true, false, true>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);     \
-        } else if (bvh) {                                                                                         \
-            if (tex) hipLaunchKernelGGL((KERNEL<true, true>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);   \
-            else hipLaunchKernelGGL((KERNEL<true, false>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);      \
-        } else {                                                                                                  \
-            if (tex) hipLaunchKernelGGL((KERNEL<false, true>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);  \
-            else hipLaunchKernelGGL((KERNEL<false, false>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);     \
-        }                                                                                                         \
-        return hipGetLastError();                                                                                 \
-    }
-hipError_t launch_mcmc_bootstrap(const PtParams& p_in, const McmcParams& m, hipStream_t stream) AKR_MCMC_LAUNCH(k_mcmc_bootstrap, m.n_bootstrap, p, m)
-hipError_t launch_mcmc_init(const PtParams& p_in, const McmcParams& m, hipStream_t stream) AKR_MCMC_LAUNCH(k_mcmc_init, m.chain_count, p, m)
-hipError_t launch_mcmc_advance(const PtParams& p_in, const McmcParams& m, uint32_t mutations_per_chain, float contribution, hipStream_t stream)
-    AKR_MCMC_LAUNCH(k_mcmc_advance, m.chain_count, p, m, mutations_per_chain, contribution)
-#undef AKR_MCMC_LAUNCH
+// The launch the three kernels share: one thread per item, the LDS of a scene's traversal stacks or staged tables + graph-value slots.
+// pick(BVH, TEX, INST) names the kernel's instantiation; args follow the parameter block. Meshes + instances (mcmc_opt.rs:686-746 over the
+// reference's two-level accel): the BVH kernel with INST, whatever bvh_nodes says.
+template <class Pick, class... A>
+static hipError_t mcmc_launch(const PtParams& p_in, uint32_t count, hipStream_t stream, Pick pick, const A&... args) {
+    const uint32_t blocks = (count + 255u) / 256u;
+    if (blocks == 0) return hipSuccess;
+    const bool bvh = p_in.sc.bvh_nodes != nullptr, tex = p_in.sc.tex.nodes != nullptr;
+    size_t lds;
+    const PtParams p = with_tex_slots(p_in, bvh ? p_in.sc.bvh_stack_depth * 256 * 4 : p_in.stage_total, lds);
+    dispatch_bools([&](auto B, auto T, auto I) { launch_kernel(pick(std::bool_constant<B() || I()>{}, T, I), blocks, lds, stream, p, args...); },
+                   bvh, tex, p_in.sc.in2.on != 0);
+    return hipGetLastError();
+}
+hipError_t launch_mcmc_bootstrap(const PtParams& p, const McmcParams& m, hipStream_t stream) {
+    return mcmc_launch(p, m.n_bootstrap, stream, [](auto B, auto T, auto I) { return k_mcmc_bootstrap<B(), T(), I()>; }, m);
+}
+hipError_t launch_mcmc_init(const PtParams& p, const McmcParams& m, hipStream_t stream) {
+    return mcmc_launch(p, m.chain_count, stream, [](auto B, auto T, auto I) { return k_mcmc_init<B(), T(), I()>; }, m);
+}
+hipError_t launch_mcmc_advance(const PtParams& p, const McmcParams& m, uint32_t mutations_per_chain, float contribution, hipStream_t stream) {
+    return mcmc_launch(p, m.chain_count, stream, [](auto B, auto T, auto I) { return k_mcmc_advance<B(), T(), I()>; }, m, mutations_per_chain, contribution);
+}
 
 }  // namespace akr

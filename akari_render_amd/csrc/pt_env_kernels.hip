@@ -1,48 +1,13 @@
 // pt_env_kernels.hip -- k_pt_pass for flattened scenes with an environment light (device/denv.h; ENV = true), in a translation unit of
-// their own so that the library's build compiles them beside pt_kernels.hip. The launch paths are those of launch_pt_pass (pt_launch.h)
-// without DEFER and SIMPLE: BVH or exhaustive x force_diffuse x textures x sampler family x staged tables (BVH path; the exhaustive path
-// always stages). Kept scenes run k_pt_pass_inst<.., ENV> (pt_inst_env_kernels.hip), the wavefront schedule k_wf_shade<.., ENV>
-// (wf_env_kernels.hip).
-#include <algorithm>
-#define AKR_PT_LAUNCH_KERNEL_ONLY 1
+// their own so that the library's build compiles them beside pt_kernels.hip. The launcher is launch_pt_pass's (pt_launch.h) with ENV on,
+// which rules out DEFER and SIMPLE: BVH or exhaustive x force_diffuse x textures x sampler family x staged tables (BVH path; the
+// exhaustive path always stages). Kept scenes run k_pt_pass_inst<.., ENV> (pt_inst_env_kernels.hip), the wavefront schedule
+// k_wf_shade<.., ENV> (wf_env_kernels.hip).
 #include "pt_launch.h"
 
 namespace akr {
 
-hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream) {
-    size_t lds;
-    uint32_t blocks;
-    const PtParams q = pt_pass_layout(p, lds, blocks);
-    if (blocks == 0) return hipSuccess;
-    const bool fd = p.force_diffuse != 0, tex = p.sc.tex.nodes != nullptr, pmj = p.sampler != 0;
-    const bool bvh = p.sc.bvh_nodes != nullptr, stage = p.stage_total != 0;
-    if (!bvh && !stage) return hipErrorInvalidValue;  // (the exhaustive kernels read their tables from LDS: the host guarantees the fit)
-#define AKR_ENV4(B, F, T, S)                                                                                                             \
-    {                                                                                                                                  \
-        if (pmj) {                                                                                                                     \
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)(k_pt_pass<B, F, T, true, S, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_pt_pass<B, F, T, true, S, false, false, true>), dim3(blocks), dim3(256), lds, stream, q);          \
-        } else {                                                                                                                       \
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)(k_pt_pass<B, F, T, false, S, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_pt_pass<B, F, T, false, S, false, false, true>), dim3(blocks), dim3(256), lds, stream, q);         \
-        }                                                                                                                              \
-    }
-#define AKR_ENV3(B, F, T)                            \
-    {                                               \
-        if (!B || stage) AKR_ENV4(B, F, T, true)    \
-        else AKR_ENV4(B, F, T, false)               \
-    }
-    if (bvh) {
-        if (tex) { if (fd) AKR_ENV3(true, true, true) else AKR_ENV3(true, false, true) }
-        else { if (fd) AKR_ENV3(true, true, false) else AKR_ENV3(true, false, false) }
-    } else {
-        if (tex) { if (fd) AKR_ENV4(false, true, true, true) else AKR_ENV4(false, false, true, true) }
-        else { if (fd) AKR_ENV4(false, true, false, true) else AKR_ENV4(false, false, false, true) }
-    }
-#undef AKR_ENV3
-#undef AKR_ENV4
-    return hipGetLastError();
-}
+hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream) { return launch_pt_pass_t<true>(p, stream); }
 
 // ---------------------------------------------------------------------------------------------------- test hook
 // mode 0: in = u (2 floats / item) -> out = wi.xyz, pdf, valid (5 floats); mode 1: in = direction (3 floats) -> out = pdf, radiance.rgb (4 floats)

@@ -1,8 +1,8 @@
-// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances (pt_inst_kernels.hip). A header
+// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances, and its launcher. A header
 // so that the instantiations of scenes with an environment light (pt_inst_env_kernels.hip, ENV = true) are compiled in a translation unit of
-// their own: those of pt_inst_kernels.hip, and their code, are the ones of a library without environments.
+// their own: those of pt_inst_kernels.hip (ENV = false), and their code, are the ones of a library without environments.
 #pragma once
-#include "device/pt_pass.h"
+#include "pt_launch.h"
 
 #ifndef AKR_PT_MIN_WAVES_INST
 #define AKR_PT_MIN_WAVES_INST AKR_PT_MIN_WAVES_BVH
@@ -16,6 +16,18 @@ namespace akr {
 template <bool FD, bool TEX, bool PMJ, bool ENV = false>
 __global__ __launch_bounds__(256, TEX ? AKR_PT_MIN_WAVES_INST_TEX : AKR_PT_MIN_WAVES_INST) void k_pt_pass_inst(const PtParams p) {
     pt_pass_body<true, FD, TEX, PMJ, false, false, 0u, true, ENV>(p);
+}
+
+// force_diffuse x textures x sampler family, in the LDS layout of k_pt_pass
+template <bool ENV>
+hipError_t launch_pt_pass_inst_t(const PtParams& p, hipStream_t stream) {
+    size_t lds;
+    uint32_t blocks;
+    const PtParams q = pt_pass_layout(p, lds, blocks);
+    if (blocks == 0) return hipSuccess;
+    dispatch_bools([&](auto F, auto T, auto P) { launch_kernel<true>(k_pt_pass_inst<F(), T(), P(), ENV>, blocks, lds, stream, q); },
+                   p.force_diffuse != 0, p.sc.tex.nodes != nullptr, p.sampler != 0);
+    return hipGetLastError();
 }
 
 }  // namespace akr

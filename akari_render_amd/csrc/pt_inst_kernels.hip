@@ -1,6 +1,7 @@
 // pt_inst_kernels.hip -- k_pt_pass for scenes kept as meshes + instances (host/scene_inst.cpp): the same persistent-lane path
 // tracer over the two-level traversal of device/dinst_trav.h. BVH kernels without staged tables, deferral or absent-lobe masks:
-// force_diffuse x textures x sampler family (those of scenes with an environment light: pt_inst_env_kernels.hip).
+// force_diffuse x textures x sampler family; kernel and launcher: pt_inst_kernel.h (ENV = false here; scenes with an environment light:
+// pt_inst_env_kernels.hip).
 #include "pt_inst_kernel.h"
 
 namespace akr {
@@ -31,26 +32,8 @@ hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* me
 }
 
 hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream) {
-    size_t lds;
-    uint32_t blocks;
-    const PtParams q = pt_pass_layout(p, lds, blocks);
-    if (blocks == 0) return hipSuccess;
     if (p.sc.env) return launch_pt_pass_inst_env(p, stream);  // an environment light: pt_inst_env_kernels.hip
-    const bool fd = p.force_diffuse != 0, tex = p.sc.tex.nodes != nullptr, pmj = p.sampler != 0;
-#define AKR_LAUNCH_INST(F, T, S)                                                                                                          \
-    {                                                                                                                                   \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)(k_pt_pass_inst<F, T, S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_pt_pass_inst<F, T, S>), dim3(blocks), dim3(256), lds, stream, q);                                            \
-    }
-    if (fd) {
-        if (tex) { if (pmj) AKR_LAUNCH_INST(true, true, true) else AKR_LAUNCH_INST(true, true, false) }
-        else { if (pmj) AKR_LAUNCH_INST(true, false, true) else AKR_LAUNCH_INST(true, false, false) }
-    } else {
-        if (tex) { if (pmj) AKR_LAUNCH_INST(false, true, true) else AKR_LAUNCH_INST(false, true, false) }
-        else { if (pmj) AKR_LAUNCH_INST(false, false, true) else AKR_LAUNCH_INST(false, false, false) }
-    }
-#undef AKR_LAUNCH_INST
-    return hipGetLastError();
+    return launch_pt_pass_inst_t<false>(p, stream);
 }
 
 }  // namespace akr

@@ -1,4 +1,4 @@
-// pt_kernels.hip -- hand-written gfx950 kernels of the `pt` integrator. k_pt_pass: device/pt_pass.h.
+// pt_kernels.hip -- hand-written gfx950 kernels of the `pt` integrator. k_pt_pass: device/pt_pass.h, its launcher: pt_launch.h (ENV = false here).
 #include <algorithm>
 #include "device/pt_pass.h"
 #include "pt_launch.h"
@@ -145,6 +145,12 @@ __global__ void k_probe_material(PtParams p, uint32_t material, uint32_t n, cons
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
+// spec_fn: the session's per-scene kernel (host/specialise.cpp); it wraps the body of whatever the scene is, so it is launched from here
+hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn) {
+    if (p.sc.in2.on && !spec_fn) return launch_pt_pass_inst(p, stream);  // meshes + instances: pt_inst_kernels.hip
+    if (p.sc.env && !spec_fn) return launch_pt_pass_env(p, stream);      // an environment light: pt_env_kernels.hip
+    return launch_pt_pass_t<false>(p, stream, spec_fn);
+}
 hipError_t launch_probe_material(const PtParams& p, uint32_t material, uint32_t n, const float* uv, uint32_t* out, hipStream_t stream) {
     size_t lds;
     const PtParams q = with_tex_slots(p, 0, lds);
@@ -177,17 +183,14 @@ hipError_t launch_probe_bsdf(const DMaterial* m, const float* table, int mode, c
     return hipGetLastError();
 }
 hipError_t launch_probe_intersect(const PtParams& p, uint32_t n, const float* rays, uint32_t* out, float* bary, hipStream_t stream) {
-    if (p.sc.in2.on)
-        hipLaunchKernelGGL((k_probe_intersect<true, true>), dim3((n + 255) / 256), dim3(256), p.sc.bvh_stack_depth * 256 * 4, stream, p, n, rays, out, bary);
-    else if (p.sc.bvh_nodes != nullptr)
-        hipLaunchKernelGGL(k_probe_intersect<true>, dim3((n + 255) / 256), dim3(256), p.sc.bvh_stack_depth * 256 * 4, stream, p, n, rays, out, bary);
-    else
-        hipLaunchKernelGGL(k_probe_intersect<false>, dim3((n + 255) / 256), dim3(256), 0, stream, p, n, rays, out, bary);
+    const bool bvh = p.sc.bvh_nodes != nullptr, inst = p.sc.in2.on != 0;  // (a kept scene: the two-level traversal, whatever bvh_nodes says)
+    dispatch_bools([&](auto B, auto I) {
+        launch_kernel(k_probe_intersect<B() || I(), I()>, (n + 255) / 256, B() || I() ? p.sc.bvh_stack_depth * 256 * 4 : 0, stream, p, n, rays, out, bary);
+    }, bvh, inst);
     return hipGetLastError();
 }
 hipError_t launch_probe_si(const PtParams& p, uint32_t n, const uint32_t* inst_prim, const float* bary, float* out, hipStream_t stream) {
-    if (p.sc.in2.on) hipLaunchKernelGGL(k_probe_si<true>, dim3((n + 255) / 256), dim3(256), 0, stream, p, n, inst_prim, bary, out);
-    else hipLaunchKernelGGL(k_probe_si<false>, dim3((n + 255) / 256), dim3(256), 0, stream, p, n, inst_prim, bary, out);
+    dispatch_bools([&](auto I) { launch_kernel(k_probe_si<I()>, (n + 255) / 256, 0, stream, p, n, inst_prim, bary, out); }, p.sc.in2.on != 0);
     return hipGetLastError();
 }
 

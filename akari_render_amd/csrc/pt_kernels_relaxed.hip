@@ -3,8 +3,10 @@
 // The same source as pt_kernels.hip's instantiations -- pt_pass.h, every device header -- compiled a second time with
 // -ffp-contract=fast, without correctly rounded division / square root, with denormals flushed (build.py RELAXED_FLAGS) and
 // with AKR_ARITH_RELAXED = 1, inside another namespace so that neither the kernels nor a header's inline function can be
-// mistaken for the contract-bound ones at link time. Films are the oracle's to relRMSE < 1e-3 (north_star's bar; measured
-// ~1e-5, tests/test_gpu_relaxed.py), not to the bit: the bit-exact tier stays the default and is what verifies this one.
+// mistaken for the contract-bound ones at link time. Films are not the oracle's to the bit, and at fixed seed not within
+// north_star's relRMSE < 1e-3 either except on the headline configuration's shard (1e-5 .. 4e-5 outside the few pixels
+// where a sample takes another decision, 8e-4 .. 9e-3 with them; tests/test_gpu_relaxed.py): the bit-exact tier stays the default and
+// is what verifies this one. The launcher is pt_launch.h's; kept scenes and scenes with an environment light are refused here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -15,5 +17,7 @@
 #undef akr
 
 extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, hipStream_t stream) {
-    return akr_rx::launch_pt_pass(*static_cast<const akr_rx::PtParams*>(params), stream, nullptr);
+    const akr_rx::PtParams& p = *static_cast<const akr_rx::PtParams*>(params);
+    if (p.sc.in2.on || p.sc.env) return hipErrorInvalidValue;  // (the host never sends a kept scene or one with an environment light to this tier: api_pt.cpp)
+    return akr_rx::launch_pt_pass_t<false>(p, stream);
 }

@@ -193,56 +193,39 @@ __global__ __launch_bounds__(256, INST ? AKR_WF_TRACE_INST_WAVES : 1) void k_wf_
 
 // ---------------------------------------------------------------------------------------------------- launchers
 hipError_t launch_wf_init(const PtParams& p, const WfBuffers& wf, hipStream_t stream) {
-    uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
+    const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
     if (blocks == 0) return hipSuccess;
-    if (p.sampler) hipLaunchKernelGGL(k_wf_init<true>, dim3(blocks), dim3(256), 0, stream, p, wf);
-    else hipLaunchKernelGGL(k_wf_init<false>, dim3(blocks), dim3(256), 0, stream, p, wf);
+    dispatch_bools([&](auto P) { launch_kernel(k_wf_init<P()>, blocks, 0, stream, p, wf); }, p.sampler != 0);
     return hipGetLastError();
 }
 hipError_t launch_wf_shade(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
-    uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
-    if (blocks == 0) return hipSuccess;
-    const bool tex = p.sc.tex.nodes != nullptr, pmj = p.sampler != 0;
-    const bool inst = p.sc.in2.on != 0;
     if (p.sc.env) return launch_wf_shade_env(p, wf, q_out, stream);  // an environment light: wf_env_kernels.hip
-#define AKR_WF_SHADE(T, S, Q, L)                                                                                              \
-    {                                                                                                                       \
-        if (inst) hipLaunchKernelGGL((k_wf_shade<T, S, true>), dim3(blocks), dim3(256), L, stream, Q, wf, q_out);              \
-        else hipLaunchKernelGGL((k_wf_shade<T, S, false>), dim3(blocks), dim3(256), L, stream, Q, wf, q_out);                  \
-    }
-    if (tex) {
-        size_t lds;
-        const PtParams q = with_tex_slots(p, 0, lds);
-        if (pmj) AKR_WF_SHADE(true, true, q, lds) else AKR_WF_SHADE(true, false, q, lds)
-    } else {
-        if (pmj) AKR_WF_SHADE(false, true, p, 0) else AKR_WF_SHADE(false, false, p, 0)
-    }
-#undef AKR_WF_SHADE
-    return hipGetLastError();
+    return launch_wf_shade_t<false>(p, wf, q_out, stream);
+}
+// The trace launch of a scene: its kernel (textures x kept or flattened), its parameter block and its dynamic LDS -- the traversal stacks, then
+// the graph-value slots of a scene with textures. One place, so that the occupancy query and the launch cannot name different kernels.
+struct WfTraceLaunch {
+    void (*kernel)(const PtParams, const WfBuffers, uint32_t);
+    PtParams q;
+    size_t lds;
+};
+static WfTraceLaunch wf_trace_launch(const PtParams& p) {
+    const bool tex = p.sc.tex.nodes != nullptr;
+    WfTraceLaunch l{nullptr, p, (size_t)p.sc.bvh_stack_depth * 256 * 4};
+    if (tex) l.q = with_tex_slots(p, l.lds, l.lds);
+    dispatch_bools([&](auto T, auto I) { l.kernel = k_wf_trace<T(), I()>; }, tex, p.sc.in2.on != 0);
+    return l;
 }
 // Workgroups of the persistent trace kernel one CU holds at once (registers and the LDS stacks of this scene's tree decide).
 uint32_t wf_trace_blocks_per_cu(const PtParams& p) {
+    const WfTraceLaunch l = wf_trace_launch(p);
     int n = 0;
-    const bool tex = p.sc.tex.nodes != nullptr;
-    size_t lds = (size_t)p.sc.bvh_stack_depth * 256 * 4;
-    if (tex) (void)with_tex_slots(p, lds, lds);
-    const bool inst = p.sc.in2.on != 0;
-    hipError_t e = inst ? (tex ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wf_trace<true, true>, 256, lds)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wf_trace<false, true>, 256, lds))
-                        : (tex ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wf_trace<true, false>, 256, lds)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wf_trace<false, false>, 256, lds));
-    if (e != hipSuccess || n < 1) n = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, l.kernel, 256, l.lds) != hipSuccess || n < 1) n = 4;
     return (uint32_t)std::min(n, 8);
 }
 hipError_t launch_wf_trace(const PtParams& p, const WfBuffers& wf, uint32_t q_in, uint32_t n_blocks, hipStream_t stream) {
-    const bool inst = p.sc.in2.on != 0;
-    if (p.sc.tex.nodes != nullptr) {
-        size_t lds;
-        const PtParams q = with_tex_slots(p, p.sc.bvh_stack_depth * 256 * 4, lds);
-        if (inst) hipLaunchKernelGGL((k_wf_trace<true, true>), dim3(n_blocks), dim3(256), lds, stream, q, wf, q_in);
-        else hipLaunchKernelGGL((k_wf_trace<true, false>), dim3(n_blocks), dim3(256), lds, stream, q, wf, q_in);
-    } else if (inst) hipLaunchKernelGGL((k_wf_trace<false, true>), dim3(n_blocks), dim3(256), p.sc.bvh_stack_depth * 256 * 4, stream, p, wf, q_in);
-    else hipLaunchKernelGGL((k_wf_trace<false, false>), dim3(n_blocks), dim3(256), p.sc.bvh_stack_depth * 256 * 4, stream, p, wf, q_in);
+    const WfTraceLaunch l = wf_trace_launch(p);
+    launch_kernel(l.kernel, n_blocks, l.lds, stream, l.q, wf, q_in);
     return hipGetLastError();
 }
 

@@ -1,9 +1,11 @@
-// wf_path.h -- the path half of the wavefront schedule (wf_kernels.hip): the path state's records in HBM, the ray queues, k_wf_init and
-// k_wf_shade. A header so that the shade kernels of scenes with an environment light (wf_env_kernels.hip, ENV = true) are compiled in a
-// translation unit of their own: the instantiations of wf_kernels.hip and their code are those of a library without environments.
+// wf_path.h -- the path half of the wavefront schedule (wf_kernels.hip): the path state's records in HBM, the ray queues, k_wf_init,
+// k_wf_shade and its launcher. A header so that the shade kernels of scenes with an environment light (wf_env_kernels.hip, ENV = true) are
+// compiled in a translation unit of their own: the instantiations of wf_kernels.hip (ENV = false) and their code are those of a library
+// without environments.
 #pragma once
 #include <algorithm>
 #include "device/dpath.h"
+#include "launch.h"
 
 namespace akr {
 
@@ -165,6 +167,20 @@ __global__ __launch_bounds__(256, TEX ? 1 : AKR_WF_SHADE_WAVES) void k_wf_shade(
     }
     wf_enqueue(p, wf, q_out, slot, r, resume);
     flush_counters(p, r, TraceCounters{0, 0, 0}, true);
+}
+
+
+// textures x sampler family x kept or flattened scene
+template <bool ENV>
+hipError_t launch_wf_shade_t(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
+    const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
+    if (blocks == 0) return hipSuccess;
+    const bool tex = p.sc.tex.nodes != nullptr;
+    size_t lds = 0;
+    const PtParams q = tex ? with_tex_slots(p, 0, lds) : p;
+    dispatch_bools([&](auto T, auto P, auto I) { launch_kernel(k_wf_shade<T(), P(), I(), ENV>, blocks, lds, stream, q, wf, q_out); },
+                   tex, p.sampler != 0, p.sc.in2.on != 0);
+    return hipGetLastError();
 }
 
 }  // namespace akr
