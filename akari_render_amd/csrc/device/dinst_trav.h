@@ -87,16 +87,6 @@ AKR_D void resolve_pending(const DScene& sc, TravI& s, bool any_hit) {
     const vec3 c0 = xyz(m[0]), c1 = xyz(m[1]), c2 = xyz(m[2]), tr = xyz(m[3]);
     const vec3 A = xf_point(c0, c1, c2, tr, xyz(q0)), B = xf_point(c0, c1, c2, tr, xyz(q1)), C = xf_point(c0, c1, c2, tr, xyz(q2));
     float wr[12];
-#if defined(AKR_INST_FAKE_EXACT)  // timing only: f32 rows (films differ)
-    {
-        const vec3 e1 = B - A, e2 = C - A, n = cross(e1, e2);
-        const float det = dot(n, n), inv = 1.0f / det;
-        const vec3 r0 = cross(e2, n) * inv, r1 = cross(n, e1) * inv, r2 = n * inv;
-        wr[0] = r0.x; wr[1] = r0.y; wr[2] = r0.z; wr[3] = -dot(r0, A);
-        wr[4] = r1.x; wr[5] = r1.y; wr[6] = r1.z; wr[7] = -dot(r1, A);
-        wr[8] = r2.x; wr[9] = r2.y; wr[10] = r2.z; wr[11] = -dot(r2, A);
-    }
-#else
     // The coplanar-neighbour rule (dinst.h share_plane_row: an odd triangle lying in its even neighbour's plane carries that neighbour's plane
     // row) was decided once per scene for every instance-triangle (k_inst_share_bits: inst_pair_shares below). Here the third row is computed
     // from the neighbour's vertices instead of the triangle's own -- one code path, no test at the candidate; a triangle that does not share
@@ -109,7 +99,6 @@ AKR_D void resolve_pending(const DScene& sc, TravI& s, bool any_hit) {
     }
     woop_edge_rows(A, B, C, wr);
     woop_plane_row(P0, P1, P2, wr + 8);
-#endif
     float t, u, v;
     bool h = tri_test(s.wo, s.wd, make_float4(wr[0], wr[1], wr[2], wr[3]), make_float4(wr[4], wr[5], wr[6], wr[7]), make_float4(wr[8], wr[9], wr[10], wr[11]), s.tmin, s.tmax,
                       t, u, v);
@@ -118,14 +107,8 @@ AKR_D void resolve_pending(const DScene& sc, TravI& s, bool any_hit) {
 #endif
     if (h && sc.has_alpha) h = alpha_test_inst<TEX>(sc, m, inst, prim, tri_off, q0, q1, q2, q3, u, v);
     if (h) {
-        if (any_hit) {
-            s.best = gid;
-            s.T = 0; s.G = 0; s.sp = 0;  // any hit: done
-            s.active = false;
-        } else {
-            const bool better = (s.best == kInvalid) | (t < s.best_t) | ((t == s.best_t) & (gid < s.best));
-            if (better) { s.best_t = t; s.best_u = u; s.best_v = v; s.best = gid; }
-        }
+        hit_commit(s, any_hit, gid, t, u, v);
+        if (any_hit) s.active = false;
     }
 }
 
@@ -180,9 +163,7 @@ AKR_D bool trav_step_inst(const DScene& sc, TravI& s, uint32_t* __restrict__ sta
         s.T &= s.T - 1u;
         const uint4* lf = sc.in2.tlas_leaves + (size_t)(s.tbase + b) * 4;
         const uint4 w0 = lf[0], w1 = lf[1], w2 = lf[2], w3 = lf[3];
-#if !defined(AKR_INST_COUNT)
         cnt.nodes++;
-#endif
         if (s.sp + 3 <= sc.bvh_stack_depth) {
             stack[s.sp * 256u] = s.G; s.sp++;
             stack[s.sp * 256u] = s.tbase; s.sp++;
@@ -197,23 +178,10 @@ AKR_D bool trav_step_inst(const DScene& sc, TravI& s, uint32_t* __restrict__ sta
     }
     // ---- stage 2: a node of either level: disect.h trav_step's box test on the current level's ray
     if ((s.T == 0) & ((s.G >> 24) != 0)) {
-        const uint32_t j = 31u - (uint32_t)__builtin_clz(s.G);  // nearest pending sibling
-        s.G &= ~(1u << j);
-        if ((s.G >> 24) != 0) {  // the others wait as one entry
-            if (s.sp < sc.bvh_stack_depth) {
-                stack[s.sp * 256u] = s.G;
-                s.sp++;
-            } else {
-                cnt.overflow = 1;
-            }
-        }
-        const uint32_t slot = (j - 24u) ^ (s.octinv4 & 7u);
-        const uint32_t idx = s.node_off + (s.G & 0xffffffu) + slot;
+        const uint32_t idx = s.node_off + node_pop(s, stack, sc.bvh_stack_depth, cnt);
         const uint4* p = sc.bvh_nodes + (size_t)idx * (kBvhNodeWords / 4);
         const uint4 w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3];
-#if !defined(AKR_INST_COUNT)
         cnt.nodes++;
-#endif
         const float limit = s.best_t;
         const float bx = u2f((w0.w & 0xffu) << 23) * s.inv.x, by = u2f(((w0.w >> 8) & 0xffu) << 23) * s.inv.y, bz = u2f(((w0.w >> 16) & 0xffu) << 23) * s.inv.z;
         const float ax = __builtin_fmaf(u2f(w0.x), s.inv.x, s.noi.x), ay = __builtin_fmaf(u2f(w0.y), s.inv.y, s.noi.y), az = __builtin_fmaf(u2f(w0.z), s.inv.z, s.noi.z);
@@ -301,9 +269,6 @@ AKR_D bool trace_inst(const DScene& sc, vec3 o, vec3 d, float tmin, float tmax, 
     uint32_t waited = 0;
     bool blocked = false;
     while (s.active | (s.pend_rec != kInvalid)) {
-#if defined(AKR_INST_COUNT) && AKR_INST_COUNT == 3
-        if ((uint32_t)__builtin_ctzll(__ballot(true)) == (threadIdx.x & 63u)) cnt.nodes++;
-#endif
         if (s.pend_rec == kInvalid) blocked = false;
         if (s.active & !blocked) blocked = trav_step_inst<TEX>(sc, s, stack, cnt);
         const bool pending = s.pend_rec != kInvalid;
@@ -313,13 +278,6 @@ AKR_D bool trace_inst(const DScene& sc, vec3 o, vec3 d, float tmin, float tmax, 
         waited++;
         if (waited >= AKR_INST_PATIENCE || __ballot(s.active & !wait) == 0 || __popcll(__ballot(pending)) >= AKR_INST_QUORUM) {
             waited = 0;
-#if defined(AKR_INST_COUNT) && AKR_INST_COUNT == 1   // measurement builds: n_node_visits counts exact tests (lanes) instead
-            if (pending) cnt.nodes++;
-#elif defined(AKR_INST_COUNT) && AKR_INST_COUNT == 2  // ... or the times a wave ran the exact test
-            if (pending && (uint32_t)__builtin_ctzll(__ballot(pending)) == (threadIdx.x & 63u)) cnt.nodes++;
-#elif defined(AKR_INST_COUNT) && AKR_INST_COUNT == 3  // ... or the loop iterations of the waves
-            if (false) cnt.nodes++;
-#endif
             if (pending) resolve_pending<TEX>(sc, s, ANY_HIT);
 #if defined(AKR_INST_PRETEST_CHECK)
             if (s.check_t == -2.0f) cnt.overflow = 1;

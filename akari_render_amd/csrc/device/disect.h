@@ -149,58 +149,23 @@ AKR_D bool trace_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmin, float 
 }
 
 // Exhaustive intersector for a PAIR of rays per lane: the closest-hit ray of the next path vertex and the shadow ray
-// of the current one are both known once a vertex has been shaded, so one walk over the (wave-uniform, scalar-cache
-// resident) records serves both: half the scalar loads and loop overhead of two separate walks, and two independent
-// dependency chains per record for the VALU to overlap. A ray that does not exist for a lane is passed with
-// tmax < tmin and can never hit.
+// of the current one are both known once a vertex has been shaded, so one walk over the records serves both: half the
+// loads and loop overhead of two separate walks, and two independent dependency chains per record for the VALU to
+// overlap. A ray that does not exist for a lane is passed with tmax < tmin and can never hit.
 //
-// WALK selects where a record's coefficients sit when the VALU reads them (measured variants):
-//   0  SGPRs: s_load through the scalar cache, every fma of the affine rows names one SGPR operand. A SIMD accepts one
-//      scalar-operand VALU instruction per ~4.3 cycles against ~2.15 for a VGPR-only one (tools/micro/valu_rate.hip), and the
-//      rows come 16 such instructions in a row.
-//   1  VGPRs: the records are staged in LDS with the shading tables and every lane reads the same address (a broadcast
-//      ds_read_b128, 4 LDS cycles per wave and row); all of the test's arithmetic is then VGPR-only.
-//   2  SGPRs, but the two rays of the pair go through the rows as ONE packed instruction (v_pk_fma_f32 with the coefficient
-//      broadcast): half as many scalar-operand instructions; a packed f32 op holds the VALU for two slots either way.
-//   3  records in LDS, every fma of plane solve and inside test packed over the two rays, the coefficient broadcast from one half
-//      of a register pair by op_sel (no copies, no register-bank conflicts: 417 instead of 535 modelled issue cycles per two records,
-//      tools/valu_cost_report.py) -- and 3 % SLOWER than 1 on C2 and C3: half as many independent instructions per wave.
-//   4  records in LDS, scalar fmas as in 1, with the cheaper bookkeeping of 3: the alpha test unswitched out of the loop (inside
-//      it the wave-uniform flag cost every record a v_cndmask + v_cmp), min / max without the compiler's canonicalising v_max x, x,
-//      the shadow ray's margin folded with one v_max, and only (t, id) of the best hit selected per record -- its (u, v) are
-//      recomputed once after the walk. +4.2 % on C2, +3.3 % on C3 over 1 (same box, profiles/r4_ab_walk.txt). The default.
-// The arithmetic (operation order, fma placement) is identical in all of them: films do not change.
+// The records are read from LDS (`lds_recs`: pt_pass.h stages them behind the shading tables, padded by two records): every lane reads
+// the same address, a broadcast ds_read_b128, so all of the test's arithmetic is VGPR-only. A SIMD accepts one scalar-operand VALU
+// instruction per ~4.3 cycles against ~2.15 for a VGPR-only one (tools/micro/valu_rate.hip), and the rows of a record read through the
+// scalar cache come 16 such instructions in a row. The bookkeeping per record is cut down too (a v_cmp costs 4.4 cycles and a v_cndmask
+// on its result 3.7): the alpha test is unswitched out of the loop, min / max come without the compiler's canonicalising v_max x, x, the
+// shadow ray's margin is folded with one v_max, and only (t, id) of the best hit are selected per record -- its (u, v) are recomputed
+// once after the walk. Two records per trip on alternating register sets: a one-record software prefetch without the moves that
+// rotating a single set costs.
+// Five other forms were measured and retired (records through the scalar cache, both rays packed into v_pk_fma_f32 with and
+// without op_sel broadcast, lockstep pairs of coplanar records); this one was +4.2 % on C2 and +3.3 % on C3 over the next best:
+// HISTORY.md, profiles/r4_ab_walk.txt. The arithmetic (operation order, fma placement) is tri_plane / tri_uv / hit_margin's.
 typedef float v2f __attribute__((ext_vector_type(2)));
-AKR_D v2f pk_fma(float a, v2f b, v2f c) { return __builtin_elementwise_fma((v2f){a, a}, b, c); }
-AKR_D v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-// WALK 3: v_pk_fma_f32 / v_pk_mul_f32 with ONE half of a 64-bit register pair feeding both lanes (op_sel / op_sel_hi): the
-// coefficient of a record row, read from LDS as part of a 128-bit quad, multiplies the closest-hit ray's value in the low lane and
-// the shadow ray's in the high lane without ever being copied. Each lane is the IEEE fma / mul the scalar instruction computes.
-//   SA / SC = which half (0 = low, 1 = high) of `a` / `c` is broadcast.
 typedef float v4f __attribute__((ext_vector_type(4)));
-template <int SA>
-AKR_D v2f pk_fma_b(v2f a, v2f b, v2f c) {  // {a[SA], a[SA]} * b + c
-    v2f r;
-    if (SA == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-template <int SA, int SC>
-AKR_D v2f pk_fma_bb(v2f a, v2f b, v2f c) {  // {a[SA], a[SA]} * b + {c[SC], c[SC]}
-    v2f r;
-    if (SA == 0 && SC == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    else if (SA == 0 && SC == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    else if (SA == 1 && SC == 1) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-template <int SA>
-AKR_D v2f pk_mul_b(v2f a, v2f b) {  // {a[SA], a[SA]} * b
-    v2f r;
-    if (SA == 0) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // IEEE minNum / maxNum as the instruction computes them, without the v_max x, x the compiler puts in front of fminf / fmaxf to quiet
 // a possible signalling NaN (4.4 cycles of the SIMD each, tools/micro/vgpr_bank.hip; arithmetic never produces one)
 AKR_D float min_raw(float a, float b) {
@@ -213,9 +178,9 @@ AKR_D float max_raw(float a, float b) {
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-template <bool TEX = false, bool UNROLL = false, int WALK = 0>
+template <bool TEX = false>
 AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, uint32_t ex0, vec3 so, vec3 sd, float stmax,
-                                 uint32_t sex0, uint32_t sex1, Hit& hit, bool& found, bool& occluded, const float4* lds_recs = nullptr) {
+                                 uint32_t sex0, uint32_t sex1, Hit& hit, bool& found, bool& occluded, const float4* lds_recs) {
     // best_t starts one ulp above tmax: "t < best_t" then admits a first hit at t == tmax and keeps, among equal t, the
     // lowest id afterwards (ascending k, strict '<') without a separate "no hit yet" test
     float best_t = next_up(tmax);
@@ -223,189 +188,69 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     float best_u = 0.0f, best_v = 0.0f;
     float occ_margin = -1.0f;  // max over the records of the shadow ray's margin: >= 0 <=> something occludes
     const uint32_t n = sc.n_tris;
-    typedef const float __attribute__((address_space(4))) * ConstF;
-    ConstF recs = (ConstF)(uintptr_t)sc.woop;
-    auto load_rec = [&](uint32_t k, float4& a, float4& b, float4& c) {
-        if (WALK == 1) {  // the same LDS address in every lane: broadcast reads
-            const float4* r = lds_recs + 3 * (size_t)k;
-            a = r[0]; b = r[1]; c = r[2];
-            return;
+    const v4f* lrec = (const v4f*)lds_recs;
+    const bool has_alpha = __builtin_amdgcn_readfirstlane((int)sc.has_alpha) != 0;  // (a scalar branch per walk, nothing per lane)
+    // the two rays' plane solves of the current plane, as pairs {closest-hit ray, shadow ray}: t and the hit point
+    v2f T2 = {0.0f, 0.0f}, hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};
+    auto record = [&](auto alpha_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
+        constexpr bool ALPHA = decltype(alpha_tag)::value;
+        if (!((sc.plane_share_mask >> k) & 1ull)) {  // wave-uniform: one plane solve per ray per coplanar pair of records
+            const PlaneHit a = tri_plane(o, d, make_float4(q2.x, q2.y, q2.z, q2.w)), b = tri_plane(so, sd, make_float4(q2.x, q2.y, q2.z, q2.w));
+            T2 = (v2f){a.t, b.t};
+            hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
         }
-        ConstF r = recs + 12 * (size_t)k;
-        a = make_float4(r[0], r[1], r[2], r[3]);
-        b = make_float4(r[4], r[5], r[6], r[7]);
-        c = make_float4(r[8], r[9], r[10], r[11]);
-    };
-    PlaneHit ph{0.0f, 0.0f, 0.0f, 0.0f}, sph{0.0f, 0.0f, 0.0f, 0.0f};
-    const v2f ox2 = {o.x, so.x}, oy2 = {o.y, so.y}, oz2 = {o.z, so.z}, dx2 = {d.x, sd.x}, dy2 = {d.y, sd.y}, dz2 = {d.z, sd.z};
-    v2f hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};  // WALK 2: the two rays' hit points on the current plane
-    auto record = [&](uint32_t k, const float4& r0, const float4& r1, const float4& r2) {
         float u, v, su, sv;
-        if (WALK == 2) {
-            // tri_plane / tri_uv for both rays at once, component 0 = closest-hit ray, 1 = shadow ray; the same fma chains
-            if (!((sc.plane_share_mask >> k) & 1ull)) {
-                const v2f den = pk_fma(r2.x, dx2, pk_fma(r2.y, dy2, (v2f){r2.z, r2.z} * dz2));
-                const v2f num = pk_fma(r2.x, ox2, pk_fma(r2.y, oy2, pk_fma(r2.z, oz2, (v2f){r2.w, r2.w})));
-                ph.t = div_f(-num.x, den.x);
-                sph.t = div_f(-num.y, den.y);
-                const v2f t2 = {ph.t, sph.t};
-                hx2 = pk_fma(t2, dx2, ox2); hy2 = pk_fma(t2, dy2, oy2); hz2 = pk_fma(t2, dz2, oz2);
-            }
-            const v2f u2 = pk_fma(r0.x, hx2, pk_fma(r0.y, hy2, pk_fma(r0.z, hz2, (v2f){r0.w, r0.w})));
-            const v2f v2 = pk_fma(r1.x, hx2, pk_fma(r1.y, hy2, pk_fma(r1.z, hz2, (v2f){r1.w, r1.w})));
-            u = u2.x; su = u2.y; v = v2.x; sv = v2.y;
-        } else {
-            if (!((sc.plane_share_mask >> k) & 1ull)) {  // wave-uniform: one plane solve per ray per coplanar pair of records
-                ph = tri_plane(o, d, r2);
-                sph = tri_plane(so, sd, r2);
-            }
-            tri_uv(ph, r0, r1, u, v);
-            tri_uv(sph, r0, r1, su, sv);
-        }
-        const float t = ph.t, st = sph.t;
-        float m = hit_margin(t, u, v, tmax), sm = hit_margin(st, su, sv, stmax);
+        tri_uv(PlaneHit{T2.x, hx2.x, hy2.x, hz2.x}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), u, v);
+        tri_uv(PlaneHit{T2.y, hx2.y, hy2.y, hz2.y}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), su, sv);
+        const v2f u2 = {u, su}, v2 = {v, sv};
+        // hit_margin: min(min(min(u, v), 1 - (u + v)), min(t, tmax - t)) per ray
+        const v2f s2 = {1.0f - (u2.x + v2.x), 1.0f - (u2.y + v2.y)};
+        const v2f w2 = {tmax - T2.x, stmax - T2.y};
+        float m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), min_raw(T2.x, w2.x));
+        float sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), min_raw(T2.y, w2.y));
         m = (k == ex0) ? -1.0f : m;
         sm = (k == sex0) ? -1.0f : sm;
         sm = (k == sex1) ? -1.0f : sm;
-        if (sc.has_alpha) {
+        if (ALPHA) {
             // k through readfirstlane: opaque to loop strength reduction, which otherwise keeps this block's record pointer and
-            // hash constant as induction variables updated on the scalar unit every trip, alpha or not
+            // hash constant as induction variables updated on the scalar unit every trip
             const uint32_t ka = __builtin_amdgcn_readfirstlane(k);
-            if (m >= 0.0f && !alpha_test<TEX>(sc, ka, u, v)) m = -1.0f;
-            if (sm >= 0.0f && !alpha_test<TEX>(sc, ka, su, sv)) sm = -1.0f;
+            if (m >= 0.0f && !alpha_test<TEX>(sc, ka, u2.x, v2.x)) m = -1.0f;
+            if (sm >= 0.0f && !alpha_test<TEX>(sc, ka, u2.y, v2.y)) sm = -1.0f;
         }
-        const float tc = (m >= 0.0f) ? t : __builtin_inff();
+        // only the distance and the id of the best hit are tracked here; its (u, v) are recomputed after the walk (below)
+        const float tc = (m >= 0.0f) ? T2.x : __builtin_inff();
         const bool better = tc < best_t;
         best_t = better ? tc : best_t;
-        best_u = better ? u : best_u;
-        best_v = better ? v : best_v;
         best = better ? k : best;
-        occ_margin = sm > occ_margin ? sm : occ_margin;  // (not fmaxf: that costs two canonicalising v_max per record)
+        // max over the records of the shadow ray's margin (a NaN margin leaves it as it is, like the comparison it replaces; only
+        // the sign of the result is read)
+        occ_margin = max_raw(occ_margin, sm);
     };
-    if (WALK == 3 || WALK == 4 || WALK == 5) {  // 4: the same loop with scalar fmas instead of packed ones; 5: 4 + lockstep pairs
-        // Both rays of the pair through every fma of the plane solve and of the inside test as ONE packed instruction. A scalar
-        // v_fma_f32 costs its SIMD 2.2 cycles unless its three source registers all have the same parity (the register file's two
-        // banks): then 4.4 -- and which registers a value lands in is the allocator's choice, 13 of the 76 three-source instructions
-        // of the two-record trip were hit (tools/valu_cost_report.py). A v_pk_fma_f32 costs 4.4 for its two results whatever its
-        // registers are. The records' rows are read from LDS as 128-bit quads; a row's coefficient is one half of a 64-bit register
-        // pair and is broadcast to both lanes by op_sel, the rays' components are pairs {closest-hit ray, shadow ray} throughout.
-        // The comparisons of a record are cut down too: a v_cmp costs 4.4 cycles and a v_cndmask on its result 3.7.
-        const v4f* lrec = (const v4f*)lds_recs;
-        const bool has_alpha = __builtin_amdgcn_readfirstlane((int)sc.has_alpha) != 0;  // (a scalar branch per record, nothing per lane)
-        const v2f tmax2 = {tmax, stmax};
-        v2f T2 = {0.0f, 0.0f};
-        auto record3 = [&](auto alpha_tag, auto shared_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
-            constexpr bool ALPHA = decltype(alpha_tag)::value;
-            constexpr bool SHARED = decltype(shared_tag)::value;  // the caller knows that this record shares the plane solved last
-            const v2f r0xy = __builtin_shufflevector(q0, q0, 0, 1), r0zw = __builtin_shufflevector(q0, q0, 2, 3);
-            const v2f r1xy = __builtin_shufflevector(q1, q1, 0, 1), r1zw = __builtin_shufflevector(q1, q1, 2, 3);
-            v2f u2, v2;
-            if (WALK == 4 || WALK == 5) {
-                if (!SHARED && !((sc.plane_share_mask >> k) & 1ull)) {
-                    const PlaneHit a = tri_plane(o, d, make_float4(q2.x, q2.y, q2.z, q2.w)), b = tri_plane(so, sd, make_float4(q2.x, q2.y, q2.z, q2.w));
-                    T2 = (v2f){a.t, b.t};
-                    hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
-                }
-                float u, v, su, sv;
-                tri_uv(PlaneHit{T2.x, hx2.x, hy2.x, hz2.x}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), u, v);
-                tri_uv(PlaneHit{T2.y, hx2.y, hy2.y, hz2.y}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), su, sv);
-                u2 = (v2f){u, su}; v2 = (v2f){v, sv};
-            } else {
-            if (!SHARED && !((sc.plane_share_mask >> k) & 1ull)) {
-                const v2f r2xy = __builtin_shufflevector(q2, q2, 0, 1), r2zw = __builtin_shufflevector(q2, q2, 2, 3);
-                // tri_plane for both rays: den = fma(x, d.x, fma(y, d.y, z * d.z)), num = fma(x, o.x, fma(y, o.y, fma(z, o.z, w)))
-                const v2f den = pk_fma_b<0>(r2xy, dx2, pk_fma_b<1>(r2xy, dy2, pk_mul_b<0>(r2zw, dz2)));
-                const v2f num = pk_fma_b<0>(r2xy, ox2, pk_fma_b<1>(r2xy, oy2, pk_fma_bb<0, 1>(r2zw, oz2, r2zw)));
-                T2 = (v2f){div_f(-num.x, den.x), div_f(-num.y, den.y)};
-                hx2 = pk_fma(T2, dx2, ox2); hy2 = pk_fma(T2, dy2, oy2); hz2 = pk_fma(T2, dz2, oz2);
-            }
-            // tri_uv: u = fma(r0.x, p.x, fma(r0.y, p.y, fma(r0.z, p.z, r0.w))), v likewise from r1
-            u2 = pk_fma_b<0>(r0xy, hx2, pk_fma_b<1>(r0xy, hy2, pk_fma_bb<0, 1>(r0zw, hz2, r0zw)));
-            v2 = pk_fma_b<0>(r1xy, hx2, pk_fma_b<1>(r1xy, hy2, pk_fma_bb<0, 1>(r1zw, hz2, r1zw)));
-            }
-            // hit_margin: min(min(min(u, v), 1 - (u + v)), min(t, tmax - t)) per ray
-            v2f s2, w2;
-            if (WALK == 4 || WALK == 5) {
-                s2 = (v2f){1.0f - (u2.x + v2.x), 1.0f - (u2.y + v2.y)};
-                w2 = (v2f){tmax - T2.x, stmax - T2.y};
-            } else {
-                s2 = (v2f){1.0f, 1.0f} - (u2 + v2);
-                w2 = tmax2 - T2;
-            }
-            float m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), min_raw(T2.x, w2.x));
-            float sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), min_raw(T2.y, w2.y));
-            m = (k == ex0) ? -1.0f : m;
-            sm = (k == sex0) ? -1.0f : sm;
-            sm = (k == sex1) ? -1.0f : sm;
-            if (ALPHA) {
-                const uint32_t ka = __builtin_amdgcn_readfirstlane(k);
-                if (m >= 0.0f && !alpha_test<TEX>(sc, ka, u2.x, v2.x)) m = -1.0f;
-                if (sm >= 0.0f && !alpha_test<TEX>(sc, ka, u2.y, v2.y)) sm = -1.0f;
-            }
-            // only the distance and the id of the best hit are tracked here; its (u, v) are recomputed after the walk (below)
-            const float tc = (m >= 0.0f) ? T2.x : __builtin_inff();
-            const bool better = tc < best_t;
-            best_t = better ? tc : best_t;
-            best = better ? k : best;
-            // max over the records of the shadow ray's margin (a NaN margin leaves it as it is, like the comparison it replaces; only
-            // the sign of the result is read)
-            occ_margin = max_raw(occ_margin, sm);
-        };
-        // The loop exists twice, with and without the alpha test of a candidate: left as a run-time branch inside ONE loop, the
-        // (wave-uniform) flag is turned into a lane mask and back by every record of every scene -- a v_cndmask and a v_cmp, 8.8
-        // cycles of 240 -- to merge the two values of the margins behind the branch.
-        auto walk3 = [&](auto alpha_tag) {
-            v4f a0 = lrec[0], a1 = lrec[1], a2 = lrec[2], b0, b1, b2;
-            uint32_t k = 0;
-            for (; k + 1 < n; k += 2) {
-                b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
-                if (WALK == 5 && ((sc.plane_share_mask >> (k + 1)) & 1ull)) {
-                    // the two triangles of a quad: one plane solve, then both inside tests in ONE basic block (no branch between
-                    // them), so that the scheduler can interleave the two records' chains
-                    record3(alpha_tag, BoolTag<false>{}, k, a0, a1, a2);
-                    a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
-                    record3(alpha_tag, BoolTag<true>{}, k + 1, b0, b1, b2);
-                } else {
-                    record3(alpha_tag, BoolTag<false>{}, k, a0, a1, a2);
-                    a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
-                    record3(alpha_tag, BoolTag<false>{}, k + 1, b0, b1, b2);
-                }
-            }
-            if (k < n) record3(alpha_tag, BoolTag<false>{}, k, a0, a1, a2);
-        };
-        if (has_alpha) walk3(BoolTag<true>{});
-        else walk3(BoolTag<false>{});
-        // (u, v) of the closest hit, once per walk instead of two selects per record: the record's rows from LDS again (a per-lane
-        // address now) and the hit point o + t d with the t the walk kept -- the very operations on the very operands of the walk
-        // (hx2.x = fma(T2.x, d.x, o.x), u2.x = the fma chain over row 0), so the bits are the walk's.
-        if (best != kInvalid) {
-            const v4f q0 = lrec[3 * best], q1 = lrec[3 * best + 1];
-            const float px = __builtin_fmaf(best_t, d.x, o.x), py = __builtin_fmaf(best_t, d.y, o.y), pz = __builtin_fmaf(best_t, d.z, o.z);
-            best_u = __builtin_fmaf(q0.x, px, __builtin_fmaf(q0.y, py, __builtin_fmaf(q0.z, pz, q0.w)));
-            best_v = __builtin_fmaf(q1.x, px, __builtin_fmaf(q1.y, py, __builtin_fmaf(q1.z, pz, q1.w)));
-        }
-    } else if (UNROLL) {
-        // two records per trip on alternating register sets: the one-record software prefetch without the scalar moves that
-        // rotating a single pair of sets costs per record (buffer padded by two records). +5 % in the small force_diffuse
-        // kernel, -3 % in the full-graph kernel, whose 111 KB of code already overflow the instruction cache.
-        float4 a0, a1, a2, b0, b1, b2;
-        load_rec(0, a0, a1, a2);
+    // The loop exists twice, with and without the alpha test of a candidate: left as a run-time branch inside ONE loop, the
+    // (wave-uniform) flag is turned into a lane mask and back by every record of every scene -- a v_cndmask and a v_cmp, 8.8
+    // cycles of 240 -- to merge the two values of the margins behind the branch.
+    auto walk = [&](auto alpha_tag) {
+        v4f a0 = lrec[0], a1 = lrec[1], a2 = lrec[2], b0, b1, b2;
         uint32_t k = 0;
         for (; k + 1 < n; k += 2) {
-            load_rec(k + 1, b0, b1, b2);
-            record(k, a0, a1, a2);
-            load_rec(k + 2, a0, a1, a2);
-            record(k + 1, b0, b1, b2);
+            b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
+            record(alpha_tag, k, a0, a1, a2);
+            a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
+            record(alpha_tag, k + 1, b0, b1, b2);
         }
-        if (k < n) record(k, a0, a1, a2);
-    } else {
-        float4 n0, n1, n2;
-        load_rec(0, n0, n1, n2);
-        for (uint32_t k = 0; k < n; k++) {
-            const float4 r0 = n0, r1 = n1, r2 = n2;
-            load_rec(k + 1, n0, n1, n2);  // prefetch
-            record(k, r0, r1, r2);
-        }
+        if (k < n) record(alpha_tag, k, a0, a1, a2);
+    };
+    if (has_alpha) walk(BoolTag<true>{});
+    else walk(BoolTag<false>{});
+    // (u, v) of the closest hit, once per walk instead of two selects per record: the record's rows from LDS again (a per-lane
+    // address now) and the hit point o + t d with the t the walk kept -- the very operations on the very operands of the walk
+    // (tri_plane's px = fma(t, d.x, o.x), tri_uv's fma chain over row 0), so the bits are the walk's.
+    if (best != kInvalid) {
+        const v4f q0 = lrec[3 * best], q1 = lrec[3 * best + 1];
+        const float px = __builtin_fmaf(best_t, d.x, o.x), py = __builtin_fmaf(best_t, d.y, o.y), pz = __builtin_fmaf(best_t, d.z, o.z);
+        best_u = __builtin_fmaf(q0.x, px, __builtin_fmaf(q0.y, py, __builtin_fmaf(q0.z, pz, q0.w)));
+        best_v = __builtin_fmaf(q1.x, px, __builtin_fmaf(q1.y, py, __builtin_fmaf(q1.z, pz, q1.w)));
     }
     found = best != kInvalid;
     hit.t = found ? best_t : tmax;
@@ -470,6 +315,41 @@ AKR_D void trav_begin(Trav& s, vec3 o, vec3 d, float tmin, float tmax, uint32_t 
     s.active = tmax >= tmin;
 }
 
+// ---- pieces of a step that exist once: trav_step_staged and trav_step below and dinst_trav.h trav_step_inst (a TravI is a Trav) ----
+// Take the nearest pending sibling of the lane's node group; the others wait on the stack as one entry. Returns the child's index
+// (relative to the tree's first node).
+AKR_D uint32_t node_pop(Trav& s, uint32_t* __restrict__ stack, uint32_t depth, TraceCounters& cnt) {
+    const uint32_t j = 31u - (uint32_t)__builtin_clz(s.G);  // nearest pending sibling
+    s.G &= ~(1u << j);
+    if ((s.G >> 24) != 0) {  // the others wait as one entry
+        if (s.sp < depth) {
+            stack[s.sp * 256u] = s.G;
+            s.sp++;
+        } else {
+            cnt.overflow = 1;  // unreachable for a tree scene_build.cpp accepted; kept as a tripwire (akr_pt_stats)
+        }
+    }
+    const uint32_t slot = (j - 24u) ^ (s.octinv4 & 7u);
+    return (s.G & 0xffffffu) + slot;
+}
+// A candidate that passed every test: an any-hit ray is done, a closest-hit ray keeps the smaller t and, among equal t, the lower id.
+AKR_D void hit_commit(Trav& s, bool any_hit, uint32_t gid, float t, float u, float v) {
+    if (any_hit) {
+        s.best = gid;
+        s.T = 0; s.G = 0; s.sp = 0;  // any hit: done
+    } else {
+        const bool better = (s.best == kInvalid) | (t < s.best_t) | ((t == s.best_t) & (gid < s.best));
+        if (better) { s.best_t = t; s.best_u = u; s.best_v = v; s.best = gid; }
+    }
+}
+// A triangle that passed tri_test: the ray's two exclusion slots, the stochastic alpha test, then hit_commit.
+template <bool TEX>
+AKR_D void hit_accept(const DScene& sc, Trav& s, bool any_hit, uint32_t gid, float t, float u, float v) {
+    bool h = (gid != s.ex0) & (gid != s.ex1);
+    if (h && sc.has_alpha) h = alpha_test<TEX>(sc, gid, u, v);
+    if (h) hit_commit(s, any_hit, gid, t, u, v);
+}
+
 // One step of one lane: a triangle test if one is pending, else the next node. MODE 0: closest hit, 1: any hit, 2: `any_rt`
 // decides per lane (the wavefront schedule traces both kinds of ray in one loop).
 // TILE: the launch keeps the first sc.bvh_tile_nodes nodes (the top levels, breadth-first order: host/bvh.cpp) in LDS at `tile`;
@@ -478,10 +358,7 @@ AKR_D void trav_begin(Trav& s, vec3 o, vec3 d, float tmin, float tmax, uint32_t 
 // The same step in two stages: a lane that leaves the node test with leaf triangles tests the first one in the SAME step (two
 // dependent fetches per step, a fifth fewer steps per ray). Same visits in the same order. Measured (round 5): BVH kernel of the
 // textured room 602 -> 630 Msamples/s, 1 M-triangle hall unchanged, 10 M-triangle hall 317 -> 299: used by the kernels of scenes with
-// textures only (AKR_BVH_STAGED: 0 never, 1 those, 2 all).
-#ifndef AKR_BVH_STAGED
-#define AKR_BVH_STAGED 1
-#endif
+// textures only (trav_step below picks it iff TEX).
 template <int MODE, bool TEX, bool TILE = false>
 AKR_D void trav_step_staged(const DScene& sc, Trav& s, uint32_t* __restrict__ stack, TraceCounters& cnt, bool any_rt = false, const uint4* tile = nullptr) {
     const bool any_hit = MODE == 2 ? any_rt : (MODE == 1);
@@ -490,18 +367,7 @@ AKR_D void trav_step_staged(const DScene& sc, Trav& s, uint32_t* __restrict__ st
             s.sp--;
             s.G = stack[s.sp * 256u];
         }
-        const uint32_t j = 31u - (uint32_t)__builtin_clz(s.G);
-        s.G &= ~(1u << j);
-        if ((s.G >> 24) != 0) {
-            if (s.sp < sc.bvh_stack_depth) {
-                stack[s.sp * 256u] = s.G;
-                s.sp++;
-            } else {
-                cnt.overflow = 1;
-            }
-        }
-        const uint32_t slot = (j - 24u) ^ (s.octinv4 & 7u);
-        const uint32_t idx = (s.G & 0xffffffu) + slot;
+        const uint32_t idx = node_pop(s, stack, sc.bvh_stack_depth, cnt);
         const uint4* p = sc.bvh_nodes + (size_t)idx * (kBvhNodeWords / 4);
         uint4 w0, w1, w2, w3;
         if (TILE && idx < sc.bvh_tile_nodes) {
@@ -555,26 +421,13 @@ AKR_D void trav_step_staged(const DScene& sc, Trav& s, uint32_t* __restrict__ st
         float t, u, v;
         bool h = tri_test(s.o, s.d, make_float4(u2f(w0.x), u2f(w0.y), u2f(w0.z), u2f(w0.w)), make_float4(u2f(w1.x), u2f(w1.y), u2f(w1.z), u2f(w1.w)),
                           make_float4(u2f(w2.x), u2f(w2.y), u2f(w2.z), u2f(w2.w)), s.tmin, s.tmax, t, u, v);
-        if (h) {
-            const uint32_t gid = w3.x;
-            h = (gid != s.ex0) & (gid != s.ex1);
-            if (h && sc.has_alpha) h = alpha_test<TEX>(sc, gid, u, v);
-            if (h) {
-                if (any_hit) {
-                    s.best = gid;
-                    s.T = 0; s.G = 0; s.sp = 0;
-                } else {
-                    const bool better = (s.best == kInvalid) | (t < s.best_t) | ((t == s.best_t) & (gid < s.best));
-                    if (better) { s.best_t = t; s.best_u = u; s.best_v = v; s.best = gid; }
-                }
-            }
-        }
+        if (h) hit_accept<TEX>(sc, s, any_hit, w3.x, t, u, v);
     }
     s.active = (s.T != 0) | ((s.G >> 24) != 0) | (s.sp != 0);
 }
 template <int MODE, bool TEX, bool TILE = false>
 AKR_D void trav_step(const DScene& sc, Trav& s, uint32_t* __restrict__ stack, TraceCounters& cnt, bool any_rt = false, const uint4* tile = nullptr) {
-    if constexpr (AKR_BVH_STAGED == 2 || (AKR_BVH_STAGED == 1 && TEX)) {
+    if constexpr (TEX) {
         trav_step_staged<MODE, TEX, TILE>(sc, s, stack, cnt, any_rt, tile);
         return;
     }
@@ -592,18 +445,7 @@ AKR_D void trav_step(const DScene& sc, Trav& s, uint32_t* __restrict__ stack, Tr
             s.sp--;
             s.G = stack[s.sp * 256u];
         }
-        const uint32_t j = 31u - (uint32_t)__builtin_clz(s.G);  // nearest pending sibling
-        s.G &= ~(1u << j);
-        if ((s.G >> 24) != 0) {  // the others wait as one entry
-            if (s.sp < sc.bvh_stack_depth) {
-                stack[s.sp * 256u] = s.G;
-                s.sp++;
-            } else {
-                cnt.overflow = 1;  // unreachable for a tree scene_build.cpp accepted; kept as a tripwire (akr_pt_stats)
-            }
-        }
-        const uint32_t slot = (j - 24u) ^ (s.octinv4 & 7u);
-        const uint32_t idx = (s.G & 0xffffffu) + slot;
+        const uint32_t idx = node_pop(s, stack, sc.bvh_stack_depth, cnt);
         p = sc.bvh_nodes + (size_t)idx * (kBvhNodeWords / 4);
         if (TILE && idx < sc.bvh_tile_nodes) {
             in_tile = true;
@@ -634,7 +476,7 @@ AKR_D void trav_step(const DScene& sc, Trav& s, uint32_t* __restrict__ stack, Tr
         float t, u, v;
         bool h = tri_test(s.o, s.d, make_float4(u2f(w0.x), u2f(w0.y), u2f(w0.z), u2f(w0.w)), make_float4(u2f(w1.x), u2f(w1.y), u2f(w1.z), u2f(w1.w)),
                           make_float4(u2f(w2.x), u2f(w2.y), u2f(w2.z), u2f(w2.w)), s.tmin, s.tmax, t, u, v);
-        if (h) {
+        if (h) {  // hit_accept, written out: as a call here it costs the non-textured BVH kernels of mcmc / gpt 4 to 12 bytes of scratch
             const uint32_t gid = w3.x;
             h = (gid != s.ex0) & (gid != s.ex1);
             if (h && sc.has_alpha) h = alpha_test<TEX>(sc, gid, u, v);

@@ -8,10 +8,6 @@
 #include "drng.h"
 #include "../kernels.h"
 
-#ifndef AKR_TEX_LEAN
-#define AKR_TEX_LEAN 0  // 1 = the kernels of scenes with textures recompute the normal-map frame where it is read too (dbsdf.h: lean)
-#endif
-
 namespace akr {
 
 // ----------------------------------------------------------------------------------------------------------
@@ -356,7 +352,7 @@ AKR_D void stage_scene_tables(const PtParams& p, uint32_t* lds, PtParams& staged
     staged.sc.area_pdf = (const float*)dst[8];
     // Texture-fed materials: a textured hit walks its node list (32 B per node), reads image headers and the raw input record
     // in dependent chains; from LDS each link is a ds_read instead of an L1 / L2 round trip. Texels stay in HBM.
-    // The host stages either all of it or nothing (api.cpp fill_params, scene_build.cpp), so a TEX kernel that stages at all
+    // The host stages either all of it or nothing (api_pt.cpp fill_params, scene_build.cpp), so a TEX kernel that stages at all
     // reads the texture tables through LDS addresses unconditionally.
     // The 16 KB albedo table of the specular layer / coat (three to five trilinear lookups of 8 gathers each per shaded vertex),
     // for the kernels of scenes with textures, whose L1 is busy with texels: textured room 822 -> 861 Msamples/s. The plain
@@ -407,8 +403,8 @@ struct PathRegs {
     vec3 film_rgb;
     float film_w;
     uint32_t c_samples, c_closest, c_shadow, c_shaded;
-    bool carry;  // BVH kernels: the lane's rays of the last intersection phase are still being traced (pt_kernels.hip: AKR_PT_STRAGGLERS)
-    // a vertex whose shading was put off by one iteration (pt_kernels.hip: conductor hits are shaded on even iterations only)
+    bool carry;  // BVH kernels: the lane's rays of the last intersection phase are still being traced (pt_pass.h: AKR_PT_STRAGGLERS)
+    // a vertex whose shading was put off by one iteration (pt_pass.h: conductor hits are shaded on even iterations only)
     bool deferred;
     uint32_t d_gid;
     float d_u, d_v;
@@ -564,10 +560,8 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
                 vec3 u_bsdf = next_3d<PMJ>(p, r.smp);
                 // sample_surface_and_shade_direct, pt.rs:297-323
                 ShadePoint sp;
-                shade_point_init(sp, mat, si.frame, si.ng, force_diffuse, /*lean=*/!TEX || AKR_TEX_LEAN != 0, /*absent=*/ABSENT);
-#ifndef AKR_NO_WO_CACHE  // (A/B switch of tools/r2_ab.sh)
+                shade_point_init(sp, mat, si.frame, si.ng, force_diffuse, /*lean=*/!TEX, /*absent=*/ABSENT);
                 if (FD != 1) shade_point_cache_wo(sp, mat, sc.ggx_table, wo);
-#endif
                 if (dl.valid) {
                     BsdfEval e = shade_evaluate(sp, mat, sc.ggx_table, wo, dl.wi);
                     float w = mis_weight(dl.pdf, e.pdf);

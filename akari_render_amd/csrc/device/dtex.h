@@ -15,10 +15,6 @@
 
 namespace akr {
 
-#ifndef AKR_TEX_FAST_UNORM
-#define AKR_TEX_FAST_UNORM 1
-#endif
-
 // ---- images ------------------------------------------------------------------------------------------------------
 enum : uint32_t { IMG_RGBA8 = 0, IMG_RGBA32F = 1 };
 enum : uint32_t { TEXF_NEAREST = 0, TEXF_LINEAR = 1 };
@@ -61,7 +57,7 @@ AKR_HD bool tex_wrap(int& i, int n, uint32_t mode) {
 // division algorithm with a reciprocal known in advance, three operations instead of the eleven of an IEEE division and the
 // same bits for all 256 bytes (tests/test_textures.py checks the identity exhaustively; four taps x four channels per lookup).
 AKR_HD float unorm8(uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__) && AKR_TEX_FAST_UNORM
+#if defined(__HIP_DEVICE_COMPILE__)
     const float y = 0.003921568859368563f, fb = (float)b;
     const float q = fb * y;
     return __builtin_fmaf(__builtin_fmaf(-255.0f, q, fb), y, q);
@@ -358,9 +354,6 @@ AKR_HD void eval_material_graph(const TexScene& ts, uint32_t first, uint32_t cou
 // `uv` and folded. `m` must hold the material's folded record on entry.
 AKR_HD void material_at(const TexScene& ts, uint32_t material, vec2 uv, DMaterial& m) {
     if (!(m.flags & MF_TEXTURED)) return;
-#if defined(AKR_DIAG_NO_GRAPH) && defined(__HIP_DEVICE_COMPILE__)  // diagnostic builds only (wrong images): what graph evaluation + re-folding cost
-    return;
-#endif
 #if defined(AKR_SPEC_GRAPHS)
     spec_material_at(ts, material, uv, m);
 #else
@@ -368,9 +361,7 @@ AKR_HD void material_at(const TexScene& ts, uint32_t material, vec2 uv, DMateria
     uint32_t map[IN_COUNT];
     for (uint32_t i = 0; i < IN_COUNT; i++) map[i] = m.tex_input[i];
     MatInputs in = ts.mat_inputs[material];
-#if !(defined(AKR_DIAG_NO_EVAL) && defined(__HIP_DEVICE_COMPILE__))  // diagnostic: re-fold the raw inputs without evaluating the graph
     eval_material_graph(ts, first, count & kTexCountMask, uv, in);
-#endif
     const uint32_t keep = m.flags & (MF_TEXTURED | MF_ALPHA_TEXTURED);
     fold_inputs(in, m);
     m.flags |= keep;

@@ -33,10 +33,7 @@ namespace akr {
 #ifndef AKR_PT_MIN_WAVES_BVH_TEX
 #define AKR_PT_MIN_WAVES_BVH_TEX 3  // BVH kernels of such a scene (399 -> 517)
 #endif
-// (AKR_WALK_*, AKR_PT_PARK_*, AKR_BVH_TILE, AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too)
-#ifndef AKR_PT_MERGED_RAYS
-#define AKR_PT_MERGED_RAYS 1  // BVH path: a lane starts its shadow ray the moment its closest-hit ray is done (one loop)
-#endif
+// (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_plan)
 // ABSENT: lobes the scene cannot have (dbsdf.h AB_*). The precompiled kernels know 0 and AB_SIMPLE (PtParams.simple_scene: scenes without
 // textures); a per-scene kernel gets the mask of its scene.
 // INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h); BVH kernels without STAGE / DEFER only.
@@ -52,7 +49,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
     if (STAGE) stage_scene_tables<BVH, TEX, !BVH && !FD && TEX>(p, lds_stack, staged);
     const PtParams& q = STAGE ? staged : p;
     const DScene& sc = q.sc;
-    constexpr bool TILE = BVH && !TEX && !INST && AKR_BVH_TILE != 0;
+    constexpr bool TILE = BVH && !TEX && !INST;  // the top of the tree in LDS (disect.h: TILE), as many nodes as the launcher finds room for
     constexpr uint32_t STRAG = BVH ? (INST ? AKR_PT_STRAGGLERS_INST : (TEX ? AKR_PT_STRAGGLERS_TEX : AKR_PT_STRAGGLERS)) : 0;
     const uint4* tile = (const uint4*)(lds_stack + p.tile_offset);
     if (TILE) {  // nodes 0 .. bvh_tile_nodes - 1
@@ -61,26 +58,16 @@ AKR_D void pt_pass_body(const PtParams& p) {
         for (uint32_t i = threadIdx.x; i < p.sc.bvh_tile_nodes * kBvhNodeWords; i += 256u) l[i] = g[i];
         __syncthreads();
     }
-    constexpr int WALK = FD ? AKR_WALK_FD : (TEX ? AKR_WALK_TEX : AKR_WALK_FULL);
     const float4* lds_recs = nullptr;
-    if (!BVH && (WALK == 1 || WALK >= 3)) {  // the triangle records behind the staged tables (launch_pt_pass sizes the block)
+    if (!BVH) {  // the exhaustive walk reads the triangle records from LDS, behind the staged tables (pt_lds_plan sizes the block)
         uint32_t* l = lds_stack + (p.stage_total >> 2);
         const uint32_t* g = (const uint32_t*)p.sc.woop;
         for (uint32_t i = threadIdx.x; i < (p.sc.n_tris + 2u) * 12u; i += 256u) l[i] = g[i];
         __syncthreads();
         lds_recs = (const float4*)l;
     }
-    // Which 256 work items a workgroup takes. Workgroups are dealt to the chip's 8 XCDs round-robin (workgroup b runs on XCD b % 8)
-    // and every XCD has its own 4 MiB L2: with the identity mapping each XCD sees every eighth 32x8-pixel strip of the whole frame,
-    // so all eight L2s hold the same mix of the scene. BANDS gives XCD x the x-th contiguous eighth of the item space (items
-    // enumerate the rank's tiles in row-major order: a horizontal band of the image), so that an L2 only has to hold the part of
-    // the tree its band's rays walk. Only the assignment of pixels to workgroups changes: films are the same bit for bit.
-    uint32_t vblock = blockIdx.x;
-    if (BVH && AKR_PT_XCD_BANDS) {
-        const uint32_t nb = gridDim.x, xcd = blockIdx.x & 7u, local = blockIdx.x >> 3;
-        vblock = xcd * (nb >> 3) + (xcd < (nb & 7u) ? xcd : (nb & 7u)) + local;
-    }
-    const uint32_t item = vblock * 256u + threadIdx.x;
+    // (an XCD-aware assignment of work items to workgroups was measured and not adopted: HISTORY.md, profiles/r4_ab_walk.txt)
+    const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     uint32_t px = 0, py = 0;
     const bool in_frame = item < p.n_items && item_to_pixel(p, item, px, py);
     const uint32_t pix = px + py * p.width;
@@ -89,7 +76,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
     if (PMJ && p.bn_offset != 0) pmj_bluenoise_stage(p, px, py);  // before the first draw (path_regs_init generates the first camera ray)
     PathRegs r;
     path_regs_init<PMJ>(r, q, in_frame, pix, sx, sy);
-    constexpr bool PARK = !FD && (TEX ? AKR_PT_PARK_TEX != 0 : (BVH ? AKR_PT_PARK_BVH != 0 : AKR_PT_PARK_FULL != 0));
+    constexpr bool PARK = !FD && TEX;  // cold path state in LDS while a vertex is shaded (dpath.h: PARK)
     uint32_t* park = lds_stack + p.park_offset + threadIdx.x;
     if (PARK) {
         park_put(park, PK_PIX, pix);
@@ -113,7 +100,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                 static_assert(kCarrySlotsInstanced == kCarrySlotsInst, "LDS plan and traversal disagree");
                 trace_pair_inst<TEX, STRAG>(sc, r.has_ray, r.ro, r.rd, r.ray_ex0, r.has_shadow, r.s_o, r.s_d, r.s_tmax, r.s_ex0, r.s_ex1, r.carry, hit, found, occluded, tc.stack,
                                             lds_stack + p.carry_offset + threadIdx.x, tc.cnt);
-            } else if (BVH && AKR_PT_MERGED_RAYS && STRAG > 0) {
+            } else if (BVH && STRAG > 0) {
                 // The merged loop below ends when the wave's LONGEST pair of rays is done: on the 10 M-triangle hall 40 % of its
                 // lane-steps do work, the rest is lanes waiting for the tail of the ray-length distribution. Here the phase ends
                 // when at most 1/n of the lanes that entered it are still tracing. Those lanes keep their traversal -- position
@@ -167,7 +154,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     cy[8 * 256] = phase;
                     if (phase == 1u) { cy[9 * 256] = f2u(hit.t); cy[10 * 256] = f2u(hit.u); cy[11 * 256] = f2u(hit.v); cy[12 * 256] = hit.gid; }
                 }
-            } else if (BVH && AKR_PT_MERGED_RAYS) {
+            } else if (BVH) {
                 // Both rays of the iteration through ONE traversal loop: a lane whose closest-hit ray is done goes straight on
                 // to its shadow ray, so the wave pays for its longest PAIR of rays instead of its longest closest-hit ray plus
                 // its longest shadow ray (rays of a wave differ in length by an order of magnitude; the loop is the same code for
@@ -191,15 +178,9 @@ AKR_D void pt_pass_body(const PtParams& p) {
                         }
                     }
                 }
-            } else if (BVH) {
-                if (r.has_ray) found = trace_bvh<false, TEX>(sc, r.ro, r.rd, 0.0f, 1e20f, r.ray_ex0, kInvalid, hit, tc.stack, tc.cnt);
-                if (r.has_shadow) {
-                    Hit sh;
-                    occluded = trace_bvh<true, TEX>(sc, r.s_o, r.s_d, 0.0f, r.s_tmax, r.s_ex0, r.s_ex1, sh, tc.stack, tc.cnt);
-                }
             } else {
-                trace_pair_exhaustive<TEX, FD || (!TEX && AKR_WALK_FULL_UNROLL != 0), WALK>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f,
-                                            r.s_ex0, r.s_ex1, hit, found, occluded, lds_recs);
+                trace_pair_exhaustive<TEX>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1, hit, found,
+                                           occluded, lds_recs);
             }
             if (DEFER) {
                 // A scene with one metal among diffuse surfaces: every wave carries a few lanes on the metal at every
@@ -217,7 +198,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     r.deferred = false;
                 } else if (r.has_ray && found && (iteration & q.defer_metal)) {
                     const uint32_t mat = f2u(sc.shade[(size_t)hit.gid * SHADE_ROWS + 6].y);
-                    if (sc.materials[mat].flags & q.defer_flags) {  // MF_EVAL_METAL and / or MF_TEXTURED, the host's choice (api.cpp fill_params)
+                    if (sc.materials[mat].flags & q.defer_flags) {  // MF_EVAL_METAL and / or MF_TEXTURED, the host's choice (api_pt.cpp fill_params)
                         r.d_gid = hit.gid; r.d_u = hit.u; r.d_v = hit.v;
                         r.deferred = true;
                         r.has_ray = false;  // path_step resolves the shadow ray and finishes the previous sample, no more

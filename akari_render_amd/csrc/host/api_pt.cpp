@@ -52,7 +52,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
             p.bluenoise = se->ctx->bluenoise.as<uint16_t>();
         }
     }
-    {  // LDS staging of the tables the shading phase gathers from (pt_kernels.hip: STAGE)
+    {  // LDS staging of the tables the shading phase gathers from (device/pt_pass.h: STAGE)
         const CompiledScene& cs = s->cs;
         const bool bvh = !cs.bvh_nodes.empty() || cs.instanced.on;
         // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
@@ -99,7 +99,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         }
         p.simple_scene = (simple && se->simple_kernels_option && !cs.env.on) ? 1u : 0u;  // (no SIMPLE kernels with an environment light)
     }
-    {   // hits on "expensive" materials on even iterations only (pt_kernels.hip: DEFER): pays when SOME materials are expensive and
+    {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
         // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
         // instead a shader graph to evaluate at the hit.
         const CompiledScene& cs = s->cs;

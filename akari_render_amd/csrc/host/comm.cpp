@@ -15,7 +15,7 @@
 #include "../../../include/akari_hip.h"
 
 namespace akr {
-// defined in api.cpp
+// defined in api_common.cpp and api_aux.cpp
 int32_t film_device_view(akr_film* film, int* device, hipStream_t* stream, float** data, size_t* n_floats);
 int32_t api_fail(int32_t code, const std::string& msg);
 int32_t gpt_reduce_view(akr_gpt_session* se, akr_film** film, int* device, hipStream_t* stream, float** sums, size_t* n_sums);

@@ -747,7 +747,7 @@ void compile_scene(const FlatScene& flat, CompiledScene& out) {
     // (AKR_FORCE_BVH=1 builds the BVH for tiny scenes too: lets the tests run both intersectors on scenes/cbox)
     const TuningOptions tune = tuning();
     const uint32_t kExhaustiveMax = tune.force_bvh ? 0u : 64u;
-    // the exhaustive kernels stage the shading tables in LDS (pt_kernels.hip): a tiny mesh with a huge material list goes the BVH way
+    // the exhaustive kernels stage the shading tables in LDS (device/pt_pass.h: STAGE): a tiny mesh with a huge material list goes the BVH way
     size_t stage = 0;
     for (size_t b : {out.shade.size() * 4, out.normals.size() * 4, out.inst.size() * 4, out.materials.size() * sizeof(DMaterial),
                      (size_t)out.n_lights * 32, out.area_entries.size() * 16, out.light_pdf.size() * 4, out.area_pdf.size() * 4,

@@ -9,34 +9,10 @@
 
 namespace akr {
 
-// ---- build switches of k_pt_pass (pt_kernels.hip); each default is the winner of a same-box A/B run ----
-#ifndef AKR_WALK_FD
-#define AKR_WALK_FD 4    // exhaustive pair walk of the force_diffuse kernel: which form of the walk (disect.h: WALK; 4 measured best in round 4)
-#endif
-#ifndef AKR_WALK_FULL
-#define AKR_WALK_FULL 4  // the same for the full-graph exhaustive kernels of scenes without textures
-#endif
-#ifndef AKR_WALK_TEX
-#define AKR_WALK_TEX 4   // the same for the exhaustive kernels of scenes with textures (round 3: 0, the scalar-cache walk)
-#endif
-#ifndef AKR_WALK_FULL_UNROLL
-#define AKR_WALK_FULL_UNROLL 1  // full-graph exhaustive kernels: two records per trip of the pair walk, as the force_diffuse kernel does
-#endif
-#ifndef AKR_PT_PARK_FULL
-#define AKR_PT_PARK_FULL 0  // exhaustive full-graph kernels without textures: cold path state in LDS while a vertex is shaded (dpath.h: PARK)
-#endif
-#ifndef AKR_PT_PARK_BVH
-#define AKR_PT_PARK_BVH 0   // the same for the BVH full-graph kernels without textures
-#endif
-#ifndef AKR_BVH_TILE
-#define AKR_BVH_TILE 1  // BVH kernels: 1 = the top of the tree in LDS (disect.h: TILE), as many nodes as launch_pt_pass finds room for
-#endif
-#ifndef AKR_PT_XCD_BANDS
-#define AKR_PT_XCD_BANDS 0  // BVH kernels: 1 = XCD x renders the x-th contiguous eighth of the launch's work items (pt_kernels.hip)
-#endif
+// ---- build switches of k_pt_pass (device/pt_pass.h); each default is the winner of a same-box A/B run ----
 #ifndef AKR_PT_STRAGGLERS
 #define AKR_PT_STRAGGLERS 8  // BVH kernels: n > 0 = an intersection phase ends when at most 1/n of the lanes that entered it are still
-                             // tracing; those lanes keep their traversal and go on in the next phase (see k_pt_pass)
+                             // tracing; those lanes keep their traversal and go on in the next phase (device/pt_pass.h)
 #endif
 #ifndef AKR_PT_STRAGGLERS_TEX
 #define AKR_PT_STRAGGLERS_TEX 0  // the same for the BVH kernels of scenes with textures (measured separately)
@@ -44,31 +20,28 @@ namespace akr {
 #ifndef AKR_PT_STRAGGLERS_INST
 #define AKR_PT_STRAGGLERS_INST 8  // the same for the kernels of scenes kept as meshes + instances (dinst_trav.h trace_pair_inst)
 #endif
-#ifndef AKR_PT_PARK_TEX
-#define AKR_PT_PARK_TEX 1   // the same for the full-graph kernels of scenes with textures (exhaustive and BVH)
-#endif
 // LDS columns per lane (one word per slot, slot s of lane i at word s * 256 + i): cold path state parked while a vertex is shaded
-// (dpath.h: PARK), and a traversal carried over to the next intersection phase (pt_kernels.hip).
+// (dpath.h: PARK), and a traversal carried over to the next intersection phase (device/pt_pass.h).
 constexpr uint32_t kParkSlots = 16, kParkSlotsNoDefer = 13;  // dpath.h: PK_*
-constexpr uint32_t kCarrySlots = 13;                         // pt_kernels.hip: a carried traversal
+constexpr uint32_t kCarrySlots = 13;                         // device/pt_pass.h: a carried traversal
 constexpr uint32_t kCarrySlotsInstanced = 16;                // ... of a scene kept as meshes + instances (dinst_trav.h)
 constexpr size_t kBlueNoiseColumnBytes = 48 * 256 * 2;          // dpath.h pmj_bluenoise_stage: one u16 per array and lane
 // What a k_pt_pass launch keeps in LDS beyond traversal stacks, staged tables and graph values, by kernel instantiation
 // (BVH / force_diffuse / textured scene / conductor deferral): used by the launcher and by the host's staging decision.
+// The exhaustive kernels keep the triangle records there (disect.h trace_pair_exhaustive), the full-graph kernels of scenes with
+// textures park cold path state (dpath.h: PARK), the BVH kernels of scenes without textures keep the top of the tree (disect.h: TILE).
 struct PtLdsPlan {
     size_t recs_bytes, park_bytes, carry_bytes;
     bool tile;
 };
 inline PtLdsPlan pt_lds_plan(bool bvh, bool fd, bool tex, bool defer, uint32_t n_tris) {
     PtLdsPlan pl;
-    const int walk = fd ? AKR_WALK_FD : (tex ? AKR_WALK_TEX : AKR_WALK_FULL);
-    const bool recs_in_lds = !bvh && (walk == 1 || walk >= 3);
-    const bool park = !fd && (tex ? AKR_PT_PARK_TEX != 0 : (bvh ? AKR_PT_PARK_BVH != 0 : AKR_PT_PARK_FULL != 0));
+    const bool park = !fd && tex;
     const bool strag = bvh && (tex ? AKR_PT_STRAGGLERS_TEX : AKR_PT_STRAGGLERS) > 0;
-    pl.recs_bytes = recs_in_lds ? (size_t)(n_tris + 2) * 48 : 0;
+    pl.recs_bytes = !bvh ? (size_t)(n_tris + 2) * 48 : 0;
     pl.park_bytes = park ? (size_t)(defer ? kParkSlots : kParkSlotsNoDefer) * 256 * 4 : 0;
     pl.carry_bytes = strag ? (size_t)kCarrySlots * 256 * 4 : 0;
-    pl.tile = bvh && !tex && AKR_BVH_TILE != 0;
+    pl.tile = bvh && !tex;
     return pl;
 }
 // a workgroup's share of the CU's 160 KB: a quarter (four waves per SIMD), a third for the kernels of textured scenes (three)
@@ -114,12 +87,12 @@ struct PtParams {
     uint32_t stage_bytes[13];  // [12]: the GGX albedo table (full-graph exhaustive kernels)
     uint32_t stage_total;
     uint32_t simple_scene;   // no coat, no transmission, no normal map, no glass material, no textures: the full-graph kernels without that code
-    uint32_t defer_metal;    // iterations with (iteration & defer_metal) != 0 put hits on "expensive" materials off by one iteration (pt_kernels.hip: DEFER)
+    uint32_t defer_metal;    // iterations with (iteration & defer_metal) != 0 put hits on "expensive" materials off by one iteration (device/pt_pass.h: DEFER)
     uint32_t defer_flags;    // ... expensive = (DMaterial.flags & defer_flags) != 0: MF_EVAL_METAL (the conductor lobe), MF_TEXTURED (a graph to evaluate)
     uint32_t tex_slots;      // TEX scenes: value slots per lane of the graph evaluation (LDS, after the launch's other blocks)
     uint32_t tile_offset;    // BVH kernels with a node tile (disect.h: TILE): word offset of the tile; its size is sc.bvh_tile_nodes
     uint32_t park_offset;    // kernels that park cold path state in LDS while shading (dpath.h: PARK): word offset of the columns
-    uint32_t carry_offset;   // BVH kernels that let a wave's longest rays run on into the next iteration (pt_kernels.hip): their columns
+    uint32_t carry_offset;   // BVH kernels that let a wave's longest rays run on into the next iteration (device/pt_pass.h): their columns
     uint32_t bn_offset;      // pmj02bn sampler, k_pt_pass: word offset of the lanes' blue-noise columns (48 x 256 x 2 B, dpath.h), 0 = the table in HBM
     // wavefront schedule, option wf_sort: the ray queues are sorted by (Morton code of the origin in the scene's box, octant of the direction)
     uint32_t wf_sort;

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256, pt_pass_min_waves(BVH, FD, TEX)) void k_pt_pas
     pt_pass_body<BVH, FD, TEX, PMJ, STAGE, DEFER, SIMPLE ? AB_SIMPLE : 0u, false, ENV>(p);
 }
 
-// Dynamic LDS of a k_pt_pass launch and where its blocks start: [traversal stacks][staged tables][triangle records (WALK 1)][node
+// Dynamic LDS of a k_pt_pass launch and where its blocks start: [traversal stacks][staged tables][triangle records (exhaustive kernels)][node
 // tile][park columns][carry columns][blue-noise columns (pmj02bn)][graph values]. Shared by the precompiled kernels, the per-scene
 // kernels and the instanced-scene kernels (pt_inst_kernel.h).
 inline PtParams pt_pass_layout(const PtParams& p, size_t& lds, uint32_t& blocks) {
