@@ -107,6 +107,11 @@ class EnvironmentDesc(C.Structure):
                 ("color", C.c_float * 3), ("strength", C.c_float), ("rotation", C.c_float * 9), ("_pad2", C.c_uint32)]
 
 
+class LensDesc(C.Structure):
+    """akr_lens_desc: the camera's thin lens (radius 0 = a pinhole)."""
+    _fields_ = [("radius", C.c_float), ("focal_distance", C.c_float)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("c2w", C.c_float * 16), ("fov", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -467,6 +472,14 @@ class EnvironmentData:
 
 
 @dataclass
+class LensData:
+    """The thin lens of a scene's camera: a disk of `radius` in the camera's x / y plane, focused `focal_distance` along the optical axis
+    (lens_radius and focal_length of the reference's PerspectiveCamera)."""
+    radius: float
+    focal_distance: float
+
+
+@dataclass
 class CameraData:
     c2w: np.ndarray  # (16,) f32 column-major
     fov: float  # radians
@@ -485,6 +498,7 @@ class SceneData:
     material_names: List[str] = field(default_factory=list)
     images: List["ImageData"] = field(default_factory=list)
     environment: Optional[EnvironmentData] = None  # set by capi.Scene through akr_scene_set_environment (not part of akr_scene_desc)
+    lens: Optional[LensData] = None  # set by capi.Scene through akr_scene_set_lens (not part of akr_scene_desc / akr_camera_desc)
 
     def n_triangles(self) -> int:
         return sum(self.meshes[i.mesh].indices.shape[0] for i in self.instances)

@@ -41,7 +41,7 @@ EXPORTS = [
     "akr_device_count", "akr_comm_unique_id", "akr_comm_create", "akr_comm_wrap", "akr_comm_destroy", "akr_film_reduce",
     "akr_pt_kernel_info", "akr_scene_spec_source", "akr_host_spec_compile", "akr_host_spec_compile_text",
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
-    "akr_scene_set_environment", "akr_scene_get_environment",
+    "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -50,7 +50,7 @@ TEST_EXPORTS = [
     "akr_probe_surface_interaction", "akr_probe_material_inputs", "akr_host_decode_png", "akr_host_decode_jpeg",
     "akr_host_decode_exr", "akr_host_decode_tiff", "akr_host_decode_dds", "akr_host_pmj02bn_tables",
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
-    "akr_probe_env_sample", "akr_probe_env_pdf",
+    "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
 ]
 
 
@@ -88,7 +88,7 @@ def lib() -> C.CDLL:
     L.akr_struct_size.argtypes = [C.c_int32]
     for sid, cls in enumerate((abi.MeshDesc, abi.InstanceDesc, abi.MaterialDesc, abi.CameraDesc, abi.SceneDesc, abi.PtConfig, abi.PtStats, abi.SceneInfo,
                                abi.KernelInfo, abi.AovConfig, abi.GptConfig, abi.McmcConfig, abi.McmcResult, abi.McmcPartial,
-                               abi.EnvironmentDesc), start=1):
+                               abi.EnvironmentDesc, abi.LensDesc), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -111,6 +111,10 @@ def lib() -> C.CDLL:
     proto("akr_scene_get_light", vp, u32, up, fp, fp)
     proto("akr_scene_set_environment", vp, C.POINTER(abi.EnvironmentDesc))
     proto("akr_scene_get_environment", vp, C.POINTER(abi.EnvironmentDesc))
+    proto("akr_scene_set_lens", vp, C.POINTER(abi.LensDesc))
+    proto("akr_scene_get_lens", vp, C.POINTER(abi.LensDesc))
+    proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
+    proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_env_sample", vp, vp, u32, fp, fp)
     proto("akr_probe_env_pdf", vp, vp, u32, fp, fp)
     proto("akr_scene_get_ggx_table", vp, fp)
@@ -258,6 +262,9 @@ class Scene:
             env = getattr(source, "environment", None)
             if env is not None:
                 self._set_environment_data(env)
+            lens = getattr(source, "lens", None)
+            if lens is not None:
+                self.set_lens(lens.radius, lens.focal_distance)
 
     def close(self):
         if self.h:
@@ -284,11 +291,11 @@ class Scene:
         return buf.value.decode()
 
     def spec_compile(self, bvh: bool = False, pmj: bool = False, stage: bool = True, defer: bool = False, min_waves: int = 3, arch: str = "gfx950", inst: bool = False,
-                     env: bool = False) -> int:
+                     env: bool = False, lens: bool = False) -> int:
         """akr_host_spec_compile: hiprtc-compiles the scene's per-scene kernel (no device needed); returns the code object's size."""
         nbytes = C.c_uint64()
         log = C.create_string_buffer(4096)
-        flags = (1 if bvh else 0) | (2 if pmj else 0) | (4 if stage else 0) | (8 if defer else 0) | (16 if inst else 0) | (32 if env else 0)
+        flags = (1 if bvh else 0) | (2 if pmj else 0) | (4 if stage else 0) | (8 if defer else 0) | (16 if inst else 0) | (32 if env else 0) | (64 if lens else 0)
         check(lib().akr_host_spec_compile(self.h, flags, min_waves, arch.encode(), C.byref(nbytes), log, 4096))
         return nbytes.value
 
@@ -328,6 +335,36 @@ class Scene:
             im = np.ctypeslib.as_array(d.texels, shape=(n,)).astype(np.float32, copy=True).reshape(d.height, d.width, 4)
             return abi.EnvironmentData(image=im, strength=float(d.strength), rotation=rot, filter=int(d.filter))
         return abi.EnvironmentData(color=tuple(float(c) for c in d.color), strength=float(d.strength), rotation=rot)
+
+    def set_lens(self, radius: Optional[float] = None, focal_distance: float = 0.0):
+        """akr_scene_set_lens: a thin lens of `radius`, focused `focal_distance` along the optical axis. radius None or 0: removes the lens."""
+        if radius is None:
+            check(lib().akr_scene_set_lens(self.h, None))
+            return
+        d = abi.LensDesc(float(radius), float(focal_distance))
+        check(lib().akr_scene_set_lens(self.h, C.byref(d)))
+
+    def lens(self) -> Optional[abi.LensData]:
+        """akr_scene_get_lens: the lens as the scene holds it (None without one)."""
+        d = abi.LensDesc()
+        check(lib().akr_scene_get_lens(self.h, C.byref(d)))
+        return abi.LensData(float(d.radius), float(d.focal_distance)) if d.radius > 0.0 else None
+
+    def _camera_rays(self, fn, head, pixels, u_filter, u_lens, filter_type, filter_radius):
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1, 2)
+        n = px.shape[0]
+        u = np.ascontiguousarray(np.concatenate([np.asarray(u_filter, np.float32).reshape(n, 2), np.asarray(u_lens, np.float32).reshape(n, 2)], axis=1))
+        out = np.zeros((n, 6), np.float32)
+        check(fn(*head, int(filter_type), float(filter_radius), n, px.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(u), _fp(out)))
+        return out
+
+    def host_lens_ray(self, pixels, u_filter, u_lens, filter_type: int = 0, filter_radius: float = 0.5) -> np.ndarray:
+        """akr_host_lens_ray (test hook, no GPU): the camera rays (n, 6) = o.xyz, d.xyz of (n, 2) pixels for given u_filter, u_lens (n, 2 each)."""
+        return self._camera_rays(lib().akr_host_lens_ray, (self.h,), pixels, u_filter, u_lens, filter_type, filter_radius)
+
+    def probe_camera_rays(self, pixels, u_filter, u_lens, filter_type: int = 0, filter_radius: float = 0.5) -> np.ndarray:
+        """akr_probe_camera_rays (test hook): the same on the device."""
+        return self._camera_rays(lib().akr_probe_camera_rays, (self.ctx.h, self.h), pixels, u_filter, u_lens, filter_type, filter_radius)
 
     def probe_env_sample(self, u: np.ndarray) -> np.ndarray:
         """akr_probe_env_sample (test hook): (n, 2) uniform points -> (n, 5) wi.xyz, pdf, valid."""
@@ -428,11 +465,11 @@ class Scene:
         c = abi.CameraDesc()
         check(lib().akr_scene_get_camera(self.h, C.byref(c)))
         cam = abi.CameraData(np.array(list(c.c2w), dtype=np.float32), float(c.fov), c.width, c.height)
-        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment())
+        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment(), lens=self.lens())
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels")."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop)."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 

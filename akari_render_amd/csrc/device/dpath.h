@@ -33,7 +33,7 @@ AKR_D bool item_to_pixel(const PtParams& p, uint32_t item, uint32_t& px, uint32_
 }
 
 // film.rs:32-49
-AKR_D vec2 filter_sample(const PtParams& p, vec2 u) {
+AKR_HD vec2 filter_sample(const PtParams& p, vec2 u) {
     if (p.filter_type == 0) return mk2((u.x - 0.5f) * p.filter_radius, (u.y - 0.5f) * p.filter_radius);
     float width = p.filter_radius;
     float sigma = width / 3.0f;
@@ -193,8 +193,8 @@ AKR_D void sampler_end_pass(const PtParams& p, Sampler& s) {
     }  // pmj02bn: the state is stored as it is; dim is reset by the next start()
 }
 
-// camera/mod.rs:70-103
-AKR_D void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec3& o, vec3& d) {
+// the pinhole direction in camera space of film sample (pixel, u_filter): camera/mod.rs:70-96. Shared by the pinhole and the lens.
+AKR_HD vec3 camera_space_dir(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter) {
     vec2 fpixel = mk2((float)px + 0.5f, (float)py + 0.5f);
     vec2 offset = filter_sample(p, u_filter);
     vec2 pf = mk2(fpixel.x + offset.x, fpixel.y + offset.y);
@@ -203,7 +203,11 @@ AKR_D void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u
     float qy = ((m[1] * pf.x + m[5] * pf.y) + m[9] * 0.0f) + m[13] * 1.0f;
     float qz = ((m[2] * pf.x + m[6] * pf.y) + m[10] * 0.0f) + m[14] * 1.0f;
     float qw = ((m[3] * pf.x + m[7] * pf.y) + m[11] * 0.0f) + m[15] * 1.0f;
-    d = normalize(div_s(mk3(qx, qy, qz), qw));
+    return normalize(div_s(mk3(qx, qy, qz), qw));
+}
+// camera/mod.rs:70-103 (AKR_HD: the test hook akr_host_lens_ray runs this text on the host)
+AKR_HD void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec3& o, vec3& d) {
+    d = camera_space_dir(p, px, py, u_filter);
     o = mk3(0, 0, 0);
     if (!p.c2w_identity) {
         const float* c = p.c2w;
@@ -212,9 +216,55 @@ AKR_D void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u
                 (c[2] * d.x + c[6] * d.y) + c[10] * d.z);
     }
 }
-template <bool PMJ>
+// The thin lens (the reference stores lens_radius and focal_length in PerspectiveCameraData, camera/mod.rs:105-118,
+// and leaves them unused). concentric_disk: Shirley-Chiu, unit square -> unit disk.
+AKR_HD vec2 concentric_disk(vec2 u) {
+    const float sx = 2.0f * u.x - 1.0f, sy = 2.0f * u.y - 1.0f;
+    if (sx == 0.0f && sy == 0.0f) return mk2(0.0f, 0.0f);
+    const float kPiOver4 = 0.785398163397448310f, kPiOver2 = 1.570796326794896619f;
+    float r, theta;
+    if (abs_f(sx) > abs_f(sy)) {
+        r = sx;
+        theta = kPiOver4 * (sy / sx);
+    } else {
+        r = sy;
+        theta = kPiOver2 - kPiOver4 * (sx / sy);
+    }
+    float sn, cs;
+    sincos_f(theta, sn, cs);
+    return mk2(r * cs, r * sn);
+}
+// generate_ray_from with a lens of radius p.lens_radius > 0 focused at distance p.lens_focal along the optical axis: the pinhole
+// direction dc in camera space meets the plane of focus at dc * ft; the ray leaves the lens point l towards that point.
+AKR_HD void generate_ray_lens_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& o, vec3& d) {
+    const vec3 dc = camera_space_dir(p, px, py, u_filter);
+    const vec2 ab = concentric_disk(u_lens);
+    const vec3 l = mk3(p.lens_radius * ab.x, p.lens_radius * ab.y, 0.0f);
+    const float ft = p.lens_focal / (-dc.z);
+    const vec3 p_focus = dc * ft;
+    d = normalize(p_focus - l);
+    o = l;
+    if (!p.c2w_identity) {  // c2w . point(l) and c2w . vector(d)
+        const float* c = p.c2w;
+        const float ox = ((c[0] * l.x + c[4] * l.y) + c[8] * l.z) + c[12] * 1.0f;
+        const float oy = ((c[1] * l.x + c[5] * l.y) + c[9] * l.z) + c[13] * 1.0f;
+        const float oz = ((c[2] * l.x + c[6] * l.y) + c[10] * l.z) + c[14] * 1.0f;
+        const float ow = ((c[3] * l.x + c[7] * l.y) + c[11] * l.z) + c[15] * 1.0f;
+        o = div_s(mk3(ox, oy, oz), ow);
+        d = mk3((c[0] * d.x + c[4] * d.y) + c[8] * d.z, (c[1] * d.x + c[5] * d.y) + c[9] * d.z,
+                (c[2] * d.x + c[6] * d.y) + c[10] * d.z);
+    }
+}
+// LENS: u_lens is the next_2d right after the filter's; the pinhole camera does not draw it
+template <bool PMJ, bool LENS = false>
 AKR_D void generate_ray(const PtParams& p, uint32_t px, uint32_t py, Sampler& smp, vec3& o, vec3& d) {
-    generate_ray_from(p, px, py, next_2d<PMJ>(p, smp), o, d);
+    const vec2 u_filter = next_2d<PMJ>(p, smp);
+    if (LENS) {
+        const vec2 u_lens = next_2d<PMJ>(p, smp);
+        generate_ray_lens_from(p, px, py, u_filter, u_lens, o, d);
+    } else {
+        generate_ray_from(p, px, py, u_filter, o, d);
+    }
 }
 
 AKR_D float mis_weight(float a, float b) {  // pt.rs:962-973 with power = 1
@@ -423,7 +473,7 @@ static_assert(PK_END <= kParkSlots, "park column too small");
 AKR_D void park_put(uint32_t* park, uint32_t slot, uint32_t v) { park[slot * 256u] = v; }
 AKR_D uint32_t park_get(const uint32_t* park, uint32_t slot) { return park[slot * 256u]; }
 
-template <bool PMJ = false>
+template <bool PMJ = false, bool LENS = false>
 AKR_D void path_regs_init(PathRegs& r, const PtParams& p, bool active, uint32_t pix, uint32_t sx, uint32_t sy) {
     const size_t N = (size_t)p.width * p.height;
     r.ro = mk3(0, 0, 0); r.rd = mk3(0, 0, 1); r.ray_ex0 = kInvalid;
@@ -445,7 +495,7 @@ AKR_D void path_regs_init(PathRegs& r, const PtParams& p, bool active, uint32_t 
         r.film_rgb = mk3(p.film[3 * (size_t)pix + 0], p.film[3 * (size_t)pix + 1], p.film[3 * (size_t)pix + 2]);
         r.film_w = p.film[6 * N + pix];
         sampler_start<PMJ>(p, r.smp);  // sampler.start()
-        generate_ray<PMJ>(p, sx, sy, r.smp, r.ro, r.rd);
+        generate_ray<PMJ, LENS>(p, sx, sy, r.smp, r.ro, r.rd);
     }
 }
 
@@ -464,7 +514,7 @@ AKR_D void shifted_pixel(const PtParams& p, uint32_t px, uint32_t py, uint32_t& 
 // FD: 1 / 0 = force_diffuse known at compile time (the reference's JIT also specialises the kernel on it: the branch
 // at pt.rs:268 is taken while tracing the kernel, so a force_diffuse kernel contains no Principled code); -1 = read
 // p.force_diffuse at run time.
-template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h)
+template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
 AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found, bool occluded, uint32_t pix_in, uint32_t sx_in, uint32_t sy_in,
                      uint32_t* park = nullptr) {
     const bool force_diffuse = FD < 0 ? (p.force_diffuse != 0) : (FD != 0);
@@ -639,7 +689,7 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
             if (more) {
                 sampler_start<PMJ>(p, r.smp);
                 const uint32_t sx = PARK ? park_get(park, PK_SX) : sx_in, sy = PARK ? park_get(park, PK_SY) : sy_in;
-                generate_ray<PMJ>(p, sx, sy, r.smp, r.ro, r.rd);
+                generate_ray<PMJ, LENS>(p, sx, sy, r.smp, r.ro, r.rd);
                 r.ray_ex0 = kInvalid;
             } else {
                 r.has_ray = false;

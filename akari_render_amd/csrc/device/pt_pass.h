@@ -38,7 +38,8 @@ namespace akr {
 // textures); a per-scene kernel gets the mask of its scene.
 // INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h); BVH kernels without STAGE / DEFER only.
 // ENV: the scene has an environment light (device/denv.h); kernels without DEFER / SIMPLE only.
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false>
+// LENS: the camera has a thin lens (dpath.h generate_ray); kernels without DEFER / SIMPLE only.
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false>
 AKR_D void pt_pass_body(const PtParams& p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];  // BVH: kBvhStackDepth x 256 words; else: staged tables
     TraceCtx tc;
@@ -75,7 +76,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
     shifted_pixel(p, px, py, sx, sy);
     if (PMJ && p.bn_offset != 0) pmj_bluenoise_stage(p, px, py);  // before the first draw (path_regs_init generates the first camera ray)
     PathRegs r;
-    path_regs_init<PMJ>(r, q, in_frame, pix, sx, sy);
+    path_regs_init<PMJ, LENS>(r, q, in_frame, pix, sx, sy);
     constexpr bool PARK = !FD && TEX;  // cold path state in LDS while a vertex is shaded (dpath.h: PARK)
     uint32_t* park = lds_stack + p.park_offset + threadIdx.x;
     if (PARK) {
@@ -207,8 +208,8 @@ AKR_D void pt_pass_body(const PtParams& p) {
             }
             if (STRAG > 0 && r.carry) {
                 // still tracing: nothing to resolve or shade yet
-            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV>(q, r, hit, found, occluded, 0, 0, 0, park);
-            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV>(q, r, hit, found, occluded, pix, sx, sy);
+            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV, LENS>(q, r, hit, found, occluded, 0, 0, 0, park);
+            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS>(q, r, hit, found, occluded, pix, sx, sy);
         }
     }
     flush_counters(p, r, tc.cnt, BVH);

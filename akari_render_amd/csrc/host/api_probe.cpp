@@ -5,6 +5,7 @@
 #include "../../../include/akari_hip_test.h"
 #include "../device/dinst.h"
 #include "../device/disect.h"
+#include "../device/dpath.h"
 
 extern "C" {
 
@@ -163,6 +164,50 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context* ctx, akr_scene* scene, ui
 }
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context* ctx, akr_scene* scene, uint32_t n, const float* dirs3, float* out4) {
     return probe_env(ctx, scene, 1, n, dirs3, out4, "akr_probe_env_pdf");
+}
+// the camera's ray generation (device/dpath.h): the parameter block's camera part as fill_params sets it
+static PtParams camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {
+    PtParams p;
+    std::memset(&p, 0, sizeof p);
+    std::memcpy(p.r2c, s->r2c, 64);
+    std::memcpy(p.c2w, s->c2w, 64);
+    p.c2w_identity = s->c2w_identity;
+    p.width = s->flat.camera.width;
+    p.height = s->flat.camera.height;
+    p.filter_type = filter_type;
+    p.filter_radius = filter_radius;
+    p.lens_radius = s->flat.lens.radius;
+    p.lens_focal = s->flat.lens.focal_distance;
+    return p;
+}
+AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6) {
+    if (!scene || !pixels2 || !u4 || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_lens_ray: NULL argument");
+    if (filter_type > AKR_FILTER_GAUSSIAN) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_lens_ray: unknown filter_type");
+    const PtParams p = camera_params(scene, filter_type, filter_radius);
+    for (uint32_t i = 0; i < n; i++) {
+        const float* u = u4 + 4ull * i;
+        vec3 o, d;
+        if (p.lens_radius > 0.0f) generate_ray_lens_from(p, pixels2[2ull * i], pixels2[2ull * i + 1], mk2(u[0], u[1]), mk2(u[2], u[3]), o, d);
+        else generate_ray_from(p, pixels2[2ull * i], pixels2[2ull * i + 1], mk2(u[0], u[1]), o, d);
+        float* r = out6 + 6ull * i;
+        r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+    }
+    return AKR_OK;
+}
+AKR_TEST_API int32_t akr_probe_camera_rays(akr_context* ctx, akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2,
+                                      const float* u4, float* out6) {
+    if (!ctx || !scene || !pixels2 || !u4 || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_camera_rays: NULL argument");
+    if (filter_type > AKR_FILTER_GAUSSIAN) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_camera_rays: unknown filter_type");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf dpx, du, dout;
+        dpx.upload(std::vector<uint32_t>(pixels2, pixels2 + 2ull * n));
+        du.upload(std::vector<float>(u4, u4 + 4ull * n));
+        dout.alloc(6ull * n * 4);
+        if (n) HIP_CHECK(launch_probe_camera_rays(camera_params(scene, filter_type, filter_radius), n, dpx.as<uint32_t>(), du.as<float>(), dout.as<float>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) HIP_CHECK(hipMemcpy(out6, dout.p, 6ull * n * 4, hipMemcpyDeviceToHost));
+    });
 }
 AKR_TEST_API int32_t akr_probe_surface_interaction(akr_context* ctx, akr_scene* scene, uint32_t n, const uint32_t* inst_prim, const float* bary,
                                               float* out) {

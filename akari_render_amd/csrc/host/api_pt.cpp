@@ -97,7 +97,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
             if (m.kind == MAT_GLASS) simple = false;
             if (m.kind == MAT_PRINCIPLED && ((m.flags & (MF_COAT | MF_EVAL_DIEL | MF_NORMAL_MAP)) != 0 || m.transmission != 0.0f || m.coat_weight != 0.0f)) simple = false;
         }
-        p.simple_scene = (simple && se->simple_kernels_option && !cs.env.on) ? 1u : 0u;  // (no SIMPLE kernels with an environment light)
+        p.simple_scene = (simple && se->simple_kernels_option && !cs.env.on && s->flat.lens.radius == 0.0f) ? 1u : 0u;  // (no SIMPLE kernels with an environment light or a lens)
     }
     {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
         // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
@@ -116,7 +116,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         bool want = n_dear > 0 && 2 * n_dear <= n_surface;
         uint32_t mask = 1u;  // iterations with (iteration & mask) != 0 put those hits off
         if (se->defer_metal_option >= 0) { mask = (uint32_t)se->defer_metal_option; want = mask != 0; }  // akr_option_set("defer_metal"): measurements / tests
-        p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on && !cs.env.on) ? mask : 0u;  // (nor DEFER ones)
+        p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on && !cs.env.on && s->flat.lens.radius == 0.0f) ? mask : 0u;  // (nor DEFER ones)
         p.defer_flags = flags;
     }
     p.wf_sort = se->wf_sort ? 1u : 0u;
@@ -143,6 +143,8 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         p.owned_tiles = nullptr;
         p.n_items = p.tiles_x * p.tiles_y * p.tile_w * p.tile_h;
     }
+    p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
+    p.lens_focal = s->flat.lens.focal_distance;
 }
 std::vector<uint32_t> akr_api::owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count) {
     std::vector<std::pair<uint32_t, uint32_t>> mine;  // (Morton code, tile)
@@ -522,6 +524,8 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
             se->arith_relaxed = t.arith == 1 && for_pt_kernel && !scene->cs.instanced.on && !se->wavefront;
             if (se->arith_relaxed && scene->cs.env.on)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
+            if (se->arith_relaxed && scene->flat.lens.radius > 0.0f)
+                throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)");
             if (!for_pt_kernel) se->spec_status = "not a pt session";
             else if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
             else if (se->wavefront) se->spec_status = "wavefront schedule";
@@ -546,6 +550,7 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
                 rq.stage = se->params.stage_total != 0;
                 rq.defer = se->params.defer_metal != 0;
                 rq.env = scene->cs.env.on;
+                rq.lens = scene->flat.lens.radius > 0.0f;
                 rq.min_waves = se->spec_waves;
                 se->spec = ctx->spec_cache.get(scene->spec_header, rq, ctx->props.gcnArchName, may_compile);
                 se->spec_status = se->spec->status;
@@ -691,7 +696,7 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         info->specialised = se->spec_active ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
         info->kernel_flags = (se->scene->cs.bvh_nodes.empty() ? 0u : 1u) | (se->params.sampler != 0 ? 2u : 0u) | (se->params.stage_total != 0 ? 4u : 0u) |
-                             (se->params.defer_metal != 0 ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u);
+                             (se->params.defer_metal != 0 ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (se->scene->flat.lens.radius > 0.0f ? 32u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;

@@ -111,10 +111,35 @@ static void count_device_bytes(akr_scene* s) {
         s->device_bytes += b->bytes;
 }
 
+// A lens moves the ray origins off the camera's position, and the padding of the scene's boxes was sized from the largest coordinate magnitude an
+// origin can have (scene_build.cpp, scene_inst.cpp: the camera's translation against the scene's box). The trees of a scene
+// are the ones of its lens-less compile, so the lens is accepted only where every origin on its disk stays inside that magnitude.
+static void check_lens_reach(const akr_scene* s, const HostLens& lens) {
+    const CompiledScene& cs = s->cs;
+    if (lens.radius == 0.0f || (cs.bvh_nodes.empty() && !cs.instanced.on)) return;  // (the exhaustive walk has no boxes)
+    const float* c2w = s->flat.camera.c2w;
+    float bound[3], moved[16];
+    lens_origin_bound(c2w, lens.radius, bound);
+    std::memcpy(moved, c2w, sizeof moved);
+    bool inside = true;
+    for (int a = 0; a < 3; a++) {
+        const float m = std::max(std::max(std::fabs(cs.scene_lo[a]), std::fabs(cs.scene_hi[a])), std::fabs(c2w[12 + a]));
+        if (bound[a] > m) inside = false;
+        moved[12 + a] = bound[a];
+    }
+    // flattened scenes: the padding looks at max(diagonal, reach) only -- unchanged is enough; kept scenes also use the per-axis magnitudes
+    if (inside || (!cs.instanced.on && bvh_box_padding(cs.scene_lo, cs.scene_hi, moved) == bvh_box_padding(cs.scene_lo, cs.scene_hi, c2w))) return;
+    char msg[320];
+    std::snprintf(msg, sizeof msg, "lens: a lens of radius %g puts ray origins at coordinates up to (%g, %g, %g), beyond the magnitude the scene's acceleration "
+                  "structure was padded for (its box and the camera position); use a smaller radius", lens.radius, bound[0], bound[1], bound[2]);
+    throw std::invalid_argument(msg);
+}
+
 void akr_api::scene_finish(akr_scene* s) {
     akr_context* ctx = s->ctx;
     compile_scene(s->flat, s->cs);
     compile_environment(s->flat, s->cs);
+    check_lens_reach(s, s->flat.lens);  // (a lens from the file, option `lens`)
     CompiledScene& cs = s->cs;
     camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity);
     if (!ctx) {  // host-only scene: inspectable, not renderable
@@ -303,6 +328,22 @@ AKR_API int32_t akr_scene_get_environment(const akr_scene* s, akr_environment_de
     out->strength = e.strength;
     return AKR_OK;
 }
+AKR_API int32_t akr_scene_set_lens(akr_scene* s, const akr_lens_desc* desc) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_lens: scene is NULL");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_set_lens: a session holds the scene (end it first)");
+        HostLens lens;
+        if (desc) lens = lens_from_values(desc->radius, desc->focal_distance);
+        check_lens_reach(s, lens);
+        s->flat.lens = lens;
+    });
+}
+AKR_API int32_t akr_scene_get_lens(const akr_scene* s, akr_lens_desc* out) {
+    if (!s || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_lens: NULL argument");
+    out->radius = s->flat.lens.radius;
+    out->focal_distance = s->flat.lens.focal_distance;
+    return AKR_OK;
+}
 AKR_API int32_t akr_scene_get_light(const akr_scene* s, uint32_t light, uint32_t* instance, float* power, float* pdf) {
     if (!s || light >= s->cs.n_lights) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_light: bad argument");
     if (instance) *instance = s->cs.light_inst[light];
@@ -449,7 +490,7 @@ AKR_API int32_t akr_host_spec_compile(akr_scene* scene, uint32_t flags, uint32_t
         }
         if (header.empty()) throw Unsupported("unsupported: the scene has no per-scene code (no texture-fed material, or too many shader kinds)");
         SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u;
+        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u; rq.lens = flags & 64u;
         rq.min_waves = (int)min_waves;
         std::vector<char> code;
         std::string text;
@@ -464,7 +505,7 @@ AKR_API int32_t akr_host_spec_compile_text(const char* spec_header, uint32_t fla
     if (!spec_header || !arch || !out_path) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_spec_compile_text: NULL argument");
     return guarded([&] {
         SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u;
+        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u; rq.lens = flags & 64u;
         rq.min_waves = (int)min_waves;
         std::vector<char> code;
         std::string log;

@@ -1,9 +1,10 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler]
+//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
-// with the independent sampler and the same seed.
+// with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
+// through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,13 +16,15 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
               "  -m, --method <METHOD>    Render method config file (\"type\": \"pt\")\n"
               "  -d, --device <DEVICE>    HIP device ordinal (default 0)\n"
               "  -v, --verbose\n"
               "      --save-intermediate  write {name}-{spp}.exr after every pass\n"
-              "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files");
+              "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files\n"
+              "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
+              "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's");
 }
 
 // akari-cli --spec-compile <header file> <out.co> <arch> <flags> <min waves>: the library's helper process for per-scene kernels
@@ -45,6 +48,8 @@ int main(int argc, char** argv) {
     std::string scene, method, name;
     int device = 0, verbose = 0, save_intermediate = 0, save_stats = 0, indep = 0;
     unsigned w = 0, h = 0;
+    int dof = 0;
+    float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(1); } return argv[++i]; };
@@ -55,11 +60,25 @@ int main(int argc, char** argv) {
         else if (a == "--save-intermediate") save_intermediate = 1;
         else if (a == "--save-stats") { name = next(); save_stats = 1; }
         else if (a == "--independent-sampler") indep = 1;
+        else if (a == "--depth-of-field") dof = 1;
+        else if (a == "--lens-radius" || a == "--focal-distance") {
+            const char* text = next();
+            char* end = nullptr;
+            const float v = std::strtof(text, &end);
+            if (end == text || *end != 0 || !(v >= 0.0f)) { std::fprintf(stderr, "akari-cli: %s wants a number >= 0, got '%s'\n", a.c_str(), text); return 1; }
+            (a == "--lens-radius" ? lens_radius : focal_distance) = v;
+        }
         else if (a == "--resolution") { if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { usage(); return 1; } }
         else if (a == "--gui") { std::fputs("akari-cli: --gui is not supported by the HIP integrator\n", stderr); return 1; }
         else { usage(); return 1; }
     }
     if (scene.empty() || method.empty()) { usage(); return 1; }
+    // a lens needs both numbers: each comes from the command line or, with --depth-of-field, from the scene file
+    if (!dof && (lens_radius >= 0.0f) != (focal_distance >= 0.0f)) {
+        std::fprintf(stderr, "akari-cli: %s alone describes no lens: give --lens-radius and --focal-distance together, or add --depth-of-field to take the other "
+                             "from the scene file's focal_distance / fstop\n", lens_radius >= 0.0f ? "--lens-radius" : "--focal-distance");
+        return 1;
+    }
     std::ifstream mf(method);
     if (!mf) { std::fprintf(stderr, "akari-cli: cannot open %s\n", method.c_str()); return 1; }
     std::stringstream ss;
@@ -68,7 +87,15 @@ int main(int argc, char** argv) {
     akr_scene* sc = nullptr;
     auto die = [&](const char* what) { std::fprintf(stderr, "akari-cli: %s: %s\n", what, akr_last_error()); std::exit(1); };
     if (akr_context_create(device, &ctx) != AKR_OK) die("device");
+    if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
+    if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
+        akr_lens_desc lens;
+        if (akr_scene_get_lens(sc, &lens) != AKR_OK) die("lens");
+        if (lens_radius >= 0.0f) lens.radius = lens_radius;
+        if (focal_distance >= 0.0f) lens.focal_distance = focal_distance;
+        if (akr_scene_set_lens(sc, &lens) != AKR_OK) die("lens");
+    }
     akr_render_session ses;
     ses.save_intermediate = save_intermediate;
     ses.save_stats = save_stats;

@@ -45,6 +45,19 @@ struct HostEnvironment {
     float strength = 0.0f;
     float rotation[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // environment -> world, row-major
 };
+// The camera's thin lens (akr_lens_desc). radius == 0: a pinhole.
+struct HostLens {
+    float radius = 0.0f, focal_distance = 0.0f;
+};
+// an akr_lens_desc checked (throws std::invalid_argument); radius == 0 comes back as "no lens"
+inline HostLens lens_from_values(float radius, float focal_distance) {
+    if (!std::isfinite(radius) || !std::isfinite(focal_distance) || radius < 0.0f || focal_distance < 0.0f)
+        throw std::invalid_argument("lens: radius and focal_distance must be finite and >= 0");
+    if (radius > 0.0f && !(focal_distance > 0.0f)) throw std::invalid_argument("lens: a radius > 0 needs a focal_distance > 0");
+    HostLens l;
+    if (radius > 0.0f) { l.radius = radius; l.focal_distance = focal_distance; }
+    return l;
+}
 // Owning copy of an akr_scene_desc.
 struct FlatScene {
     std::vector<HostMesh> meshes;
@@ -55,6 +68,7 @@ struct FlatScene {
     std::vector<HostImage> images;
     std::vector<HostGraph> graphs;  // empty, or one per material
     HostEnvironment env;
+    HostLens lens;  // akr_scene_set_lens, or the file's focal_distance / fstop under option `lens` (not part of akr_scene_desc)
     static FlatScene from_desc(const akr_scene_desc& d);
 };
 
@@ -143,6 +157,13 @@ inline float bvh_box_padding(const float lo[3], const float hi[3], const float* 
     const float diag = __builtin_sqrtf(diag2);
     return 4e-6f * (diag > reach ? diag : reach);
 }
+// Per axis, the largest |coordinate| of a ray origin on the lens disk: o = T + radius (a c2w[0..2] + b c2w[4..6]) with a^2 + b^2 <= 1
+// (device/dpath.h generate_ray_lens_from), over the camera's w.
+inline void lens_origin_bound(const float* c2w /* column-major 4x4 */, float radius, float out[3]) {
+    const double w = std::fabs((double)c2w[15]) > 0.0 ? std::fabs((double)c2w[15]) : 1.0;
+    for (int a = 0; a < 3; a++)
+        out[a] = (float)(((double)std::fabs(c2w[12 + a]) + (double)radius * std::sqrt((double)c2w[a] * c2w[a] + (double)c2w[4 + a] * c2w[4 + a])) / w * 1.000001);
+}
 
 // Conditioning of a triangle's (u, v) parametrisation. The inside test computes u = r0 . p + c0 with |r0| = |e2| / |n| (v likewise with
 // |r1| = |e1| / |n|): two of its three fma roundings act on partial sums of size S = |r0||p| + |c0| <= 2 |r0||p|, the rounded row and the
@@ -203,6 +224,7 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   arith        AKR_ARITH=1              pt megakernel in the relaxed arithmetic tier (flattened scenes; precompiled kernels): hardware rcp / sqrt /
 //                                         sin / cos / log / exp and contraction instead of the bit-exact contract
 //   pad_percent  (no environment hook)    test hook: box padding in percent of the derived value (100)
+//   lens         AKR_LENS=1               akr_scene_load gives the camera the thin lens of the file's focal_distance and fstop (the reference reads both and renders a pinhole)
 //   wf_sort      AKR_WF_SORT=1            wavefront schedule: ray queues sorted by origin cell + direction octant before each trace launch
 //   wf_groups    AKR_WF_GROUPS=<g>        wavefront schedule: the slots run as g groups with queues and streams of their own (api_pt.cpp wf_run); 0 = the library decides
 //   wf_carry     AKR_WF_CARRY=0           wavefront schedule: 0 = every trace launch traces its rays to the end (1, default: a wave that finds the queue empty and
@@ -227,6 +249,7 @@ struct TuningOptions {
     int wf_carry = 1;  // wavefront schedule: 1 = the last rays of a trace launch are carried into the next one (wf_kernels.hip), 0 = every launch traces to the end
     int sched_trial = -1;  // flattened scenes under option wavefront = -1: a timed trial of both schedules at the start of a long render (api_pt.cpp schedule_trial):
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
+    int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
 };
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it

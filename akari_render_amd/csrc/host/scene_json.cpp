@@ -547,6 +547,12 @@ FlatScene load_scene_json(const std::string& path) {
     flat.camera.fov = cd.at("fov").as_f32() * (kPiF / 180.0f);  // f32::to_radians
     flat.camera.width = (uint32_t)cd.at("sensor_width").as_number();
     flat.camera.height = (uint32_t)cd.at("sensor_height").as_number();
+    // focal_distance / fstop: the reference turns them into lens_radius and focal_length of PerspectiveCameraData (load.rs:177-189) and its
+    // generate_ray never reads them; the exporter writes the pair whether or not depth of field is on. Option `lens` = 1 makes them the camera's lens.
+    if (tuning().lens != 0 && cd.has("focal_distance") && cd.has("fstop")) {
+        const float focal_distance = cd.at("focal_distance").as_f32(), fstop = cd.at("fstop").as_f32();
+        flat.lens = lens_from_values(focal_distance / (2.0f * fstop), focal_distance);
+    }
     return flat;
 }
 

@@ -267,9 +267,10 @@ Rtc& rtc() {
 std::string wrapper_source(const SpecRequest& rq) {
     return fmt("// per-scene instantiation of k_pt_pass (host/specialise.cpp)\n#define AKR_SPEC_GRAPHS 1\n#include \"device/pt_pass.h\"\n"
                "extern \"C\" __global__ __launch_bounds__(256, %d) void akr_pt_pass_spec(const akr::PtParams p) {\n"
-               "    akr::pt_pass_body<%s, false, true, %s, %s, %s, akr::kSpecAbsent, %s%s>(p);\n}\n",
+               "    akr::pt_pass_body<%s, false, true, %s, %s, %s, akr::kSpecAbsent, %s%s%s>(p);\n}\n",
                rq.min_waves, (rq.bvh || rq.inst) ? "true" : "false", rq.pmj ? "true" : "false", (rq.stage && !rq.inst) ? "true" : "false",
-               (rq.defer && !rq.inst && !rq.env) ? "true" : "false", rq.inst ? "true" : "false", rq.env ? ", true" : "");
+               (rq.defer && !rq.inst && !rq.env && !rq.lens) ? "true" : "false", rq.inst ? "true" : "false", (rq.env || rq.lens) ? (rq.env ? ", true" : ", false") : "",
+               rq.lens ? ", true" : "");
 }
 std::vector<std::string> compile_options(const std::string& arch) {
     std::vector<std::string> o;
@@ -357,7 +358,7 @@ bool compile_in_helper(const std::string& helper, const std::string& spec_header
         std::ofstream f(hdr, std::ios::binary);
         f.write(spec_header.data(), (std::streamsize)spec_header.size());
     }
-    const std::string flags = std::to_string((rq.bvh ? 1 : 0) | (rq.pmj ? 2 : 0) | (rq.stage ? 4 : 0) | (rq.defer ? 8 : 0) | (rq.inst ? 16 : 0) | (rq.env ? 32 : 0)), waves = std::to_string(rq.min_waves);
+    const std::string flags = std::to_string((rq.bvh ? 1 : 0) | (rq.pmj ? 2 : 0) | (rq.stage ? 4 : 0) | (rq.defer ? 8 : 0) | (rq.inst ? 16 : 0) | (rq.env ? 32 : 0) | (rq.lens ? 64 : 0)), waves = std::to_string(rq.min_waves);
     // posix_spawn, not fork + setup code: the host process has threads (HIP runtime, the application's own)
     std::vector<std::string> env_store;
     for (char** e = environ; e && *e; e++)

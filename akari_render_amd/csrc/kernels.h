@@ -102,6 +102,8 @@ struct PtParams {
     uint32_t shard_rank, shard_count;
     uint32_t tile_w, tile_h, tiles_x, tiles_y;
     const uint32_t* owned_tiles;  // shard_count > 1: the tiles (row-major ids) this rank owns, in Morton order (tile_owner below); else null
+    // thin lens (dpath.h generate_ray_lens_from): radius > 0 = the session runs the LENS kernels, which alone read these
+    float lens_radius, lens_focal;
 };
 
 // Which rank owns tile (tx, ty) of a frame shared by `count` ranks: its position on the Z-order (Morton) curve, modulo the ranks
@@ -206,6 +208,15 @@ hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream);  // pt_in
 hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream);   // pt_env_kernels.hip: scenes with an environment light (device/denv.h)
 hipError_t launch_pt_pass_inst_env(const PtParams& p, hipStream_t stream);  // pt_inst_env_kernels.hip: kept scenes with an environment light
 hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
+// the LENS = true instantiations (the camera has a thin lens: p.lens_radius > 0), each in a translation unit of its own
+hipError_t launch_pt_pass_lens(const PtParams& p, hipStream_t stream);      // pt_lens_kernels.hip: flattened scenes; one with an environment goes on to ...
+hipError_t launch_pt_pass_lens_env(const PtParams& p, hipStream_t stream);  // ... pt_lens_env_kernels.hip
+hipError_t launch_pt_pass_inst_lens(const PtParams& p, hipStream_t stream);                    // pt_inst_lens_kernels.hip: kept scenes
+hipError_t launch_wf_init_lens(const PtParams& p, const WfBuffers& wf, hipStream_t stream);   // wf_lens_kernels.hip
+hipError_t launch_wf_shade_lens(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);
+hipError_t launch_aov_lens(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream);  // aov_lens_kernels.hip
+// pt_lens_kernels.hip, test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
+hipError_t launch_probe_camera_rays(const PtParams& p, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6, hipStream_t stream);
 // spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled instantiation, or nullptr
 hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn = nullptr);
 hipError_t launch_gpt_sample(const PtParams& p, const GptParams& g, hipStream_t stream);

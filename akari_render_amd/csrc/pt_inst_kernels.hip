@@ -32,6 +32,7 @@ hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* me
 }
 
 hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream) {
+    if (p.lens_radius > 0.0f) return launch_pt_pass_inst_lens(p, stream);  // a thin lens: pt_inst_lens_kernels.hip
     if (p.sc.env) return launch_pt_pass_inst_env(p, stream);  // an environment light: pt_inst_env_kernels.hip
     return launch_pt_pass_inst_t<false>(p, stream);
 }

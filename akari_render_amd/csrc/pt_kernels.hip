@@ -148,6 +148,7 @@ __global__ void k_probe_material(PtParams p, uint32_t material, uint32_t n, cons
 // spec_fn: the session's per-scene kernel (host/specialise.cpp); it wraps the body of whatever the scene is, so it is launched from here
 hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn) {
     if (p.sc.in2.on && !spec_fn) return launch_pt_pass_inst(p, stream);  // meshes + instances: pt_inst_kernels.hip
+    if (p.lens_radius > 0.0f && !spec_fn) return launch_pt_pass_lens(p, stream);  // a thin lens: pt_lens_kernels.hip, pt_lens_env_kernels.hip
     if (p.sc.env && !spec_fn) return launch_pt_pass_env(p, stream);      // an environment light: pt_env_kernels.hip
     return launch_pt_pass_t<false>(p, stream, spec_fn);
 }

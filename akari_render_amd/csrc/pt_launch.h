@@ -1,8 +1,9 @@
 // pt_launch.h -- k_pt_pass, the LDS plan of its launches and the launcher that picks the instantiation. Templates and inline functions
 // only: every translation unit that instantiates the kernel includes it and gets the instantiations its launcher names, no others.
 // Those are pt_kernels.hip (the AKR-F32 contract: the default, and the verifier), pt_kernels_relaxed.hip (the relaxed arithmetic tier,
-// device/dmath.h AKR_ARITH_RELAXED; there everything below lives in namespace akr_rx) and pt_env_kernels.hip (ENV = true: scenes with an
-// environment light). The kept-scene launchers (pt_inst_kernel.h) share the LDS plan.
+// device/dmath.h AKR_ARITH_RELAXED; there everything below lives in namespace akr_rx), pt_env_kernels.hip (ENV = true: scenes with an
+// environment light) and pt_lens_kernels.hip / pt_lens_env_kernels.hip (LENS = true: cameras with a thin lens, without / with an environment).
+// The kept-scene launchers (pt_inst_kernel.h) share the LDS plan.
 #pragma once
 #include <algorithm>
 #include "device/pt_pass.h"
@@ -10,9 +11,9 @@
 
 namespace akr {
 
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, bool SIMPLE = false, bool ENV = false>
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, bool SIMPLE = false, bool ENV = false, bool LENS = false>
 __global__ __launch_bounds__(256, pt_pass_min_waves(BVH, FD, TEX)) void k_pt_pass(const PtParams p) {
-    pt_pass_body<BVH, FD, TEX, PMJ, STAGE, DEFER, SIMPLE ? AB_SIMPLE : 0u, false, ENV>(p);
+    pt_pass_body<BVH, FD, TEX, PMJ, STAGE, DEFER, SIMPLE ? AB_SIMPLE : 0u, false, ENV, LENS>(p);
 }
 
 // Dynamic LDS of a k_pt_pass launch and where its blocks start: [traversal stacks][staged tables][triangle records (exhaustive kernels)][node
@@ -53,8 +54,9 @@ inline PtParams pt_pass_layout(const PtParams& p, size_t& lds, uint32_t& blocks)
     return with_tex_slots(pp, base, lds);
 }
 // The precompiled k_pt_pass of a flattened scene, or the session's per-scene kernel. ENV: the scene has an environment light (device/denv.h);
-// launch_pt_pass (pt_kernels.hip) and launch_pt_pass_env (pt_env_kernels.hip) are the two instantiations, each in its own translation unit.
-template <bool ENV>
+// LENS: the camera has a thin lens (device/dpath.h generate_ray). launch_pt_pass (pt_kernels.hip), launch_pt_pass_env (pt_env_kernels.hip) and the two
+// of launch_pt_pass_lens (pt_lens_kernels.hip, pt_lens_env_kernels.hip) are the instantiations, each in its own translation unit.
+template <bool ENV, bool LENS = false>
 hipError_t launch_pt_pass_t(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn = nullptr) {
     size_t lds;
     uint32_t blocks;
@@ -69,13 +71,13 @@ hipError_t launch_pt_pass_t(const PtParams& p, hipStream_t stream, hipFunction_t
     if (ENV && !bvh && p.stage_total == 0) return hipErrorInvalidValue;  // (the exhaustive kernels read their tables from LDS: the host guarantees the fit)
     const bool stage = !bvh || p.stage_total != 0;  // staged tables: the exhaustive kernels always, the BVH kernels where they fit
     // deferred metal vertices: full-graph kernels, of BVH scenes those with textures; the absent-lobe masks of SIMPLE: full-graph kernels
-    // of scenes without textures; neither where there is an environment light
-    const bool defer = !ENV && p.defer_metal != 0 && !fd && (!bvh || tex);
-    const bool simple = !ENV && p.simple_scene != 0 && !fd && !tex;
+    // of scenes without textures; neither where there is an environment light or a lens
+    const bool defer = !ENV && !LENS && p.defer_metal != 0 && !fd && (!bvh || tex);
+    const bool simple = !ENV && !LENS && p.simple_scene != 0 && !fd && !tex;
     dispatch_bools([&](auto B, auto F, auto T, auto P, auto S, auto D, auto X) {
         // (what the rules above cannot produce is not compiled)
-        if constexpr ((B() || S()) && !(D() && (F() || (B() && !T()))) && !(X() && (F() || T())) && !(ENV && (D() || X())))
-            launch_kernel<true>(k_pt_pass<B(), F(), T(), P(), S(), D(), X(), ENV>, blocks, lds, stream, q);
+        if constexpr ((B() || S()) && !(D() && (F() || (B() && !T()))) && !(X() && (F() || T())) && !((ENV || LENS) && (D() || X())))
+            launch_kernel<true>(k_pt_pass<B(), F(), T(), P(), S(), D(), X(), ENV, LENS>, blocks, lds, stream, q);
     }, bvh, fd, tex, pmj, stage, defer, simple);
     return hipGetLastError();
 }

@@ -193,12 +193,11 @@ __global__ __launch_bounds__(256, INST ? AKR_WF_TRACE_INST_WAVES : 1) void k_wf_
 
 // ---------------------------------------------------------------------------------------------------- launchers
 hipError_t launch_wf_init(const PtParams& p, const WfBuffers& wf, hipStream_t stream) {
-    const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
-    if (blocks == 0) return hipSuccess;
-    dispatch_bools([&](auto P) { launch_kernel(k_wf_init<P()>, blocks, 0, stream, p, wf); }, p.sampler != 0);
-    return hipGetLastError();
+    if (p.lens_radius > 0.0f) return launch_wf_init_lens(p, wf, stream);  // a thin lens: wf_lens_kernels.hip
+    return launch_wf_init_t<false>(p, wf, stream);
 }
 hipError_t launch_wf_shade(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
+    if (p.lens_radius > 0.0f) return launch_wf_shade_lens(p, wf, q_out, stream);  // a thin lens: wf_lens_kernels.hip
     if (p.sc.env) return launch_wf_shade_env(p, wf, q_out, stream);  // an environment light: wf_env_kernels.hip
     return launch_wf_shade_t<false>(p, wf, q_out, stream);
 }

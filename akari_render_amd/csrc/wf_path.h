@@ -1,7 +1,7 @@
 // wf_path.h -- the path half of the wavefront schedule (wf_kernels.hip): the path state's records in HBM, the ray queues, k_wf_init,
 // k_wf_shade and its launcher. A header so that the shade kernels of scenes with an environment light (wf_env_kernels.hip, ENV = true) are
 // compiled in a translation unit of their own: the instantiations of wf_kernels.hip (ENV = false) and their code are those of a library
-// without environments.
+// without environments. The same for cameras with a thin lens (LENS = true: k_wf_init and k_wf_shade, wf_lens_kernels.hip).
 #pragma once
 #include <algorithm>
 #include "device/dpath.h"
@@ -111,7 +111,7 @@ AKR_D void wf_enqueue(const PtParams& p, const WfBuffers& wf, uint32_t q, uint32
     }
 }
 
-template <bool PMJ>
+template <bool PMJ, bool LENS = false>  // LENS: the camera has a thin lens (device/dpath.h generate_ray)
 __global__ __launch_bounds__(256) void k_wf_init(const PtParams p, const WfBuffers wf) {
     const uint32_t slot = wf.slot_base + blockIdx.x * 256u + threadIdx.x;
     uint32_t px = 0, py = 0;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_wf_init(const PtParams p, const WfBuffe
     uint32_t sx, sy;
     shifted_pixel(p, px, py, sx, sy);
     PathRegs r;
-    path_regs_init<PMJ>(r, p, in_frame, pix, sx, sy);
+    path_regs_init<PMJ, LENS>(r, p, in_frame, pix, sx, sy);
     if (slot < wf.slot_end) {
         wf_store(wf, slot, r);
         if (wf.pend) wf.pend[slot] = 0u;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_wf_init(const PtParams p, const WfBuffe
 #ifndef AKR_WF_SHADE_WAVES
 #define AKR_WF_SHADE_WAVES 1  // waves per SIMD the shade kernel's register allocation must leave room for (1 = whatever it needs)
 #endif
-template <bool TEX, bool PMJ, bool INST = false, bool ENV = false>  // ENV: the scene has an environment light (device/denv.h)
+template <bool TEX, bool PMJ, bool INST = false, bool ENV = false, bool LENS = false>  // ENV: the scene has an environment light (device/denv.h); LENS: a thin lens
 __global__ __launch_bounds__(256, TEX ? 1 : AKR_WF_SHADE_WAVES) void k_wf_shade(const PtParams p, const WfBuffers wf, uint32_t q_out) {
     const uint32_t slot = wf.slot_base + blockIdx.x * 256u + threadIdx.x;
     PathRegs r;
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256, TEX ? 1 : AKR_WF_SHADE_WAVES) void k_wf_shade(
         Hit hit;
         hit.gid = f2u(hv.x); hit.u = hv.y; hit.v = hv.z; hit.t = 0.0f;
         bool found = hit.gid != kInvalid, occluded = f2u(hv.w) != 0;
-        path_step<-1, TEX, PMJ, 0, 0u, INST, ENV>(p, r, hit, found, occluded, pix, sx, sy);
+        path_step<-1, TEX, PMJ, 0, 0u, INST, ENV, LENS>(p, r, hit, found, occluded, pix, sx, sy);
         wf_store(wf, slot, r);
     }
     // the queue the trace launch before this one emptied is the next shade launch's to fill: its counts and the queue head back to zero
@@ -171,15 +171,24 @@ __global__ __launch_bounds__(256, TEX ? 1 : AKR_WF_SHADE_WAVES) void k_wf_shade(
 
 
 // textures x sampler family x kept or flattened scene
-template <bool ENV>
+template <bool ENV, bool LENS = false>
 hipError_t launch_wf_shade_t(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
     const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
     if (blocks == 0) return hipSuccess;
     const bool tex = p.sc.tex.nodes != nullptr;
     size_t lds = 0;
     const PtParams q = tex ? with_tex_slots(p, 0, lds) : p;
-    dispatch_bools([&](auto T, auto P, auto I) { launch_kernel(k_wf_shade<T(), P(), I(), ENV>, blocks, lds, stream, q, wf, q_out); },
+    dispatch_bools([&](auto T, auto P, auto I) { launch_kernel(k_wf_shade<T(), P(), I(), ENV, LENS>, blocks, lds, stream, q, wf, q_out); },
                    tex, p.sampler != 0, p.sc.in2.on != 0);
+    return hipGetLastError();
+}
+
+// sampler family
+template <bool LENS>
+hipError_t launch_wf_init_t(const PtParams& p, const WfBuffers& wf, hipStream_t stream) {
+    const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
+    if (blocks == 0) return hipSuccess;
+    dispatch_bools([&](auto P) { launch_kernel(k_wf_init<P(), LENS>, blocks, 0, stream, p, wf); }, p.sampler != 0);
     return hipGetLastError();
 }
 

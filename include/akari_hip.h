@@ -307,6 +307,22 @@ AKR_API int32_t akr_scene_set_environment(akr_scene *scene, const akr_environmen
 /* The environment as decoded (texels owned by the scene); width = height = 0 and strength = 0 when there is none. A constant
  * colour comes back as width = height = 0 with its colour. */
 AKR_API int32_t akr_scene_get_environment(const akr_scene *scene, akr_environment_desc *out);
+/* Thin lens of the scene's camera (pt and aov integrators): depth of field. A camera ray starts at a point of a disk of
+ * `radius` around the camera position, in the camera's x / y plane, and passes through the point where the pinhole ray of the same film
+ * sample meets the plane of focus, `focal_distance` along the optical axis. The sample weight is the filter's: no vignetting. A host that
+ * holds the reference's PerspectiveCamera passes its lens_radius and focal_length (camera/mod.rs:105-118). radius = 0 is no
+ * lens, and a render without one draws, computes and costs what it did before lenses existed. gpt, mcmc_opt and the relaxed arithmetic tier
+ * refuse a scene with one (AKR_ERR_UNSUPPORTED). Not part of akr_camera_desc / akr_scene_desc. */
+typedef struct {
+    float radius;           /* >= 0, in world units (of camera space); 0 = a pinhole */
+    float focal_distance;   /* > 0 when radius > 0 */
+} akr_lens_desc;
+/* Sets (or, desc = NULL or radius = 0, removes) the camera's lens. Refused while a session holds the scene; refused with
+ * AKR_ERR_INVALID_ARGUMENT for non-finite or negative values, for radius > 0 without focal_distance > 0, and for a lens so large that ray
+ * origins on it would leave the coordinate magnitude the scene's acceleration structure was padded for. */
+AKR_API int32_t akr_scene_set_lens(akr_scene *scene, const akr_lens_desc *desc);
+/* The lens as the scene holds it; radius = focal_distance = 0 without one. */
+AKR_API int32_t akr_scene_get_lens(const akr_scene *scene, akr_lens_desc *out);
 /* The folded ggx_dielectric_s table in use (4096 floats), for comparison with a golden copy. */
 AKR_API int32_t akr_scene_get_ggx_table(const akr_scene *scene, float *dst4096);
 /* Host-side copy of the flattened description akr_scene_load produced (for loader tests):
@@ -451,7 +467,7 @@ typedef struct {
     uint32_t absent_mask;     /* lobes no material of the scene can have: 1 coat, 2 transmission, 4 normal map, 8 glass, 16 conductor */
     uint32_t min_waves;       /* waves per SIMD the kernel was compiled for */
     uint32_t vgprs, scratch_bytes;
-    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith) */
+    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens) */
     uint32_t _pad;
     double compile_ms;        /* hiprtc compile at akr_pt_begin (0 on a cache hit) */
     double load_ms;           /* cache lookup + module load */
@@ -639,7 +655,7 @@ AKR_API const char *akr_version(void);
 typedef enum {
     AKR_STRUCT_MESH_DESC = 1, AKR_STRUCT_INSTANCE_DESC, AKR_STRUCT_MATERIAL_DESC, AKR_STRUCT_CAMERA_DESC, AKR_STRUCT_SCENE_DESC,
     AKR_STRUCT_PT_CONFIG, AKR_STRUCT_PT_STATS, AKR_STRUCT_SCENE_INFO, AKR_STRUCT_KERNEL_INFO, AKR_STRUCT_AOV_CONFIG, AKR_STRUCT_GPT_CONFIG,
-    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC
+    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC, AKR_STRUCT_LENS_DESC
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
@@ -679,6 +695,9 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *   "arith"        (AKR_ARITH=1)            pt megakernel of flattened scenes in the relaxed arithmetic tier (hardware rcp / sqrt / sin / cos /
  *                                           log / exp, contraction): faster, NOT bit-identical to the reference arithmetic
  *   "pad_percent"  (no environment hook)    test hook: padding of the acceleration structures' boxes in percent of the derived value
+ *   "lens"         (AKR_LENS=1)             akr_scene_load: 1 = the camera gets the thin lens of the file's focal_distance and fstop, radius =
+ *                                           focal_distance / (2 fstop) (load.rs:177-179); 0 (default) = a pinhole, which is how the reference
+ *                                           renders every file -- its exporter writes the pair whether or not depth of field is on
  * Values out of an option's range fail with AKR_ERR_INVALID_ARGUMENT.
  * A session reads the options once, when it begins (akr_pt_begin / akr_gpt_begin / ...): a later akr_option_set does not change it.
  * "wavefront" = 1 on a scene without a BVH renders with the megakernel. Unknown names fail with AKR_ERR_INVALID_ARGUMENT. */

@@ -72,6 +72,16 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context *ctx, akr_scene *scene, ui
 
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context *ctx, akr_scene *scene, uint32_t n, const float *dirs3, float *out4);
 
+/* The camera ray of the scene's camera and lens (csrc/device/dpath.h generate_ray_from / generate_ray_lens_from) for n items:
+ * pixels2 = (x, y) as u32, u4 = u_filter.xy, u_lens.xy (u_lens is ignored without a lens), out6 = o.xyz, d.xyz in world space.
+ *   akr_host_lens_ray       the shared text on the host (no GPU; works on a host-only scene)
+ *   akr_probe_camera_rays   the same on the device */
+AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene *scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2, const float *u4,
+                                  float *out6);
+
+AKR_TEST_API int32_t akr_probe_camera_rays(akr_context *ctx, akr_scene *scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2,
+                                      const float *u4, float *out6);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);

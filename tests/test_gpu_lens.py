@@ -1,0 +1,357 @@
+"""The thin lens on the GPU (the LENS kernels): the device's camera rays against the host's, nothing moves without a lens,
+one film under every route, a plane in focus is as sharp as the pinhole's, a half-plane out of focus has the closed-form blur, aov through
+the lens, the refusals, and akari-cli --depth-of-field. The oracle has no lens: bit-identities, a restated definition (tests/test_lens.py)
+and closed forms are what pins it."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from akari_render_amd import abi, capi, distributed
+from oracle import pyoracle, scene_json
+from tests.helpers import instanced_scene, make_config, n_bit_diff, resolve_np
+from tests.test_environment import sample_image, scene_json_text
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+LENS_BIT = 32
+
+
+def _session(ctx, scene, cfg):
+    w, h = scene.info().width, scene.info().height
+    film = capi.Film(ctx, w, h)
+    se = capi.PtSession(ctx, scene, cfg, film)
+    se.passes(1000, blocking=True)
+    states = se.sampler_states(w * h)
+    info = se.kernel_info()
+    se.end()
+    return film.read(), states, info
+
+
+def _rot(ax, ay):
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    return ry @ rx
+
+
+# ---------------------------------------------------------------------------------------------------------------- probe
+@pytest.mark.parametrize("rotated", [False, True], ids=["identity", "rotated"])
+def test_probe_equals_host(ctx, rotated):
+    from tests.test_lens import _camera
+    sd = _camera(40, 24, rotated)
+    scene = capi.Scene(ctx, sd)
+    rng = np.random.default_rng(5)
+    n = 20000
+    pixels = np.stack([rng.integers(0, 40, n), rng.integers(0, 24, n)], axis=1).astype(np.uint32)
+    u_filter, u_lens = rng.random((n, 2), dtype=F), rng.random((n, 2), dtype=F)
+    u_lens[:3] = [[0.5, 0.5], [0.25, 0.25], [0.0, 0.0]]
+    for lens in (None, (0.3, 2.5), (1.5, 0.75)):
+        scene.set_lens(*lens) if lens else scene.set_lens(None)
+        for ft, fr in ((abi.FILTER_BOX, 0.5), (abi.FILTER_GAUSSIAN, 1.5)):
+            dev = scene.probe_camera_rays(pixels, u_filter, u_lens, ft, fr)
+            host = scene.host_lens_ray(pixels, u_filter, u_lens, ft, fr)
+            assert np.array_equal(dev.view(np.uint32), host.view(np.uint32)), (lens, ft)
+
+
+# ---------------------------------------------------------------------------------------------------------------- nothing moves without a lens
+def test_nothing_moves_without_a_lens(ctx, cbox_path):
+    w = h = 48
+    sd = scene_json.load_scene(cbox_path, w, h)
+    cfg = make_config(spp=8, spp_per_pass=4, max_depth=8, sampler_seed=3)
+    o_states = pyoracle.init_pcg32_states(w * h, cfg.sampler_seed)
+    o_film, _ = pyoracle.OracleScene(sd).render(cfg, states=o_states)  # (the oracle leaves its final sampler states in o_states)
+    scene = capi.Scene(ctx, sd)
+    film, states, info = _session(ctx, scene, cfg)
+    assert n_bit_diff(film, o_film) == 0 and np.array_equal(states, o_states)
+    assert info["kernel_flags"] & LENS_BIT == 0
+    scene.set_lens(0.2, 5.0)
+    with_lens, lens_states, info = _session(ctx, scene, cfg)
+    assert info["kernel_flags"] & LENS_BIT == LENS_BIT
+    assert n_bit_diff(with_lens, o_film) != 0 and not np.array_equal(lens_states, o_states)
+    for how in ("null", "zero"):
+        scene.set_lens(0.2, 5.0)
+        scene.set_lens(None) if how == "null" else scene.set_lens(0.0, 5.0)
+        film, states, info = _session(ctx, scene, cfg)
+        assert n_bit_diff(film, o_film) == 0, how
+        assert np.array_equal(states, o_states), how
+        assert info["kernel_flags"] & LENS_BIT == 0, how
+
+
+# ---------------------------------------------------------------------------------------------------------------- one film under every route
+def _route_scene(root, with_env):
+    sd = instanced_scene(width=40, height=32, n_inst=4, n=2, emissive_instances=1, textured=True)
+    sd.ggx_table = np.fromfile(os.path.join(root, "tests", "golden", "ggx_dielectric_s.f32"), dtype=np.float32)
+    if with_env:
+        img = sample_image(W=48, H=24, seed=4) * np.float32(0.6)
+        sd.environment = abi.EnvironmentData(image=img, strength=1.5, rotation=_rot(0.0, -0.4).astype(np.float32), filter=abi.TEX_FILTER_LINEAR)
+    # the helper's camera stands outside the scene's box along z, where its tilted lens plane has a component: no radius would be accepted on a
+    # scene with a tree. Moved inside the box's range it still sees the blobs, the floor and the light.
+    c2w = np.array(sd.camera.c2w, dtype=np.float32)
+    c2w[14] = 5.0
+    sd.camera.c2w = c2w
+    sd.lens = abi.LensData(0.0625, 4.0)
+    return sd
+
+
+@pytest.mark.parametrize("with_env", [False, True], ids=["no_env", "env"])
+@pytest.mark.parametrize("sampler", [abi.SAMPLER_INDEPENDENT, abi.SAMPLER_PMJ02BN, abi.SAMPLER_SOBOL], ids=["independent", "pmj02bn", "sobol"])
+def test_one_film_under_every_route(ctx, root, sampler, with_env):
+    sd = _route_scene(root, with_env)
+    w, h = sd.camera.width, sd.camera.height
+    cfg = make_config(spp=12, spp_per_pass=4, max_depth=6, sampler_type=sampler, sampler_seed=7)
+    with capi.options(force_bvh=0, instancing=0, wavefront=0, specialise=0):
+        exh = capi.Scene(ctx, sd)
+        assert exh.info().uses_bvh == 0 and exh.lens() == sd.lens
+        ref, ref_states, info = _session(ctx, exh, cfg)
+        assert info["kernel_flags"] & LENS_BIT
+        # the lens does reach the film
+        exh.set_lens(None)
+        pin, _, _ = _session(ctx, exh, cfg)
+        assert n_bit_diff(pin, ref) > 0
+    variants = {
+        "bvh": dict(force_bvh=1, instancing=0, wavefront=0, specialise=0),
+        "one_pass_at_a_time": dict(force_bvh=1, instancing=0, wavefront=0, specialise=0, max_fused_passes=1),
+        "wavefront": dict(force_bvh=1, instancing=0, wavefront=1, specialise=0),
+        "wavefront_carried": dict(force_bvh=1, instancing=0, wavefront=1, specialise=0, wf_carry=2),
+        "sched_trial": dict(force_bvh=1, instancing=0, wavefront=-1, specialise=0, sched_trial=1),
+        "instancing": dict(force_bvh=1, instancing=1, wavefront=0, specialise=0),
+        "instancing_wavefront": dict(force_bvh=1, instancing=1, wavefront=1, specialise=0),
+        "specialise": dict(force_bvh=0, instancing=0, wavefront=0, specialise=1),
+        "specialise_bvh": dict(force_bvh=1, instancing=0, wavefront=0, specialise=1),
+    }
+    for name, opts in variants.items():
+        with capi.options(**opts):
+            scene = capi.Scene(ctx, sd)
+            film, states, info = _session(ctx, scene, cfg)
+        if name.startswith("specialise"):
+            assert info["specialised"] == 1, info
+        assert info["kernel_flags"] & LENS_BIT, name
+        assert n_bit_diff(film, ref) == 0, f"{name}: {n_bit_diff(film, ref)} film floats differ"
+        assert np.array_equal(states, ref_states), name
+    with capi.options(force_bvh=1, instancing=0, wavefront=0, specialise=0):
+        scene = capi.Scene(ctx, sd)
+        acc = np.zeros(7 * w * h, np.float32)
+        for r in range(8):
+            film = capi.Film(ctx, w, h)
+            capi.pt_render(ctx, scene, distributed.shard_config(cfg, r, 8, 8, 8), film)
+            part = film.read()
+            assert not np.any((acc != 0) & (part != 0))
+            acc += part
+    assert n_bit_diff(acc, ref) == 0
+    if sampler != abi.SAMPLER_INDEPENDENT:
+        with capi.options(force_bvh=0, instancing=0, wavefront=0, specialise=0):
+            scene = capi.Scene(ctx, sd)
+            film = capi.Film(ctx, w, h)
+            for b, c in ((0, 5), (5, 4), (9, 3)):
+                se = capi.PtSession(ctx, scene, make_config(spp=12, spp_per_pass=4, max_depth=6, sampler_type=sampler, sampler_seed=7,
+                                                            sample_begin=b, sample_count=c), film)
+                assert se.passes(1000, blocking=True) == c
+                states = se.sampler_states(w * h)
+                se.end()
+        assert n_bit_diff(film.read(), ref) == 0
+        assert np.array_equal(states, ref_states)
+
+
+# ---------------------------------------------------------------------------------------------------------------- focus
+EMISSION = (4.0, 3.0, 2.0)
+
+
+def _emitter_scene(verts, width, height, c2w=None):
+    """One emissive quad with a black base (verts: 4 x 3, counter-clockwise seen from the camera), camera at the origin looking down -z with
+    tan(fov / 2) = 1/2 -- or the whole arrangement moved by the rigid transform c2w (4 x 4)."""
+    m = np.eye(4) if c2w is None else np.asarray(c2w, dtype=np.float64)
+    v = (np.asarray(verts, dtype=np.float64) @ m[:3, :3].T + m[:3, 3]).astype(F)
+    mesh = abi.MeshData(vertices=v, indices=np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32))
+    mat = abi.MaterialData(kind=abi.MAT_EMISSION, base_color=(0.0, 0.0, 0.0), emission_color=EMISSION, emission_strength=1.0)
+    eye = np.eye(4, dtype=F).reshape(16).copy()
+    cam = abi.CameraData(c2w=m.astype(F).T.reshape(16).copy(), fov=float(2.0 * np.arctan(0.5)), width=width, height=height)
+    return abi.SceneData([mesh], [abi.InstanceData(0, [0], eye)], [mat], cam)
+
+
+def _focus_cfg(spp, sampler=abi.SAMPLER_INDEPENDENT):
+    return make_config(spp=spp, spp_per_pass=min(spp, 64), max_depth=1, filter_type=abi.FILTER_BOX, filter_radius=1.0, sampler_type=sampler, sampler_seed=5)
+
+
+@pytest.mark.parametrize("sampler", [abi.SAMPLER_INDEPENDENT, abi.SAMPLER_SOBOL], ids=["independent", "sobol"])
+def test_in_focus_is_sharp(ctx, sampler):
+    """A quad in the plane of focus (z = -F, F = 4): with tan(fov / 2) = 1/2 and a 64 x 64 frame the plane point of film position p is
+    p / 16 - 2, so the quad [-1, 1]^2 has its edges on the pixel boundaries 16 and 48. The box filter of radius 1 makes a pixel's footprint
+    the pixel. Exempt: the pixel rows and columns that touch an edge (15, 16, 47, 48) -- rounding may move a sample across."""
+    W = H = 64
+    Fd = 4.0
+    sd = _emitter_scene([[-1, -1, -Fd], [1, -1, -Fd], [1, 1, -Fd], [-1, 1, -Fd]], W, H)
+    cfg = _focus_cfg(32, sampler)
+    # the oracle first: the pinhole film is constant inside the quad
+    o_film, _ = pyoracle.OracleScene(sd).render(cfg)
+    o_img = o_film[: 3 * W * H].reshape(H, W, 3)
+    inside = np.zeros((H, W), bool)
+    inside[17:47, 17:47] = True
+    outside = np.ones((H, W), bool)
+    outside[15:49, 15:49] = False
+    exempt = ~(inside | outside)
+    assert int(exempt.sum()) == 34 * 34 - 30 * 30
+    assert np.all(o_img[inside] == o_img[20, 20]) and np.all(o_img[20, 20] > 0) and np.all(o_img[outside] == 0)
+    scene = capi.Scene(ctx, sd)
+    pin, _, _ = _session(ctx, scene, cfg)
+    assert n_bit_diff(pin, o_film) == 0
+    for R in (0.05, 0.5):
+        scene.set_lens(R, Fd)
+        film, _, info = _session(ctx, scene, cfg)
+        assert info["kernel_flags"] & LENS_BIT
+        img, pimg = film[: 3 * W * H].reshape(H, W, 3), pin[: 3 * W * H].reshape(H, W, 3)
+        assert np.array_equal(img[inside].view(np.uint32), pimg[inside].view(np.uint32)), R
+        assert np.all(img[outside] == 0), R
+        assert np.array_equal(film[6 * W * H:], pin[6 * W * H:])  # the weights: one per sample everywhere
+    # the same quad out of focus is NOT sharp: the test above is not vacuous
+    scene.set_lens(0.5, 2.0)
+    film, _, _ = _session(ctx, scene, cfg)
+    img = film[: 3 * W * H].reshape(H, W, 3)
+    assert np.any(img[outside] != 0) and np.any(img[inside] != pin[: 3 * W * H].reshape(H, W, 3)[inside])
+
+
+def _disk_fraction(s):
+    """G(s): the fraction of the unit disk with first coordinate below s."""
+    s = np.clip(s, -1.0, 1.0)
+    return 0.5 + (s * np.sqrt(1.0 - s * s) + np.arcsin(s)) / np.pi
+
+
+@pytest.mark.parametrize("rotated", [False, True], ids=["axis_aligned", "rotated_camera"])
+@pytest.mark.parametrize("D,R", [(2.0, 0.625), (8.0, 1.25)], ids=["nearer_than_focus", "beyond_focus"])
+def test_out_of_focus_has_the_closed_form_blur(ctx, D, R, rotated):
+    """The emitter is the half-plane x < 0 at depth D, the lens is focused at F = 4. The ray of film point X (camera plane z = -1) through
+    the lens point l meets the plane at x = D X + l.x (1 - D / F); l.x / R is the first coordinate of a uniform point of the unit disk
+    (the concentric mapping preserves area), so the sample sees the emitter with probability
+        p(X) = G(-D X / |R (1 - D / F)|),   G(s) = 1/2 + (s sqrt(1 - s^2) + asin s) / pi on [-1, 1], clamped outside
+    -- with c = R (1 - D / F): l.x c < -D X is a < s = -D X / c for c > 0 (D < F) and a > s for c < 0 (D > F), the mirrored cap, G(-s):
+    the absolute value covers both sides of the plane of focus (the issue's text gives s without it, which is the D < F case). The pixel's
+    value / the emitter's value is p averaged over the pixel's box footprint; a sample is a Bernoulli trial."""
+    W, H, Fd, spp = 128, 16, 4.0, 256
+    big = 200.0
+    c2w = None
+    if rotated:
+        c2w = np.eye(4)
+        c2w[:3, :3] = _rot(0.35, -0.6)
+        c2w[:3, 3] = [3.0, -2.0, 5.0]
+    sd = _emitter_scene([[-big, -big, -D], [0, -big, -D], [0, big, -D], [-big, big, -D]], W, H, c2w)
+    scene = capi.Scene(ctx, sd)
+    cfg = _focus_cfg(spp)
+    pin, _, _ = _session(ctx, scene, cfg)
+    pimg = pin[: 3 * W * H].reshape(H, W, 3)
+    full = pimg[8, 2]  # deep inside the emitter: spp hits
+    assert np.all(full > 0) and np.all(pimg[:, :60] == full) and np.all(pimg[:, 68:] == 0)
+    scene.set_lens(R, Fd)
+    film, _, info = _session(ctx, scene, cfg)
+    assert info["kernel_flags"] & LENS_BIT
+    img = film[: 3 * W * H].reshape(H, W, 3)
+    hits = img[:, :, 0].astype(np.float64) / float(full[0]) * spp  # hits per pixel
+    assert np.allclose(hits, np.round(hits), atol=1e-3)
+    p_hat = hits / spp
+    # expected: p averaged over the footprint [px, px + 1) (midpoint rule, 256 points); X = (2 p / W - 1) / 2
+    sub = (np.arange(256) + 0.5) / 256
+    xs = ((np.arange(W)[:, None] + sub[None, :]) * 2.0 / W - 1.0) * 0.5
+    p = _disk_fraction(-D * xs / abs(R * (1.0 - D / Fd))).mean(axis=1)
+    blur_px = np.count_nonzero((p > 1e-3) & (p < 1 - 1e-3))
+    assert blur_px >= 30, blur_px
+    tol = 6.0 * np.sqrt(p * (1.0 - p) / spp)
+    err = np.abs(p_hat - p[None, :])
+    assert np.all(err <= tol[None, :] + 1e-12), (float((err - tol[None, :]).max()), np.argwhere(err > tol[None, :] + 1e-12)[:5])
+    col = p_hat.mean(axis=0)
+    tol_col = 6.0 * np.sqrt(p * (1.0 - p) / (spp * H))
+    assert np.all(np.abs(col - p) <= tol_col + 1e-12), float((np.abs(col - p) - tol_col).max())
+    # and the blur is there: the pinhole's step is not within these bounds
+    assert np.any(np.abs(pimg[:, :, 0] / full[0] - p[None, :]) > tol[None, :] + 1e-12)
+
+
+def test_aov_through_the_lens(ctx):
+    W = H = 64
+    Fd = 4.0
+    sd = _emitter_scene([[-1, -1, -Fd], [1, -1, -Fd], [1, 1, -Fd], [-1, 1, -Fd]], W, H)
+    scene = capi.Scene(ctx, sd)
+    a = abi.AovConfig.default()
+    a.spp, a.aov, a.filter_type, a.filter_radius = 16, abi.AOV_NS, abi.FILTER_BOX, 1.0
+    pin = capi.Film(ctx, W, H)
+    capi.aov_render(ctx, scene, a, pin)
+    scene.set_lens(0.5, Fd)
+    lens = capi.Film(ctx, W, H)
+    capi.aov_render(ctx, scene, a, lens)
+    p, l = pin.read()[: 3 * W * H].reshape(H, W, 3), lens.read()[: 3 * W * H].reshape(H, W, 3)
+    assert np.any(p[17:47, 17:47] != 0)
+    assert np.array_equal(l[17:47, 17:47].view(np.uint32), p[17:47, 17:47].view(np.uint32))
+    outside = np.ones((H, W), bool)
+    outside[15:49, 15:49] = False
+    assert np.all(l[outside] == 0)
+    # out of focus the feature buffer blurs with the beauty pass
+    scene.set_lens(0.5, 2.0)
+    capi.aov_render(ctx, scene, a, lens := capi.Film(ctx, W, H))
+    assert np.any(lens.read()[: 3 * W * H].reshape(H, W, 3)[outside] != 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- refusals, CLI
+def test_refusals(ctx, root):
+    sd = _route_scene(root, with_env=False)
+    scene = capi.Scene(ctx, sd)
+    w, h = sd.camera.width, sd.camera.height
+    film = capi.Film(ctx, w, h)
+    g = abi.GptConfig.default()
+    g.spp, g.max_depth = 4, 4
+    with pytest.raises(capi.AkariError) as e:
+        capi.gpt_render(ctx, scene, g, film)
+    assert e.value.code == capi.ERR_UNSUPPORTED and "lens" in str(e.value)
+    m = abi.McmcConfig.default()
+    m.spp, m.max_depth, m.n_chains, m.n_bootstrap = 2, 4, 256, 1024
+    with pytest.raises(capi.AkariError) as e:
+        capi.mcmc_render(ctx, scene, m, film)
+    assert e.value.code == capi.ERR_UNSUPPORTED and "lens" in str(e.value)
+    with capi.options(arith=1, wavefront=0, instancing=0):
+        with pytest.raises(capi.AkariError) as e:
+            capi.pt_render(ctx, scene, make_config(spp=4), film)
+    assert e.value.code == capi.ERR_UNSUPPORTED and "lens" in str(e.value)
+    se = capi.PtSession(ctx, scene, make_config(spp=4), film)
+    try:
+        with pytest.raises(capi.AkariError) as e:
+            scene.set_lens(0.1, 2.0)
+        assert e.value.code == capi.ERR_INVALID_ARGUMENT
+        with pytest.raises(capi.AkariError):
+            scene.set_lens(None)
+    finally:
+        se.end()
+    scene.set_lens(None)  # no session now: allowed, and the other integrators render again
+    capi.gpt_render(ctx, scene, g, film)
+
+
+def test_cli_depth_of_field(ctx, root, tmp_path):
+    from akari_render_amd import build
+    cli = build.build_cli()
+    L = (0.25, 0.5, 0.75)
+    # the quad at distance 3 under a constant environment; the file says focal_distance 1, fstop 2.8 (radius 1 / 5.6)
+    spath = scene_json_text(tmp_path, {"color": list(L), "strength": 2.0}, fov=90.0)
+    outs = {}
+    for name, flags in (("plain", []), ("plain_again", []), ("dof", ["--depth-of-field"]),
+                        ("override", ["--depth-of-field", "--lens-radius", "0.3", "--focal-distance", "3"]),
+                        ("values_only", ["--lens-radius", "0.3", "--focal-distance", "1.5"])):
+        out = tmp_path / f"{name}.exr"
+        method = {"method": {"type": "pt", "spp": 16, "spp_per_pass": 16, "max_depth": 4}, "sampler": {"type": "independent", "seed": 1}, "film": {"out": str(out)}}
+        mpath = tmp_path / f"{name}.json"
+        mpath.write_text(json.dumps(method))
+        res = subprocess.run([cli, "-s", spath, "-m", str(mpath)] + flags, cwd=tmp_path, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, (name, res.stdout, res.stderr)
+        outs[name] = capi.host_decode_exr(open(out, "rb").read())
+    # half a lens, or something that is no number, is an error with a message (not a silent pinhole)
+    for flags in (["--lens-radius", "0.3"], ["--focal-distance", "2"], ["--depth-of-field", "--lens-radius", "abc"], ["--lens-radius", "-1", "--focal-distance", "2"]):
+        res = subprocess.run([cli, "-s", spath, "-m", str(tmp_path / "plain.json")] + flags, cwd=tmp_path, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 1 and "akari-cli: --" in res.stderr, (flags, res.stderr)
+    # without the flag: the pinhole image -- what the library renders for the file through the C ABI, where the loader's default is no lens
+    scene = capi.Scene(ctx, spath)
+    assert scene.lens() is None
+    film = capi.Film(ctx, 16, 16)
+    capi.pt_render(ctx, scene, make_config(spp=16, spp_per_pass=16, max_depth=4, sampler_seed=1), film)
+    assert np.array_equal(outs["plain"], outs["plain_again"])
+    want = np.float32(L) * np.float32(2.0)
+    for y, x in ((0, 0), (0, 15), (15, 0), (15, 15)):
+        assert np.array_equal(outs["plain"][y, x, :3], want)
+    assert np.allclose(outs["plain"][..., :3], resolve_np(film.read(), 16, 16).reshape(16, 16, 3), rtol=0, atol=0)
+    for name in ("dof", "override", "values_only"):
+        assert np.any(outs[name] != outs["plain"]), name
+    assert np.any(outs["dof"] != outs["override"])
