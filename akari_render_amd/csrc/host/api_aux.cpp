@@ -16,7 +16,7 @@ AKR_API int32_t akr_aov_config_default(akr_aov_config* c) {  // aov::Config::def
 AKR_API int32_t akr_aov_render(akr_context* ctx, akr_scene* scene, const akr_aov_config* cfg, akr_film* film, akr_pt_stats* stats) {
     if (!ctx || !scene || !cfg || !film) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_aov_render: NULL argument");
     if (cfg->aov > AKR_AOV_ROUGHNESS) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_aov_render: unknown aov");
-    // the session machinery of the path tracer provides sampler states, counters, sharding and the kernel parameters
+    // the render base provides sampler states, counters, sharding and the kernel parameters (one pass of all spp)
     akr_pt_config pc;
     akr_pt_config_default(&pc);
     pc.spp = cfg->spp; pc.spp_per_pass = cfg->spp ? cfg->spp : 1;
@@ -24,25 +24,18 @@ AKR_API int32_t akr_aov_render(akr_context* ctx, akr_scene* scene, const akr_aov
     pc.sampler_type = cfg->sampler_type; pc.sampler_seed = cfg->sampler_seed;
     pc.shard_rank = cfg->shard_rank; pc.shard_count = cfg->shard_count; pc.tile_w = cfg->tile_w; pc.tile_h = cfg->tile_h;
     pc.color = cfg->color;
-    akr_pt_session* se = nullptr;
-    int32_t rc = pt_begin(ctx, scene, &pc, film, &se, /*for_pt_kernel=*/false);
+    RenderBase* se = nullptr;
+    int32_t rc = render_begin(ctx, scene, &pc, film, &se);
     if (rc != AKR_OK) return rc;
     rc = guarded([&] {
         if (cfg->spp == 0) return;
-        fill_params(se, 1, cfg->spp);
         LaunchTimer timer(se);
         HIP_CHECK(launch_aov(se->params, cfg->spp, cfg->aov, cfg->remap ? 1u : 0u, ctx->stream));
         timer.stop();
         se->n_launches++;
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
-    std::string err = g_last_error;
-    int32_t rc2 = akr_pt_end(se, stats);
-    if (rc != AKR_OK) {
-        g_last_error = err;
-        return rc;
-    }
-    return rc2;
+    return end_keeping_first_error(rc, [&] { return base_end(se, stats); });
 }
 
 // ------------------------------------------------------------------------------------------------ gpt integrator
@@ -64,10 +57,10 @@ struct akr_gpt_session {
     akr_scene* scene = nullptr;
     akr_film* film = nullptr;
     akr_gpt_config cfg;
-    akr_pt_session* pt = nullptr;  // sampler states, counters, kernel parameters, timing
+    RenderBase* base = nullptr;  // sampler states, counters, kernel parameters (n_items: the pixels this rank samples), timing
     DevBuf scratch, sums, item_pixels;
     GptParams g;
-    uint32_t W = 0, H = 0, spp_done = 0, n_items = 0;
+    uint32_t W = 0, H = 0, spp_done = 0;
     bool recon = false;
     size_t n_sums() const { return recon ? 6 * (size_t)W * H + 12 * (size_t)(W + 1) * (H + 1) : 0; }
 };
@@ -106,13 +99,13 @@ AKR_API int32_t akr_gpt_begin(akr_context* ctx, akr_scene* scene, const akr_gpt_
     pc.filter_type = cfg->filter_type; pc.filter_radius = cfg->filter_radius;
     pc.sampler_type = cfg->sampler_type; pc.sampler_seed = cfg->sampler_seed;
     pc.color = cfg->color;
-    akr_pt_session* pt = nullptr;
-    int32_t rc = pt_begin(ctx, scene, &pc, film, &pt, /*for_pt_kernel=*/false);
+    RenderBase* base = nullptr;
+    int32_t rc = render_begin(ctx, scene, &pc, film, &base);
     if (rc != AKR_OK) return rc;
     std::unique_ptr<akr_gpt_session> se;
     rc = guarded([&] {
         se = std::make_unique<akr_gpt_session>();  // (inside guarded: a bad_alloc must not cross the C ABI)
-        se->ctx = ctx; se->scene = scene; se->film = film; se->cfg = *cfg; se->pt = pt; se->W = W; se->H = H;
+        se->ctx = ctx; se->scene = scene; se->film = film; se->cfg = *cfg; se->base = base; se->W = W; se->H = H;
         const size_t N = (size_t)W * H, NG = (size_t)(W + 1) * (H + 1);
         se->recon = cfg->reconstruction != AKR_GPT_RECON_NONE;
         se->scratch.alloc(15 * N * sizeof(float));
@@ -130,8 +123,6 @@ AKR_API int32_t akr_gpt_begin(akr_context* ctx, akr_scene* scene, const akr_gpt_
             float* b = se->sums.as<float>();
             g.acc_p = b; g.sqr_p = b + 3 * N; g.acc_gx = b + 6 * N; g.acc_gy = g.acc_gx + 3 * NG; g.sqr_gx = g.acc_gy + 3 * NG; g.sqr_gy = g.sqr_gx + 3 * NG;
         }
-        fill_params(pt, 1, 1);
-        se->n_items = pt->params.n_items;
         g.shard_count = 1;
         if (shard && shard->shard_count > 1) {
             // The rank folds (k_gpt_update) the pixels of its own tiles; a pixel's value gathers what its neighbours' offset paths
@@ -140,9 +131,9 @@ AKR_API int32_t akr_gpt_begin(akr_context* ctx, akr_scene* scene, const akr_gpt_
             // and the upper neighbour, whose +x / +y gradients the update reads). Every rank keeps the whole frame's sampler states,
             // and a halo pixel draws the same numbers on every rank that samples it. The list is built here, once: own pixels
             // tile by tile in 8x8 blocks (the order of item_to_pixel), then the halo.
-            const uint32_t tw = shard->tile_w ? shard->tile_w : 32, th = shard->tile_h ? shard->tile_h : 32;
+            const TileGrid grid = tile_grid(shard->tile_w, shard->tile_h, W, H, shard->shard_rank, shard->shard_count);
+            const uint32_t tw = grid.tile_w, th = grid.tile_h, tiles_x = grid.tiles_x, tiles_y = grid.tiles_y;
             if (tw % 8 != 0 || th % 8 != 0) throw std::invalid_argument("akr_shard: tile sizes must be multiples of 8");
-            const uint32_t tiles_x = (W + tw - 1) / tw, tiles_y = (H + th - 1) / th;
             g.shard_rank = shard->shard_rank; g.shard_count = shard->shard_count; g.tile_w = tw; g.tile_h = th; g.tiles_x = tiles_x;
             auto owned = [&](uint32_t x, uint32_t y) { return tile_owner(x / tw, y / th, shard->shard_count) == shard->shard_rank; };
             std::vector<uint32_t> list;
@@ -170,16 +161,11 @@ AKR_API int32_t akr_gpt_begin(akr_context* ctx, akr_scene* scene, const akr_gpt_
                 }
             se->item_pixels.upload(list);
             g.item_pixels = se->item_pixels.as<uint32_t>();
-            se->n_items = (uint32_t)list.size();
+            base->params.n_items = (uint32_t)list.size();
         }
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
-    if (rc != AKR_OK) {
-        std::string err = g_last_error;
-        akr_pt_end(pt, nullptr);
-        g_last_error = err;
-        return rc;
-    }
+    if (rc != AKR_OK) return end_keeping_first_error(rc, [&] { return base_end(base, nullptr); });
     *out = se.release();
     return AKR_OK;
 }
@@ -188,18 +174,16 @@ AKR_API int32_t akr_gpt_sample(akr_gpt_session* se, uint32_t n_samples, int32_t 
     return guarded([&] {
         se->ctx->bind();
         const uint32_t left = se->cfg.spp - se->spp_done, n = n_samples == 0 ? left : std::min(n_samples, left);
-        akr_pt_session* pt = se->pt;
-        fill_params(pt, 1, 1);
-        pt->params.n_items = se->n_items;
-        LaunchTimer timer(pt);
+        RenderBase* base = se->base;
+        LaunchTimer timer(base);
         for (uint32_t s = 0; s < n; s++) {  // gpt.rs:468-485: kernel + update_kernel per sample
-            HIP_CHECK(launch_gpt_sample(pt->params, se->g, se->ctx->stream));
+            HIP_CHECK(launch_gpt_sample(base->params, se->g, se->ctx->stream));
             HIP_CHECK(launch_gpt_update(se->g, se->W, se->H, se->film->data, se->ctx->stream));
         }
         timer.stop();
-        pt->n_launches += 2 * n;
+        base->n_launches += 2 * n;
         se->spp_done += n;
-        pt->spp_done = se->spp_done;
+        base->spp_done = se->spp_done;
         if (blocking) HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
     });
 }
@@ -238,7 +222,7 @@ AKR_API int32_t akr_gpt_finish(akr_gpt_session* se, float* aux, akr_pt_stats* st
         const size_t N = (size_t)W * H, NG = (size_t)(W + 1) * (H + 1);
         const GptParams& g = se->g;
         DevBuf old;
-        LaunchTimer timer(se->pt);
+        LaunchTimer timer(se->base);
         if (!se->recon) {
             film->splat_scale = 1.0f / (float)cfg->spp;  // gpt.rs:463-466
         } else if (cfg->spp > 0) {  // gpt.rs:495-606
@@ -265,21 +249,14 @@ AKR_API int32_t akr_gpt_finish(akr_gpt_session* se, float* aux, akr_pt_stats* st
             HIP_CHECK(hipMemcpy(aux + 3 * N, g.acc_gx, 6 * NG * sizeof(float), hipMemcpyDeviceToHost));
         }
     });
-    std::string err = g_last_error;
-    int32_t rc2 = akr_pt_end(se->pt, stats);
-    delete se;
-    if (rc != AKR_OK) {
-        g_last_error = err;
-        return rc;
-    }
-    return rc2;
+    return end_keeping_first_error(rc, [&] { return akr_gpt_abort(se, stats); });
 }
 // Ends a session WITHOUT the splat scale / reconstruction sweeps of akr_gpt_finish: the film keeps whatever the samples (and a
 // reduce) left in it. For a rank that is not the root of akr_gpt_reduce (its partial sums would reconstruct into garbage) and for
 // abandoning a render.
 AKR_API int32_t akr_gpt_abort(akr_gpt_session* se, akr_pt_stats* stats) {
     if (!se) return AKR_OK;
-    int32_t rc = akr_pt_end(se->pt, stats);
+    int32_t rc = base_end(se->base, stats);
     delete se;
     return rc;
 }
@@ -288,13 +265,7 @@ AKR_API int32_t akr_gpt_render(akr_context* ctx, akr_scene* scene, const akr_gpt
     int32_t rc = akr_gpt_begin(ctx, scene, cfg, nullptr, film, &se);
     if (rc != AKR_OK) return rc;
     rc = akr_gpt_sample(se, 0, 0);
-    std::string err = g_last_error;
-    int32_t rc2 = akr_gpt_finish(se, aux, stats);
-    if (rc != AKR_OK) {
-        g_last_error = err;
-        return rc;
-    }
-    return rc2;
+    return end_keeping_first_error(rc, [&] { return akr_gpt_finish(se, aux, stats); });
 }
 
 // ------------------------------------------------------------------------------------------------ mcmc_opt integrator
@@ -340,14 +311,13 @@ int32_t akr_api::mcmc_render_impl(akr_context* ctx, akr_scene* scene, const akr_
     pc.indirect_only = cfg->direct_spp >= 0 ? 1u : 0u;
     pc.filter_type = cfg->filter_type; pc.filter_radius = cfg->filter_radius;
     pc.color = cfg->color;
-    akr_pt_session* se = nullptr;
-    int32_t rc = pt_begin(ctx, scene, &pc, film, &se, /*for_pt_kernel=*/false);
+    RenderBase* se = nullptr;
+    int32_t rc = render_begin(ctx, scene, &pc, film, &se);
     if (rc != AKR_OK) return rc;
     rc = guarded([&] {
         const uint32_t depth = cfg->mcmc_depth == 0xffffffffu ? cfg->max_depth : cfg->mcmc_depth;
         const uint32_t dim = 4 + 1 + (1 + depth) * (3 + 3 + 1);  // sample_dimension, mcmc_opt.rs:230-232
         const uint32_t n_chains = cfg->n_chains, n_boot = cfg->n_bootstrap;
-        fill_params(se, 1, 1);
         // init_pcg32_buffer_with_seed(n, seed): the bootstrap seeds and the chains' samplers are prefixes of the same stream
         const size_t n_seeds = std::max(n_chains, n_boot);
         std::vector<Pcg32> seeds(n_seeds);
@@ -470,13 +440,7 @@ int32_t akr_api::mcmc_render_impl(akr_context* ctx, akr_scene* scene, const akr_
         }
         if (chain_states) std::memcpy(chain_states, states.data(), n_chains * sizeof(MarkovState));
     });
-    std::string err = g_last_error;
-    int32_t rc2 = akr_pt_end(se, stats);
-    if (rc != AKR_OK) {
-        g_last_error = err;
-        return rc;
-    }
-    return rc2;
+    return end_keeping_first_error(rc, [&] { return base_end(se, stats); });
 }
 
 extern "C" {

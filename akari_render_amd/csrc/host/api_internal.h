@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstdio>
 #include <chrono>
@@ -111,6 +112,27 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
+// A frame cut into tiles (0 = the default size, 32) and the pixels of the tiles rank `rank` of `count` owns, whole tiles counted
+struct TileGrid {
+    uint32_t tile_w = 32, tile_h = 32, tiles_x = 0, tiles_y = 0, n_items = 0;
+};
+inline TileGrid tile_grid(uint32_t tile_w, uint32_t tile_h, uint32_t width, uint32_t height, uint32_t rank, uint32_t count) {
+    TileGrid g;
+    auto or_default = [](uint32_t t) { return t ? t : 32u; };
+    g.tile_w = or_default(tile_w);
+    g.tile_h = or_default(tile_h);
+    g.tiles_x = (width + g.tile_w - 1) / g.tile_w;
+    g.tiles_y = (height + g.tile_h - 1) / g.tile_h;
+    uint32_t n = g.tiles_x * g.tiles_y;
+    if (count > 1) {
+        n = 0;
+        for (uint32_t ty = 0; ty < g.tiles_y; ty++)
+            for (uint32_t tx = 0; tx < g.tiles_x; tx++) n += tile_owner(tx, ty, count) == rank ? 1u : 0u;
+    }
+    g.n_items = n * g.tile_w * g.tile_h;
+    return g;
+}
+
 }  // namespace akr_api
 using namespace akr_api;
 
@@ -174,52 +196,29 @@ struct akr_film {
     size_t n_floats() const { return 7ull * width * height; }
 };
 
-struct akr_pt_session {
+// What every integrator's session holds (pt, aov, gpt, mcmc_opt): made by base_begin, ended by base_end (api_pt.cpp).
+struct RenderBase {
     akr_context* ctx = nullptr;
     akr_scene* scene = nullptr;
     akr_film* film = nullptr;
     akr_pt_config cfg;
     DevBuf states, counters;
+    TileGrid grid;             // the frame's tiles and this rank's share of them
     DevBuf owned_tiles;        // shard_count > 1: PtParams.owned_tiles
-    uint32_t n_owned_tiles = 0;
-    // wavefront schedule (wf_kernels.hip): path state SoA + ray queues
-    bool wavefront = false;
-    int sched_trial = 0;  // flattened scenes, option wavefront = -1: 1 = the first blocking akr_pt_passes call times both schedules and keeps the faster (api_pt.cpp), 2 = done
-    DevBuf wf_state, wf_queues, wf_ctrl, wf_pend, wf_carry;
-    // option wf_sort: keys of the queue entries, the sorted copies the trace kernel reads, rocPRIM's scratch
-    bool wf_sort = false;
-    DevBuf wf_keys, wf_sorted, wf_sort_tmp;
-    uint32_t *wf_sorted_closest = nullptr, *wf_sorted_shadow = nullptr, *wf_sorted_keys = nullptr;
-    WfBuffers wf;
-    uint32_t wf_slots = 0, wf_trace_blocks = 0;
-    // slot groups (option wf_groups; api_pt.cpp wf_run): each with its own queues, counters and stream
-    std::vector<WfBuffers> wf_group;
-    std::vector<hipStream_t> wf_streams;
-    std::vector<hipEvent_t> wf_join;
-    hipEvent_t wf_fork = nullptr;
     uint32_t spp_done = 0, n_launches = 0;
-    uint64_t passes_launched = 0;  // passes of all akr_pt_passes launches so far (kernel_ms / passes_launched = what a pass costs)
     uint32_t pmj_spp = 1;  // the spp the pmj02bn sampler stratifies for (the method's total spp)
-    const akr_scene::ColorSet* color_set = nullptr;  // the scene's tables for cfg.color != 0 (looked up under the scene's lock by akr_pt_begin)
-    // the process-wide tuning options as they were when the session began (akr_pt_begin): an akr_option_set from another thread
-    // cannot change the kernel of a running session
+    const akr_scene::ColorSet* color_set = nullptr;  // the scene's tables for cfg.color != 0 (looked up under the scene's lock by base_begin)
+    // the process-wide tuning options that shape the parameter block as they were when the session began (base_begin): an
+    // akr_option_set from another thread cannot change the kernel of a running session
     int defer_metal_option = -1;
     int simple_kernels_option = 1;
     int defer_on_option = 0;
-    int max_fused_option = 0;
-    // per-scene kernel (host/specialise.cpp): set by akr_pt_begin when the options ask for one and the compile succeeded; the
-    // precompiled interpreter kernel otherwise. spec_active also shapes fill_params (no value slots in LDS, the kernel's own LDS budget).
-    bool spec_active = false;
-    bool arith_relaxed = false;  // option arith = 1 and the session is one the relaxed tier covers: launches go to pt_kernels_relaxed.hip
-    int spec_waves = 3;
-    std::shared_ptr<SpecKernel> spec;
-    std::string spec_status = "not requested";
     // timed regions on the context's stream: pairs still in flight, and the elapsed time of the completed ones (folded in and
     // destroyed as they complete, so a long progressive session holds a bounded number of events)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double kernel_ms = 0.0;
-    PtParams params;
-    bool holds_scene = false;  // counted in scene->sessions (pt_begin)
+    PtParams params;  // the session's constant block (session_params); a launch sets n_passes / last_pass_spp (set_launch_passes)
+    bool holds_scene = false;  // counted in scene->sessions (base_begin)
     void fold_events(bool all) {  // all: the stream has been synchronised
         size_t keep = 0;
         for (size_t i = 0; i < pending.size(); i++) {
@@ -235,11 +234,8 @@ struct akr_pt_session {
         }
         pending.resize(keep);
     }
-    ~akr_pt_session() {
+    virtual ~RenderBase() {
         if (holds_scene) scene->sessions--;
-        for (hipStream_t st : wf_streams) (void)hipStreamDestroy(st);
-        for (hipEvent_t ev : wf_join) (void)hipEventDestroy(ev);
-        if (wf_fork) (void)hipEventDestroy(wf_fork);
         for (auto& ev : pending) {
             (void)hipEventDestroy(ev.first);
             (void)hipEventDestroy(ev.second);
@@ -247,13 +243,50 @@ struct akr_pt_session {
     }
 };
 
+// wavefront schedule (wf_kernels.hip): path state SoA + ray queues. A pt session holds one only while that schedule renders it.
+struct WavefrontState {
+    DevBuf state, queues, ctrl, pend, carry;
+    // option wf_sort: keys of the queue entries, the sorted copies the trace kernel reads, rocPRIM's scratch
+    bool sort = false;
+    DevBuf keys, sorted, sort_tmp;
+    uint32_t *sorted_closest = nullptr, *sorted_shadow = nullptr, *sorted_keys = nullptr;
+    WfBuffers buf;
+    uint32_t slots = 0, trace_blocks = 0;
+    // slot groups (option wf_groups; api_pt.cpp wf_run): each with its own queues, counters and stream
+    std::vector<WfBuffers> group;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> join;
+    hipEvent_t fork = nullptr;
+    ~WavefrontState() {
+        for (hipStream_t st : streams) (void)hipStreamDestroy(st);
+        for (hipEvent_t ev : join) (void)hipEventDestroy(ev);
+        if (fork) (void)hipEventDestroy(fork);
+    }
+};
+
+// The pt integrator's session: the base plus what only k_pt_pass and the wavefront schedule need. The other integrators hold a plain
+// RenderBase, so a per-scene kernel's parameter block (no graph value slots in LDS) cannot reach their kernels.
+struct akr_pt_session : RenderBase {
+    std::unique_ptr<WavefrontState> wf;  // set = the wavefront schedule renders the session
+    int sched_trial = 0;  // flattened scenes, option wavefront = -1: 1 = the first blocking akr_pt_passes call times both schedules and keeps the faster (api_pt.cpp), 2 = done
+    uint64_t passes_launched = 0;  // passes of all akr_pt_passes launches so far (kernel_ms / passes_launched = what a pass costs)
+    int max_fused_option = 0;  // option max_fused_passes when the session began
+    // per-scene kernel (host/specialise.cpp): set by akr_pt_begin when the options ask for one and the compile succeeded; the
+    // precompiled interpreter kernel otherwise. spec_active also shapes session_params (no value slots in LDS, the kernel's own LDS budget).
+    bool spec_active = false;
+    bool arith_relaxed = false;  // option arith = 1 and the session is one the relaxed tier covers: launches go to pt_kernels_relaxed.hip
+    int spec_waves = 3;
+    std::shared_ptr<SpecKernel> spec;
+    std::string spec_status = "not requested";
+};
+
 namespace akr_api {
 // One timed region on a session's stream. The event pair is handed to the session by stop(); if the region is left by an
 // exception the pair is destroyed here.
 struct LaunchTimer {
-    akr_pt_session* se;
+    RenderBase* se;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit LaunchTimer(akr_pt_session* s) : se(s) {
+    explicit LaunchTimer(RenderBase* s) : se(s) {
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
         HIP_CHECK(hipEventRecord(e0, se->ctx->stream));
@@ -273,8 +306,30 @@ struct LaunchTimer {
 };
 
 // api_pt.cpp
-int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out, bool for_pt_kernel);
-void fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_pass_spp);
+// What all four integrators begin with: the config validated, the film's size checked, the colour set, sampler states, counters, the
+// owned-tile list, the scene reference. Throws; the caller then computes the session's parameter block (session_params).
+void base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film);
+// base_begin + the block every integrator but pt renders with, behind the C ABI's error boundary (aov, gpt, mcmc_opt)
+int32_t render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, RenderBase** out);
+int32_t base_end(RenderBase* se, akr_pt_stats* stats);  // the stats read back, the session deleted (the scene released)
+// The session's kernel parameter block, computed once: everything but the two fields of set_launch_passes is constant while the
+// session lives (n_passes = 1 full pass until a launch says otherwise). The arguments are what only pt varies.
+void session_params(RenderBase* se, bool spec_active = false, int spec_waves = 3, bool wf_sort = false);
+inline void set_launch_passes(RenderBase* se, uint32_t n_passes, uint32_t last_pass_spp) {
+    se->params.n_passes = n_passes;
+    se->params.last_pass_spp = last_pass_spp;
+}
+// the camera part of a parameter block: r2c, c2w, c2w_identity, width, height, filter, lens
+void camera_params(PtParams& p, const akr_scene* s, uint32_t filter_type, float filter_radius);
+// Ends a session after `rc`, the status of what ran in it: the first error and its message are what the caller sees.
+template <typename End>
+int32_t end_keeping_first_error(int32_t rc, End&& end) {
+    const std::string err = g_last_error;
+    const int32_t rc2 = end();
+    if (rc == AKR_OK) return rc2;
+    g_last_error = err;
+    return rc;
+}
 uint32_t session_samples(const akr_pt_config& c);
 // the tiles (row-major ids) rank `rank` of `count` owns, in Morton order (kernels.h tile_owner)
 std::vector<uint32_t> owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count);

@@ -165,25 +165,17 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context* ctx, akr_scene* scene, ui
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context* ctx, akr_scene* scene, uint32_t n, const float* dirs3, float* out4) {
     return probe_env(ctx, scene, 1, n, dirs3, out4, "akr_probe_env_pdf");
 }
-// the camera's ray generation (device/dpath.h): the parameter block's camera part as fill_params sets it
-static PtParams camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {
+// the camera's ray generation (device/dpath.h): the parameter block's camera part, filled by the sessions' own function
+static PtParams probe_camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {
     PtParams p;
     std::memset(&p, 0, sizeof p);
-    std::memcpy(p.r2c, s->r2c, 64);
-    std::memcpy(p.c2w, s->c2w, 64);
-    p.c2w_identity = s->c2w_identity;
-    p.width = s->flat.camera.width;
-    p.height = s->flat.camera.height;
-    p.filter_type = filter_type;
-    p.filter_radius = filter_radius;
-    p.lens_radius = s->flat.lens.radius;
-    p.lens_focal = s->flat.lens.focal_distance;
+    camera_params(p, s, filter_type, filter_radius);
     return p;
 }
 AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6) {
     if (!scene || !pixels2 || !u4 || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_lens_ray: NULL argument");
     if (filter_type > AKR_FILTER_GAUSSIAN) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_lens_ray: unknown filter_type");
-    const PtParams p = camera_params(scene, filter_type, filter_radius);
+    const PtParams p = probe_camera_params(scene, filter_type, filter_radius);
     for (uint32_t i = 0; i < n; i++) {
         const float* u = u4 + 4ull * i;
         vec3 o, d;
@@ -204,7 +196,7 @@ AKR_TEST_API int32_t akr_probe_camera_rays(akr_context* ctx, akr_scene* scene, u
         dpx.upload(std::vector<uint32_t>(pixels2, pixels2 + 2ull * n));
         du.upload(std::vector<float>(u4, u4 + 4ull * n));
         dout.alloc(6ull * n * 4);
-        if (n) HIP_CHECK(launch_probe_camera_rays(camera_params(scene, filter_type, filter_radius), n, dpx.as<uint32_t>(), du.as<float>(), dout.as<float>(), ctx->stream));
+        if (n) HIP_CHECK(launch_probe_camera_rays(probe_camera_params(scene, filter_type, filter_radius), n, dpx.as<uint32_t>(), du.as<float>(), dout.as<float>(), ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         if (n) HIP_CHECK(hipMemcpy(out6, dout.p, 6ull * n * 4, hipMemcpyDeviceToHost));
     });

@@ -1,17 +1,26 @@
 // api_pt.cpp -- the `pt` integrator: kernel parameters, sessions, both schedules, per-scene kernels (C ABI of libakari_hip.so, include/akari_hip.h; shared internals: api_internal.h)
 #include "api_internal.h"
 
-void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_pass_spp) {
-    PtParams& p = se->params;
-    const akr_scene* s = se->scene;
-    const akr_pt_config& c = se->cfg;
-    std::memset(&p, 0, sizeof p);
-    p.sc = s->dscene;
+void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_type, float filter_radius) {
     std::memcpy(p.r2c, s->r2c, 64);
     std::memcpy(p.c2w, s->c2w, 64);
     p.c2w_identity = s->c2w_identity;
     p.width = s->flat.camera.width;
     p.height = s->flat.camera.height;
+    p.filter_type = filter_type;
+    p.filter_radius = filter_radius;
+    p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
+    p.lens_focal = s->flat.lens.focal_distance;
+}
+void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, bool wf_sort) {
+    PtParams& p = se->params;
+    const akr_scene* s = se->scene;
+    const akr_pt_config& c = se->cfg;
+    const CompiledScene& cs = s->cs;
+    const bool bvh = cs.has_tree();
+    std::memset(&p, 0, sizeof p);
+    p.sc = s->dscene;
+    camera_params(p, s, c.filter_type, c.filter_radius);
     p.max_depth = c.max_depth;
     p.rr_depth = c.rr_depth;
     p.use_nee = c.use_nee;
@@ -20,11 +29,8 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
     p.debug_depth = c.debug_depth;
     p.pixel_offset[0] = c.pixel_offset[0];
     p.pixel_offset[1] = c.pixel_offset[1];
-    p.filter_type = c.filter_type;
-    p.filter_radius = c.filter_radius;
     p.pass_spp = c.spp_per_pass;
-    p.n_passes = n_passes;
-    p.last_pass_spp = last_pass_spp;
+    set_launch_passes(se, 1, c.spp_per_pass);
     p.start = pcg_start_constants();
     p.states = se->states.as<Pcg32>();
     p.film = se->film->data;
@@ -53,8 +59,6 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         }
     }
     {  // LDS staging of the tables the shading phase gathers from (device/pt_pass.h: STAGE)
-        const CompiledScene& cs = s->cs;
-        const bool bvh = !cs.bvh_nodes.empty() || cs.instanced.on;
         // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
         // BVH path: the per-scene tables only, if they fit beside the traversal stacks
         size_t bytes[13] = {bvh ? 0 : cs.shade.size() * 4, bvh ? 0 : cs.normals.size() * 4, cs.inst.size() * 4, cs.materials.size() * sizeof(DMaterial),
@@ -69,13 +73,13 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         for (int i = 0; i < 12; i++) total += (bytes[i] + 15) & ~(size_t)15;
         std::memset(p.stage_bytes, 0, sizeof p.stage_bytes);
         p.stage_total = 0;
-        p.tex_slots = (cs.has_textures && !se->spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
+        p.tex_slots = (cs.has_textures && !spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
         // one workgroup's dynamic LDS stays within 64 KB: traversal stacks + staged tables + the graph evaluation's value slots
         // what the launch keeps in LDS besides the staged tables: traversal stacks, graph values, and the columns / records of pt_lds_plan
         const PtLdsPlan plan = pt_lds_plan(bvh, c.force_diffuse != 0, cs.has_textures, /*defer: the larger park block*/ true, cs.n_tris);
         const size_t other = (bvh ? (size_t)p.sc.bvh_stack_depth * 256 * 4 : 0) + (size_t)p.tex_slots * kTexValStride * sizeof(TexVal) + plan.recs_bytes +
                              plan.park_bytes + plan.carry_bytes;
-        const size_t lds_budget = (se->spec_active && se->spec_waves >= 4) ? pt_lds_budget(false) : pt_lds_budget(cs.has_textures);
+        const size_t lds_budget = (spec_active && spec_waves >= 4) ? pt_lds_budget(false) : pt_lds_budget(cs.has_textures);
         if (!cs.instanced.on && total <= (bvh ? kStageMaxBytesBvh : kStageMaxBytes) && (!bvh || other + total <= lds_budget)) {  // (the instanced-scene kernels do not stage)  // all of it or nothing (a TEX kernel reads its tables through LDS addresses)
             // the albedo table as well for the full-graph exhaustive kernel of a textured scene (stage_scene_tables: GGX), if three
             // workgroups per CU still fit (AKR_PT_MIN_WAVES_TEX = 3: 160 KB / 3)
@@ -91,7 +95,6 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
     {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
         // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
         // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
-        const CompiledScene& cs = s->cs;
         bool simple = !cs.has_textures;
         for (const DMaterial& m : cs.materials) {
             if (m.kind == MAT_GLASS) simple = false;
@@ -102,8 +105,6 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
     {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
         // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
         // instead a shader graph to evaluate at the hit.
-        const CompiledScene& cs = s->cs;
-        const bool bvh = !cs.bvh_nodes.empty() || cs.instanced.on;
         uint32_t flags = MF_EVAL_METAL;
         // (measured on the textured room, BVH kernel: conductor hits deferred 591 Msamples/s, textured hits 573, both 573, none 544)
         if (bvh && cs.has_textures) flags = se->defer_on_option == 2 ? MF_TEXTURED : (se->defer_on_option == 3 ? (MF_EVAL_METAL | MF_TEXTURED) : MF_EVAL_METAL);
@@ -119,7 +120,7 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
         p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on && !cs.env.on && s->flat.lens.radius == 0.0f) ? mask : 0u;  // (nor DEFER ones)
         p.defer_flags = flags;
     }
-    p.wf_sort = se->wf_sort ? 1u : 0u;
+    p.wf_sort = wf_sort ? 1u : 0u;
     for (int a = 0; a < 3; a++) {  // the sort key's grid: 128 cells per axis over the scene's box
         const float lo = s->cs.scene_lo[a], ext = s->cs.scene_hi[a] - s->cs.scene_lo[a];
         p.sort_lo[a] = lo;
@@ -127,24 +128,12 @@ void akr_api::fill_params(akr_pt_session* se, uint32_t n_passes, uint32_t last_p
     }
     p.shard_rank = c.shard_count > 1 ? c.shard_rank : 0;
     p.shard_count = c.shard_count > 1 ? c.shard_count : 1;
-    p.tile_w = c.tile_w ? c.tile_w : 32;
-    p.tile_h = c.tile_h ? c.tile_h : 32;
-    p.tiles_x = (p.width + p.tile_w - 1) / p.tile_w;
-    p.tiles_y = (p.height + p.tile_h - 1) / p.tile_h;
-    if (p.shard_count > 1) {
-        if (se->owned_tiles.p == nullptr && se->n_owned_tiles == 0) {  // once per session: the configuration does not change
-            const std::vector<uint32_t> list = owned_tiles(p.tiles_x, p.tiles_y, p.shard_rank, p.shard_count);
-            se->n_owned_tiles = (uint32_t)list.size();
-            if (!list.empty()) se->owned_tiles.upload(list);
-        }
-        p.owned_tiles = se->owned_tiles.as<uint32_t>();
-        p.n_items = se->n_owned_tiles * p.tile_w * p.tile_h;
-    } else {
-        p.owned_tiles = nullptr;
-        p.n_items = p.tiles_x * p.tiles_y * p.tile_w * p.tile_h;
-    }
-    p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
-    p.lens_focal = s->flat.lens.focal_distance;
+    p.tile_w = se->grid.tile_w;
+    p.tile_h = se->grid.tile_h;
+    p.tiles_x = se->grid.tiles_x;
+    p.tiles_y = se->grid.tiles_y;
+    p.owned_tiles = se->owned_tiles.as<uint32_t>();  // (null unless shard_count > 1: base_begin)
+    p.n_items = se->grid.n_items;
 }
 std::vector<uint32_t> akr_api::owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count) {
     std::vector<std::pair<uint32_t, uint32_t>> mine;  // (Morton code, tile)
@@ -182,36 +171,30 @@ static uint32_t wf_auto_items(const akr_scene* scene) {
     const bool carry = tuning().wf_carry != 0 && tuning().wf_sort == 0;
     return (uint32_t)std::min<uint64_t>(2000000u, carry ? 500000u + mesh_bytes / 55u : 700000u + mesh_bytes / 18u);
 }
-static uint32_t session_items(const akr_pt_config& c, uint32_t width, uint32_t height) {  // = fill_params' n_items
-    const uint32_t tw = c.tile_w ? c.tile_w : 32, th = c.tile_h ? c.tile_h : 32;
-    const uint32_t tiles_x = (width + tw - 1) / tw, tiles_y = (height + th - 1) / th;
-    if (c.shard_count <= 1) return tiles_x * tiles_y * tw * th;
-    uint32_t n = 0;
-    for (uint32_t ty = 0; ty < tiles_y; ty++)
-        for (uint32_t tx = 0; tx < tiles_x; tx++) n += tile_owner(tx, ty, c.shard_count) == c.shard_rank ? 1u : 0u;
-    return n * tw * th;
-}
-static bool choose_wavefront(const akr_scene* scene, const akr_pt_config& cfg, bool for_pt_kernel) {
+static bool choose_wavefront(const akr_pt_session* se) {
+    const akr_scene* scene = se->scene;
     const int opt = tuning().wavefront;
-    const bool can = !scene->cs.bvh_nodes.empty() || scene->cs.instanced.on;
-    if (opt == 0 || !can) return false;
+    if (opt == 0 || !scene->cs.has_tree()) return false;
     if (opt > 0) return true;
-    return for_pt_kernel && scene->cs.instanced.on &&
-           session_items(cfg, scene->flat.camera.width, scene->flat.camera.height) >= wf_auto_items(scene);
+    return scene->cs.instanced.on && se->grid.n_items >= wf_auto_items(scene);
 }
 
-static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
-    se->wf_slots = n_slots;
+// The wavefront schedule's buffers for the session: a slot per item of the session's parameter block
+static std::unique_ptr<WavefrontState> wf_allocate(const akr_pt_session* se, bool sort) {
+    auto ws = std::make_unique<WavefrontState>();
+    const uint32_t n_slots = se->params.n_items;
+    ws->slots = n_slots;
+    ws->sort = sort;
     const size_t n = n_slots ? n_slots : 1;
-    se->wf_state.alloc(12 * n * 16);  // 10 float4 + 2 uint4 arrays
-    char* base = (char*)se->wf_state.p;
+    ws->state.alloc(12 * n * 16);  // 10 float4 + 2 uint4 arrays
+    char* base = (char*)ws->state.p;
     auto take = [&](size_t k) { void* p = base + k * n * 16; return p; };
-    WfBuffers& w = se->wf;
+    WfBuffers& w = ws->buf;
     w.ray_o = (float4*)take(0); w.ray_d = (float4*)take(1); w.sh_o = (float4*)take(2); w.sh_d = (float4*)take(3);
     w.sh_c = (float4*)take(4); w.hit = (float4*)take(5); w.beta = (float4*)take(6); w.rad = (float4*)take(7);
     w.base = (float4*)take(8); w.film = (float4*)take(9); w.rng = (uint4*)take(10); w.misc = (uint4*)take(11);
-    se->wf_queues.alloc(4 * n * sizeof(uint32_t));
-    uint32_t* q = (uint32_t*)se->wf_queues.p;
+    ws->queues.alloc(4 * n * sizeof(uint32_t));
+    uint32_t* q = (uint32_t*)ws->queues.p;
     w.queue_closest[0] = q; w.queue_closest[1] = q + n; w.queue_shadow[0] = q + 2 * n; w.queue_shadow[1] = q + 3 * n;
     w.key_closest[0] = w.key_closest[1] = w.key_shadow[0] = w.key_shadow[1] = nullptr;
     // carried rays (wf_kernels.hip): a record per (kind, slot) = 12 words + this scene's traversal stack. Not with option wf_sort (a carried ray has no key).
@@ -221,22 +204,22 @@ static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
     w.carry_queue = carry_test ? (uint32_t)tuning().wf_carry : 65536u;
     w.carry_lanes = carry_test ? 56u : 16u;
     w.carry_steps = carry_test ? 4u : 48u;
-    if (tuning().wf_carry != 0 && !se->wf_sort && n_slots > 0) {
+    if (tuning().wf_carry != 0 && !sort && n_slots > 0) {
         w.carry_words = (12u + se->params.sc.bvh_stack_depth + 3u) & ~3u;  // (16-byte aligned records)
-        se->wf_pend.alloc(n * sizeof(uint32_t));
-        se->wf_carry.alloc(2 * n * (size_t)w.carry_words * sizeof(uint32_t));
-        w.pend = (uint32_t*)se->wf_pend.p;
-        w.carry = (uint32_t*)se->wf_carry.p;
+        ws->pend.alloc(n * sizeof(uint32_t));
+        ws->carry.alloc(2 * n * (size_t)w.carry_words * sizeof(uint32_t));
+        w.pend = (uint32_t*)ws->pend.p;
+        w.carry = (uint32_t*)ws->carry.p;
     }
-    if (se->wf_sort) {
-        se->wf_keys.alloc(4 * n * sizeof(uint32_t));
-        uint32_t* k = (uint32_t*)se->wf_keys.p;
+    if (sort) {
+        ws->keys.alloc(4 * n * sizeof(uint32_t));
+        uint32_t* k = (uint32_t*)ws->keys.p;
         w.key_closest[0] = k; w.key_closest[1] = k + n; w.key_shadow[0] = k + 2 * n; w.key_shadow[1] = k + 3 * n;
-        se->wf_sorted.alloc(3 * n * sizeof(uint32_t));
-        se->wf_sorted_closest = (uint32_t*)se->wf_sorted.p;
-        se->wf_sorted_shadow = se->wf_sorted_closest + n;
-        se->wf_sorted_keys = se->wf_sorted_closest + 2 * n;
-        se->wf_sort_tmp.alloc(wf_sort_temp_bytes((uint32_t)n));
+        ws->sorted.alloc(3 * n * sizeof(uint32_t));
+        ws->sorted_closest = (uint32_t*)ws->sorted.p;
+        ws->sorted_shadow = ws->sorted_closest + n;
+        ws->sorted_keys = ws->sorted_closest + 2 * n;
+        ws->sort_tmp.alloc(wf_sort_temp_bytes((uint32_t)n));
     }
     // ---- slot groups. A trace launch ends with its slowest rays, a hundred dependent fetches deep, while the rest of the chip idles, and a
     // launch group is a hundred such launches (the slots with the longest paths decide): measured on the kept 1080p forest that tail is
@@ -252,10 +235,9 @@ static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
     const int opt_groups = tuning().wf_groups;
     // With carried rays (option wf_carry, the default since the end of round 6) a launch has no such tail and one group wins at every size measured
     // (1080p, x 100 k: 175 against 158 with two; 4K: 220 against 203): the automatic choice is two groups only without them.
-    uint32_t groups = se->wf_sort ? 1u : (opt_groups > 0 ? (uint32_t)opt_groups : (mesh_bytes > (16u << 20) && w.carry == nullptr ? 2u : 1u));
+    uint32_t groups = sort ? 1u : (opt_groups > 0 ? (uint32_t)opt_groups : (mesh_bytes > (16u << 20) && w.carry == nullptr ? 2u : 1u));
     groups = std::min(groups, std::max(1u, n_slots / 65536u));  // (small frames: a group should still be a few waves per CU)
-    se->wf_ctrl.alloc((size_t)groups * 8 * sizeof(uint32_t));  // per group: qcount[4], qhead, n_active
-    se->wf_group.clear();
+    ws->ctrl.alloc((size_t)groups * 8 * sizeof(uint32_t));  // per group: qcount[4], qhead, n_active
     for (uint32_t g = 0; g < groups; g++) {
         WfBuffers wg = w;
         // boundaries on whole 1024-slot tiles
@@ -266,22 +248,20 @@ static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
             wg.queue_closest[k] = w.queue_closest[k] + wg.slot_base;
             wg.queue_shadow[k] = w.queue_shadow[k] + wg.slot_base;
         }
-        uint32_t* c = (uint32_t*)se->wf_ctrl.p + 8 * g;
+        uint32_t* c = (uint32_t*)ws->ctrl.p + 8 * g;
         wg.qcount = c; wg.qhead = c + 4; wg.n_active = c + 5;
-        se->wf_group.push_back(wg);
+        ws->group.push_back(wg);
     }
-    for (hipStream_t st : se->wf_streams) (void)hipStreamDestroy(st);
-    se->wf_streams.clear();
     if (groups > 1) {
         for (uint32_t g = 0; g < groups; g++) {
             hipStream_t st = nullptr;
             HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            se->wf_streams.push_back(st);
+            ws->streams.push_back(st);
             hipEvent_t ev = nullptr;
             HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            se->wf_join.push_back(ev);
+            ws->join.push_back(ev);
         }
-        if (!se->wf_fork) HIP_CHECK(hipEventCreateWithFlags(&se->wf_fork, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&ws->fork, hipEventDisableTiming));
     }
     // persistent trace kernel: as many workgroups as the CUs hold at once (occupancy API: registers + this tree's LDS stacks)
     // ... but no more than the scene's data can feed: every resident wave is 64 more rays gathering from the tree, and past the L2s and the
@@ -292,7 +272,8 @@ static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
     const uint64_t scene_bytes = sc->device_bytes;
     per_cu = std::min(per_cu, scene_bytes > (1200ull << 20) ? 4u : (scene_bytes > (400ull << 20) ? 5u : 8u));
     if (const char* e = std::getenv("AKR_WF_TRACE_BLOCKS_PER_CU")) per_cu = (uint32_t)std::max(1, std::min(8, std::atoi(e)));  // (measurement hook)
-    se->wf_trace_blocks = (uint32_t)se->ctx->props.multiProcessorCount * per_cu;
+    ws->trace_blocks = (uint32_t)se->ctx->props.multiProcessorCount * per_cu;
+    return ws;
 }
 
 // One launch group of the wavefront schedule = `fused` passes for every slot: init, then trace/shade iterations until
@@ -300,27 +281,28 @@ static void wf_allocate(akr_pt_session* se, uint32_t n_slots) {
 static void wf_run(akr_pt_session* se) {
     hipStream_t main_st = se->ctx->stream;
     const PtParams& p = se->params;
-    const uint32_t groups = (uint32_t)se->wf_group.size();
-    HIP_CHECK(hipMemsetAsync(se->wf_ctrl.p, 0, se->wf_ctrl.bytes, main_st));
+    WavefrontState& ws = *se->wf;
+    const uint32_t groups = (uint32_t)ws.group.size();
+    HIP_CHECK(hipMemsetAsync(ws.ctrl.p, 0, ws.ctrl.bytes, main_st));
     std::vector<hipStream_t> streams(groups, main_st);
     if (groups > 1) {  // the groups' streams start after everything the session's stream holds so far ...
-        HIP_CHECK(hipEventRecord(se->wf_fork, main_st));
+        HIP_CHECK(hipEventRecord(ws.fork, main_st));
         for (uint32_t g = 0; g < groups; g++) {
-            streams[g] = se->wf_streams[g];
-            HIP_CHECK(hipStreamWaitEvent(streams[g], se->wf_fork, 0));
+            streams[g] = ws.streams[g];
+            HIP_CHECK(hipStreamWaitEvent(streams[g], ws.fork, 0));
         }
     }
     struct Join {  // ... and the session's stream goes on after all of them, also when this function is left by an exception
-        akr_pt_session* se; std::vector<hipStream_t>& st; hipStream_t main_st;
+        WavefrontState& ws; std::vector<hipStream_t>& st; hipStream_t main_st;
         ~Join() {
             if (st.size() < 2) return;
             for (size_t g = 0; g < st.size(); g++) {
-                (void)hipEventRecord(se->wf_join[g], st[g]);
-                (void)hipStreamWaitEvent(main_st, se->wf_join[g], 0);
+                (void)hipEventRecord(ws.join[g], st[g]);
+                (void)hipStreamWaitEvent(main_st, ws.join[g], 0);
             }
         }
-    } join{se, streams, main_st};
-    for (uint32_t g = 0; g < groups; g++) HIP_CHECK(launch_wf_init(p, se->wf_group[g], streams[g]));
+    } join{ws, streams, main_st};
+    for (uint32_t g = 0; g < groups; g++) HIP_CHECK(launch_wf_init(p, ws.group[g], streams[g]));
     int check_every = 16, since_check = 0;  // iterations between two looks at the device (every look drains the stream)
     uint32_t q = 0;
     std::vector<uint8_t> done(groups, 0);
@@ -328,10 +310,10 @@ static void wf_run(akr_pt_session* se) {
         // option wf_sort (one group): the sizes of the queue this iteration traces (rocPRIM wants the element count on the host): one small
         // read-back per iteration, before the counters are reset -- it also ends the loop the moment the last path has finished
         uint32_t nc = 0, ns = 0;
-        const bool sort_now = se->wf_sort && iter > 0;  // (the first iteration's camera rays are in pixel order: coherent as they are)
+        const bool sort_now = ws.sort && iter > 0;  // (the first iteration's camera rays are in pixel order: coherent as they are)
         if (sort_now) {
             uint32_t counts[6];
-            HIP_CHECK(hipMemcpyAsync(counts, se->wf_ctrl.p, sizeof counts, hipMemcpyDeviceToHost, main_st));
+            HIP_CHECK(hipMemcpyAsync(counts, ws.ctrl.p, sizeof counts, hipMemcpyDeviceToHost, main_st));
             HIP_CHECK(hipStreamSynchronize(main_st));
             if (counts[5] == 0) break;  // n_active after the last shade
             nc = counts[2 * q];
@@ -339,28 +321,28 @@ static void wf_run(akr_pt_session* se) {
         }
         for (uint32_t g = 0; g < groups; g++) {
             if (done[g]) continue;
-            const WfBuffers& wg = se->wf_group[g];
+            const WfBuffers& wg = ws.group[g];
             hipStream_t st = streams[g];
             // queue q holds the rays to trace. (The head, the other queue's counts and the active counter are reset by the kernels themselves:
             // k_wf_trace zeroes n_active, k_wf_shade the counts of the queue just traced and the head.)
             if (sort_now) {
                 WfBuffers sorted = wg;
-                HIP_CHECK(wf_sort_pairs(se->wf_sort_tmp.p, se->wf_sort_tmp.bytes, wg.key_closest[q], se->wf_sorted_keys, wg.queue_closest[q], se->wf_sorted_closest, nc, st));
-                HIP_CHECK(wf_sort_pairs(se->wf_sort_tmp.p, se->wf_sort_tmp.bytes, wg.key_shadow[q], se->wf_sorted_keys, wg.queue_shadow[q], se->wf_sorted_shadow, ns, st));
-                sorted.queue_closest[q] = se->wf_sorted_closest;
-                sorted.queue_shadow[q] = se->wf_sorted_shadow;
-                HIP_CHECK(launch_wf_trace(p, sorted, q, se->wf_trace_blocks, st));
+                HIP_CHECK(wf_sort_pairs(ws.sort_tmp.p, ws.sort_tmp.bytes, wg.key_closest[q], ws.sorted_keys, wg.queue_closest[q], ws.sorted_closest, nc, st));
+                HIP_CHECK(wf_sort_pairs(ws.sort_tmp.p, ws.sort_tmp.bytes, wg.key_shadow[q], ws.sorted_keys, wg.queue_shadow[q], ws.sorted_shadow, ns, st));
+                sorted.queue_closest[q] = ws.sorted_closest;
+                sorted.queue_shadow[q] = ws.sorted_shadow;
+                HIP_CHECK(launch_wf_trace(p, sorted, q, ws.trace_blocks, st));
             } else {
-                HIP_CHECK(launch_wf_trace(p, wg, q, se->wf_trace_blocks, st));
+                HIP_CHECK(launch_wf_trace(p, wg, q, ws.trace_blocks, st));
             }
             HIP_CHECK(launch_wf_shade(p, wg, 1 - q, st));
         }
         q = 1 - q;
-        if (!se->wf_sort && ++since_check >= check_every) {
+        if (!ws.sort && ++since_check >= check_every) {
             since_check = 0;
             std::vector<uint32_t> n_active(groups, 0);
             for (uint32_t g = 0; g < groups; g++)
-                if (!done[g]) HIP_CHECK(hipMemcpyAsync(&n_active[g], se->wf_group[g].n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, streams[g]));
+                if (!done[g]) HIP_CHECK(hipMemcpyAsync(&n_active[g], ws.group[g].n_active, sizeof(uint32_t), hipMemcpyDeviceToHost, streams[g]));
             bool all = true;
             for (uint32_t g = 0; g < groups; g++) {
                 if (done[g]) continue;
@@ -371,7 +353,7 @@ static void wf_run(akr_pt_session* se) {
             // the last slots' paths: launches with next to nothing to do -- look more often, so that fewer of them run for nothing
             uint64_t left = 0;
             for (uint32_t g = 0; g < groups; g++) left += n_active[g];
-            check_every = left * 64 < se->wf_slots ? 4 : 16;
+            check_every = left * 64 < ws.slots ? 4 : 16;
         }
         if (iter > (1ull << 26)) throw RenderError("wavefront schedule did not terminate");
     }
@@ -386,31 +368,25 @@ static void wf_run(akr_pt_session* se) {
 // by up to 2 x), >= 1 M pixels (the persistent trace kernel wants its lanes refilled), >= 16 passes to render; a scene whose paths practically
 // never end at a light or in the open (shaded vertices per closest-hit ray >= 0.97 in the megakernel's two passes: the hall 0.999) skips the
 // wavefront half -- it has measured slower on every such scene. Option sched_trial: 0 = never, 1 = every session on a scene with a tree (tests).
-static bool schedule_trial_eligible(const akr_pt_session* se, bool for_pt_kernel) {
+static bool schedule_trial_eligible(const akr_pt_session* se) {
     const TuningOptions t = tuning();
     const akr_scene* sc = se->scene;
-    if (t.wavefront != -1 || t.sched_trial == 0 || !for_pt_kernel || se->wavefront || se->arith_relaxed || se->spec_active) return false;
-    if (sc->cs.instanced.on || sc->cs.bvh_nodes.empty() || t.wf_sort != 0) return false;
+    if (t.wavefront != -1 || t.sched_trial == 0 || se->wf || se->arith_relaxed || se->spec_active) return false;
+    if (sc->cs.instanced.on || !sc->cs.has_tree() || t.wf_sort != 0) return false;
     if (t.sched_trial == 1) return true;
     const uint64_t passes = (session_samples(se->cfg) + se->cfg.spp_per_pass - 1) / se->cfg.spp_per_pass;
-    return !sc->cs.has_textures && sc->device_bytes >= (256ull << 20) && passes >= 16 &&
-           session_items(se->cfg, sc->flat.camera.width, sc->flat.camera.height) >= 1000000u;
+    return !sc->cs.has_textures && sc->device_bytes >= (256ull << 20) && passes >= 16 && se->grid.n_items >= 1000000u;
 }
-static void read_stats(akr_pt_session* se, akr_pt_stats* stats);
-static void wf_release(akr_pt_session* se) {
-    for (DevBuf* b : {&se->wf_state, &se->wf_queues, &se->wf_ctrl, &se->wf_pend, &se->wf_carry, &se->wf_keys, &se->wf_sorted, &se->wf_sort_tmp}) b->release();
-    se->wf_group.clear();
-}
+static void read_stats(RenderBase* se, akr_pt_stats* stats);
 
-static void validate_config(const akr_pt_config& c) {
+static void validate_config(const akr_pt_config& c, const TileGrid& grid) {
     if (c.spp_per_pass == 0) throw std::invalid_argument("akr_pt_config: spp_per_pass must be > 0");
     if (c.filter_type > AKR_FILTER_GAUSSIAN) throw std::invalid_argument("akr_pt_config: unknown filter_type");
     if (c.sampler_type > AKR_SAMPLER_SOBOL) throw std::invalid_argument("akr_pt_config: unknown sampler_type");
     if (c.color > (AKR_COLOR_REPR_ACESCG | AKR_COLOR_RGB_ACESCG)) throw std::invalid_argument("akr_pt_config: unknown colour pipeline bits");
     if (c.sampler_type == AKR_SAMPLER_PMJ02BN && c.spp > 65536u)
         throw std::invalid_argument("Pmj02BnSampler supports up to 65536 spp (sampler/mod.rs:381-387)");
-    uint32_t tw = c.tile_w ? c.tile_w : 32, th = c.tile_h ? c.tile_h : 32;
-    if ((tw % 8) || (th % 8)) throw std::invalid_argument("akr_pt_config: tile_w and tile_h must be multiples of 8");
+    if ((grid.tile_w % 8) || (grid.tile_h % 8)) throw std::invalid_argument("akr_pt_config: tile_w and tile_h must be multiples of 8");
     if (c.shard_count > 1 && c.shard_rank >= c.shard_count) throw std::invalid_argument("akr_pt_config: shard_rank >= shard_count");
     if (c.sample_begin != 0 || c.sample_count != 0) {  // sample-range split (akari_hip.h)
         if (c.sampler_type != AKR_SAMPLER_PMJ02BN && c.sampler_type != AKR_SAMPLER_SOBOL)
@@ -446,89 +422,108 @@ AKR_API int32_t akr_pt_config_from_json(const char* text, akr_pt_config* cfg, ch
 }
 
 }  // extern "C"
-// for_pt_kernel: the session will launch k_pt_pass (akr_pt_passes). The aov / gpt / mcmc_opt integrators come through here as well for
-// sampler states, counters and the kernel parameter block, but launch their own kernels, which interpret shader graphs: they must not
-// get a per-scene kernel -- nor its parameter block, which has no graph value slots in LDS (found by the full GPU suite: a cached
-// per-scene kernel made a later mcmc_opt render of the same scene evaluate its graphs without value slots).
-int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out, bool for_pt_kernel) {
-    if (!ctx || !scene || !cfg || !film || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: NULL argument");
+// The aov / gpt / mcmc_opt integrators begin here as well, for sampler states, counters and the kernel parameter block, but launch their own
+// kernels, which interpret shader graphs. They hold a RenderBase and not a pt session, so a per-scene kernel's block cannot reach them.
+void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film) {
+    if (!ctx || !scene || !cfg || !film) throw std::invalid_argument("akr_pt_begin: NULL argument");
+    if (scene->ctx != ctx) throw std::invalid_argument("akr_pt_begin: the scene was not created on this context (host-only scenes cannot render)");
+    se->grid = tile_grid(cfg->tile_w, cfg->tile_h, scene->flat.camera.width, scene->flat.camera.height, cfg->shard_rank, cfg->shard_count);
+    validate_config(*cfg, se->grid);
+    if (film->width != scene->flat.camera.width || film->height != scene->flat.camera.height)
+        throw std::invalid_argument("film resolution does not match the scene camera (pt.rs:1072-1073)");
+    ctx->bind();
+    se->ctx = ctx;
+    se->scene = scene;
+    se->film = film;
+    se->cfg = *cfg;
+    std::unique_lock<std::mutex> color_lock(scene->color_sets_mutex);
+    if (cfg->color != 0 && !scene->color_sets.count(cfg->color)) {
+        // ColorPipeline other than sRGB / sRGB: the scene's constants were folded for the default pipeline; fold them again
+        // for this one (svm/texture/mod.rs:9-43 at every Rgb / spectral_uplift node) and keep the tables with the scene
+        CompiledScene tmp;
+        tmp.images = scene->cs.images;
+        std::vector<akr_material_desc> descs;
+        compile_materials(scene->flat, cfg->color, tmp, descs);
+        auto set = std::make_unique<akr_scene::ColorSet>();
+        set->materials.upload(tmp.materials);
+        if (tmp.has_textures) {
+            set->tex_nodes.upload(tmp.tex_nodes);
+            set->mat_inputs.upload(tmp.mat_inputs);
+        }
+        scene->color_sets[cfg->color] = std::move(set);
+    }
+    if (cfg->color != 0) se->color_set = scene->color_sets.at(cfg->color).get();  // stable: the map owns it through a unique_ptr
+    color_lock.unlock();
+    const uint64_t n = (uint64_t)film->width * film->height;
+    // init_pcg32_buffer_with_seed (sampler/mod.rs:148-160): host StdRng(seed) u64 per pixel, device new_seq_offset
+    if (cfg->sampler_type == AKR_SAMPLER_PMJ02BN || cfg->sampler_type == AKR_SAMPLER_SOBOL) {
+        // Pmj02BnState per pixel (sampler/mod.rs:451-466): sample_index = u32::MAX, pixel = (x, y), kept in a Pcg32 slot
+        if (cfg->sampler_type == AKR_SAMPLER_PMJ02BN) ctx->ensure_pmj_tables();
+        se->pmj_spp = cfg->spp ? cfg->spp : 1;
+        std::vector<Pcg32> init(n);
+        // a sample range [b, ..) starts with sample_index = b - 1: the next start() makes it b (sampler/mod.rs:650-663)
+        const uint64_t first = cfg->sample_begin ? (uint64_t)(cfg->sample_begin - 1u) : 0xffffffffull;
+        for (uint64_t i = 0; i < n; i++) init[i] = Pcg32{first, (i % film->width) | ((i / film->width) << 32)};
+        se->states.upload(init);
+    } else {
+        std::vector<uint64_t> seeds(n);
+        StdRng rng(cfg->sampler_seed);
+        for (auto& v : seeds) v = rng.next_u64();
+        DevBuf dseeds;
+        dseeds.upload(seeds);
+        se->states.alloc(n * sizeof(Pcg32));
+        HIP_CHECK(launch_init_pcg32(dseeds.as<uint64_t>(), se->states.p, n, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));  // dseeds goes out of scope
+    }
+    se->counters.alloc(8 * kStatStripes * sizeof(uint64_t));
+    HIP_CHECK(hipMemsetAsync(se->counters.p, 0, se->counters.bytes, ctx->stream));
+    if (cfg->shard_count > 1) se->owned_tiles.upload(owned_tiles(se->grid.tiles_x, se->grid.tiles_y, cfg->shard_rank, cfg->shard_count));
+    const TuningOptions t = tuning();
+    se->defer_metal_option = t.defer_metal;
+    se->simple_kernels_option = t.simple_kernels;
+    se->defer_on_option = t.defer_on;
+    scene->sessions++;
+    se->holds_scene = true;
+}
+int32_t akr_api::render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, RenderBase** out) {
     *out = nullptr;
-    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: the scene was not created on this context (host-only scenes cannot render)");
     return guarded([&] {
-        validate_config(*cfg);
-        if (film->width != scene->flat.camera.width || film->height != scene->flat.camera.height)
-            throw std::invalid_argument("film resolution does not match the scene camera (pt.rs:1072-1073)");
-        ctx->bind();
+        auto se = std::make_unique<RenderBase>();
+        base_begin(se.get(), ctx, scene, cfg, film);
+        session_params(se.get());
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *out = se.release();
+    });
+}
+// pt_kernels_relaxed.hip: launch_pt_pass of the relaxed arithmetic tier (its PtParams is this one, in another namespace)
+extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, hipStream_t stream);
+extern "C" {
+AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out) {
+    if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: NULL argument");
+    *out = nullptr;
+    return guarded([&] {
         auto se = std::make_unique<akr_pt_session>();
-        se->ctx = ctx;
-        se->scene = scene;
-        se->film = film;
-        se->cfg = *cfg;
-        std::unique_lock<std::mutex> color_lock(scene->color_sets_mutex);
-        if (cfg->color != 0 && !scene->color_sets.count(cfg->color)) {
-            // ColorPipeline other than sRGB / sRGB: the scene's constants were folded for the default pipeline; fold them again
-            // for this one (svm/texture/mod.rs:9-43 at every Rgb / spectral_uplift node) and keep the tables with the scene
-            CompiledScene tmp;
-            tmp.images = scene->cs.images;
-            std::vector<akr_material_desc> descs;
-            compile_materials(scene->flat, cfg->color, tmp, descs);
-            auto set = std::make_unique<akr_scene::ColorSet>();
-            set->materials.upload(tmp.materials);
-            if (tmp.has_textures) {
-                set->tex_nodes.upload(tmp.tex_nodes);
-                set->mat_inputs.upload(tmp.mat_inputs);
-            }
-            scene->color_sets[cfg->color] = std::move(set);
-        }
-        if (cfg->color != 0) se->color_set = scene->color_sets.at(cfg->color).get();  // stable: the map owns it through a unique_ptr
-        color_lock.unlock();
-        const uint64_t n = (uint64_t)film->width * film->height;
-        // init_pcg32_buffer_with_seed (sampler/mod.rs:148-160): host StdRng(seed) u64 per pixel, device new_seq_offset
-        if (cfg->sampler_type == AKR_SAMPLER_PMJ02BN || cfg->sampler_type == AKR_SAMPLER_SOBOL) {
-            // Pmj02BnState per pixel (sampler/mod.rs:451-466): sample_index = u32::MAX, pixel = (x, y), kept in a Pcg32 slot
-            if (cfg->sampler_type == AKR_SAMPLER_PMJ02BN) ctx->ensure_pmj_tables();
-            se->pmj_spp = cfg->spp ? cfg->spp : 1;
-            std::vector<Pcg32> init(n);
-            // a sample range [b, ..) starts with sample_index = b - 1: the next start() makes it b (sampler/mod.rs:650-663)
-            const uint64_t first = cfg->sample_begin ? (uint64_t)(cfg->sample_begin - 1u) : 0xffffffffull;
-            for (uint64_t i = 0; i < n; i++) init[i] = Pcg32{first, (i % film->width) | ((i / film->width) << 32)};
-            se->states.upload(init);
-        } else {
-            std::vector<uint64_t> seeds(n);
-            StdRng rng(cfg->sampler_seed);
-            for (auto& v : seeds) v = rng.next_u64();
-            DevBuf dseeds;
-            dseeds.upload(seeds);
-            se->states.alloc(n * sizeof(Pcg32));
-            HIP_CHECK(launch_init_pcg32(dseeds.as<uint64_t>(), se->states.p, n, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));  // dseeds goes out of scope
-        }
-        se->counters.alloc(8 * kStatStripes * sizeof(uint64_t));
-        HIP_CHECK(hipMemsetAsync(se->counters.p, 0, se->counters.bytes, ctx->stream));
-        se->wavefront = choose_wavefront(scene, *cfg, for_pt_kernel);
-        se->wf_sort = se->wavefront && tuning().wf_sort != 0;
+        base_begin(se.get(), ctx, scene, cfg, film);
+        const bool wavefront = choose_wavefront(se.get());
+        const bool wf_sort = wavefront && tuning().wf_sort != 0;
         {
             const TuningOptions t = tuning();
-            se->defer_metal_option = t.defer_metal;
-            se->simple_kernels_option = t.simple_kernels;
-            se->defer_on_option = t.defer_on;
             se->max_fused_option = t.max_fused_passes;
             // A per-scene kernel (host/specialise.cpp) for the megakernel of a scene with texture-fed materials: always / never by
             // option, else when the render is long enough for a first-use compile to pay.
-            const uint64_t samples = n * (uint64_t)session_samples(*cfg);
+            const uint64_t samples = (uint64_t)film->width * film->height * (uint64_t)session_samples(*cfg);
             // (automatic: a kernel that is already cached is used whatever the render's size; a compile -- about a second -- only
             // when the render is long enough to win it back)
             const bool may_compile = t.specialise == 1 || samples >= kSpecAutoSamples;
             // The relaxed arithmetic tier (pt_kernels_relaxed.hip): the precompiled megakernels of flattened scenes. Everything else --
             // kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
-            se->arith_relaxed = t.arith == 1 && for_pt_kernel && !scene->cs.instanced.on && !se->wavefront;
+            se->arith_relaxed = t.arith == 1 && !scene->cs.instanced.on && !wavefront;
             if (se->arith_relaxed && scene->cs.env.on)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
             if (se->arith_relaxed && scene->flat.lens.radius > 0.0f)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)");
-            if (!for_pt_kernel) se->spec_status = "not a pt session";
-            else if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
-            else if (se->wavefront) se->spec_status = "wavefront schedule";
+            if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
+            else if (wavefront) se->spec_status = "wavefront schedule";
             else if (!scene->cs.has_textures) se->spec_status = "the scene has no texture-fed material";
             else if (t.specialise == 0) se->spec_status = "option specialise = 0";
             else if (cfg->force_diffuse) se->spec_status = "force_diffuse kernels evaluate no surface graphs";
@@ -542,9 +537,11 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
                 }
                 se->spec_waves = t.specialise_waves ? t.specialise_waves : 3;
                 se->spec_active = true;
-                fill_params(se.get(), 1, cfg->spp_per_pass);  // which instantiation the session's launches use
+            }
+            session_params(se.get(), se->spec_active, se->spec_waves, wf_sort);
+            if (se->spec_active) {  // which instantiation the session's launches use: as the block for a per-scene kernel says
                 SpecRequest rq;
-                rq.bvh = !scene->cs.bvh_nodes.empty() || scene->cs.instanced.on;
+                rq.bvh = scene->cs.has_tree();
                 rq.inst = scene->cs.instanced.on;
                 rq.pmj = se->params.sampler != 0;
                 rq.stage = se->params.stage_total != 0;
@@ -554,25 +551,17 @@ int32_t akr_api::pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_confi
                 rq.min_waves = se->spec_waves;
                 se->spec = ctx->spec_cache.get(scene->spec_header, rq, ctx->props.gcnArchName, may_compile);
                 se->spec_status = se->spec->status;
-                if (!se->spec->fn) se->spec_active = false;  // the interpreter kernel renders the same film
+                if (!se->spec->fn) {  // the interpreter kernel renders the same film: with graph value slots in LDS and its own LDS budget
+                    se->spec_active = false;
+                    session_params(se.get(), false, se->spec_waves, wf_sort);
+                }
             }
         }
-        if (se->wavefront) {
-            fill_params(se.get(), 1, cfg->spp_per_pass);  // for n_items
-            wf_allocate(se.get(), se->params.n_items);
-        }
-        se->sched_trial = schedule_trial_eligible(se.get(), for_pt_kernel) ? 1 : 0;
+        if (wavefront) se->wf = wf_allocate(se.get(), wf_sort);
+        se->sched_trial = schedule_trial_eligible(se.get()) ? 1 : 0;
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        scene->sessions++;
-        se->holds_scene = true;
         *out = se.release();
     });
-}
-// pt_kernels_relaxed.hip: launch_pt_pass of the relaxed arithmetic tier (its PtParams is this one, in another namespace)
-extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, hipStream_t stream);
-extern "C" {
-AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out) {
-    return pt_begin(ctx, scene, cfg, film, out, /*for_pt_kernel=*/true);
 }
 AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blocking, uint32_t* spp_done) {
     if (!se) return fail(AKR_ERR_INVALID_ARGUMENT, "session is NULL");
@@ -602,9 +591,9 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
                 done += last;
                 fused++;
             }
-            fill_params(se, fused, last);
+            set_launch_passes(se, fused, last);
             LaunchTimer timer(se);
-            if (se->wavefront) wf_run(se);
+            if (se->wf) wf_run(se);
             else if (se->arith_relaxed) HIP_CHECK(akr_launch_pt_pass_relaxed(&se->params, se->ctx->stream));
             else HIP_CHECK(launch_pt_pass(se->params, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr));
             timer.stop();
@@ -630,19 +619,14 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             if (ratio >= 0.97 && tuning().sched_trial != 1) {
                 std::snprintf(msg, sizeof msg, "megakernel (no trial of the other schedule: %.3f shaded vertices per closest-hit ray, a closed scene)", ratio);
             } else {
-                se->wavefront = true;
-                fill_params(se, 1, se->cfg.spp_per_pass);  // for n_items
-                wf_allocate(se, se->params.n_items);
+                se->wf = wf_allocate(se, /*sort=*/false);
                 timed(wf, unused);
                 const bool keep = wf < 0.95 * mk;
                 // (a session on the megakernel never says "wavefront": callers tell the schedule by that word)
                 std::snprintf(msg, sizeof msg, keep ? "wavefront schedule (timed trial, 2 passes each: %.3g ns per sample against the megakernel's %.3g)"
                                                     : "megakernel (timed trial, 2 passes each: %.3g ns per sample against the other schedule's %.3g)",
                               (keep ? wf : mk) * 1e6, (keep ? mk : wf) * 1e6);
-                if (!keep) {
-                    se->wavefront = false;
-                    wf_release(se);
-                }
+                if (!keep) se->wf.reset();
             }
             se->spec_status = msg;
         }
@@ -659,14 +643,19 @@ AKR_API int32_t akr_pt_read_sampler_states(akr_pt_session* se, uint64_t* dst) {
         HIP_CHECK(hipMemcpy(dst, se->states.p, se->states.bytes, hipMemcpyDeviceToHost));
     });
 }
-static void read_stats(akr_pt_session* se, akr_pt_stats* stats) {
+// the session's eight counters, summed over their stripes, once everything on its stream has run
+static std::array<uint64_t, 8> read_counters(RenderBase* se) {
     se->ctx->bind();
     HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
     std::vector<uint64_t> stripes(8 * kStatStripes);
     HIP_CHECK(hipMemcpy(stripes.data(), se->counters.p, stripes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::array<uint64_t, 8> c{};
     for (uint32_t k = 0; k < kStatStripes; k++)
         for (int i = 0; i < 8; i++) c[i] += stripes[8 * k + i];
+    return c;
+}
+static void read_stats(RenderBase* se, akr_pt_stats* stats) {
+    const std::array<uint64_t, 8> c = read_counters(se);
     se->fold_events(true);
     const double ms = se->kernel_ms;
     if (stats) {
@@ -707,36 +696,27 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
             info->load_ms = se->spec->load_ms;
         }
         std::snprintf(info->status, sizeof info->status, "%s", se->spec_status.c_str());
-        if (se->wavefront && se->wf.carry != nullptr && se->counters.p) {  // what the launches so far carried over (wf_kernels.hip; counter 7)
-            se->ctx->bind();
-            HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
-            std::vector<uint64_t> stripes(8 * kStatStripes);
-            HIP_CHECK(hipMemcpy(stripes.data(), se->counters.p, stripes.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            uint64_t carried = 0;
-            for (uint32_t k = 0; k < kStatStripes; k++) carried += stripes[8 * k + 7];
+        if (se->wf && se->wf->buf.carry != nullptr && se->counters.p) {  // what the launches so far carried over (wf_kernels.hip; counter 7)
+            const uint64_t carried = read_counters(se)[7];
             std::snprintf(info->status, sizeof info->status, "%s; %llu rays carried into a later trace launch", se->spec_status.c_str(), (unsigned long long)carried);
         }
     });
-}AKR_API int32_t akr_pt_end(akr_pt_session* se, akr_pt_stats* stats) {
-    if (!se) return AKR_OK;
-    int32_t rc = guarded([&] { read_stats(se, stats); });
-    (void)hipSetDevice(se->ctx->device);
-    delete se;
-    return rc;
 }
+AKR_API int32_t akr_pt_end(akr_pt_session* se, akr_pt_stats* stats) { return base_end(se, stats); }
 AKR_API int32_t akr_pt_render(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_stats* stats) {
     akr_pt_session* se = nullptr;
     int32_t rc = akr_pt_begin(ctx, scene, cfg, film, &se);
     if (rc != AKR_OK) return rc;
     uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
     rc = akr_pt_passes(se, n_passes, 1, nullptr);
-    std::string err = g_last_error;
-    int32_t rc2 = akr_pt_end(se, stats);
-    if (rc != AKR_OK) {
-        g_last_error = err;
-        return rc;
-    }
-    return rc2;
+    return end_keeping_first_error(rc, [&] { return akr_pt_end(se, stats); });
 }
 
 }  // extern "C"
+int32_t akr_api::base_end(RenderBase* se, akr_pt_stats* stats) {
+    if (!se) return AKR_OK;
+    int32_t rc = guarded([&] { read_stats(se, stats); });
+    (void)hipSetDevice(se->ctx->device);
+    delete se;
+    return rc;
+}

@@ -272,6 +272,8 @@ AKR_API int32_t akr_scene_destroy(akr_scene* scene) {
 }
 AKR_API int32_t akr_scene_set_resolution(akr_scene* s, uint32_t width, uint32_t height) {
     if (!s || !width || !height) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_resolution: bad argument");
+    // (a session's film, sampler states and parameter block are sized for the resolution it began with)
+    if (s->sessions.load() != 0) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_resolution: a session holds the scene (end it first)");
     s->flat.camera.width = width;
     s->flat.camera.height = height;
     camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity);

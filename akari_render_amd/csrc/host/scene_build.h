@@ -140,6 +140,8 @@ struct CompiledScene {
     bool has_alpha = false;
     bool needs_ggx_table = false;
     float scene_lo[3], scene_hi[3];
+    // an acceleration structure (flattened: bvh_nodes; kept as meshes + instances: instanced.nodes), or the exhaustive walk over <= 64 triangles
+    bool has_tree() const { return !bvh_nodes.empty() || instanced.on; }
 };
 
 // Padding of the acceleration structure's boxes. It covers the round-off of the slab test and of the triangle test, and both scale

@@ -75,6 +75,23 @@ def test_zero_samples_and_config_validation(ctx, cbox_path):
         capi.pt_render(ctx, scene, make_config(spp=4), capi.Film(ctx, 8, 16))
 
 
+def test_resolution_is_fixed_while_a_session_holds_the_scene(ctx, cbox_path):
+    """A session's film, sampler states and parameter block are sized when it begins: akr_scene_set_resolution is refused until it ends
+    (as akr_scene_set_lens and akr_scene_set_environment are)."""
+    scene = capi.Scene(ctx, cbox_path, 16, 16)
+    film = capi.Film(ctx, 16, 16)
+    se = capi.PtSession(ctx, scene, make_config(spp=4, spp_per_pass=2), film)
+    se.passes(1, blocking=True)
+    with pytest.raises(capi.AkariError) as e:
+        scene.set_resolution(24, 8)
+    assert e.value.code == capi.ERR_INVALID_ARGUMENT and "a session holds the scene" in str(e.value)
+    assert (scene.info().width, scene.info().height) == (16, 16)
+    se.passes(1, blocking=True)  # the session goes on at the size it began with
+    assert se.end()["n_samples"] == 16 * 16 * 4
+    scene.set_resolution(24, 8)
+    assert (scene.info().width, scene.info().height) == (24, 8)
+
+
 def test_4k_film_one_pass(ctx, cbox_path):
     """BASELINE configs[4] frame size (3840x2160, 232 MB film): every pixel takes its samples and the values are finite (the
     size-independent properties; bit parity is asserted at sizes the oracle renders in seconds)."""
