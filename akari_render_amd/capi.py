@@ -51,6 +51,7 @@ TEST_EXPORTS = [
     "akr_host_decode_exr", "akr_host_decode_tiff", "akr_host_decode_dds", "akr_host_pmj02bn_tables",
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
+    "akr_probe_div", "akr_probe_intersect_pair",
 ]
 
 
@@ -190,6 +191,8 @@ def lib() -> C.CDLL:
     proto("akr_probe_math", vp, u32, fp, fp, fp, fp)
     proto("akr_probe_bsdf", vp, C.POINTER(abi.MaterialDesc), fp, i32, fp, u32, fp, fp)
     proto("akr_probe_intersect", vp, vp, u32, fp, up, fp)
+    proto("akr_probe_div", vp, u32, fp, fp, fp, fp)
+    proto("akr_probe_intersect_pair", vp, vp, u32, fp, up, up, fp)
     proto("akr_probe_surface_interaction", vp, vp, u32, up, fp, fp)
     proto("akr_probe_material_inputs", vp, vp, u32, u32, fp, fp)
     proto("akr_probe_material_inputs_host", vp, u32, u32, u32, fp, fp)
@@ -733,6 +736,16 @@ def probe_math(ctx: Context, x: np.ndarray):
     return s, c, l
 
 
+def probe_div(ctx: Context, a: np.ndarray, b: np.ndarray):
+    """a / b on the device: (the pair walk's division without range scaling, the contract's division)."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    assert a.shape == b.shape
+    fast, ieee = np.zeros_like(a), np.zeros_like(a)
+    check(lib().akr_probe_div(ctx.h, a.size, _fp(a), _fp(b), _fp(fast), _fp(ieee)))
+    return fast, ieee
+
+
 def probe_bsdf(ctx: Context, m: abi.MaterialData, mode: int, wo, data: np.ndarray, table: Optional[np.ndarray] = None) -> np.ndarray:
     ms = m.to_struct()
     wo = np.ascontiguousarray(wo, dtype=np.float32)
@@ -749,6 +762,18 @@ def probe_intersect(ctx: Context, scene: Scene, rays: np.ndarray):
     bary = np.zeros((rays.shape[0], 2), dtype=np.float32)
     check(lib().akr_probe_intersect(ctx.h, scene.h, rays.shape[0], _fp(rays), _up(out), _fp(bary)))
     return out, bary
+
+
+def probe_intersect_pair(ctx: Context, scene: Scene, rays: np.ndarray, excl: np.ndarray):
+    """The pair walk as the pt kernel calls it. rays (n, 16): o d tmax - | so sd stmax -; excl (n, 3): ex0 | sex0 sex1 (global triangle
+    ids, 0xffffffff = none). -> out (n, 4) u32: found, gid, occluded, took the IEEE walk; tuv (n, 3) f32."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 16)
+    excl = np.ascontiguousarray(excl, dtype=np.uint32).reshape(-1, 3)
+    assert rays.shape[0] == excl.shape[0]
+    out = np.zeros((rays.shape[0], 4), dtype=np.uint32)
+    tuv = np.zeros((rays.shape[0], 3), dtype=np.float32)
+    check(lib().akr_probe_intersect_pair(ctx.h, scene.h, rays.shape[0], _fp(rays), _up(excl), _up(out), _fp(tuv)))
+    return out, tuv
 
 
 def probe_surface_interaction(ctx: Context, scene: Scene, inst_prim: np.ndarray, bary: np.ndarray) -> np.ndarray:

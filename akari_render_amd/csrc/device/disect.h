@@ -178,9 +178,69 @@ AKR_D float max_raw(float a, float b) {
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-template <bool TEX = false>
+// min(a, |b|), one instruction (the abs is a source modifier)
+AKR_D float min_abs_raw(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// max(|a|, |b|, |c|); a NaN operand is ignored (maxNum)
+AKR_D float max3_abs_raw(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+// tri_plane with the division's range-scaling steps left out (dmath.h div_f_unscaled), and the smallest |numerator| seen so far in `lo`
+AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
+    float dz = __builtin_fmaf(r2.x, d.x, __builtin_fmaf(r2.y, d.y, r2.z * d.z));
+    float oz = __builtin_fmaf(r2.x, o.x, __builtin_fmaf(r2.y, o.y, __builtin_fmaf(r2.z, o.z, r2.w)));
+    lo = min_abs_raw(lo, oz);
+    PlaneHit h;
+    h.t = div_f_unscaled(-oz, dz);
+    h.px = __builtin_fmaf(h.t, d.x, o.x);
+    h.py = __builtin_fmaf(h.t, d.y, o.y);
+    h.pz = __builtin_fmaf(h.t, d.z, o.z);
+    return h;
+}
+
+// A shortcut of the pair walk, bit-neutral, switched per instantiation of the walk (what it buys where: profiles/walk_div_mask_ab.md).
+//
+// UNSCALED_DIV -- speculate and validate. The plane solves use div_f_unscaled (8 instructions for the compiler's 12; dmath.h says on which
+// set S of operands it is the contract's quotient). Whether a solve's operands are in S is not tested per solve -- a compare and a branch
+// would cost what the shortcut saves -- but once per walk, and a wave with a lane that fails repeats the walk with the compiler's division
+// (walk_ieee below: rolled, one record per trip; it runs in a vanishing share of the walks) and takes that result. What is checked, per
+// ray that exists (tmax >= 0; a ray that does not exist is never accepted whatever its t, because min(t, tmax - t) < 0 or NaN for tmax < 0):
+//   before the walk   |o| <= B and |d| <= 2 per component, tmax <= 1e20. The host chose B (dscene.h walk_bound_word) so that under these
+//                     bounds every plane row of the scene gives |oz| < 2^46 and |dz| < 2^46 (api_scene.cpp; a negative bound = no such
+//                     bound exists, the scene always takes walk_ieee). A NaN component passes the test (maxNum ignores it), harmlessly:
+//                     it makes oz or dz NaN for EVERY row (0 * NaN = NaN), t is NaN on either path and no record is accepted on either.
+//   after the walk    lo = the smallest |oz| over the solves >= 2^-47. (One v_min_f32 per solve. A zero numerator must not stay:
+//                     the sequence returns +0 for -0 / b where IEEE gives -0.)
+// Why that suffices. For a solve of a checked lane, a = -oz and b = dz have 2^-47 <= |a| < 2^47 and |b| < 2^47. Of the conditions of S,
+// "a's biased exponent >= 24" holds (it is >= 80), "|b| <= 2^125" holds, and exp(a) - exp(b) >= -47 - 46 > -125. So (a, b) can leave S
+// only through b zero or denormal, or through exp(a) - exp(b) >= 96. In both cases the exact quotient has |t| > 2^79 (|a| >= 2^-47 over
+// |b| < 2^-126; or 2^(96 - 1)), which is > 1e20 >= tmax: IEEE's quotient (+-inf for b = 0) fails min(t, tmax - t) >= 0, the record is
+// rejected. The unscaled sequence returns for such a pair a value of magnitude > 1e20, +-inf or NaN (checked on the device for both kinds
+// of exit, tests/test_gpu_div_unscaled.py), which fails the same test -- for t = NaN every operand of the margin is NaN. The record is
+// rejected on both paths, and no bit of its t reaches the result: best_t, the recomputed (u, v) and the sign of occ_margin come from
+// accepted records only, whose pairs are in S.
+// (tmax and stmax are taken to be numbers: a NaN would read as "the ray does not exist" and skip the checks while min(t, NaN) = t could still
+// accept a record. The callers pass 1e20, -1 or a light sample's distance, which is finite by construction: dpath.h sample_direct.)
+// (Measured with it and retired: the excluded ids as bit masks, v_bfe_i32 + v_or on the margin's bits per ray and record in place of the
+// comparisons below -- the compiler already folds the three comparisons into three v_cmp and one v_cndmask; -1.7 % on C2, same file.)
+template <bool DIV>
+struct WalkOpt {
+    static constexpr bool unscaled_div = DIV;
+};
+template <int V>
+struct IntTag {
+    static constexpr int value = V;
+};
+
+template <bool TEX = false, class OPT = WalkOpt<true>>
 AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, uint32_t ex0, vec3 so, vec3 sd, float stmax,
-                                 uint32_t sex0, uint32_t sex1, Hit& hit, bool& found, bool& occluded, const float4* lds_recs) {
+                                 uint32_t sex0, uint32_t sex1, Hit& hit, bool& found, bool& occluded, const float4* lds_recs, uint32_t* took_ieee_walk = nullptr) {
+    constexpr bool UNSCALED = OPT::unscaled_div && !AKR_RX;
     // best_t starts one ulp above tmax: "t < best_t" then admits a first hit at t == tmax and keeps, among equal t, the
     // lowest id afterwards (ascending k, strict '<') without a separate "no hit yet" test
     float best_t = next_up(tmax);
@@ -192,10 +252,14 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     const bool has_alpha = __builtin_amdgcn_readfirstlane((int)sc.has_alpha) != 0;  // (a scalar branch per walk, nothing per lane)
     // the two rays' plane solves of the current plane, as pairs {closest-hit ray, shadow ray}: t and the hit point
     v2f T2 = {0.0f, 0.0f}, hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};
-    auto record = [&](auto alpha_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
-        constexpr bool ALPHA = decltype(alpha_tag)::value;
+    float lo = __builtin_inff(), slo = __builtin_inff();  // UNSCALED: the smallest |oz| of the walk, per ray
+    // alpha_tag: 0 = no alpha test, 1 = alpha test, 2 = has_alpha decides at run time; div_tag: the plane solves use div_f_unscaled
+    auto record = [&](auto alpha_tag, auto div_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
+        constexpr int ALPHA = decltype(alpha_tag)::value;
+        constexpr bool FAST = decltype(div_tag)::value;
         if (!((sc.plane_share_mask >> k) & 1ull)) {  // wave-uniform: one plane solve per ray per coplanar pair of records
-            const PlaneHit a = tri_plane(o, d, make_float4(q2.x, q2.y, q2.z, q2.w)), b = tri_plane(so, sd, make_float4(q2.x, q2.y, q2.z, q2.w));
+            const float4 r2 = make_float4(q2.x, q2.y, q2.z, q2.w);
+            const PlaneHit a = FAST ? tri_plane_unscaled(o, d, r2, lo) : tri_plane(o, d, r2), b = FAST ? tri_plane_unscaled(so, sd, r2, slo) : tri_plane(so, sd, r2);
             T2 = (v2f){a.t, b.t};
             hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
         }
@@ -211,7 +275,7 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
         m = (k == ex0) ? -1.0f : m;
         sm = (k == sex0) ? -1.0f : sm;
         sm = (k == sex1) ? -1.0f : sm;
-        if (ALPHA) {
+        if (ALPHA == 1 || (ALPHA == 2 && has_alpha)) {
             // k through readfirstlane: opaque to loop strength reduction, which otherwise keeps this block's record pointer and
             // hash constant as induction variables updated on the scalar unit every trip
             const uint32_t ka = __builtin_amdgcn_readfirstlane(k);
@@ -231,18 +295,43 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     // (wave-uniform) flag is turned into a lane mask and back by every record of every scene -- a v_cndmask and a v_cmp, 8.8
     // cycles of 240 -- to merge the two values of the margins behind the branch.
     auto walk = [&](auto alpha_tag) {
+        const BoolTag<UNSCALED> div_tag{};
         v4f a0 = lrec[0], a1 = lrec[1], a2 = lrec[2], b0, b1, b2;
         uint32_t k = 0;
         for (; k + 1 < n; k += 2) {
             b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
-            record(alpha_tag, k, a0, a1, a2);
+            record(alpha_tag, div_tag, k, a0, a1, a2);
             a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
-            record(alpha_tag, k + 1, b0, b1, b2);
+            record(alpha_tag, div_tag, k + 1, b0, b1, b2);
         }
-        if (k < n) record(alpha_tag, k, a0, a1, a2);
+        if (k < n) record(alpha_tag, div_tag, k, a0, a1, a2);
     };
-    if (has_alpha) walk(BoolTag<true>{});
-    else walk(BoolTag<false>{});
+    // the same walk with the compiler's division, kept small: one record per trip, the alpha flag read at run time
+    auto walk_ieee = [&] {
+        best_t = next_up(tmax); best = kInvalid; occ_margin = -1.0f;
+#pragma clang loop unroll(disable)
+        for (uint32_t k = 0; k < n; k++) {
+            record(IntTag<2>{}, BoolTag<false>{}, k, lrec[3 * k], lrec[3 * k + 1], lrec[3 * k + 2]);
+        }
+    };
+    if (UNSCALED) {
+        const float ob = lds_recs[3u * (n + 1u) + 2u].w;  // dscene.h walk_bound_word: the last word of the records' padding
+        const bool pre_bad = ((tmax >= 0.0f) & !((max3_abs_raw(o.x, o.y, o.z) <= ob) & (max3_abs_raw(d.x, d.y, d.z) <= 2.0f) & (tmax <= 1e20f))) |
+                             ((stmax >= 0.0f) & !((max3_abs_raw(so.x, so.y, so.z) <= ob) & (max3_abs_raw(sd.x, sd.y, sd.z) <= 2.0f) & (stmax <= 1e20f)));
+        bool redo = __builtin_amdgcn_ballot_w64(pre_bad) != 0;
+        if (!redo) {
+            if (has_alpha) walk(IntTag<1>{});
+            else walk(IntTag<0>{});
+            const bool bad = ((tmax >= 0.0f) & (lo < 0x1p-47f)) | ((stmax >= 0.0f) & (slo < 0x1p-47f));
+            redo = __builtin_amdgcn_ballot_w64(bad) != 0;
+        }
+        if (redo) walk_ieee();
+        if (took_ieee_walk) *took_ieee_walk = redo ? 1u : 0u;
+    } else {
+        if (has_alpha) walk(IntTag<1>{});
+        else walk(IntTag<0>{});
+        if (took_ieee_walk) *took_ieee_walk = 0u;
+    }
     // (u, v) of the closest hit, once per walk instead of two selects per record: the record's rows from LDS again (a per-lane
     // address now) and the hit point o + t d with the t the walk kept -- the very operations on the very operands of the walk
     // (tri_plane's px = fma(t, d.x, o.x), tri_uv's fma chain over row 0), so the bits are the walk's.

@@ -5,6 +5,9 @@
 // correctly rounded division and sqrt (-fhip-fp32-correctly-rounded-divide-sqrt), and sin/cos/log given by
 // the polynomial kernels below instead of the device math library -- so a film rendered here is a pure
 // function of (scene, config, seed), reproducible bit-for-bit on any IEEE machine that follows the same text.
+// One division is written out by hand: div_f_unscaled below is the compiler's expansion of a / b minus its range-scaling steps, the
+// same bits on the operand set S it documents; its one caller (disect.h, the pair walk) validates the operands and repeats the walk
+// with a / b when they are not in S, so the contract holds for every input.
 #pragma once
 #if !defined(__HIPCC_RTC__)  // hiprtc (per-scene kernels, host/specialise.cpp) brings the HIP runtime declarations and the fixed-width integers itself
 #include <hip/hip_runtime.h>
@@ -80,6 +83,34 @@ AKR_HD float div_f(float a, float b) {
     return a * __builtin_amdgcn_rcpf(b);
 #else
     return a / b;
+#endif
+}
+// a / b without the range-scaling steps of the compiler's expansion: bit for bit div_f(a, b) for (a, b) in the set S below, anything
+// (including a wrong sign of zero, inf or NaN) elsewhere. Contract tier, device code; the relaxed tier and the host keep div_f.
+//
+// Under the contract's flags a / b compiles to v_div_scale_f32 x2, v_rcp_f32, v_fma, v_fmac, v_mul, v_fma, v_fmac, v_fma, v_div_fmas_f32,
+// v_div_fixup_f32: Newton-Raphson on the reciprocal and three residual corrections of the quotient. The two v_div_scale pre-scale
+// denominator and numerator by 2^+-64 (2^+-32) when an intermediate could leave the normal range, v_div_fmas undoes that on the last fma,
+// and v_div_fixup replaces the result in the special cases (zero, inf, NaN operands, a quotient that over- or underflows). On
+//   S = { (a, b) : b normal and |b| <= 2^125;  biased exponent of a >= 24;  -125 <= exp(a) - exp(b) <= 95 }
+// none of them acts: v_div_scale returns its operand unchanged with vcc = 0 (the denominator is scaled only when b is denormal or
+// |b| > 2^125 or exp(a) - exp(b) >= 96; the numerator only when a's biased exponent is < 24 or the quotient could underflow,
+// exp(a) - exp(b) <= -126), v_div_fmas with vcc = 0 is a plain fma, and v_div_fixup passes a finite quotient of finite nonzero operands
+// through. What is left is the sequence below: the same operations on the same operands in the same order, so the same bits.
+// tests/test_gpu_div_unscaled.py holds the device to this, at every edge of S from both sides.
+// Who calls this has to know its operands are in S, or that nothing of the result is used when they are not (disect.h).
+AKR_HD float div_f_unscaled(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__) && !AKR_RX
+    const float r0 = __builtin_amdgcn_rcpf(b);
+    const float e0 = __builtin_fmaf(-b, r0, 1.0f);
+    const float r1 = __builtin_fmaf(e0, r0, r0);
+    const float q0 = a * r1;
+    const float e1 = __builtin_fmaf(-b, q0, a);
+    const float q1 = __builtin_fmaf(e1, r1, q0);
+    const float e2 = __builtin_fmaf(-b, q1, a);
+    return __builtin_fmaf(e2, r1, q1);
+#else
+    return div_f(a, b);
 #endif
 }
 AKR_HD float sqrt_f(float x) {

@@ -1,7 +1,8 @@
 // dscene.h -- the scene as it lives in HBM, and the hit -> SurfaceInteraction reconstruction.
 //
 // Layout (all arrays 16-byte aligned, read with 16-byte vector loads):
-//   woop      exhaustive path: 3 x float4 per triangle (the ray-triangle test's 48 B record), global order;
+//   woop      exhaustive path: 3 x float4 per triangle (the ray-triangle test's 48 B record), global order, then two records of padding whose
+//             last word is the pair walk's origin bound (kWalkBoundWord; disect.h UNSCALED_DIV);
 //             BVH path: 4 x float4 per triangle in traversal order = the 48 B record | global triangle id | 12 B unused
 //             (one 64-byte fetch per test; global id = inst_tri_offset[inst] + prim)
 //   bvh_nodes 6-wide compressed nodes of 64 B (host/bvh.cpp)
@@ -26,6 +27,11 @@ constexpr uint32_t kBvhTriWords = 16;                   // BVH path: 12 words Wo
 // kBvhStackDepth is the deepest tree a scene may have; a launch sizes its stacks from the tree the scene actually got
 // (DScene.bvh_stack_depth: 10 levels for the 10 M-triangle hall -- 10 KB of LDS per workgroup instead of 24).
 constexpr uint32_t kBvhStackDepth = 24;
+// Exhaustive path: the word of the records' padding (records n_tris and n_tris + 1, never tested) that holds the pair walk's origin bound B: a ray
+// with |o| <= B and |d| <= 2 per component has |oz|, |dz| < 2^46 on every plane row (disect.h UNSCALED_DIV); negative = no such bound. Written
+// by scene_finish (api_scene.cpp walk_origin_bound) only; left at the padding's 0, a scene is still rendered correctly, but every walk then
+// repeats with the compiler's division -- silently slower. (Kept out of DScene: the by-value argument of every kernel keeps its layout.)
+AKR_HD uint32_t walk_bound_word(uint32_t n_tris) { return 12u * (n_tris + 1u) + 11u; }
 
 // shade record rows (float4 each):
 //  0: v0.xyz | uv0.x     1: v1.xyz | uv0.y     2: v2.xyz | uv1.x     (object-space vertices)

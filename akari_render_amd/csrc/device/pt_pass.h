@@ -33,6 +33,11 @@ namespace akr {
 #ifndef AKR_PT_MIN_WAVES_BVH_TEX
 #define AKR_PT_MIN_WAVES_BVH_TEX 3  // BVH kernels of such a scene (399 -> 517)
 #endif
+// The pair walk's shortcut (disect.h WalkOpt: division without range scaling) per exhaustive instantiation. On for the kernels of scenes
+// without textures (C2 +0.6 ... +1.4 %, C3 +1.3 ... +2.1 %, the reference's default configuration +3.1 %), off for those with: the textured
+// room's interpreter kernel measured 878 -> 869 Msamples/s with it, three alternating runs, the parent's spread 1.7 (profiles/walk_div_mask_ab.md).
+template <bool TEX>
+using PairWalkOpt = WalkOpt<!TEX>;
 // (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_plan)
 // ABSENT: lobes the scene cannot have (dbsdf.h AB_*). The precompiled kernels know 0 and AB_SIMPLE (PtParams.simple_scene: scenes without
 // textures); a per-scene kernel gets the mask of its scene.
@@ -180,7 +185,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     }
                 }
             } else {
-                trace_pair_exhaustive<TEX>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1, hit, found,
+                trace_pair_exhaustive<TEX, PairWalkOpt<TEX>>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1, hit, found,
                                            occluded, lds_recs);
             }
             if (DEFER) {

@@ -100,6 +100,22 @@ AKR_TEST_API int32_t akr_probe_math(akr_context* ctx, uint32_t n, const float* x
         }
     });
 }
+AKR_TEST_API int32_t akr_probe_div(akr_context* ctx, uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee) {
+    if (!ctx || !a || !b || !out_fast || !out_ieee) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_div: NULL argument");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf da, db, df, di;
+        da.upload(std::vector<float>(a, a + n));
+        db.upload(std::vector<float>(b, b + n));
+        df.alloc((size_t)n * 4); di.alloc((size_t)n * 4);
+        if (n) HIP_CHECK(launch_probe_div(n, da.as<float>(), db.as<float>(), df.as<float>(), di.as<float>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) {
+            HIP_CHECK(hipMemcpy(out_fast, df.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(out_ieee, di.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
 AKR_TEST_API int32_t akr_probe_bsdf(akr_context* ctx, const akr_material_desc* m, const float* table, int32_t mode, const float* wo, uint32_t n,
                                const float* in, float* out) {
     if (!ctx || !m || !wo || !in || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_bsdf: NULL argument");
@@ -141,6 +157,26 @@ AKR_TEST_API int32_t akr_probe_intersect(akr_context* ctx, akr_scene* scene, uin
         if (n) {
             HIP_CHECK(hipMemcpy(hit_inst_prim, dout.p, 3ull * n * 4, hipMemcpyDeviceToHost));
             HIP_CHECK(hipMemcpy(bary, db.p, 2ull * n * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+AKR_TEST_API int32_t akr_probe_intersect_pair(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rays16, const uint32_t* excl3, uint32_t* out4, float* tuv3) {
+    if (!ctx || !scene || !rays16 || !excl3 || !out4 || !tuv3) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_intersect_pair: NULL argument");
+    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_intersect_pair: scene belongs to another context");
+    if (scene->dscene.bvh_nodes || scene->dscene.in2.on || scene->dscene.n_tris > 64)
+        return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_intersect_pair: the pair walk serves scenes of at most 64 triangles");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf dr, de, dout, dt;
+        dr.upload(std::vector<float>(rays16, rays16 + 16ull * n));
+        de.upload(std::vector<uint32_t>(excl3, excl3 + 3ull * n));
+        dout.alloc(4ull * n * 4);
+        dt.alloc(3ull * n * 4);
+        if (n) HIP_CHECK(launch_probe_intersect_pair(probe_params(scene), n, dr.as<float>(), de.as<uint32_t>(), dout.as<uint32_t>(), dt.as<float>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) {
+            HIP_CHECK(hipMemcpy(out4, dout.p, 4ull * n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(tuv3, dt.p, 3ull * n * 4, hipMemcpyDeviceToHost));
         }
     });
 }

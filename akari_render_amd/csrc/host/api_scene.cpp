@@ -111,6 +111,26 @@ static void count_device_bytes(akr_scene* s) {
         s->device_bytes += b->bytes;
 }
 
+// The pair walk's origin bound (dscene.h walk_bound_word): the largest power of two B <= 2^40 such that a ray with |o| <= B and |d| <= 2 per component gives, on every plane row
+// (x, y, z, w) of the n records, |oz| = |x o.x + y o.y + z o.z + w| < 2^46 and |dz| = |x d.x + y d.y + z d.z| < 2^46 -- what the pair walk's
+// division without range scaling assumes of its operands (device/disect.h UNSCALED_DIV). Bounded here in double by the triangle
+// inequality against 2^45: the factor of two covers the rounding of the f32 fma chains (a few parts in 2^24) many times over.
+// -1: a row is not finite or too large for any such B; the scene's walks then keep the compiler's division.
+static float walk_origin_bound(const std::vector<float>& woop, uint32_t n) {
+    double s_max = 0.0, w_max = 0.0;
+    for (uint32_t k = 0; k < n; k++) {
+        const float* r = &woop[12ull * k + 8];
+        if (!(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]))) return -1.0f;
+        s_max = std::max(s_max, std::fabs((double)r[0]) + std::fabs((double)r[1]) + std::fabs((double)r[2]));
+        w_max = std::max(w_max, std::fabs((double)r[3]));
+    }
+    const double limit = 0x1p45;
+    if (!(2.0 * s_max <= limit && w_max < limit)) return -1.0f;
+    double b = 0x1p40;
+    while (b >= 0x1p-40 && s_max * b + w_max > limit) b *= 0.5;
+    return b >= 0x1p-40 ? (float)b : -1.0f;
+}
+
 // A lens moves the ray origins off the camera's position, and the padding of the scene's boxes was sized from the largest coordinate magnitude an
 // origin can have (scene_build.cpp, scene_inst.cpp: the camera's translation against the scene's box). The trees of a scene
 // are the ones of its lens-less compile, so the lens is accepted only where every origin on its disk stays inside that magnitude.
@@ -148,6 +168,8 @@ void akr_api::scene_finish(akr_scene* s) {
         return;
     }
     ctx->bind();
+    if (cs.bvh_nodes.empty() && !cs.instanced.on && cs.woop.size() > walk_bound_word(cs.n_tris))  // exhaustive path: the pair walk's origin bound, in the records' padding
+        cs.woop[walk_bound_word(cs.n_tris)] = walk_origin_bound(cs.woop, cs.n_tris);
     s->woop.upload(cs.woop);
     s->tri_gid.upload(cs.tri_gid);
     s->shade.upload(cs.shade);

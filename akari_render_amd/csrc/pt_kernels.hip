@@ -68,6 +68,13 @@ __global__ void k_probe_math(uint32_t n, const float* __restrict__ x, float* s, 
     c[i] = cv;
     l[i] = log_f(x[i]);
 }
+// a / b by the pair walk's division without range scaling (dmath.h div_f_unscaled) and by the contract's
+__global__ void k_probe_div(uint32_t n, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out_fast, float* __restrict__ out_ieee) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out_fast[i] = div_f_unscaled(a[i], b[i]);
+    out_ieee[i] = div_f(a[i], b[i]);
+}
 __global__ void k_probe_bsdf(const DMaterial* __restrict__ m, const float* __restrict__ table, int mode, vec3 wo, uint32_t n,
                              const float* __restrict__ in, float* __restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,6 +119,33 @@ __global__ __launch_bounds__(256) void k_probe_intersect(PtParams p, uint32_t n,
     out[3 * i + 2] = prim;
     bary[2 * i + 0] = found ? h.u : 0.0f;
     bary[2 * i + 1] = found ? h.v : 0.0f;
+}
+// trace_pair_exhaustive as pt_pass_body calls it: the records staged in LDS, one closest-hit and one shadow ray per lane (a ray with
+// tmax < 0 does not exist). rays: o.xyz d.xyz tmax - | so.xyz sd.xyz stmax - (16 floats), excl: ex0 sex0 sex1 (record ids or kInvalid);
+// out: found gid occluded took_ieee_walk, out_tuv: t u v of the hit
+__global__ __launch_bounds__(256) void k_probe_intersect_pair(PtParams p, uint32_t n, const float* __restrict__ rays, const uint32_t* __restrict__ excl, uint32_t* __restrict__ out,
+                                                              float* __restrict__ out_tuv) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    const uint32_t* g = (const uint32_t*)p.sc.woop;
+    for (uint32_t i = threadIdx.x; i < (p.sc.n_tris + 2u) * 12u; i += 256u) lds_stack[i] = g[i];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < n;
+    const float* r = rays + 16 * (size_t)(act ? i : 0);
+    const uint32_t* e = excl + 3 * (size_t)(act ? i : 0);
+    Hit h;
+    bool found = false, occluded = false;
+    uint32_t redo = 0;
+    trace_pair_exhaustive<false>(p.sc, mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]), act ? r[6] : -1.0f, e[0], mk3(r[8], r[9], r[10]), mk3(r[11], r[12], r[13]),
+                                 act ? r[14] : -1.0f, e[1], e[2], h, found, occluded, (const float4*)lds_stack, &redo);
+    if (!act) return;
+    out[4 * i + 0] = found ? 1u : 0u;
+    out[4 * i + 1] = h.gid;
+    out[4 * i + 2] = occluded ? 1u : 0u;
+    out[4 * i + 3] = redo;
+    out_tuv[3 * i + 0] = h.t;
+    out_tuv[3 * i + 1] = h.u;
+    out_tuv[3 * i + 2] = h.v;
 }
 template <bool INST>
 __global__ void k_probe_si(PtParams p, uint32_t n, const uint32_t* __restrict__ inst_prim, const float* __restrict__ bary, float* __restrict__ out) {
@@ -176,6 +210,14 @@ hipError_t launch_ggx_table(const uint64_t* seeds, float* table, uint32_t sample
 }
 hipError_t launch_probe_math(uint32_t n, const float* x, float* s, float* c, float* l, hipStream_t stream) {
     hipLaunchKernelGGL(k_probe_math, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, s, c, l);
+    return hipGetLastError();
+}
+hipError_t launch_probe_div(uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee, hipStream_t stream) {
+    hipLaunchKernelGGL(k_probe_div, dim3((n + 255) / 256), dim3(256), 0, stream, n, a, b, out_fast, out_ieee);
+    return hipGetLastError();
+}
+hipError_t launch_probe_intersect_pair(const PtParams& p, uint32_t n, const float* rays, const uint32_t* excl, uint32_t* out, float* out_tuv, hipStream_t stream) {
+    launch_kernel(k_probe_intersect_pair, (n + 255) / 256, (p.sc.n_tris + 2u) * 48u, stream, p, n, rays, excl, out, out_tuv);
     return hipGetLastError();
 }
 hipError_t launch_probe_bsdf(const DMaterial* m, const float* table, int mode, const float* wo, uint32_t n, const float* in, float* out,

@@ -52,6 +52,9 @@ AKR_TEST_API int32_t akr_host_alias_table(const float *weights, uint32_t n, uint
 /* sin/cos/log of the kernels' elementary functions for n inputs. */
 AKR_TEST_API int32_t akr_probe_math(akr_context *ctx, uint32_t n, const float *x, float *sin_out, float *cos_out, float *log_out);
 
+/* a / b for n pairs: by the pair walk's division without range scaling (csrc/device/dmath.h div_f_unscaled) and by the contract's a / b. */
+AKR_TEST_API int32_t akr_probe_div(akr_context *ctx, uint32_t n, const float *a, const float *b, float *out_fast, float *out_ieee);
+
 /* BSDF of material `m` on a flat surface (normal +z, world == local; cf. akari_test.rs:16-439):
  * mode 0: in = wi (3 floats / item)  -> out = f.rgb, pdf (4 floats / item)
  * mode 1: in = u  (3 floats / item)  -> out = wi.xyz, f.rgb, pdf, valid (8 floats / item) */
@@ -61,6 +64,13 @@ AKR_TEST_API int32_t akr_probe_bsdf(akr_context *ctx, const akr_material_desc *m
 /* Closest hit of n rays (o.xyz, d.xyz, tmin, tmax = 8 floats / ray) -> hit(0/1), inst, prim as u32 and u, v. */
 AKR_TEST_API int32_t akr_probe_intersect(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rays, uint32_t *hit_inst_prim,
                                     float *bary);
+
+/* The pair walk of scenes of at most 64 triangles (csrc/device/disect.h trace_pair_exhaustive) as the pt kernel calls it, n lanes:
+ * rays16 = o.xyz d.xyz tmax - | so.xyz sd.xyz stmax - (closest-hit ray | shadow ray; tmax < 0: the lane has no such ray),
+ * excl3 = excluded global triangle ids ex0 | sex0 sex1 (0xffffffff: none) -> out4 = found, gid, occluded, whether the lane's wave
+ * repeated the walk with the contract's division; tuv3 = t, u, v of the closest hit. */
+AKR_TEST_API int32_t akr_probe_intersect_pair(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rays16, const uint32_t *excl3, uint32_t *out4,
+                                         float *tuv3);
 
 AKR_TEST_API int32_t akr_probe_surface_interaction(akr_context *ctx, akr_scene *scene, uint32_t n, const uint32_t *inst_prim,
                                               const float *bary, float *out);
