@@ -51,7 +51,7 @@ TEST_EXPORTS = [
     "akr_host_decode_exr", "akr_host_decode_tiff", "akr_host_decode_dds", "akr_host_pmj02bn_tables",
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
-    "akr_probe_div", "akr_probe_intersect_pair",
+    "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2",
 ]
 
 
@@ -189,6 +189,7 @@ def lib() -> C.CDLL:
     proto("akr_host_pcg_start", u64p, u64)
     proto("akr_host_alias_table", fp, u32, up, fp, fp)
     proto("akr_probe_math", vp, u32, fp, fp, fp, fp)
+    proto("akr_probe_math2", vp, u32, fp, fp)
     proto("akr_probe_bsdf", vp, C.POINTER(abi.MaterialDesc), fp, i32, fp, u32, fp, fp)
     proto("akr_probe_intersect", vp, vp, u32, fp, up, fp)
     proto("akr_probe_div", vp, u32, fp, fp, fp, fp)
@@ -734,6 +735,14 @@ def probe_math(ctx: Context, x: np.ndarray):
     s, c, l = (np.zeros_like(x) for _ in range(3))
     check(lib().akr_probe_math(ctx.h, x.size, _fp(x), _fp(s), _fp(c), _fp(l)))
     return s, c, l
+
+
+def probe_math2(ctx: Context, x: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """(n, 6) float32: exp_f(x), pow_f(x, y), atan2_f(y, x), sqrt_f(x), rcp_f(x), srgb_to_linear1(x) on the device (contract tier)."""
+    xy = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.float32), np.asarray(y, dtype=np.float32)], axis=1))
+    out = np.zeros((xy.shape[0], 6), dtype=np.float32)
+    check(lib().akr_probe_math2(ctx.h, xy.shape[0], _fp(xy), _fp(out)))
+    return out
 
 
 def probe_div(ctx: Context, a: np.ndarray, b: np.ndarray):

@@ -729,6 +729,14 @@ AKR_HD void shade_point_cache_wo(ShadePoint& sp, const DMaterial& m, const float
     sp.wo_cached = true;
 }
 
+// to_local / to_world of the identity frame, which the reference puts around every Principled closure that has no normal map (normal_map(),
+// mod.rs:1391-1392): (1 x + 0 y) + 0 z and so on, written as the fused operations that give the same bits (0 * y is exact). Not a no-op:
+// a component that is -0 comes out as +0 unless the other two are negative, and a non-finite component reaches the other two as NaN.
+AKR_HD vec3 identity_frame_pass(vec3 v) {
+    return mk3(__builtin_fmaf(0.0f, v.z, __builtin_fmaf(0.0f, v.y, v.x)), __builtin_fmaf(0.0f, v.z, __builtin_fmaf(0.0f, v.x, v.y)),
+               __builtin_fmaf(0.0f, v.x, 0.0f * v.y) + v.z);
+}
+
 // closure.evaluate(wo, wi) for world-space directions -> (f * |cos|, pdf); pt.rs:268-279 for force_diffuse
 AKR_HD BsdfEval shade_evaluate(const ShadePoint& sp, const DMaterial& m, const float* __restrict__ table, vec3 wo, vec3 wi) {
     BsdfEval zero{mk3(0, 0, 0), 0.0f};
@@ -747,6 +755,8 @@ AKR_HD BsdfEval shade_evaluate(const ShadePoint& sp, const DMaterial& m, const f
                 li = to_local(nf, li);
             } else {
                 if (!check_wo_wi_valid(mk3(0, 0, 1), sp_ng_local(sp), lo, li)) return zero;
+                lo = identity_frame_pass(lo);
+                li = identity_frame_pass(li);
             }
             return principled_eval(m, table, lo, li, sp.wo_cached ? &sp.wo_albedo : nullptr, sp.absent);
         }
@@ -776,10 +786,10 @@ AKR_HD BsdfSample shade_sample(const ShadePoint& sp, const DMaterial& m, const f
             case MAT_PRINCIPLED: {
                 const bool nm = !(sp.absent & AB_NORMAL_MAP) && (m.flags & MF_NORMAL_MAP) != 0;
                 const Frame nf = nm ? sp_nm_frame(sp, m) : Frame{mk3(0, 0, 1), mk3(1, 0, 0), mk3(0, 1, 0)};
-                vec3 lo2 = nm ? to_local(nf, lo) : lo;
+                vec3 lo2 = nm ? to_local(nf, lo) : identity_frame_pass(lo);
                 vec3 w2;
                 valid = principled_sample_wi(m, table, lo2, u_select, u_sample, w2, sp.wo_cached ? &sp.wo_albedo : nullptr, sp.absent);
-                wl = nm ? to_world(nf, w2) : w2;
+                wl = nm ? to_world(nf, w2) : identity_frame_pass(w2);
                 valid = valid & check_wo_wi_valid(nf.n, sp_ng_local(sp), lo, wl);
                 break;
             }

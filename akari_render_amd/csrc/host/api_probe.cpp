@@ -100,6 +100,18 @@ AKR_TEST_API int32_t akr_probe_math(akr_context* ctx, uint32_t n, const float* x
         }
     });
 }
+AKR_TEST_API int32_t akr_probe_math2(akr_context* ctx, uint32_t n, const float* xy, float* out6) {
+    if (!ctx || !xy || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_math2: NULL argument");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf dxy, dout;
+        dxy.upload(std::vector<float>(xy, xy + 2ull * n));
+        dout.alloc(6ull * n * 4);
+        if (n) HIP_CHECK(launch_probe_math2(n, dxy.as<float>(), dout.as<float>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) HIP_CHECK(hipMemcpy(out6, dout.p, 6ull * n * 4, hipMemcpyDeviceToHost));
+    });
+}
 AKR_TEST_API int32_t akr_probe_div(akr_context* ctx, uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee) {
     if (!ctx || !a || !b || !out_fast || !out_ieee) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_div: NULL argument");
     return guarded([&] {

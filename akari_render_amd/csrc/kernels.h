@@ -237,6 +237,7 @@ hipError_t launch_init_pcg32(const uint64_t* seeds, void* states, uint64_t n, hi
 hipError_t launch_film_resolve(const float* film, uint64_t n, float splat_scale, float* rgb, hipStream_t stream);
 hipError_t launch_ggx_table(const uint64_t* seeds, float* table, uint32_t samples, hipStream_t stream);
 hipError_t launch_probe_math(uint32_t n, const float* x, float* s, float* c, float* l, hipStream_t stream);
+hipError_t launch_probe_math2(uint32_t n, const float* xy, float* out, hipStream_t stream);
 hipError_t launch_probe_bsdf(const DMaterial* m, const float* table, int mode, const float* wo, uint32_t n, const float* in, float* out,
                              hipStream_t stream);
 hipError_t launch_probe_div(uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee, hipStream_t stream);

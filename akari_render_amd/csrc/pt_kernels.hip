@@ -68,6 +68,19 @@ __global__ void k_probe_math(uint32_t n, const float* __restrict__ x, float* s, 
     c[i] = cv;
     l[i] = log_f(x[i]);
 }
+// the rest of the contract's elementary functions for (x, y): out6 = exp_f(x), pow_f(x, y), atan2_f(y, x), sqrt_f(x), rcp_f(x), srgb_to_linear1(x)
+__global__ void k_probe_math2(uint32_t n, const float* __restrict__ xy, float* __restrict__ out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+    float* o = out + 6 * (size_t)i;
+    o[0] = exp_f(x);
+    o[1] = pow_f(x, y);
+    o[2] = atan2_f(y, x);
+    o[3] = sqrt_f(x);
+    o[4] = rcp_f(x);
+    o[5] = srgb_to_linear1(x);
+}
 // a / b by the pair walk's division without range scaling (dmath.h div_f_unscaled) and by the contract's
 __global__ void k_probe_div(uint32_t n, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out_fast, float* __restrict__ out_ieee) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -210,6 +223,10 @@ hipError_t launch_ggx_table(const uint64_t* seeds, float* table, uint32_t sample
 }
 hipError_t launch_probe_math(uint32_t n, const float* x, float* s, float* c, float* l, hipStream_t stream) {
     hipLaunchKernelGGL(k_probe_math, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, s, c, l);
+    return hipGetLastError();
+}
+hipError_t launch_probe_math2(uint32_t n, const float* xy, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_probe_math2, dim3((n + 255) / 256), dim3(256), 0, stream, n, xy, out);
     return hipGetLastError();
 }
 hipError_t launch_probe_div(uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee, hipStream_t stream) {

@@ -52,6 +52,10 @@ AKR_TEST_API int32_t akr_host_alias_table(const float *weights, uint32_t n, uint
 /* sin/cos/log of the kernels' elementary functions for n inputs. */
 AKR_TEST_API int32_t akr_probe_math(akr_context *ctx, uint32_t n, const float *x, float *sin_out, float *cos_out, float *log_out);
 
+/* The other elementary functions of the arithmetic contract (csrc/device/dmath.h, denv.h, dtex.h) for n pairs xy = (x, y):
+ * out6 = exp_f(x), pow_f(x, y), atan2_f(y, x), sqrt_f(x), rcp_f(x), srgb_to_linear1(x). Contract tier. */
+AKR_TEST_API int32_t akr_probe_math2(akr_context *ctx, uint32_t n, const float *xy, float *out6);
+
 /* a / b for n pairs: by the pair walk's division without range scaling (csrc/device/dmath.h div_f_unscaled) and by the contract's a / b. */
 AKR_TEST_API int32_t akr_probe_div(akr_context *ctx, uint32_t n, const float *a, const float *b, float *out_fast, float *out_ieee);
 

@@ -185,6 +185,31 @@ def test_sampler_matches_numpy_definition(dtype, filt, address):
     assert n_bit_diff(got, want) == 0
 
 
+@pytest.mark.parametrize("fmt", [np.uint8, np.float32], ids=["rgba8", "rgba32f"])
+@pytest.mark.parametrize("filt", [abi.TEX_FILTER_NEAREST, abi.TEX_FILTER_LINEAR], ids=["nearest", "linear"])
+@pytest.mark.parametrize("address", [abi.TEX_REPEAT, abi.TEX_CLIP, abi.TEX_MIRROR, abi.TEX_EXTEND], ids=["repeat", "clip", "mirror", "extend"])
+def test_sampler_matrix_properties(fmt, filt, address):
+    """Every sampler mode at the six shapes of tests/probe_matrix.py (1 x 1, one row, one column, odd, power of two, wide), on the oracle:
+    exact texel centres return the texel under both filters, clip returns zeros beyond one texel outside, [0, 1]^2 agrees with a float64
+    evaluation within (2 max(w, h) + 9) 2^-24 max|texel|; the numpy restatement and the library's host build of dtex.h give the same bits
+    (NaN, +-inf and +-3e38 coordinates included). tests/test_gpu_probe_matrix.py asks the same of the device."""
+    from tests import probe_matrix as pm
+
+    sd, first = pm.sampler_scene()
+    sc = capi.Scene(None, sd)
+    cases = pm.sampler_cases()
+    for shape in pm.SHAPES:
+        case = (filt, address, fmt, shape)
+        uv, parts = pm.sampler_uv(shape)
+        got = pyoracle.tex_sample(pm.sampler_image(case), uv)
+        n_centres, _ = pm.check_sampler_properties(case, uv, parts, got)
+        assert n_centres == shape[0] * shape[1]  # float32 holds every centre of these shapes
+        some = np.r_[0:60, parts["centres"].start : parts["special"].start + 4]  # (the restatement is a Python loop, and its int() cannot take NaN)
+        assert n_bit_diff(got[some], np_sample(pm.sampler_image(case), uv[some])) == 0
+        host = capi.probe_material_inputs(None, sc, first + cases.index(case), uv)
+        assert n_bit_diff(np.ascontiguousarray(host[:, 1:5]), got) == 0, case
+
+
 def test_graph_evaluation_host_build_matches_oracle():
     sd = textured_room(alpha_cutout=True)
     osc = pyoracle.OracleScene(sd)
