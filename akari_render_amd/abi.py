@@ -218,6 +218,27 @@ class AovConfig(_Struct):
         return c
 
 
+class DenoiseConfig(_Struct):
+    """akr_denoise_config: the a-trous filter of akr_denoise."""
+
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("demodulate", C.c_uint32),
+        ("sigma_color", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("albedo_floor", C.c_float),
+        ("_pad", C.c_uint32 * 2),
+    ]
+
+    @staticmethod
+    def default() -> "DenoiseConfig":
+        c = DenoiseConfig()
+        c.iterations, c.demodulate = 5, 1
+        c.sigma_color, c.sigma_normal, c.sigma_albedo, c.albedo_floor = 2.0, 0.125, 0.0625, 1e-3
+        return c
+
+
 GPT_RECON_NONE, GPT_RECON_UNIFORM, GPT_RECON_WEIGHTED = 0, 1, 2
 GPT_RECON_NAMES = ("none", "uniform", "weighted")
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "akr_pt_kernel_info", "akr_scene_spec_source", "akr_host_spec_compile", "akr_host_spec_compile_text",
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
     "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
+    "akr_denoise_config_default", "akr_denoise",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -51,7 +52,7 @@ TEST_EXPORTS = [
     "akr_host_decode_exr", "akr_host_decode_tiff", "akr_host_decode_dds", "akr_host_pmj02bn_tables",
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
-    "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2",
+    "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2", "akr_host_denoise", "akr_probe_denoise_times",
 ]
 
 
@@ -89,7 +90,7 @@ def lib() -> C.CDLL:
     L.akr_struct_size.argtypes = [C.c_int32]
     for sid, cls in enumerate((abi.MeshDesc, abi.InstanceDesc, abi.MaterialDesc, abi.CameraDesc, abi.SceneDesc, abi.PtConfig, abi.PtStats, abi.SceneInfo,
                                abi.KernelInfo, abi.AovConfig, abi.GptConfig, abi.McmcConfig, abi.McmcResult, abi.McmcPartial,
-                               abi.EnvironmentDesc, abi.LensDesc), start=1):
+                               abi.EnvironmentDesc, abi.LensDesc, abi.DenoiseConfig), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -203,6 +204,10 @@ def lib() -> C.CDLL:
     proto("akr_host_decode_tiff", C.c_char_p, u64, up, up, C.POINTER(C.c_uint8), u64)
     proto("akr_host_decode_dds", C.c_char_p, u64, up, up, C.POINTER(C.c_uint8), u64)
     proto("akr_host_pmj02bn_tables", up, C.POINTER(C.c_uint16))
+    proto("akr_denoise_config_default", C.POINTER(abi.DenoiseConfig))
+    proto("akr_denoise", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp)
+    proto("akr_host_denoise", C.POINTER(abi.DenoiseConfig), u32, u32, fp, f32, fp, f32, fp, f32, fp)
+    proto("akr_probe_denoise_times", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, i32, fp)
     _lib = L
     return L
 
@@ -473,7 +478,7 @@ class Scene:
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop)."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step)."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 
@@ -843,6 +848,38 @@ def aov_render(ctx: Context, scene: Scene, cfg: abi.AovConfig, film: Film) -> di
     st = abi.PtStats()
     check(lib().akr_aov_render(ctx.h, scene.h, C.byref(cfg), film.h, C.byref(st)))
     return st.as_dict()
+
+
+def denoise(ctx: Context, color: Film, albedo: Optional[Film], normal: Optional[Film], out: Film, cfg: Optional[abi.DenoiseConfig] = None) -> None:
+    """akr_denoise: the edge-avoiding a-trous filter of `color`, guided by `albedo` and `normal` (either may be None),
+    into `out` (which may be `color`). cfg None = akr_denoise_config_default."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    check(lib().akr_denoise(ctx.h, C.byref(c), color.h, albedo.h if albedo is not None else None, normal.h if normal is not None else None, out.h))
+
+
+def denoise_times(ctx: Context, color: Film, albedo: Optional[Film], normal: Optional[Film], out: Film, kernel: int, cfg: Optional[abi.DenoiseConfig] = None) -> dict:
+    """akr_probe_denoise_times (test hook): akr_denoise under level kernel `kernel` (0 gathering, 1 LDS-tiled, -1 the library's per-step choice), its parts timed by HIP events (ms)."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    t = np.zeros(11, dtype=np.float32)
+    check(lib().akr_probe_denoise_times(ctx.h, C.byref(c), color.h, albedo.h if albedo is not None else None, normal.h if normal is not None else None, out.h, kernel, _fp(t)))
+    return {"prepare": float(t[0]), "levels": [float(v) for v in t[1:1 + c.iterations]], "finish": float(t[9]), "total": float(t[10])}
+
+
+def host_denoise(width: int, height: int, color: np.ndarray, albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
+                 cfg: Optional[abi.DenoiseConfig] = None, splat_scales=(1.0, 1.0, 1.0)) -> np.ndarray:
+    """akr_host_denoise (test hook): akr_denoise's arithmetic on the host. color / albedo / normal are raw film accumulators (7 W H floats,
+    reference layout), splat_scales theirs. -> (H, W, 3), what Film.resolve() of akr_denoise's output film returns."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    films = []
+    for f in (color, albedo, normal):
+        if f is not None:
+            f = np.ascontiguousarray(f, dtype=np.float32).reshape(-1)
+            assert f.size == 7 * width * height
+        films.append(f)
+    out = np.zeros(3 * width * height, dtype=np.float32)
+    ptr = [_fp(f) if f is not None else None for f in films]
+    check(lib().akr_host_denoise(C.byref(c), width, height, ptr[0], splat_scales[0], ptr[1], splat_scales[1], ptr[2], splat_scales[2], _fp(out)))
+    return out.reshape(height, width, 3)
 
 
 def gpt_render(ctx: Context, scene: Scene, cfg: abi.GptConfig, film: Film, want_aux: bool = False):

@@ -1,6 +1,51 @@
 // api_task.cpp -- akr_render_task: the reference's render driver (akari_integrator/src/lib.rs:111-207) (C ABI of libakari_hip.so, include/akari_hip.h; shared internals: api_internal.h)
 #include "api_internal.h"
 
+namespace {
+struct FilmHolder {  // a film that dies with its scope
+    akr_film* f = nullptr;
+    FilmHolder() = default;
+    explicit FilmHolder(akr_film* film) : f(film) {}
+    FilmHolder(const FilmHolder&) = delete;
+    FilmHolder& operator=(const FilmHolder&) = delete;
+    ~FilmHolder() { if (f) akr_film_destroy(f); }
+};
+
+// "{stem}.denoised{ext}" of film.out
+std::string denoised_path(const std::string& out) {
+    const size_t slash = out.find_last_of("/\\"), dot = out.find_last_of('.');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return out + ".denoised";
+    return out.substr(0, dot) + ".denoised" + out.substr(dot);
+}
+
+// Option "denoise" (DESIGN.md 4.10): the feature passes of a finished pt task -- albedo and ns (not remapped) at `spp` samples with the task's
+// sampler, seed, filter and colour pipeline, through the scene's lens if it has one -- then akr_denoise with its defaults, in place in `film`.
+void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, akr_film* film, uint32_t spp, bool verbose) {
+    auto check = [](int32_t rc) { if (rc != AKR_OK) throw std::runtime_error(std::string(g_last_error)); };
+    akr_aov_config ac;
+    check(akr_aov_config_default(&ac));
+    ac.spp = spp;
+    ac.remap = 0;
+    ac.filter_type = cfg.filter_type;
+    ac.filter_radius = cfg.filter_radius;
+    ac.sampler_type = cfg.sampler_type;
+    ac.sampler_seed = cfg.sampler_seed;
+    ac.color = cfg.color;
+    FilmHolder albedo, normal;
+    check(akr_film_create(ctx, film->width, film->height, &albedo.f));
+    check(akr_film_create(ctx, film->width, film->height, &normal.f));
+    akr_pt_stats sa, sn;
+    ac.aov = AKR_AOV_ALBEDO;
+    check(akr_aov_render(ctx, scene, &ac, albedo.f, &sa));
+    ac.aov = AKR_AOV_NS;
+    check(akr_aov_render(ctx, scene, &ac, normal.f, &sn));
+    akr_denoise_config dc;
+    check(akr_denoise_config_default(&dc));
+    check(akr_denoise(ctx, &dc, film, albedo.f, normal.f, film));
+    if (verbose) std::fprintf(stderr, "[akari_hip] Denoised (feature passes of %u spp: %.2fms)\n", spp, sa.kernel_ms + sn.kernel_ms);
+}
+}  // namespace
+
 extern "C" {
 
 AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* method_json_text, const akr_render_session* session,
@@ -9,6 +54,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
     akr_render_session ses{0, 0, nullptr, 0, 0};
     if (session) ses = *session;
     const std::string name = ses.name ? ses.name : "default";
+    const int denoise_spp = tuning().denoise;  // read once, like a session's options
     return guarded([&] {
         std::vector<ParsedTask> tasks = parse_render_tasks(method_json_text, ses.override_sampler_independent != 0);
         const uint32_t w = scene->flat.camera.width, h = scene->flat.camera.height;
@@ -121,10 +167,15 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
             }
             if (ses.verbose) std::fprintf(stderr, "[akari_hip] Rendering finished in %.2fs (%.1f Msamples/s)\n", st.kernel_ms * 1e-3, st.n_samples / (st.kernel_ms * 1e3));
             check(akr_film_resolve(film, rgb.data()));  // film.copy_to_rgba_image(hdr = true), lib.rs:191
-            akr_film_destroy(film);
+            FilmHolder done(film);
             film = nullptr;
             write_image(task.film_out, rgb.data(), w, h);  // util::write_image(&output_image, &config.film.out), lib.rs:192
             if (stats_out) *stats_out = st;
+            if (denoise_spp > 0) {  // option "denoise": film.out is written as ever, the denoised image next to it
+                denoise_step(ctx, scene, task.cfg, done.f, (uint32_t)denoise_spp, ses.verbose != 0);
+                check(akr_film_resolve(done.f, rgb.data()));
+                write_image(denoised_path(task.film_out), rgb.data(), w, h);
+            }
         }
     });
 }

@@ -1,10 +1,11 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y]
+//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
 // with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
+// --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,7 +17,7 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
               "  -m, --method <METHOD>    Render method config file (\"type\": \"pt\")\n"
               "  -d, --device <DEVICE>    HIP device ordinal (default 0)\n"
@@ -24,7 +25,8 @@ static void usage() {
               "      --save-intermediate  write {name}-{spp}.exr after every pass\n"
               "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files\n"
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
-              "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's");
+              "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
+              "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)");
 }
 
 // akari-cli --spec-compile <header file> <out.co> <arch> <flags> <min waves>: the library's helper process for per-scene kernels
@@ -50,6 +52,7 @@ int main(int argc, char** argv) {
     unsigned w = 0, h = 0;
     int dof = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
+    int denoise = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(1); } return argv[++i]; };
@@ -61,6 +64,18 @@ int main(int argc, char** argv) {
         else if (a == "--save-stats") { name = next(); save_stats = 1; }
         else if (a == "--independent-sampler") indep = 1;
         else if (a == "--depth-of-field") dof = 1;
+        else if (a == "--denoise") {  // the number is optional: taken only if the next argument is one
+            denoise = 16;
+            if (i + 1 < argc) {
+                char* end = nullptr;
+                const long v = std::strtol(argv[i + 1], &end, 10);
+                if (end != argv[i + 1] && *end == 0) {
+                    if (v < 1 || v > 65536) { std::fprintf(stderr, "akari-cli: --denoise wants 1 .. 65536 samples, got '%s'\n", argv[i + 1]); return 1; }
+                    denoise = (int)v;
+                    i++;
+                }
+            }
+        }
         else if (a == "--lens-radius" || a == "--focal-distance") {
             const char* text = next();
             char* end = nullptr;
@@ -88,6 +103,7 @@ int main(int argc, char** argv) {
     auto die = [&](const char* what) { std::fprintf(stderr, "akari-cli: %s: %s\n", what, akr_last_error()); std::exit(1); };
     if (akr_context_create(device, &ctx) != AKR_OK) die("device");
     if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
+    if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
     if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
         akr_lens_desc lens;

@@ -234,6 +234,8 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //                                         a value n > 1 = test hook: launches of >= n rays, and waves hand over after 4 steps with up to 56 lanes left)
 //   sched_trial  AKR_SCHED_TRIAL=<v>      flattened scenes, option wavefront = -1: -1 (default) = a long render of a large frame of a large untextured scene starts with two passes
 //                                         under each schedule and goes on with the faster; 0 = never (the megakernel); 1 = every pt session on a scene with a tree (tests)
+//   denoise      AKR_DENOISE=<n>          akr_render_task: n > 0 = every pt task is followed by albedo + ns aov passes of n spp and akr_denoise, "{stem}.denoised{ext}" written
+//   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
 //   max_fused_passes (no environment hook)     most passes akr_pt_passes fuses into one launch: 0 = adaptive (16, up to 64 once a pass has been timed), else 1..64
 struct TuningOptions {
     int force_bvh = 0, bvh_balanced = 0, defer_metal = -1, wavefront = -1, simple_kernels = 1;
@@ -252,6 +254,8 @@ struct TuningOptions {
     int sched_trial = -1;  // flattened scenes under option wavefront = -1: a timed trial of both schedules at the start of a long render (api_pt.cpp schedule_trial):
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
+    int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
+    int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
     int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
 };
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it

@@ -530,6 +530,30 @@ AKR_API int32_t akr_aov_config_default(akr_aov_config *cfg);
 AKR_API int32_t akr_aov_render(akr_context *ctx, akr_scene *scene, const akr_aov_config *cfg, akr_film *film, akr_pt_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Denoiser (no reference counterpart: pt.rs:19-26 declares DenoisingFeatures, PathTracer never fills them): an
+ * edge-avoiding a-trous wavelet filter with albedo demodulation (Dammertz et al. 2010) over three films -- the noisy colour and the
+ * first-hit guides an `aov` render gives (AKR_AOV_ALBEDO; AKR_AOV_NS with remap = 0 or 1). Every film is resolved as akr_film_resolve
+ * does; x = colour / max(albedo, albedo_floor) when `demodulate`; `iterations` levels of 5 x 5 taps (B3 spline) at step 2^i, each tap
+ * weighted by exp(-(|dx|^2 / sigma_color_i^2 + |dn|^2 / sigma_normal^2 + |da|^2 / sigma_albedo^2)) with sigma_color_i = sigma_color 2^-i;
+ * taps outside the image and pixels with a non-finite value never contribute, such a pixel itself passes through. The arithmetic is
+ * defined to the bit like the integrators'. A sigma of 0 switches its term off.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t iterations;     /* 5; 0..8 */
+    uint32_t demodulate;     /* 1: divide the colour by the albedo before filtering, multiply afterwards (needs an albedo film) */
+    float sigma_color, sigma_normal, sigma_albedo;   /* >= 0, finite */
+    float albedo_floor;      /* 1e-3; > 0: the least divisor of the demodulation */
+    uint32_t _pad[2];
+} akr_denoise_config;
+AKR_API int32_t akr_denoise_config_default(akr_denoise_config *cfg);
+/* color -> out. albedo and / or normal may be NULL (that term is dropped; without albedo there is no demodulation). All films have one
+ * size and one context, else AKR_ERR_INVALID_ARGUMENT -- as for iterations > 8, a negative or non-finite sigma, a positive sigma so small
+ * that 1 / sigma^2 (for sigma_color: at the last level) is not finite in f32, albedo_floor not > 0.
+ * `out` receives rgb = the result, splat = 0, weight = 1, so akr_film_resolve(out) returns the result exactly; out may be `color`.
+ * Enqueued on the context's stream, blocks until the result is complete; work buffers (64 bytes per pixel) live for the call. */
+AKR_API int32_t akr_denoise(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *albedo, akr_film *normal, akr_film *out);
+
+/* ---------------------------------------------------------------------------------------------------
  * `gpt` integrator (Method::GradientPathTracer, akari_integrator/src/gpt.rs; "type": "gpt"): gradient-domain path tracing.
  * Per sample one base path and four offset paths through the neighbouring pixels (stride apart, mirrored at the border)
  * on the same random numbers; the offset paths rejoin the base path through the reconnection shift mapping of
@@ -655,7 +679,8 @@ AKR_API const char *akr_version(void);
 typedef enum {
     AKR_STRUCT_MESH_DESC = 1, AKR_STRUCT_INSTANCE_DESC, AKR_STRUCT_MATERIAL_DESC, AKR_STRUCT_CAMERA_DESC, AKR_STRUCT_SCENE_DESC,
     AKR_STRUCT_PT_CONFIG, AKR_STRUCT_PT_STATS, AKR_STRUCT_SCENE_INFO, AKR_STRUCT_KERNEL_INFO, AKR_STRUCT_AOV_CONFIG, AKR_STRUCT_GPT_CONFIG,
-    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC, AKR_STRUCT_LENS_DESC
+    AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC, AKR_STRUCT_LENS_DESC,
+    AKR_STRUCT_DENOISE_CONFIG
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
@@ -698,6 +723,12 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *   "lens"         (AKR_LENS=1)             akr_scene_load: 1 = the camera gets the thin lens of the file's focal_distance and fstop, radius =
  *                                           focal_distance / (2 fstop) (load.rs:177-179); 0 (default) = a pinhole, which is how the reference
  *                                           renders every file -- its exporter writes the pair whether or not depth of field is on
+ *   "denoise"      (AKR_DENOISE=n)          akr_render_task: n > 0 = after a `pt` task has written film.out, albedo and ns are rendered with the aov
+ *                                           integrator at n spp (the task's sampler, seed, filter and colour pipeline), akr_denoise runs with its
+ *                                           default configuration and "{stem}.denoised{ext}" is written next to film.out; 0 (default) = off. Other
+ *                                           method types ignore it. n <= 65536.
+ *   "denoise_kernel" (AKR_DENOISE_KERNEL=v) akr_denoise's level kernel: 0 = one thread per pixel gathering from global memory, 1 = the LDS-tiled
+ *                                           kernel, -1 (default) = the library decides per step. Same bits either way.
  * Values out of an option's range fail with AKR_ERR_INVALID_ARGUMENT.
  * A session reads the options once, when it begins (akr_pt_begin / akr_gpt_begin / ...): a later akr_option_set does not change it.
  * "wavefront" = 1 on a scene without a BVH renders with the megakernel. Unknown names fail with AKR_ERR_INVALID_ARGUMENT. */

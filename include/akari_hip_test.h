@@ -96,6 +96,17 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene *scene, uint32_t filter_t
 AKR_TEST_API int32_t akr_probe_camera_rays(akr_context *ctx, akr_scene *scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2,
                                       const float *u4, float *out6);
 
+/* akr_denoise on the host (no GPU): the text of csrc/device/ddenoise.h compiled for the host, over host arrays. Each film is an accumulator
+ * in the reference layout [rgb 3N | splat 3N | weight N] with its splat scale; albedo_film / normal_film may be NULL. out_rgb = 3 N floats,
+ * what akr_film_resolve returns for akr_denoise's output film. Same refusals as akr_denoise. */
+AKR_TEST_API int32_t akr_host_denoise(const akr_denoise_config *cfg, uint32_t width, uint32_t height, const float *color_film, float color_splat_scale,
+                                 const float *albedo_film, float albedo_splat_scale, const float *normal_film, float normal_splat_scale, float *out_rgb);
+
+/* akr_denoise under one level kernel (0 = gathering, 1 = LDS-tiled; -1 = the library's choice per step, what akr_denoise runs) with its parts timed by HIP events on the context's stream:
+ * times11 = milliseconds of prepare, level 0 .. 7 (0 beyond cfg->iterations), finish, the whole call (tools/denoise_bench.py). */
+AKR_TEST_API int32_t akr_probe_denoise_times(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *albedo, akr_film *normal, akr_film *out,
+                                        int32_t kernel, float *times11);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);
