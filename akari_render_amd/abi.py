@@ -353,6 +353,29 @@ class KernelInfo(C.Structure):
         return d
 
 
+class PtLaunchPlan(C.Structure):
+    """akr_pt_launch_plan (include/akari_hip_test.h): the kernel variant and LDS layout a pt session of (scene, config) would launch."""
+
+    VARIANT = ("bvh", "fd", "tex", "pmj", "stage", "defer", "simple", "inst", "env", "lens")
+    _fields_ = [
+        ("variant", C.c_uint32 * 10),
+        ("simple_scene", C.c_uint32), ("defer_metal", C.c_uint32), ("defer_flags", C.c_uint32),
+        ("stage_bytes", C.c_uint32 * 13), ("stage_total", C.c_uint32),
+        ("tile_offset", C.c_uint32), ("bvh_tile_nodes", C.c_uint32), ("park_offset", C.c_uint32), ("carry_offset", C.c_uint32),
+        ("bn_offset", C.c_uint32), ("val_offset_words", C.c_uint32),
+        ("lds_bytes", C.c_uint32), ("blocks", C.c_uint32),
+        ("specialised", C.c_uint32),
+        ("wrapper", C.c_char * 600),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("variant", "stage_bytes", "wrapper")}
+        d["variant"] = {n: int(self.variant[i]) for i, n in enumerate(self.VARIANT)}
+        d["stage_bytes"] = [int(b) for b in self.stage_bytes]
+        d["wrapper"] = self.wrapper.decode()
+        return d
+
+
 class SceneInfo(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),

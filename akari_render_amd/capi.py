@@ -53,6 +53,7 @@ TEST_EXPORTS = [
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
     "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2", "akr_host_denoise", "akr_probe_denoise_times",
+    "akr_host_pt_launch_plan",
 ]
 
 
@@ -117,6 +118,7 @@ def lib() -> C.CDLL:
     proto("akr_scene_get_lens", vp, C.POINTER(abi.LensDesc))
     proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
+    proto("akr_host_pt_launch_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, C.POINTER(abi.PtLaunchPlan))
     proto("akr_probe_env_sample", vp, vp, u32, fp, fp)
     proto("akr_probe_env_pdf", vp, vp, u32, fp, fp)
     proto("akr_scene_get_ggx_table", vp, fp)
@@ -307,6 +309,13 @@ class Scene:
         flags = (1 if bvh else 0) | (2 if pmj else 0) | (4 if stage else 0) | (8 if defer else 0) | (16 if inst else 0) | (32 if env else 0) | (64 if lens else 0)
         check(lib().akr_host_spec_compile(self.h, flags, min_waves, arch.encode(), C.byref(nbytes), log, 4096))
         return nbytes.value
+
+    def launch_plan(self, cfg: abi.PtConfig, defer_metal: int = -1, simple_kernels: int = 1, defer_on: int = 0, spec_waves: int = 0) -> dict:
+        """akr_host_pt_launch_plan (test hook, no GPU): the kernel variant, the parameter-block fields that follow from it and the LDS layout
+        of a pt session of this scene and `cfg` under the given options; spec_waves != 0: with a per-scene kernel of that many waves."""
+        out = abi.PtLaunchPlan()
+        check(lib().akr_host_pt_launch_plan(self.h, C.byref(cfg), defer_metal, simple_kernels, defer_on, spec_waves, C.byref(out)))
+        return out.as_dict()
 
     def material_folded_host(self, material: int, uv: np.ndarray):
         """akr_probe_material_folded_host: (folded records u32[n, 64], alpha f32[n], emission f32[n, 3]) of the interpreter, on the host."""

@@ -91,6 +91,8 @@ __global__ __launch_bounds__(256) void k_aov(const PtParams p_in, uint32_t spp, 
     }
 }
 
+hipError_t aov_entry_lens(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream);  // aov_lens_kernels.hip; launch_aov (aov_kernels.hip) goes there through its table
+
 template <bool LENS>
 hipError_t launch_aov_t(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream) {
     uint32_t blocks = (p.n_items + 255u) / 256u;

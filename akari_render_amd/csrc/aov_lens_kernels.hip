@@ -1,9 +1,9 @@
 // aov_lens_kernels.hip -- k_aov for a camera with a thin lens (LENS = true; aov_kernel.h): a denoiser's feature buffers see the scene as the
-// beauty pass does. launch_aov (aov_kernels.hip) hands such sessions here.
+// beauty pass does.
 #include "aov_kernel.h"
 
 namespace akr {
 
-hipError_t launch_aov_lens(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream) { return launch_aov_t<true>(p, spp, aov, remap, stream); }
+hipError_t aov_entry_lens(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream) { return launch_aov_t<true>(p, spp, aov, remap, stream); }
 
 }  // namespace akr

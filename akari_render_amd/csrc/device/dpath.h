@@ -94,7 +94,7 @@ AKR_HD float unorm16(uint32_t v) {
 }
 // bluenoise(tex_index, p): uv = p.yx() % 128 of texture tex_index % 48 (sampler/mod.rs:545-553), unorm16 -> float
 // k_pt_pass keeps a lane's pixel for the whole launch, and a pixel reads ONE texel of each of the 48 arrays: when the launch has
-// room (PtParams.bn_offset != 0, launch_pt_pass) the lane's 48 values sit in a column of LDS (pmj_bluenoise_stage below) and a
+// room (PtParams.bn_offset != 0, kernels.h pt_lds_layout) the lane's 48 values sit in a column of LDS (pmj_bluenoise_stage below) and a
 // lookup is a ds_read_u16 instead of a gather from a 1.5 MB table.
 AKR_D float pmj_bluenoise(const PtParams& p, uint32_t tex, uint32_t px, uint32_t py) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -38,12 +38,13 @@ namespace akr {
 // room's interpreter kernel measured 878 -> 869 Msamples/s with it, three alternating runs, the parent's spread 1.7 (profiles/walk_div_mask_ab.md).
 template <bool TEX>
 using PairWalkOpt = WalkOpt<!TEX>;
-// (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_plan)
+// (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_layout)
 // ABSENT: lobes the scene cannot have (dbsdf.h AB_*). The precompiled kernels know 0 and AB_SIMPLE (PtParams.simple_scene: scenes without
 // textures); a per-scene kernel gets the mask of its scene.
-// INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h); BVH kernels without STAGE / DEFER only.
-// ENV: the scene has an environment light (device/denv.h); kernels without DEFER / SIMPLE only.
-// LENS: the camera has a thin lens (dpath.h generate_ray); kernels without DEFER / SIMPLE only.
+// INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h).
+// ENV: the scene has an environment light (device/denv.h).
+// LENS: the camera has a thin lens (dpath.h generate_ray).
+// Which combinations of the flags exist as kernels: kernels.h pt_variant_compiled.
 template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false>
 AKR_D void pt_pass_body(const PtParams& p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];  // BVH: kBvhStackDepth x 256 words; else: staged tables
@@ -65,7 +66,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
         __syncthreads();
     }
     const float4* lds_recs = nullptr;
-    if (!BVH) {  // the exhaustive walk reads the triangle records from LDS, behind the staged tables (pt_lds_plan sizes the block)
+    if (!BVH) {  // the exhaustive walk reads the triangle records from LDS, behind the staged tables (pt_lds_layout sizes the block)
         uint32_t* l = lds_stack + (p.stage_total >> 2);
         const uint32_t* g = (const uint32_t*)p.sc.woop;
         for (uint32_t i = threadIdx.x; i < (p.sc.n_tris + 2u) * 12u; i += 256u) l[i] = g[i];

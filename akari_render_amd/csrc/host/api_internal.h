@@ -217,6 +217,7 @@ struct RenderBase {
     // destroyed as they complete, so a long progressive session holds a bounded number of events)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double kernel_ms = 0.0;
+    PtVariant variant{};  // which instantiation of the pt kernel the session runs (session_params; kernels.h)
     PtParams params;  // the session's constant block (session_params); a launch sets n_passes / last_pass_spp (set_launch_passes)
     bool holds_scene = false;  // counted in scene->sessions (base_begin)
     void fold_events(bool all) {  // all: the stream has been synchronised
@@ -319,6 +320,23 @@ inline void set_launch_passes(RenderBase* se, uint32_t n_passes, uint32_t last_p
     se->params.n_passes = n_passes;
     se->params.last_pass_spp = last_pass_spp;
 }
+// Which kernel a pt session of (scene, config) runs and which tables it stages in LDS: the ONE place that decides it, from the compiled scene,
+// the config and the options a session snapshots -- never from device pointers, so it answers for a host-only scene too (akr_host_pt_launch_plan).
+struct PtPlan {
+    PtVariant v;
+    uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
+    uint32_t stage_bytes[13], stage_total, tex_slots;
+};
+PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves);
+// the part of the variant that is a fact of the scene and the config: bvh, fd, tex, pmj, inst, env, lens
+PtVariant pt_scene_facts(const akr_scene* s, const akr_pt_config& c);
+// DScene.bvh_stack_depth / n_nodes of a compiled scene (scene_finish fills them in; a host-only scene has no DScene)
+inline uint32_t scene_stack_depth(const CompiledScene& cs) {
+    // one pending group per tree level at most (disect.h); a kept scene: two levels + the three words that remember the TLAS position
+    // (dinst_trav.h; scene_inst.cpp checked the bound)
+    return cs.instanced.on ? cs.bvh_depth : std::max(1u, std::min(cs.bvh_depth, kBvhStackDepth));
+}
+inline uint32_t scene_n_nodes(const CompiledScene& cs) { return (uint32_t)((cs.instanced.on ? cs.instanced.nodes.size() : cs.bvh_nodes.size()) / kBvhNodeWords); }
 // the camera part of a parameter block: r2c, c2w, c2w_identity, width, height, filter, lens
 void camera_params(PtParams& p, const akr_scene* s, uint32_t filter_type, float filter_radius);
 // Ends a session after `rc`, the status of what ran in it: the first error and its message are what the caller sees.

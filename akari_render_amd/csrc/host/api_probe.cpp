@@ -234,6 +234,33 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_t
     }
     return AKR_OK;
 }
+// What akr_pt_begin decides for (scene, config), without a session or a device: the variant and the staged tables (pt_plan), the per-scene
+// kernel's wrapper text, and the LDS layout a launch of the whole frame would get (launch_pt_pass: pt_lds_layout)
+AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves,
+                                             akr_pt_launch_plan* out) {
+    if (!scene || !cfg || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_pt_launch_plan: NULL argument");
+    return guarded([&] {
+        const CompiledScene& cs = scene->cs;
+        const bool spec = spec_waves != 0 && cs.has_textures && !cfg->force_diffuse;  // (where akr_pt_begin asks for a per-scene kernel)
+        const PtPlan pl = pt_plan(scene, *cfg, defer_metal, simple_kernels, defer_on, spec, spec ? spec_waves : 3);
+        const PtVariant& v = pl.v;
+        const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, pl.stage_total, cfg->sampler_type == AKR_SAMPLER_PMJ02BN};
+        const PtLdsLayout L = pt_lds_layout(v, sizes);
+        const TileGrid grid = tile_grid(cfg->tile_w, cfg->tile_h, scene->flat.camera.width, scene->flat.camera.height, cfg->shard_rank, cfg->shard_count);
+        std::memset(out, 0, sizeof *out);
+        const bool flags[10] = {v.bvh, v.fd, v.tex, v.pmj, v.stage, v.defer, v.simple, v.inst, v.env, v.lens};
+        for (int i = 0; i < 10; i++) out->variant[i] = flags[i] ? 1u : 0u;
+        out->simple_scene = pl.simple_scene; out->defer_metal = pl.defer_metal; out->defer_flags = pl.defer_flags;
+        std::memcpy(out->stage_bytes, pl.stage_bytes, sizeof out->stage_bytes);
+        out->stage_total = pl.stage_total;
+        out->tile_offset = L.tile_offset; out->bvh_tile_nodes = L.tile_nodes; out->park_offset = L.park_offset; out->carry_offset = L.carry_offset;
+        out->bn_offset = L.bn_offset; out->val_offset_words = L.val_offset_words;
+        out->lds_bytes = (uint32_t)L.total_bytes;
+        out->blocks = (grid.n_items + 255u) / 256u;
+        out->specialised = spec ? 1u : 0u;
+        if (spec) std::snprintf(out->wrapper, sizeof out->wrapper, "%s", spec_wrapper_source(v, spec_waves).c_str());
+    });
+}
 AKR_TEST_API int32_t akr_probe_camera_rays(akr_context* ctx, akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2,
                                       const float* u4, float* out6) {
     if (!ctx || !scene || !pixels2 || !u4 || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_camera_rays: NULL argument");

@@ -12,12 +12,94 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
     p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
     p.lens_focal = s->flat.lens.focal_distance;
 }
+PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
+    const CompiledScene& cs = s->cs;  // (stage, defer, simple: pt_plan)
+    return PtVariant{cs.has_tree(), c.force_diffuse != 0, cs.has_textures, c.sampler_type != AKR_SAMPLER_INDEPENDENT, false, false, false,
+                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f};
+}
+PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves) {
+    const CompiledScene& cs = s->cs;
+    PtPlan pl{};
+    PtVariant& v = pl.v = pt_scene_facts(s, c);
+    // The exclusion rules, applied here and nowhere else (kernels.h pt_variant_compiled states them): no DEFER and no SIMPLE kernels with an
+    // environment light or a lens; a kept scene has neither, and its kernels stage no tables.
+    const bool plain = !v.env && !v.lens;
+    {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
+        // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
+        // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
+        bool simple = !cs.has_textures;
+        for (const DMaterial& m : cs.materials) {
+            if (m.kind == MAT_GLASS) simple = false;
+            if (m.kind == MAT_PRINCIPLED && ((m.flags & (MF_COAT | MF_EVAL_DIEL | MF_NORMAL_MAP)) != 0 || m.transmission != 0.0f || m.coat_weight != 0.0f)) simple = false;
+        }
+        pl.simple_scene = (simple && simple_kernels_option && plain) ? 1u : 0u;
+        v.simple = pl.simple_scene != 0 && !v.fd && !v.tex && !v.inst;  // (full-graph kernels of scenes without textures)
+    }
+    {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
+        // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
+        // instead a shader graph to evaluate at the hit.
+        uint32_t flags = MF_EVAL_METAL;
+        // (measured on the textured room, BVH kernel: conductor hits deferred 591 Msamples/s, textured hits 573, both 573, none 544)
+        if (v.bvh && v.tex) flags = defer_on_option == 2 ? MF_TEXTURED : (defer_on_option == 3 ? (MF_EVAL_METAL | MF_TEXTURED) : MF_EVAL_METAL);
+        size_t n_dear = 0, n_surface = 0;
+        for (const DMaterial& m : cs.materials) {
+            if (m.kind == MAT_EMISSION) continue;
+            n_surface++;
+            if (m.flags & flags) n_dear++;  // the kernel's own test (pt_pass.h: DEFER), whatever the material's kind
+        }
+        bool want = n_dear > 0 && 2 * n_dear <= n_surface;
+        uint32_t mask = 1u;  // iterations with (iteration & mask) != 0 put those hits off
+        if (defer_metal_option >= 0) { mask = (uint32_t)defer_metal_option; want = mask != 0; }  // akr_option_set("defer_metal"): measurements / tests
+        // (full-graph kernels, of BVH scenes those with textures)
+        pl.defer_metal = (want && (!v.bvh || v.tex) && !v.fd && !v.inst && plain) ? mask : 0u;
+        pl.defer_flags = flags;
+        v.defer = pl.defer_metal != 0;
+    }
+    {   // LDS staging of the tables the shading phase gathers from (device/pt_pass.h: STAGE)
+        // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
+        // BVH path: the per-scene tables only, if the launch still fits its share of the CU's LDS with them (kernels.h pt_lds_layout)
+        const bool bvh = v.bvh;
+        size_t bytes[13] = {bvh ? 0 : cs.shade.size() * 4, bvh ? 0 : cs.normals.size() * 4, cs.inst.size() * 4, cs.materials.size() * sizeof(DMaterial),
+                            (size_t)cs.n_lights * sizeof(AliasPacked), cs.area_entries.size() * sizeof(AliasPacked), (size_t)cs.n_lights * sizeof(LightRec),
+                            cs.light_pdf.size() * 4, cs.area_pdf.size() * 4, 0, 0, 0, 0};
+        if (cs.has_textures) {  // the node lists have the same size in every colour pipeline
+            bytes[9] = cs.tex_nodes.size() * sizeof(DNode);
+            bytes[10] = cs.images.size() * sizeof(DImage);
+            bytes[11] = cs.mat_inputs.size() * sizeof(MatInputs);
+        }
+        size_t total = 0;
+        for (int i = 0; i < 12; i++) total += (bytes[i] + 15) & ~(size_t)15;
+        pl.tex_slots = (cs.has_textures && !spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
+        // the workgroup's share: a per-scene kernel built for four waves per SIMD has a quarter of the CU's LDS whatever the scene
+        const size_t budget = pt_lds_budget(v.tex && !(spec_active && spec_waves >= 4));
+        auto fits = [&](size_t staged) {  // (the blue-noise columns and the node tile only take what is left: not part of the question)
+            const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, (uint32_t)staged, false};
+            return pt_lds_layout(v, sizes, /*plan_larger_park=*/true).required_bytes <= budget;
+        };
+        // all of it or nothing (a TEX kernel reads its tables through LDS addresses); the kept-scene kernels do not stage
+        const bool may = !v.inst && total <= (bvh ? kStageMaxBytesBvh : kStageMaxBytes);
+        // the albedo table as well for the full-graph exhaustive kernel of a textured scene (stage_scene_tables: GGX), if three
+        // workgroups per CU still fit (AKR_PT_MIN_WAVES_TEX = 3: 160 KB / 3)
+        const size_t ggx_bytes = 4096 * sizeof(float);
+        if (may && !bvh && v.tex && !v.fd && fits(total + ggx_bytes)) {
+            bytes[12] = ggx_bytes;
+            total += ggx_bytes;
+            v.stage = true;
+        } else {
+            v.stage = may && (!bvh || fits(total));
+        }
+        if (v.stage) {
+            for (int i = 0; i < 13; i++) pl.stage_bytes[i] = (uint32_t)bytes[i];
+            pl.stage_total = (uint32_t)std::max<size_t>(total, 16);
+        }
+    }
+    if (!pt_variant_compiled(v)) throw RenderError("pt_plan: no kernel for the variant decided");  // (cannot happen: the rules above are pt_variant_compiled's)
+    return pl;
+}
 void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, bool wf_sort) {
     PtParams& p = se->params;
     const akr_scene* s = se->scene;
     const akr_pt_config& c = se->cfg;
-    const CompiledScene& cs = s->cs;
-    const bool bvh = cs.has_tree();
     std::memset(&p, 0, sizeof p);
     p.sc = s->dscene;
     camera_params(p, s, c.filter_type, c.filter_radius);
@@ -58,67 +140,15 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, b
             p.bluenoise = se->ctx->bluenoise.as<uint16_t>();
         }
     }
-    {  // LDS staging of the tables the shading phase gathers from (device/pt_pass.h: STAGE)
-        // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
-        // BVH path: the per-scene tables only, if they fit beside the traversal stacks
-        size_t bytes[13] = {bvh ? 0 : cs.shade.size() * 4, bvh ? 0 : cs.normals.size() * 4, cs.inst.size() * 4, cs.materials.size() * sizeof(DMaterial),
-                            (size_t)cs.n_lights * sizeof(AliasPacked), cs.area_entries.size() * sizeof(AliasPacked), (size_t)cs.n_lights * sizeof(LightRec),
-                            cs.light_pdf.size() * 4, cs.area_pdf.size() * 4, 0, 0, 0, 0};
-        if (cs.has_textures) {  // the node lists have the same size in every colour pipeline
-            bytes[9] = cs.tex_nodes.size() * sizeof(DNode);
-            bytes[10] = cs.images.size() * sizeof(DImage);
-            bytes[11] = cs.mat_inputs.size() * sizeof(MatInputs);
-        }
-        size_t total = 0;
-        for (int i = 0; i < 12; i++) total += (bytes[i] + 15) & ~(size_t)15;
-        std::memset(p.stage_bytes, 0, sizeof p.stage_bytes);
-        p.stage_total = 0;
-        p.tex_slots = (cs.has_textures && !spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
-        // one workgroup's dynamic LDS stays within 64 KB: traversal stacks + staged tables + the graph evaluation's value slots
-        // what the launch keeps in LDS besides the staged tables: traversal stacks, graph values, and the columns / records of pt_lds_plan
-        const PtLdsPlan plan = pt_lds_plan(bvh, c.force_diffuse != 0, cs.has_textures, /*defer: the larger park block*/ true, cs.n_tris);
-        const size_t other = (bvh ? (size_t)p.sc.bvh_stack_depth * 256 * 4 : 0) + (size_t)p.tex_slots * kTexValStride * sizeof(TexVal) + plan.recs_bytes +
-                             plan.park_bytes + plan.carry_bytes;
-        const size_t lds_budget = (spec_active && spec_waves >= 4) ? pt_lds_budget(false) : pt_lds_budget(cs.has_textures);
-        if (!cs.instanced.on && total <= (bvh ? kStageMaxBytesBvh : kStageMaxBytes) && (!bvh || other + total <= lds_budget)) {  // (the instanced-scene kernels do not stage)  // all of it or nothing (a TEX kernel reads its tables through LDS addresses)
-            // the albedo table as well for the full-graph exhaustive kernel of a textured scene (stage_scene_tables: GGX), if three
-            // workgroups per CU still fit (AKR_PT_MIN_WAVES_TEX = 3: 160 KB / 3)
-            const size_t ggx_bytes = 4096 * sizeof(float);
-            if (!bvh && cs.has_textures && !c.force_diffuse && other + total + ggx_bytes <= lds_budget) {
-                bytes[12] = ggx_bytes;
-                total += ggx_bytes;
-            }
-            for (int i = 0; i < 13; i++) p.stage_bytes[i] = (uint32_t)bytes[i];
-            p.stage_total = (uint32_t)std::max<size_t>(total, 16);
-        }
-    }
-    {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
-        // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
-        // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
-        bool simple = !cs.has_textures;
-        for (const DMaterial& m : cs.materials) {
-            if (m.kind == MAT_GLASS) simple = false;
-            if (m.kind == MAT_PRINCIPLED && ((m.flags & (MF_COAT | MF_EVAL_DIEL | MF_NORMAL_MAP)) != 0 || m.transmission != 0.0f || m.coat_weight != 0.0f)) simple = false;
-        }
-        p.simple_scene = (simple && se->simple_kernels_option && !cs.env.on && s->flat.lens.radius == 0.0f) ? 1u : 0u;  // (no SIMPLE kernels with an environment light or a lens)
-    }
-    {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
-        // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
-        // instead a shader graph to evaluate at the hit.
-        uint32_t flags = MF_EVAL_METAL;
-        // (measured on the textured room, BVH kernel: conductor hits deferred 591 Msamples/s, textured hits 573, both 573, none 544)
-        if (bvh && cs.has_textures) flags = se->defer_on_option == 2 ? MF_TEXTURED : (se->defer_on_option == 3 ? (MF_EVAL_METAL | MF_TEXTURED) : MF_EVAL_METAL);
-        size_t n_dear = 0, n_surface = 0;
-        for (const DMaterial& m : cs.materials) {
-            if (m.kind == MAT_EMISSION) continue;
-            n_surface++;
-            if (m.flags & flags) n_dear++;  // the kernel's own test (pt_pass.h: DEFER), whatever the material's kind
-        }
-        bool want = n_dear > 0 && 2 * n_dear <= n_surface;
-        uint32_t mask = 1u;  // iterations with (iteration & mask) != 0 put those hits off
-        if (se->defer_metal_option >= 0) { mask = (uint32_t)se->defer_metal_option; want = mask != 0; }  // akr_option_set("defer_metal"): measurements / tests
-        p.defer_metal = (want && (!bvh || cs.has_textures) && !c.force_diffuse && !cs.instanced.on && !cs.env.on && s->flat.lens.radius == 0.0f) ? mask : 0u;  // (nor DEFER ones)
-        p.defer_flags = flags;
+    {   // which kernel, which tables staged in LDS: decided from the scene and the config (pt_plan), kept with the session
+        const PtPlan plan = pt_plan(s, c, se->defer_metal_option, se->simple_kernels_option, se->defer_on_option, spec_active, spec_waves);
+        se->variant = plan.v;
+        std::memcpy(p.stage_bytes, plan.stage_bytes, sizeof p.stage_bytes);
+        p.stage_total = plan.stage_total;
+        p.tex_slots = plan.tex_slots;
+        p.simple_scene = plan.simple_scene;
+        p.defer_metal = plan.defer_metal;
+        p.defer_flags = plan.defer_flags;
     }
     p.wf_sort = wf_sort ? 1u : 0u;
     for (int a = 0; a < 3; a++) {  // the sort key's grid: 128 cells per axis over the scene's box
@@ -495,8 +525,6 @@ int32_t akr_api::render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_c
         *out = se.release();
     });
 }
-// pt_kernels_relaxed.hip: launch_pt_pass of the relaxed arithmetic tier (its PtParams is this one, in another namespace)
-extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, hipStream_t stream);
 extern "C" {
 AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out) {
     if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: NULL argument");
@@ -517,10 +545,12 @@ AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_co
             const bool may_compile = t.specialise == 1 || samples >= kSpecAutoSamples;
             // The relaxed arithmetic tier (pt_kernels_relaxed.hip): the precompiled megakernels of flattened scenes. Everything else --
             // kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
-            se->arith_relaxed = t.arith == 1 && !scene->cs.instanced.on && !wavefront;
-            if (se->arith_relaxed && scene->cs.env.on)
+            // Which sessions it takes is decided here and nowhere else: its translation unit holds the variants without inst, env and lens.
+            const PtVariant facts = pt_scene_facts(scene, *cfg);
+            se->arith_relaxed = t.arith == 1 && !facts.inst && !wavefront;
+            if (se->arith_relaxed && facts.env)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
-            if (se->arith_relaxed && scene->flat.lens.radius > 0.0f)
+            if (se->arith_relaxed && facts.lens)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)");
             if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
             else if (wavefront) se->spec_status = "wavefront schedule";
@@ -539,17 +569,8 @@ AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_co
                 se->spec_active = true;
             }
             session_params(se.get(), se->spec_active, se->spec_waves, wf_sort);
-            if (se->spec_active) {  // which instantiation the session's launches use: as the block for a per-scene kernel says
-                SpecRequest rq;
-                rq.bvh = scene->cs.has_tree();
-                rq.inst = scene->cs.instanced.on;
-                rq.pmj = se->params.sampler != 0;
-                rq.stage = se->params.stage_total != 0;
-                rq.defer = se->params.defer_metal != 0;
-                rq.env = scene->cs.env.on;
-                rq.lens = scene->flat.lens.radius > 0.0f;
-                rq.min_waves = se->spec_waves;
-                se->spec = ctx->spec_cache.get(scene->spec_header, rq, ctx->props.gcnArchName, may_compile);
+            if (se->spec_active) {  // the session's variant, compiled with the scene's graphs
+                se->spec = ctx->spec_cache.get(scene->spec_header, se->variant, se->spec_waves, ctx->props.gcnArchName, may_compile);
                 se->spec_status = se->spec->status;
                 if (!se->spec->fn) {  // the interpreter kernel renders the same film: with graph value slots in LDS and its own LDS budget
                     se->spec_active = false;
@@ -594,8 +615,7 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             set_launch_passes(se, fused, last);
             LaunchTimer timer(se);
             if (se->wf) wf_run(se);
-            else if (se->arith_relaxed) HIP_CHECK(akr_launch_pt_pass_relaxed(&se->params, se->ctx->stream));
-            else HIP_CHECK(launch_pt_pass(se->params, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr));
+            else HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr, se->arith_relaxed));
             timer.stop();
             se->spp_done = done;
             se->n_launches++;
@@ -684,8 +704,8 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         info->struct_size = size;
         info->specialised = se->spec_active ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
-        info->kernel_flags = (se->scene->cs.bvh_nodes.empty() ? 0u : 1u) | (se->params.sampler != 0 ? 2u : 0u) | (se->params.stage_total != 0 ? 4u : 0u) |
-                             (se->params.defer_metal != 0 ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (se->scene->flat.lens.radius > 0.0f ? 32u : 0u);
+        const PtVariant& v = se->variant;  // (bit 0: the flattened scene's tree; a kept scene's two-level traversal does not set it)
+        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;

@@ -210,11 +210,10 @@ void akr_api::scene_finish(akr_scene* s) {
     upload_lights(s);  // light tables, environment
     d.bvh_nodes = s->bvh_nodes.as<uint4>();
     d.n_tris = cs.n_tris;
-    d.n_nodes = (uint32_t)((cs.instanced.on ? cs.instanced.nodes.size() : cs.bvh_nodes.size()) / kBvhNodeWords);
+    d.n_nodes = scene_n_nodes(cs);
     d.has_alpha = cs.has_alpha ? 1u : 0u;
-    d.bvh_stack_depth = std::max(1u, std::min(cs.bvh_depth, kBvhStackDepth));  // one pending group per tree level at most (disect.h)
-    if (cs.instanced.on) {  // two levels + the three words that remember the TLAS position (dinst_trav.h); scene_inst.cpp checked the bound
-        d.bvh_stack_depth = cs.bvh_depth;
+    d.bvh_stack_depth = scene_stack_depth(cs);
+    if (cs.instanced.on) {
         d.in2.tlas_leaves = s->in2_tlas_leaves.as<uint4>();
         d.in2.mesh_tris = s->in2_mesh_tris.as<float4>();
         d.in2.mesh_pos = s->in2_mesh_pos.as<uint32_t>();
@@ -513,12 +512,11 @@ AKR_API int32_t akr_host_spec_compile(akr_scene* scene, uint32_t flags, uint32_t
             header = scene->spec_header;
         }
         if (header.empty()) throw Unsupported("unsupported: the scene has no per-scene code (no texture-fed material, or too many shader kinds)");
-        SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u; rq.lens = flags & 64u;
-        rq.min_waves = (int)min_waves;
+        const PtVariant v = pt_variant_from_bits(flags);
+        if (!pt_variant_compiled(v)) throw std::invalid_argument("per-scene kernel: the flags name a variant that does not exist (kernels.h pt_variant_compiled)");
         std::vector<char> code;
         std::string text;
-        const bool ok = spec_compile(header, rq, arch && *arch ? arch : "gfx950", code, text);
+        const bool ok = spec_compile(header, v, (int)min_waves, arch && *arch ? arch : "gfx950", code, text);
         if (log && log_len) std::snprintf(log, log_len, "%s", text.c_str());
         if (!ok) throw RenderError("per-scene kernel did not compile: " + text.substr(0, 1500));
         *code_bytes = code.size();
@@ -528,12 +526,11 @@ AKR_API int32_t akr_host_spec_compile(akr_scene* scene, uint32_t flags, uint32_t
 AKR_API int32_t akr_host_spec_compile_text(const char* spec_header, uint32_t flags, uint32_t min_waves, const char* arch, const char* out_path) {
     if (!spec_header || !arch || !out_path) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_spec_compile_text: NULL argument");
     return guarded([&] {
-        SpecRequest rq;
-        rq.bvh = flags & 1u; rq.pmj = flags & 2u; rq.stage = flags & 4u; rq.defer = flags & 8u; rq.inst = flags & 16u; rq.env = flags & 32u; rq.lens = flags & 64u;
-        rq.min_waves = (int)min_waves;
+        const PtVariant v = pt_variant_from_bits(flags);
+        if (!pt_variant_compiled(v)) throw std::invalid_argument("per-scene kernel: the flags name a variant that does not exist (kernels.h pt_variant_compiled)");
         std::vector<char> code;
         std::string log;
-        if (!spec_compile(spec_header, rq, arch, code, log, /*in_process=*/true)) throw RenderError("per-scene kernel did not compile: " + log.substr(0, 3000));
+        if (!spec_compile(spec_header, v, (int)min_waves, arch, code, log, /*in_process=*/true)) throw RenderError("per-scene kernel did not compile: " + log.substr(0, 3000));
         FILE* f = std::fopen(out_path, "wb");
         if (!f) throw IoError(std::string("cannot open ") + out_path);
         const size_t n = std::fwrite(code.data(), 1, code.size(), f);

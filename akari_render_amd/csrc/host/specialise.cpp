@@ -264,14 +264,16 @@ Rtc& rtc() {
     return r;
 }
 
-std::string wrapper_source(const SpecRequest& rq) {
+}  // namespace
+std::string spec_wrapper_source(const PtVariant& v, int min_waves) {
+    auto b = [](bool x) { return x ? "true" : "false"; };
+    // (ENV and LENS are trailing template arguments with defaults: named only from the first that is set, as the texts of earlier versions were)
     return fmt("// per-scene instantiation of k_pt_pass (host/specialise.cpp)\n#define AKR_SPEC_GRAPHS 1\n#include \"device/pt_pass.h\"\n"
                "extern \"C\" __global__ __launch_bounds__(256, %d) void akr_pt_pass_spec(const akr::PtParams p) {\n"
                "    akr::pt_pass_body<%s, false, true, %s, %s, %s, akr::kSpecAbsent, %s%s%s>(p);\n}\n",
-               rq.min_waves, (rq.bvh || rq.inst) ? "true" : "false", rq.pmj ? "true" : "false", (rq.stage && !rq.inst) ? "true" : "false",
-               (rq.defer && !rq.inst && !rq.env && !rq.lens) ? "true" : "false", rq.inst ? "true" : "false", (rq.env || rq.lens) ? (rq.env ? ", true" : ", false") : "",
-               rq.lens ? ", true" : "");
+               min_waves, b(v.bvh), b(v.pmj), b(v.stage), b(v.defer), b(v.inst), (v.env || v.lens) ? (v.env ? ", true" : ", false") : "", v.lens ? ", true" : "");
 }
+namespace {
 std::vector<std::string> compile_options(const std::string& arch) {
     std::vector<std::string> o;
     o.push_back("--offload-arch=" + arch);
@@ -279,7 +281,7 @@ std::vector<std::string> compile_options(const std::string& arch) {
     const char* const* f = embedded_compile_flags(&n);
     for (size_t i = 0; i < n; i++) o.push_back(f[i]);
     // AKR_SPEC_EXTRA_FLAGS: A/B switches of the device code for measurements (-DAKR_...=...), part of the cache key. Only switches
-    // that leave the launch's LDS layout alone are safe here: the host plans the layout from the library's own build (kernels.h).
+    // that leave the launch's LDS layout alone are safe here: the layout is kernels.h pt_lds_layout's, from the library's own build.
     if (const char* e = std::getenv("AKR_SPEC_EXTRA_FLAGS")) {
         std::istringstream ss(e);
         std::string w;
@@ -304,11 +306,11 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 }  // namespace
 
-std::string spec_cache_key(const std::string& spec_header, const SpecRequest& rq, const std::string& arch) {
+std::string spec_cache_key(const std::string& spec_header, const PtVariant& v, int min_waves, const std::string& arch) {
     uint64_t h = 0xcbf29ce484222325ull;
     h = fnv1a(h, std::string(embedded_sources_hash()));
     h = fnv1a(h, spec_header);
-    h = fnv1a(h, wrapper_source(rq));
+    h = fnv1a(h, spec_wrapper_source(v, min_waves));
     for (const std::string& o : compile_options(arch)) h = fnv1a(h, o);
     int major = 0, minor = 0;
     if (rtc().ok && rtc().Version) (void)rtc().Version(&major, &minor);
@@ -349,7 +351,7 @@ std::string helper_path() {
     p = (slash == std::string::npos ? std::string(".") : p.substr(0, slash)) + "/akari-cli";
     return access(p.c_str(), X_OK) == 0 ? p : std::string();
 }
-bool compile_in_helper(const std::string& helper, const std::string& spec_header, const SpecRequest& rq, const std::string& arch, std::vector<char>& code, std::string& log) {
+bool compile_in_helper(const std::string& helper, const std::string& spec_header, const PtVariant& v, int min_waves, const std::string& arch, std::vector<char>& code, std::string& log) {
     char dir[] = "/tmp/akr_spec_XXXXXX";
     if (!mkdtemp(dir)) return false;
     const std::string hdr = std::string(dir) + "/akr_scene_spec.h", out = std::string(dir) + "/k.co", err = std::string(dir) + "/err.txt";
@@ -358,7 +360,7 @@ bool compile_in_helper(const std::string& helper, const std::string& spec_header
         std::ofstream f(hdr, std::ios::binary);
         f.write(spec_header.data(), (std::streamsize)spec_header.size());
     }
-    const std::string flags = std::to_string((rq.bvh ? 1 : 0) | (rq.pmj ? 2 : 0) | (rq.stage ? 4 : 0) | (rq.defer ? 8 : 0) | (rq.inst ? 16 : 0) | (rq.env ? 32 : 0) | (rq.lens ? 64 : 0)), waves = std::to_string(rq.min_waves);
+    const std::string flags = std::to_string(pt_variant_bits(v)), waves = std::to_string(min_waves);
     // posix_spawn, not fork + setup code: the host process has threads (HIP runtime, the application's own)
     std::vector<std::string> env_store;
     for (char** e = environ; e && *e; e++)
@@ -392,10 +394,10 @@ bool compile_in_helper(const std::string& helper, const std::string& spec_header
 }
 }  // namespace
 
-bool spec_compile(const std::string& spec_header, const SpecRequest& rq, const std::string& arch, std::vector<char>& code, std::string& log, bool in_process) {
+bool spec_compile(const std::string& spec_header, const PtVariant& v, int min_waves, const std::string& arch, std::vector<char>& code, std::string& log, bool in_process) {
     if (!in_process && !std::getenv("AKR_SPEC_INPROCESS")) {
         const std::string helper = helper_path();
-        if (!helper.empty() && compile_in_helper(helper, spec_header, rq, arch, code, log)) return true;
+        if (!helper.empty() && compile_in_helper(helper, spec_header, v, min_waves, arch, code, log)) return true;
         code.clear();  // no helper, or it failed: this process's hiprtc
     }
     Rtc& r = rtc();
@@ -412,7 +414,7 @@ bool spec_compile(const std::string& spec_header, const SpecRequest& rq, const s
     }
     texts.push_back(spec_header.c_str());
     names.push_back("akr_scene_spec.h");
-    const std::string wrapper = wrapper_source(rq);
+    const std::string wrapper = spec_wrapper_source(v, min_waves);
     void* prog = nullptr;
     int rc = r.CreateProgram(&prog, wrapper.c_str(), "akr_pt_pass_spec.hip", (int)texts.size(), texts.data(), names.data());
     if (rc != 0) {
@@ -447,9 +449,9 @@ SpecKernel::~SpecKernel() {
     if (module) (void)hipModuleUnload(module);
 }
 
-std::shared_ptr<SpecKernel> SpecCache::get(const std::string& spec_header, const SpecRequest& rq, const std::string& arch, bool may_compile) {
+std::shared_ptr<SpecKernel> SpecCache::get(const std::string& spec_header, const PtVariant& v, int min_waves, const std::string& arch, bool may_compile) {
     std::lock_guard<std::mutex> lock(mutex_);
-    const std::string key = spec_cache_key(spec_header, rq, arch);
+    const std::string key = spec_cache_key(spec_header, v, min_waves, arch);
     auto it = loaded_.find(key);
     if (it != loaded_.end()) {
         // a second session of this process on the same kernel: nothing to compile or load
@@ -484,7 +486,7 @@ std::shared_ptr<SpecKernel> SpecCache::get(const std::string& spec_header, const
     if (code.empty()) {
         std::string log;
         const double c0 = now_ms();
-        if (!spec_compile(spec_header, rq, arch, code, log)) {
+        if (!spec_compile(spec_header, v, min_waves, arch, code, log)) {
             k->status = log.substr(0, 2000);
             return k;
         }
@@ -507,7 +509,7 @@ std::shared_ptr<SpecKernel> SpecCache::get(const std::string& spec_header, const
         std::string log;
         const double c0 = now_ms();
         code.clear();
-        if (!spec_compile(spec_header, rq, arch, code, log)) {
+        if (!spec_compile(spec_header, v, min_waves, arch, code, log)) {
             k->status = log.substr(0, 2000);
             return k;
         }

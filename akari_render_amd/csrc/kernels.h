@@ -7,6 +7,43 @@
 #include "device/drng.h"
 #include "device/dscene.h"
 
+#if !defined(__HIPCC_RTC__)
+#include <algorithm>
+// Which instantiation of pt_pass_body (device/pt_pass.h) a pt session runs, decided once per session (host/api_pt.cpp pt_decide) and
+// carried by the session; the launchers, the per-scene kernel's wrapper text and akr_pt_kernel_info all read it. Host side only, and
+// outside the namespace: the relaxed tier's translation unit compiles this header inside another one (pt_kernels_relaxed.hip).
+struct PtVariant {
+    bool bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens;
+};
+// The combinations that exist as precompiled kernels -- the one statement of the exclusion rules: the exhaustive kernels always stage;
+// DEFER only in full-graph kernels, of BVH scenes those with textures; SIMPLE only in full-graph kernels of scenes without textures;
+// neither with an environment light or a lens; a kept scene runs the BVH kernel without staged tables, DEFER or SIMPLE.
+constexpr bool pt_variant_compiled(const PtVariant& v) {
+    return (v.bvh || v.stage) && !(v.defer && (v.fd || (v.bvh && !v.tex))) && !(v.simple && (v.fd || v.tex)) && !((v.env || v.lens) && (v.defer || v.simple)) &&
+           !(v.inst && !(v.bvh && !v.stage && !v.defer && !v.simple));
+}
+// The flags of a per-scene kernel request as one integer: akr_host_spec_compile(_text), the helper process's command line (fd = false,
+// tex = true, no SIMPLE: a per-scene kernel is the full-graph kernel of a scene with textures).
+constexpr uint32_t pt_variant_bits(const PtVariant& v) {
+    return (v.bvh ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (v.inst ? 16u : 0u) | (v.env ? 32u : 0u) | (v.lens ? 64u : 0u);
+}
+constexpr PtVariant pt_variant_from_bits(uint32_t f) {
+    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0};
+}
+// pt_lds_layout (below): what it is given ...
+struct PtLdsSizes {
+    uint32_t stack_depth, n_tris, n_nodes;  // DScene.bvh_stack_depth, n_tris, n_nodes
+    uint32_t tex_slots;                     // graph value slots per lane (0: a per-scene kernel keeps them in registers)
+    uint32_t stage_bytes;                   // PtParams.stage_total
+    bool bluenoise;                         // the pmj02bn sampler's blue-noise table is there to be staged
+};
+// ... and what it answers: word offsets of the blocks, the node count of the tile, bytes
+struct PtLdsLayout {
+    uint32_t stage_offset, recs_offset, tile_offset, tile_nodes, park_offset, carry_offset, bn_offset, val_offset_words;
+    size_t required_bytes, total_bytes;  // without / with the blocks that only take what room is left (node tile, blue-noise columns)
+};
+#endif
+
 namespace akr {
 
 // ---- build switches of k_pt_pass (device/pt_pass.h); each default is the winner of a same-box A/B run ----
@@ -26,26 +63,52 @@ constexpr uint32_t kParkSlots = 16, kParkSlotsNoDefer = 13;  // dpath.h: PK_*
 constexpr uint32_t kCarrySlots = 13;                         // device/pt_pass.h: a carried traversal
 constexpr uint32_t kCarrySlotsInstanced = 16;                // ... of a scene kept as meshes + instances (dinst_trav.h)
 constexpr size_t kBlueNoiseColumnBytes = 48 * 256 * 2;          // dpath.h pmj_bluenoise_stage: one u16 per array and lane
-// What a k_pt_pass launch keeps in LDS beyond traversal stacks, staged tables and graph values, by kernel instantiation
-// (BVH / force_diffuse / textured scene / conductor deferral): used by the launcher and by the host's staging decision.
-// The exhaustive kernels keep the triangle records there (disect.h trace_pair_exhaustive), the full-graph kernels of scenes with
-// textures park cold path state (dpath.h: PARK), the BVH kernels of scenes without textures keep the top of the tree (disect.h: TILE).
-struct PtLdsPlan {
-    size_t recs_bytes, park_bytes, carry_bytes;
-    bool tile;
-};
-inline PtLdsPlan pt_lds_plan(bool bvh, bool fd, bool tex, bool defer, uint32_t n_tris) {
-    PtLdsPlan pl;
-    const bool park = !fd && tex;
-    const bool strag = bvh && (tex ? AKR_PT_STRAGGLERS_TEX : AKR_PT_STRAGGLERS) > 0;
-    pl.recs_bytes = !bvh ? (size_t)(n_tris + 2) * 48 : 0;
-    pl.park_bytes = park ? (size_t)(defer ? kParkSlots : kParkSlotsNoDefer) * 256 * 4 : 0;
-    pl.carry_bytes = strag ? (size_t)kCarrySlots * 256 * 4 : 0;
-    pl.tile = bvh && !tex;
-    return pl;
-}
+#if !defined(__HIPCC_RTC__)
+// Dynamic LDS of a pt launch (k_pt_pass, k_pt_pass_inst, a per-scene kernel) and where its blocks start, in this order:
+// [traversal stacks][staged tables][triangle records (exhaustive kernels: disect.h trace_pair_exhaustive)][node tile (BVH kernels of scenes
+// without textures: disect.h TILE)][park columns (full-graph kernels of scenes with textures: dpath.h PARK)][carry columns (BVH kernels that
+// let a wave's longest rays run on: device/pt_pass.h)][blue-noise columns (pmj02bn, exhaustive kernels)][graph values]. The tile and the
+// blue-noise columns take what room is left; `required_bytes` is the rest. The ONE place that lays a launch out: launch_pt_pass places
+// the blocks with it, and session_params (host/api_pt.cpp) decides the staging by asking it whether the launch fits.
 // a workgroup's share of the CU's 160 KB: a quarter (four waves per SIMD), a third for the kernels of textured scenes (three)
 inline size_t pt_lds_budget(bool tex) { return (tex ? 53 : 40) * 1024; }
+// plan_larger_park: size the park block for a DEFER kernel whatever the variant says. The staging decision has always planned that way; a
+// textured full-graph launch without deferral whose required bytes come within 3 * 1024 of the budget is therefore refused staging
+// that would fit. (Kept as it is: granting it changes which kernel such a scene runs.)
+inline PtLdsLayout pt_lds_layout(const PtVariant& v, const PtLdsSizes& s, bool plan_larger_park = false) {
+    PtLdsLayout L{};
+    const size_t slots = v.tex ? (size_t)s.tex_slots * kTexValStride * sizeof(TexVal) : 0;
+    const int stragglers = v.inst ? AKR_PT_STRAGGLERS_INST : (v.tex ? AKR_PT_STRAGGLERS_TEX : AKR_PT_STRAGGLERS);
+    const size_t park = (!v.fd && v.tex) ? (size_t)(v.defer || plan_larger_park ? kParkSlots : kParkSlotsNoDefer) * 256 * 4 : 0;
+    const size_t carry = (v.bvh && stragglers > 0) ? (size_t)(v.inst ? kCarrySlotsInstanced : kCarrySlots) * 256 * 4 : 0;
+    auto align = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    size_t base = v.bvh ? (size_t)s.stack_depth * 256 * 4 : 0;
+    L.stage_offset = (uint32_t)(base / 4);
+    base += s.stage_bytes;
+    L.recs_offset = (uint32_t)(base / 4);
+    base = align(base + (!v.bvh ? (size_t)(s.n_tris + 2) * 48 : 0));
+    L.required_bytes = align(base + park + carry) + slots;
+    L.tile_offset = (uint32_t)(base / 4);
+    if (v.bvh && !v.tex && !v.inst) {  // what is left of the workgroup's share after the launch's other blocks
+        const size_t other = base + park + carry + slots, budget = pt_lds_budget(v.tex) - 256;
+        if (other < budget) L.tile_nodes = (uint32_t)std::min<size_t>({(budget - other) / (kBvhNodeWords * 4), (size_t)s.n_nodes, (size_t)1024});
+        base = align(base + (size_t)L.tile_nodes * kBvhNodeWords * 4);
+    }
+    L.park_offset = (uint32_t)(base / 4);
+    base += park;
+    L.carry_offset = (uint32_t)(base / 4);
+    base += carry;
+    // pmj02bn: the lanes' blue-noise columns, if the workgroup's share has room for them (exhaustive kernels of small scenes: 24 KB next to
+    // ~13 KB of staged tables; the BVH kernels' traversal stacks leave none)
+    if (s.bluenoise && !v.bvh && base + slots + kBlueNoiseColumnBytes <= pt_lds_budget(v.tex)) {
+        L.bn_offset = (uint32_t)(align(base) / 4);
+        base = align(base) + kBlueNoiseColumnBytes;
+    }
+    L.val_offset_words = (uint32_t)((base = align(base)) / 4);
+    L.total_bytes = base + slots;
+    return L;
+}
+#endif
 
 // Launch counters (akr_pt_stats) are kStatStripes copies of 8 u64, a workgroup adding to copy blockIdx % kStatStripes: the wavefront
 // schedule flushes them once per wave and ITERATION (32 k waves x 7 atomics on seven addresses per k_wf_shade launch serialise at the
@@ -193,7 +256,19 @@ hipError_t launch_mcmc_init(const PtParams& p, const McmcParams& m, hipStream_t 
 hipError_t launch_mcmc_advance(const PtParams& p, const McmcParams& m, uint32_t mutations_per_chain, float contribution, hipStream_t stream);
 #endif
 
-// Dynamic LDS of a launch that evaluates shader graphs = its own blocks (`base_bytes`: traversal stacks, staged tables), then
+#if !defined(__HIPCC_RTC__)
+// pt_lds_layout's input as a session's parameter block holds it, and the block with a layout's offsets filled in
+inline PtLdsSizes pt_lds_sizes(const PtParams& p) {
+    return PtLdsSizes{p.sc.bvh_stack_depth, p.sc.n_tris, p.sc.n_nodes, p.tex_slots, p.stage_total, p.sampler == 1u && p.bluenoise != nullptr};
+}
+inline PtParams pt_params_with_layout(const PtParams& p, const PtLdsLayout& L) {
+    PtParams q = p;
+    q.tile_offset = L.tile_offset; q.sc.bvh_tile_nodes = L.tile_nodes; q.park_offset = L.park_offset; q.carry_offset = L.carry_offset;
+    q.bn_offset = L.bn_offset; q.sc.tex.val_offset_words = L.val_offset_words;
+    return q;
+}
+#endif
+// The simple layouts (aov, gpt, mcmc, wavefront, probes): dynamic LDS of a launch that evaluates shader graphs = its own blocks (`base_bytes`: traversal stacks, staged tables), then
 // tex_slots x 256 lanes x 16 B of value slots. Returns the parameter block with the slots' offset filled in and the total size.
 inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds_bytes) {
     PtParams q = p;
@@ -204,21 +279,13 @@ inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds
 }
 #if !defined(__HIPCC_RTC__)
 hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_inst_kernels.hip: once per kept scene (DInst::share_bits)
-hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream);  // pt_inst_kernels.hip: scenes kept as meshes + instances
-hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream);   // pt_env_kernels.hip: scenes with an environment light (device/denv.h)
-hipError_t launch_pt_pass_inst_env(const PtParams& p, hipStream_t stream);  // pt_inst_env_kernels.hip: kept scenes with an environment light
 hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
-// the LENS = true instantiations (the camera has a thin lens: p.lens_radius > 0), each in a translation unit of its own
-hipError_t launch_pt_pass_lens(const PtParams& p, hipStream_t stream);      // pt_lens_kernels.hip: flattened scenes; one with an environment goes on to ...
-hipError_t launch_pt_pass_lens_env(const PtParams& p, hipStream_t stream);  // ... pt_lens_env_kernels.hip
-hipError_t launch_pt_pass_inst_lens(const PtParams& p, hipStream_t stream);                    // pt_inst_lens_kernels.hip: kept scenes
-hipError_t launch_wf_init_lens(const PtParams& p, const WfBuffers& wf, hipStream_t stream);   // wf_lens_kernels.hip
-hipError_t launch_wf_shade_lens(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);
-hipError_t launch_aov_lens(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream);  // aov_lens_kernels.hip
 // pt_lens_kernels.hip, test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
 hipError_t launch_probe_camera_rays(const PtParams& p, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6, hipStream_t stream);
-// spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled instantiation, or nullptr
-hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn = nullptr);
+// One pass launch of a pt session: lays the LDS out (pt_lds_layout) and goes to the translation unit that holds the variant's kernel
+// (pt_kernels.hip: the table). spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled one, or nullptr;
+// relaxed: the kernels of the relaxed arithmetic tier (pt_kernels_relaxed.hip), which exist for variants without inst, env and lens
+hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t stream, hipFunction_t spec_fn = nullptr, bool relaxed = false);
 hipError_t launch_gpt_sample(const PtParams& p, const GptParams& g, hipStream_t stream);
 hipError_t launch_gpt_update(const GptParams& g, uint32_t W, uint32_t H, float* film, hipStream_t stream);
 hipError_t launch_gpt_recon_init(const GptParams& g, uint32_t W, uint32_t H, float* old, float spp, hipStream_t stream);
@@ -226,7 +293,6 @@ hipError_t launch_gpt_recon(const GptParams& g, uint32_t W, uint32_t H, const fl
 hipError_t launch_aov(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream);
 hipError_t launch_wf_init(const PtParams& p, const WfBuffers& wf, hipStream_t stream);
 hipError_t launch_wf_shade(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);
-hipError_t launch_wf_shade_env(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);  // wf_env_kernels.hip: scenes with an environment light
 uint32_t wf_trace_blocks_per_cu(const PtParams& p);
 hipError_t launch_wf_trace(const PtParams& p, const WfBuffers& wf, uint32_t q_in, uint32_t n_blocks, hipStream_t stream);
 // wf_sort.hip: key-value radix sort of a ray queue (24-bit keys)

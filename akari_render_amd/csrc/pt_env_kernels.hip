@@ -1,13 +1,11 @@
 // pt_env_kernels.hip -- k_pt_pass for flattened scenes with an environment light (device/denv.h; ENV = true), in a translation unit of
-// their own so that the library's build compiles them beside pt_kernels.hip. The launcher is launch_pt_pass's (pt_launch.h) with ENV on,
-// which rules out DEFER and SIMPLE: BVH or exhaustive x force_diffuse x textures x sampler family x staged tables (BVH path; the
-// exhaustive path always stages). Kept scenes run k_pt_pass_inst<.., ENV> (pt_inst_env_kernels.hip), the wavefront schedule
-// k_wf_shade<.., ENV> (wf_env_kernels.hip).
+// their own so that the library's build compiles them beside pt_kernels.hip: what kernels.h pt_variant_compiled leaves of k_pt_pass with ENV on.
+// Kept scenes run k_pt_pass_inst<.., ENV> (pt_inst_env_kernels.hip), the wavefront schedule k_wf_shade<.., ENV> (wf_env_kernels.hip).
 #include "pt_launch.h"
 
 namespace akr {
 
-hipError_t launch_pt_pass_env(const PtParams& p, hipStream_t stream) { return launch_pt_pass_t<true>(p, stream); }
+hipError_t pt_pass_entry_env(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) { return pt_pass_entry_t<true, false>(q, v, blocks, lds, stream); }
 
 // ---------------------------------------------------------------------------------------------------- test hook
 // mode 0: in = u (2 floats / item) -> out = wi.xyz, pdf, valid (5 floats); mode 1: in = direction (3 floats) -> out = pdf, radiance.rgb (4 floats)

@@ -1,7 +1,7 @@
-// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances, and its launcher. A header
-// so that the instantiations of scenes with an environment light (pt_inst_env_kernels.hip, ENV = true) are compiled in a translation unit of
-// their own: those of pt_inst_kernels.hip (ENV = false), and their code, are the ones of a library without environments. The same for cameras
-// with a thin lens (LENS = true, with and without an environment: pt_inst_lens_kernels.hip).
+// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances, and the entry point of a
+// translation unit that instantiates it. A header so that the instantiations of scenes with an environment light (pt_inst_env_kernels.hip,
+// ENV = true) are compiled in a translation unit of their own: those of pt_inst_kernels.hip (ENV = false), and their code, are the ones of a
+// library without environments. The same for cameras with a thin lens (LENS = true, with and without an environment: pt_inst_lens_kernels.hip).
 #pragma once
 #include "pt_launch.h"
 
@@ -19,15 +19,11 @@ __global__ __launch_bounds__(256, TEX ? AKR_PT_MIN_WAVES_INST_TEX : AKR_PT_MIN_W
     pt_pass_body<true, FD, TEX, PMJ, false, false, 0u, true, ENV, LENS>(p);
 }
 
-// force_diffuse x textures x sampler family, in the LDS layout of k_pt_pass
-template <bool ENV, bool LENS = false>
-hipError_t launch_pt_pass_inst_t(const PtParams& p, hipStream_t stream) {
-    size_t lds;
-    uint32_t blocks;
-    const PtParams q = pt_pass_layout(p, lds, blocks);
-    if (blocks == 0) return hipSuccess;
-    dispatch_bools([&](auto F, auto T, auto P) { launch_kernel<true>(k_pt_pass_inst<F(), T(), P(), ENV, LENS>, blocks, lds, stream, q); },
-                   p.force_diffuse != 0, p.sc.tex.nodes != nullptr, p.sampler != 0);
+// force_diffuse x textures x sampler family: what a kept scene's variant has left (kernels.h pt_variant_compiled)
+template <bool ENV, bool LENS>
+hipError_t pt_pass_entry_inst_t(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) {
+    if (!v.inst || v.env != ENV || v.lens != LENS || !pt_variant_compiled(v)) return hipErrorInvalidValue;
+    dispatch_bools([&](auto F, auto T, auto P) { launch_kernel<true>(k_pt_pass_inst<F(), T(), P(), ENV, LENS>, blocks, lds, stream, q); }, v.fd, v.tex, v.pmj);
     return hipGetLastError();
 }
 

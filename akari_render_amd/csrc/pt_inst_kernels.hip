@@ -1,7 +1,6 @@
 // pt_inst_kernels.hip -- k_pt_pass for scenes kept as meshes + instances (host/scene_inst.cpp): the same persistent-lane path
-// tracer over the two-level traversal of device/dinst_trav.h. BVH kernels without staged tables, deferral or absent-lobe masks:
-// force_diffuse x textures x sampler family; kernel and launcher: pt_inst_kernel.h (ENV = false here; scenes with an environment light:
-// pt_inst_env_kernels.hip).
+// tracer over the two-level traversal of device/dinst_trav.h: force_diffuse x textures x sampler family (kernels.h pt_variant_compiled); kernel
+// and entry point: pt_inst_kernel.h (ENV = false, LENS = false here).
 #include "pt_inst_kernel.h"
 
 namespace akr {
@@ -31,10 +30,6 @@ hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* me
     return hipGetLastError();
 }
 
-hipError_t launch_pt_pass_inst(const PtParams& p, hipStream_t stream) {
-    if (p.lens_radius > 0.0f) return launch_pt_pass_inst_lens(p, stream);  // a thin lens: pt_inst_lens_kernels.hip
-    if (p.sc.env) return launch_pt_pass_inst_env(p, stream);  // an environment light: pt_inst_env_kernels.hip
-    return launch_pt_pass_inst_t<false>(p, stream);
-}
+hipError_t pt_pass_entry_inst(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) { return pt_pass_entry_inst_t<false, false>(q, v, blocks, lds, stream); }
 
 }  // namespace akr

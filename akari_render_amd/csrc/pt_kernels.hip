@@ -1,4 +1,4 @@
-// pt_kernels.hip -- hand-written gfx950 kernels of the `pt` integrator. k_pt_pass: device/pt_pass.h, its launcher: pt_launch.h (ENV = false here).
+// pt_kernels.hip -- hand-written gfx950 kernels of the `pt` integrator. k_pt_pass: device/pt_pass.h, pt_launch.h (ENV = false, LENS = false here); launch_pt_pass, the router of every pt launch.
 #include <algorithm>
 #include "device/pt_pass.h"
 #include "pt_launch.h"
@@ -192,12 +192,26 @@ __global__ void k_probe_material(PtParams p, uint32_t material, uint32_t n, cons
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
-// spec_fn: the session's per-scene kernel (host/specialise.cpp); it wraps the body of whatever the scene is, so it is launched from here
-hipError_t launch_pt_pass(const PtParams& p, hipStream_t stream, hipFunction_t spec_fn) {
-    if (p.sc.in2.on && !spec_fn) return launch_pt_pass_inst(p, stream);  // meshes + instances: pt_inst_kernels.hip
-    if (p.lens_radius > 0.0f && !spec_fn) return launch_pt_pass_lens(p, stream);  // a thin lens: pt_lens_kernels.hip, pt_lens_env_kernels.hip
-    if (p.sc.env && !spec_fn) return launch_pt_pass_env(p, stream);      // an environment light: pt_env_kernels.hip
-    return launch_pt_pass_t<false>(p, stream, spec_fn);
+}  // namespace akr
+// pt_kernels_relaxed.hip: pt_pass_entry_t<false, false> of the relaxed arithmetic tier (its PtParams is akr's, in another namespace)
+extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, const PtVariant* v, uint32_t blocks, size_t lds, hipStream_t stream);
+namespace akr {
+static hipError_t pt_pass_entry_plain(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) { return pt_pass_entry_t<false, false>(q, v, blocks, lds, stream); }
+// the translation unit that holds the kernels of a variant, by [inst][env][lens]
+static constexpr PtPassEntry kPtPassEntry[2][2][2] = {{{pt_pass_entry_plain, pt_pass_entry_lens}, {pt_pass_entry_env, pt_pass_entry_lens_env}},
+                                                      {{pt_pass_entry_inst, pt_pass_entry_inst_lens}, {pt_pass_entry_inst_env, pt_pass_entry_inst_lens_env}}};
+hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t stream, hipFunction_t spec_fn, bool relaxed) {
+    const uint32_t blocks = (p.n_items + 255u) / 256u;
+    if (blocks == 0) return hipSuccess;
+    const PtLdsLayout L = pt_lds_layout(v, pt_lds_sizes(p));
+    const PtParams q = pt_params_with_layout(p, L);
+    if (spec_fn) {  // the scene's own kernel (host/specialise.cpp) wraps the body of whatever the variant is: same parameter block, same LDS layout
+        if (L.total_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)spec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total_bytes);
+        void* args[] = {(void*)&q};
+        return hipModuleLaunchKernel(spec_fn, blocks, 1, 1, 256, 1, 1, (unsigned)L.total_bytes, stream, args, nullptr);
+    }
+    if (relaxed) return akr_launch_pt_pass_relaxed(&q, &v, blocks, L.total_bytes, stream);
+    return kPtPassEntry[v.inst][v.env][v.lens](q, v, blocks, L.total_bytes, stream);
 }
 hipError_t launch_probe_material(const PtParams& p, uint32_t material, uint32_t n, const float* uv, uint32_t* out, hipStream_t stream) {
     size_t lds;

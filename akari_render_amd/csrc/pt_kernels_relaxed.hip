@@ -6,7 +6,7 @@
 // mistaken for the contract-bound ones at link time. Films are not the oracle's to the bit, and at fixed seed not within
 // north_star's relRMSE < 1e-3 either except on the headline configuration's shard (1e-5 .. 4e-5 outside the few pixels
 // where a sample takes another decision, 8e-4 .. 9e-3 with them; tests/test_gpu_relaxed.py): the bit-exact tier stays the default and
-// is what verifies this one. The launcher is pt_launch.h's; kept scenes and scenes with an environment light are refused here.
+// is what verifies this one. The entry point is pt_launch.h's; which sessions come here is decided in akr_pt_begin (host/api_pt.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -16,8 +16,7 @@
 #include "pt_launch.h"
 #undef akr
 
-extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, hipStream_t stream) {
-    const akr_rx::PtParams& p = *static_cast<const akr_rx::PtParams*>(params);
-    if (p.sc.in2.on || p.sc.env) return hipErrorInvalidValue;  // (the host never sends a kept scene or one with an environment light to this tier: api_pt.cpp)
-    return akr_rx::launch_pt_pass_t<false>(p, stream);
+// params: the parameter block with the layout's offsets filled in (launch_pt_pass_relaxed, pt_kernels.hip); it is akr::PtParams, in this namespace
+extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, const PtVariant* v, uint32_t blocks, size_t lds, hipStream_t stream) {
+    return akr_rx::pt_pass_entry_t<false, false>(*static_cast<const akr_rx::PtParams*>(params), *v, blocks, lds, stream);  // (refuses inst, env, lens)
 }

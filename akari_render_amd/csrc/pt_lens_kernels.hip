@@ -1,16 +1,13 @@
 // pt_lens_kernels.hip -- k_pt_pass for flattened scenes seen through a thin lens (LENS = true; device/dpath.h generate_ray_lens_from, DESIGN.md
-// section 4.9), in a translation unit of their own. The launcher is launch_pt_pass's (pt_launch.h) with LENS on, which rules out DEFER and SIMPLE
-// as ENV does. LENS x ENV is a full cross: scenes that also have an environment light run the instantiations of pt_lens_env_kernels.hip. Kept
+// section 4.9), in a translation unit of their own: what kernels.h pt_variant_compiled leaves of k_pt_pass with LENS on. LENS x ENV is a full
+// cross: scenes that also have an environment light run the instantiations of pt_lens_env_kernels.hip. Kept
 // scenes run k_pt_pass_inst<.., LENS> (pt_inst_lens_kernels.hip), the wavefront schedule k_wf_init / k_wf_shade<.., LENS> (wf_lens_kernels.hip),
 // the aov integrator k_aov<.., LENS> (aov_lens_kernels.hip).
 #include "pt_launch.h"
 
 namespace akr {
 
-hipError_t launch_pt_pass_lens(const PtParams& p, hipStream_t stream) {
-    if (p.sc.env) return launch_pt_pass_lens_env(p, stream);
-    return launch_pt_pass_t<false, true>(p, stream);
-}
+hipError_t pt_pass_entry_lens(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) { return pt_pass_entry_t<false, true>(q, v, blocks, lds, stream); }
 
 // ---------------------------------------------------------------------------------------------------- test hook
 // the camera ray of n items: pixel (x, y), u_filter.xy, u_lens.xy -> o.xyz, d.xyz; the pinhole's function when the camera has no lens

@@ -170,8 +170,15 @@ __global__ __launch_bounds__(256, TEX ? 1 : AKR_WF_SHADE_WAVES) void k_wf_shade(
 }
 
 
+// The entry points of the translation units that hold the ENV / LENS instantiations; launch_wf_init and launch_wf_shade (wf_kernels.hip) go
+// to them through a table
+hipError_t wf_init_entry_lens(const PtParams& p, const WfBuffers& wf, hipStream_t stream);                         // wf_lens_kernels.hip
+hipError_t wf_shade_entry_env(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);       // wf_env_kernels.hip
+hipError_t wf_shade_entry_lens(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);      // wf_lens_kernels.hip
+hipError_t wf_shade_entry_lens_env(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream);  // wf_lens_kernels.hip
+
 // textures x sampler family x kept or flattened scene
-template <bool ENV, bool LENS = false>
+template <bool ENV, bool LENS>
 hipError_t launch_wf_shade_t(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
     const uint32_t blocks = (wf.slot_end - wf.slot_base + 255u) / 256u;
     if (blocks == 0) return hipSuccess;

@@ -96,6 +96,26 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene *scene, uint32_t filter_t
 AKR_TEST_API int32_t akr_probe_camera_rays(akr_context *ctx, akr_scene *scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2,
                                       const float *u4, float *out6);
 
+/* Which kernel a pt session of (scene, cfg) would launch and how that launch's LDS is laid out, decided on the host (no GPU; works on a
+ * host-only scene): what akr_pt_begin decides, without the session. The options are the process-wide ones a session snapshots when it
+ * begins (defer_metal -1 = the library decides, simple_kernels, defer_on); spec_waves = 0: no per-scene kernel, else the per-scene kernel
+ * of that many waves per SIMD is taken to have compiled (where the session would ask for one: texture-fed materials, no force_diffuse).
+ *   variant[10]     the instantiation: bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens
+ *   simple_scene .. stage_total, tile_offset .. val_offset_words   the fields of the kernel parameter block of the same names
+ *   lds_bytes, blocks   dynamic LDS and workgroups of a launch
+ *   specialised     1 = a per-scene kernel; wrapper is then the text that instantiates it (part of the kernel cache's key), else "" */
+typedef struct akr_pt_launch_plan {
+    uint32_t variant[10];
+    uint32_t simple_scene, defer_metal, defer_flags;
+    uint32_t stage_bytes[13], stage_total;
+    uint32_t tile_offset, bvh_tile_nodes, park_offset, carry_offset, bn_offset, val_offset_words;
+    uint32_t lds_bytes, blocks;
+    uint32_t specialised;
+    char wrapper[600];
+} akr_pt_launch_plan;
+AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
+                                        int32_t spec_waves, akr_pt_launch_plan *out);
+
 /* akr_denoise on the host (no GPU): the text of csrc/device/ddenoise.h compiled for the host, over host arrays. Each film is an accumulator
  * in the reference layout [rgb 3N | splat 3N | weight N] with its splat scale; albedo_film / normal_film may be NULL. out_rgb = 3 N floats,
  * what akr_film_resolve returns for akr_denoise's output film. Same refusals as akr_denoise. */
