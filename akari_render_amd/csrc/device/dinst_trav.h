@@ -103,7 +103,7 @@ AKR_D void resolve_pending(const DScene& sc, TravI& s, bool any_hit) {
     bool h = tri_test(s.wo, s.wd, make_float4(wr[0], wr[1], wr[2], wr[3]), make_float4(wr[4], wr[5], wr[6], wr[7]), make_float4(wr[8], wr[9], wr[10], wr[11]), s.tmin, s.tmax,
                       t, u, v);
 #if defined(AKR_INST_PRETEST_CHECK)
-    if (h && s.check_t >= 0.0f && t <= s.check_t) s.check_t = -2.0f;  // (trace_inst turns this into the overflow flag: the render fails)
+    if (h && s.check_t >= 0.0f && t <= s.check_t) s.check_t = -2.0f;  // (the loop that called turns this into the overflow flag: the render fails)
 #endif
     if (h && sc.has_alpha) h = alpha_test_inst<TEX>(sc, m, inst, prim, tri_off, q0, q1, q2, q3, u, v);
     if (h) {
@@ -135,7 +135,7 @@ AKR_D bool inst_pair_shares(const DScene& sc, uint32_t inst, uint32_t prim, uint
 // every stage some lane is in; a lane that is through with one goes on to the next in the same iteration instead of waiting for the
 // wave's next one: a third fewer iterations per ray than one stage per step.) The order of a ray's node visits and candidates is the
 // one-stage-per-step order. Returns true when the lane found a second candidate for the exact test while one is pending: the
-// candidate is put back (its leaf bit set again) and the lane waits for trace_pair_inst / trace_inst to resolve the pending one.
+// candidate is put back (its leaf bit set again) and the lane waits for its loop (trace_inst, trace_pair_inst, k_wf_trace) to resolve the pending one.
 template <bool TEX>
 AKR_D bool trav_step_inst(const DScene& sc, TravI& s, uint32_t* __restrict__ stack, TraceCounters& cnt) {
     bool blocked = false;
@@ -256,6 +256,8 @@ AKR_D bool trav_step_inst(const DScene& sc, TravI& s, uint32_t* __restrict__ sta
 // take the test together -- when AKR_INST_QUORUM lanes have one, when a lane that cannot go on without its verdict (a second
 // candidate, or the end of its traversal) has waited AKR_INST_PATIENCE steps, or when no lane can go on. The order in which a ray's
 // candidates are tested changes neither the closest hit (smallest t, then smallest id) nor whether there is any.
+// The gate is written out in each of the three loops that step a kept scene's lane -- trace_inst, trace_pair_inst, wf_kernels.hip k_wf_trace --
+// each with the AKR_INST_PRETEST_CHECK tripwire: as one struct it costs their kernels spilled registers (HISTORY R7.3).
 #ifndef AKR_INST_QUORUM
 #define AKR_INST_QUORUM 16
 #endif
@@ -288,11 +290,22 @@ AKR_D bool trace_inst(const DScene& sc, vec3 o, vec3 d, float tmin, float tmax, 
     return s.best != kInvalid;
 }
 
+// A carried traversal of a kept scene as the wavefront schedule's records hold it (disect.h carry_best / carry_place / trav_resume): also the
+// TLAS leaf of the instance the ray is in -- what it re-enters the instance from -- and the candidate waiting for its exact test.
+AKR_D uint4 carry_inst(const TravI& s) { return make_uint4(s.leaf, s.pend_rec, s.pend_inst, 0u); }
+AKR_D void trav_resume(const DScene& sc, TravI& s, uint4 best, uint4 place, uint4 inst) {
+    s.leaf = inst.x; s.pend_rec = inst.y; s.pend_inst = inst.z;
+    if (s.leaf != kInvalid) {  // back into the instance the ray was in
+        const uint4* lf = sc.in2.tlas_leaves + (size_t)s.leaf * 4;
+        trav_into_instance(sc, s, lf[0], lf[1], lf[2], lf[3]);
+    }
+    trav_resume(sc, static_cast<Trav&>(s), best, place);
+}
+
 // Both rays of a path vertex through ONE loop (a lane whose closest-hit ray is done goes straight on to its shadow ray), which ends
-// when at most 1/STRAG of the lanes that entered it are still tracing: those keep their traversal -- in 16 words of LDS per lane, the
-// stack where it is -- and go on in the next intersection phase while the others shade (pt_pass.h: the flattened scenes' kernels do
-// the same, AKR_PT_STRAGGLERS). cy = the lane's LDS column (slot k at cy[k * 256]).
-constexpr uint32_t kCarrySlotsInst = 16;
+// when at most 1/STRAG of the lanes that entered it are still tracing: those keep their traversal -- in the kCarrySlotsInstanced words
+// of LDS per lane that kernels.h CY_* names, the stack where it is -- and go on in the next intersection phase while the others shade
+// (pt_pass.h: the flattened scenes' kernels do the same, AKR_PT_STRAGGLERS). cy = the lane's LDS column (slot k at cy[k * 256]).
 template <bool TEX, uint32_t STRAG>
 AKR_D void trace_pair_inst(const DScene& sc, bool has_ray, vec3 ro, vec3 rd, uint32_t ray_ex0, bool has_shadow, vec3 s_o, vec3 s_d, float s_tmax, uint32_t s_ex0,
                            uint32_t s_ex1, bool& carry, Hit& hit, bool& found, bool& occluded, uint32_t* __restrict__ stack, uint32_t* __restrict__ cy, TraceCounters& cnt) {
@@ -304,16 +317,16 @@ AKR_D void trace_pair_inst(const DScene& sc, bool has_ray, vec3 ro, vec3 rd, uin
         if (phase == 0) trav_begin_inst(s, ro, rd, 0.0f, 1e20f, ray_ex0, kInvalid);
         else trav_begin_inst(s, s_o, s_d, 0.0f, phase == 1 ? s_tmax : -1.0f, s_ex0, s_ex1);
     } else {
-        phase = cy[8 * 256];
+        phase = cy[CY_PHASE * 256];
         if (phase == 0) trav_begin_inst(s, ro, rd, 0.0f, 1e20f, ray_ex0, kInvalid);
         else {
             trav_begin_inst(s, s_o, s_d, 0.0f, s_tmax, s_ex0, s_ex1);
-            hit.t = u2f(cy[9 * 256]); hit.u = u2f(cy[10 * 256]); hit.v = u2f(cy[11 * 256]); hit.gid = cy[12 * 256];
+            hit.t = u2f(cy[CY_HIT_T * 256]); hit.u = u2f(cy[CY_HIT_U * 256]); hit.v = u2f(cy[CY_HIT_V * 256]); hit.gid = cy[CY_HIT_GID * 256];
             found = hit.gid != kInvalid;
         }
-        s.best_t = u2f(cy[0]); s.best_u = u2f(cy[1 * 256]); s.best_v = u2f(cy[2 * 256]); s.best = cy[3 * 256];
-        s.G = cy[4 * 256]; s.T = cy[5 * 256]; s.tbase = cy[6 * 256]; s.sp = cy[7 * 256];
-        s.leaf = cy[13 * 256]; s.pend_rec = cy[14 * 256]; s.pend_inst = cy[15 * 256];
+        s.best_t = u2f(cy[CY_BEST_T * 256]); s.best_u = u2f(cy[CY_BEST_U * 256]); s.best_v = u2f(cy[CY_BEST_V * 256]); s.best = cy[CY_BEST * 256];
+        s.G = cy[CY_G * 256]; s.T = cy[CY_T * 256]; s.tbase = cy[CY_TBASE * 256]; s.sp = cy[CY_SP * 256];
+        s.leaf = cy[CY_LEAF * 256]; s.pend_rec = cy[CY_PEND_REC * 256]; s.pend_inst = cy[CY_PEND_INST * 256];
         if (s.leaf != kInvalid) {
             const uint4* lf = sc.in2.tlas_leaves + (size_t)s.leaf * 4;
             trav_into_instance(sc, s, lf[0], lf[1], lf[2], lf[3]);
@@ -337,6 +350,9 @@ AKR_D void trace_pair_inst(const DScene& sc, bool has_ray, vec3 ro, vec3 rd, uin
                 if (waited >= AKR_INST_PATIENCE || __ballot(s.active & !wait) == 0 || __popcll(__ballot(pending)) >= AKR_INST_QUORUM) {
                     waited = 0;
                     if (pending) resolve_pending<TEX>(sc, s, phase == 1u);
+#if defined(AKR_INST_PRETEST_CHECK)
+                    if (s.check_t == -2.0f) cnt.overflow = 1;
+#endif
                 }
             }
             if (!s.active & (s.pend_rec == kInvalid)) {
@@ -355,11 +371,11 @@ AKR_D void trace_pair_inst(const DScene& sc, bool has_ray, vec3 ro, vec3 rd, uin
     }
     carry = STRAG > 0 && phase != 2u;
     if (STRAG > 0 && carry) {
-        cy[0] = f2u(s.best_t); cy[1 * 256] = f2u(s.best_u); cy[2 * 256] = f2u(s.best_v); cy[3 * 256] = s.best;
-        cy[4 * 256] = s.G; cy[5 * 256] = s.T; cy[6 * 256] = s.tbase; cy[7 * 256] = s.sp;
-        cy[8 * 256] = phase;
-        if (phase == 1u) { cy[9 * 256] = f2u(hit.t); cy[10 * 256] = f2u(hit.u); cy[11 * 256] = f2u(hit.v); cy[12 * 256] = hit.gid; }
-        cy[13 * 256] = s.leaf; cy[14 * 256] = s.pend_rec; cy[15 * 256] = s.pend_inst;
+        cy[CY_BEST_T * 256] = f2u(s.best_t); cy[CY_BEST_U * 256] = f2u(s.best_u); cy[CY_BEST_V * 256] = f2u(s.best_v); cy[CY_BEST * 256] = s.best;
+        cy[CY_G * 256] = s.G; cy[CY_T * 256] = s.T; cy[CY_TBASE * 256] = s.tbase; cy[CY_SP * 256] = s.sp;
+        cy[CY_PHASE * 256] = phase;
+        if (phase == 1u) { cy[CY_HIT_T * 256] = f2u(hit.t); cy[CY_HIT_U * 256] = f2u(hit.u); cy[CY_HIT_V * 256] = f2u(hit.v); cy[CY_HIT_GID * 256] = hit.gid; }
+        cy[CY_LEAF * 256] = s.leaf; cy[CY_PEND_REC * 256] = s.pend_rec; cy[CY_PEND_INST * 256] = s.pend_inst;
     }
 }
 

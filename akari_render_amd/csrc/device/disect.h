@@ -7,6 +7,7 @@
 #pragma once
 #include "drng.h"
 #include "dscene.h"
+#include "../kernels.h"  // CY_*: the columns of a carried traversal
 
 namespace akr {
 
@@ -627,6 +628,17 @@ AKR_D bool trace_bvh(const DScene& sc, vec3 o, vec3 d, float tmin, float tmax, u
     while (s.active) trav_step<ANY_HIT ? 1 : 0, TEX>(sc, s, stack, cnt);
     hit.t = s.best_t; hit.u = s.best_u; hit.v = s.best_v; hit.gid = s.best;
     return s.best != kInvalid;
+}
+
+// ---- a traversal that goes on later: the wavefront schedule's carried rays (wf_kernels.hip) ----
+// What is kept of a ray in flight, in the order of kernels.h CY_*: the best hit so far and the place in the tree, a group of four words each. The ray
+// itself is begun again from the path state before trav_resume; the stack stays where it is (LDS) or travels with the record (wavefront).
+AKR_D uint4 carry_best(const Trav& s) { return make_uint4(f2u(s.best_t), f2u(s.best_u), f2u(s.best_v), s.best); }
+AKR_D uint4 carry_place(const Trav& s) { return make_uint4(s.G, s.T, s.tbase, s.sp); }
+AKR_D void trav_resume(const DScene& sc, Trav& s, uint4 best, uint4 place) {
+    s.best_t = u2f(best.x); s.best_u = u2f(best.y); s.best_v = u2f(best.z); s.best = best.w;
+    s.G = place.x; s.T = place.y; s.tbase = place.z; s.sp = place.w;
+    s.active = (s.T != 0) | ((s.G >> 24) != 0) | (s.sp != 0);
 }
 
 }  // namespace akr

@@ -104,14 +104,13 @@ AKR_D void pt_pass_body(const PtParams& p) {
             }
             if (BVH && INST) {
                 // meshes + instances: the two-level traversal (dinst_trav.h), both rays in one loop, stragglers carried over
-                static_assert(kCarrySlotsInstanced == kCarrySlotsInst, "LDS plan and traversal disagree");
                 trace_pair_inst<TEX, STRAG>(sc, r.has_ray, r.ro, r.rd, r.ray_ex0, r.has_shadow, r.s_o, r.s_d, r.s_tmax, r.s_ex0, r.s_ex1, r.carry, hit, found, occluded, tc.stack,
                                             lds_stack + p.carry_offset + threadIdx.x, tc.cnt);
             } else if (BVH && STRAG > 0) {
                 // The merged loop below ends when the wave's LONGEST pair of rays is done: on the 10 M-triangle hall 40 % of its
                 // lane-steps do work, the rest is lanes waiting for the tail of the ray-length distribution. Here the phase ends
                 // when at most 1/n of the lanes that entered it are still tracing. Those lanes keep their traversal -- position
-                // in the tree and best hit so far in a column of LDS, the stack where it is -- skip this iteration's shading and
+                // in the tree and best hit so far in a column of LDS (kernels.h CY_*), the stack where it is -- skip this iteration's shading and
                 // continue in the next phase, while the others shade and start their next rays. Per lane only the iteration in
                 // which a vertex is shaded changes (as with DEFER): films and sampler states are the same bit for bit.
                 uint32_t* cy = lds_stack + p.carry_offset + threadIdx.x;
@@ -123,15 +122,15 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     if (phase == 0) trav_begin(s, r.ro, r.rd, 0.0f, 1e20f, r.ray_ex0, kInvalid);
                     else trav_begin(s, r.s_o, r.s_d, 0.0f, phase == 1 ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1);
                 } else {
-                    phase = cy[8 * 256];
+                    phase = cy[CY_PHASE * 256];
                     if (phase == 0) trav_begin(s, r.ro, r.rd, 0.0f, 1e20f, r.ray_ex0, kInvalid);
                     else {
                         trav_begin(s, r.s_o, r.s_d, 0.0f, r.s_tmax, r.s_ex0, r.s_ex1);
-                        hit.t = u2f(cy[9 * 256]); hit.u = u2f(cy[10 * 256]); hit.v = u2f(cy[11 * 256]); hit.gid = cy[12 * 256];
+                        hit.t = u2f(cy[CY_HIT_T * 256]); hit.u = u2f(cy[CY_HIT_U * 256]); hit.v = u2f(cy[CY_HIT_V * 256]); hit.gid = cy[CY_HIT_GID * 256];
                         found = hit.gid != kInvalid;
                     }
-                    s.best_t = u2f(cy[0]); s.best_u = u2f(cy[1 * 256]); s.best_v = u2f(cy[2 * 256]); s.best = cy[3 * 256];
-                    s.G = cy[4 * 256]; s.T = cy[5 * 256]; s.tbase = cy[6 * 256]; s.sp = cy[7 * 256];
+                    s.best_t = u2f(cy[CY_BEST_T * 256]); s.best_u = u2f(cy[CY_BEST_U * 256]); s.best_v = u2f(cy[CY_BEST_V * 256]); s.best = cy[CY_BEST * 256];
+                    s.G = cy[CY_G * 256]; s.T = cy[CY_T * 256]; s.tbase = cy[CY_TBASE * 256]; s.sp = cy[CY_SP * 256];
                     s.active = true;
                 }
                 const uint32_t n_in = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(phase != 2u));
@@ -156,10 +155,10 @@ AKR_D void pt_pass_body(const PtParams& p) {
                 }
                 r.carry = phase != 2u;
                 if (r.carry) {
-                    cy[0] = f2u(s.best_t); cy[1 * 256] = f2u(s.best_u); cy[2 * 256] = f2u(s.best_v); cy[3 * 256] = s.best;
-                    cy[4 * 256] = s.G; cy[5 * 256] = s.T; cy[6 * 256] = s.tbase; cy[7 * 256] = s.sp;
-                    cy[8 * 256] = phase;
-                    if (phase == 1u) { cy[9 * 256] = f2u(hit.t); cy[10 * 256] = f2u(hit.u); cy[11 * 256] = f2u(hit.v); cy[12 * 256] = hit.gid; }
+                    cy[CY_BEST_T * 256] = f2u(s.best_t); cy[CY_BEST_U * 256] = f2u(s.best_u); cy[CY_BEST_V * 256] = f2u(s.best_v); cy[CY_BEST * 256] = s.best;
+                    cy[CY_G * 256] = s.G; cy[CY_T * 256] = s.T; cy[CY_TBASE * 256] = s.tbase; cy[CY_SP * 256] = s.sp;
+                    cy[CY_PHASE * 256] = phase;
+                    if (phase == 1u) { cy[CY_HIT_T * 256] = f2u(hit.t); cy[CY_HIT_U * 256] = f2u(hit.u); cy[CY_HIT_V * 256] = f2u(hit.v); cy[CY_HIT_GID * 256] = hit.gid; }
                 }
             } else if (BVH) {
                 // Both rays of the iteration through ONE traversal loop: a lane whose closest-hit ray is done goes straight on
@@ -205,7 +204,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     r.deferred = false;
                 } else if (r.has_ray && found && (iteration & q.defer_metal)) {
                     const uint32_t mat = f2u(sc.shade[(size_t)hit.gid * SHADE_ROWS + 6].y);
-                    if (sc.materials[mat].flags & q.defer_flags) {  // MF_EVAL_METAL and / or MF_TEXTURED, the host's choice (api_pt.cpp fill_params)
+                    if (sc.materials[mat].flags & q.defer_flags) {  // MF_EVAL_METAL and / or MF_TEXTURED, the host's choice (api_pt.cpp pt_plan)
                         r.d_gid = hit.gid; r.d_u = hit.u; r.d_v = hit.v;
                         r.deferred = true;
                         r.has_ray = false;  // path_step resolves the shadow ray and finishes the previous sample, no more

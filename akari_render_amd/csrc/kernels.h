@@ -9,7 +9,7 @@
 
 #if !defined(__HIPCC_RTC__)
 #include <algorithm>
-// Which instantiation of pt_pass_body (device/pt_pass.h) a pt session runs, decided once per session (host/api_pt.cpp pt_decide) and
+// Which instantiation of pt_pass_body (device/pt_pass.h) a pt session runs, decided once per session (host/api_pt.cpp pt_plan) and
 // carried by the session; the launchers, the per-scene kernel's wrapper text and akr_pt_kernel_info all read it. Host side only, and
 // outside the namespace: the relaxed tier's translation unit compiles this header inside another one (pt_kernels_relaxed.hip).
 struct PtVariant {
@@ -60,8 +60,12 @@ namespace akr {
 // LDS columns per lane (one word per slot, slot s of lane i at word s * 256 + i): cold path state parked while a vertex is shaded
 // (dpath.h: PARK), and a traversal carried over to the next intersection phase (device/pt_pass.h).
 constexpr uint32_t kParkSlots = 16, kParkSlotsNoDefer = 13;  // dpath.h: PK_*
-constexpr uint32_t kCarrySlots = 13;                         // device/pt_pass.h: a carried traversal
-constexpr uint32_t kCarrySlotsInstanced = 16;                // ... of a scene kept as meshes + instances (dinst_trav.h)
+// The columns of a carried traversal (device/pt_pass.h, dinst_trav.h trace_pair_inst): best hit so far | place in the tree | which of the vertex's
+// two rays | the first ray's hit | kept scenes (dinst_trav.h): TLAS leaf of the instance the ray is in, the candidate waiting for its exact test.
+// A carried ray of the wavefront schedule (wf_kernels.hip, WfBuffers::carry) keeps the same groups of four (carry_best, carry_place, carry_inst).
+enum : uint32_t { CY_BEST_T = 0, CY_BEST_U, CY_BEST_V, CY_BEST, CY_G, CY_T, CY_TBASE, CY_SP, CY_PHASE, CY_HIT_T, CY_HIT_U, CY_HIT_V, CY_HIT_GID, CY_END,
+                  CY_LEAF = CY_END, CY_PEND_REC, CY_PEND_INST, CY_END_INST };
+constexpr uint32_t kCarrySlots = CY_END, kCarrySlotsInstanced = CY_END_INST;  // 13, 16
 constexpr size_t kBlueNoiseColumnBytes = 48 * 256 * 2;          // dpath.h pmj_bluenoise_stage: one u16 per array and lane
 #if !defined(__HIPCC_RTC__)
 // Dynamic LDS of a pt launch (k_pt_pass, k_pt_pass_inst, a per-scene kernel) and where its blocks start, in this order:

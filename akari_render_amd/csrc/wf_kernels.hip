@@ -33,30 +33,23 @@ AKR_D void wf_trav_begin(T& s, vec3 o, vec3 d, float tmin, float tmax, uint32_t 
 // group must drain, and a launch of its own per fifty steps would cost more than the tail). Nothing a path computes changes -- the iteration in
 // which a vertex is shaded does, as with the megakernel's stragglers (pt_pass.h). Measured with 8 / 16 / 32 / 48 lanes and 16 / 48 / 128 steps: all
 // within 2 % of each other (1080p forest x 100 k: 172 -- 177 Msamples/s against 124 without).
+// A record is the carried traversal of disect.h / dinst_trav.h (carry_best | carry_place | carry_inst: the fields and order of kernels.h CY_*) as
+// 16-byte groups, then the stack.
 template <bool INST, class T>
 AKR_D void wf_carry_save(const WfBuffers& wf, const T& s, const uint32_t* __restrict__ stack, uint32_t slot, bool any) {
     uint32_t* c = wf.carry + ((size_t)(any ? wf.n_slots : 0u) + slot) * wf.carry_words;  // (carry_words is a multiple of 4: 16-byte aligned records)
-    ((uint4*)c)[0] = make_uint4(f2u(s.best_t), f2u(s.best_u), f2u(s.best_v), s.best);
-    ((uint4*)c)[1] = make_uint4(s.G, s.T, s.tbase, s.sp);
-    if constexpr (INST) ((uint4*)c)[2] = make_uint4(s.leaf, s.pend_rec, s.pend_inst, 0u);
+    ((uint4*)c)[0] = carry_best(s);
+    ((uint4*)c)[1] = carry_place(s);
+    if constexpr (INST) ((uint4*)c)[2] = carry_inst(s);
     for (uint32_t k = 0; k < s.sp; k++) c[12u + k] = stack[k * 256u];
 }
 template <bool INST, class T>
 AKR_D void wf_carry_restore(const DScene& sc, const WfBuffers& wf, T& s, uint32_t* __restrict__ stack, uint32_t slot, bool any) {  // (after wf_trav_begin on the slot's ray)
     const uint32_t* c = wf.carry + ((size_t)(any ? wf.n_slots : 0u) + slot) * wf.carry_words;
     const uint4 a = ((const uint4*)c)[0], b = ((const uint4*)c)[1];
-    s.best_t = u2f(a.x); s.best_u = u2f(a.y); s.best_v = u2f(a.z); s.best = a.w;
-    s.G = b.x; s.T = b.y; s.tbase = b.z; s.sp = b.w;
-    for (uint32_t k = 0; k < s.sp; k++) stack[k * 256u] = c[12u + k];
-    if constexpr (INST) {
-        const uint4 d = ((const uint4*)c)[2];
-        s.leaf = d.x; s.pend_rec = d.y; s.pend_inst = d.z;
-        if (s.leaf != kInvalid) {
-            const uint4* lf = sc.in2.tlas_leaves + (size_t)s.leaf * 4;
-            trav_into_instance(sc, s, lf[0], lf[1], lf[2], lf[3]);
-        }
-    }
-    s.active = (s.T != 0) | ((s.G >> 24) != 0) | (s.sp != 0);
+    for (uint32_t k = 0; k < b.w; k++) stack[k * 256u] = c[12u + k];
+    if constexpr (INST) trav_resume(sc, s, a, b, ((const uint4*)c)[2]);
+    else trav_resume(sc, s, a, b);
 }
 
 // Persistent traversal kernel. Ray id = slot; ids [0, n_closest) come from the closest-hit queue, the rest from the
@@ -144,6 +137,9 @@ __global__ __launch_bounds__(256, INST ? AKR_WF_TRACE_INST_WAVES : 1) void k_wf_
                         __builtin_popcountll(__builtin_amdgcn_ballot_w64(pending)) >= AKR_INST_QUORUM) {
                         waited = 0;
                         if (pending) resolve_pending<TEX>(sc, s, any);
+#if defined(AKR_INST_PRETEST_CHECK)
+                        if (s.check_t == -2.0f) cnt.overflow = 1;
+#endif
                     }
                 }
                 finished = has && !s.active && s.pend_rec == kInvalid;
