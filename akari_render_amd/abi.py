@@ -228,7 +228,8 @@ class DenoiseConfig(_Struct):
         ("sigma_normal", C.c_float),
         ("sigma_albedo", C.c_float),
         ("albedo_floor", C.c_float),
-        ("_pad", C.c_uint32 * 2),
+        ("sigma_variance", C.c_float),  # akr_denoise_variance alone
+        ("_pad", C.c_uint32),
     ]
 
     @staticmethod
@@ -236,6 +237,7 @@ class DenoiseConfig(_Struct):
         c = DenoiseConfig()
         c.iterations, c.demodulate = 5, 1
         c.sigma_color, c.sigma_normal, c.sigma_albedo, c.albedo_floor = 2.0, 0.125, 0.0625, 1e-3
+        c.sigma_variance = 8.0
         return c
 
 

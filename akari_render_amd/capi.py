@@ -42,7 +42,7 @@ EXPORTS = [
     "akr_pt_kernel_info", "akr_scene_spec_source", "akr_host_spec_compile", "akr_host_spec_compile_text",
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
     "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
-    "akr_denoise_config_default", "akr_denoise",
+    "akr_denoise_config_default", "akr_denoise", "akr_denoise_variance",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -53,7 +53,7 @@ TEST_EXPORTS = [
     "akr_probe_material_folded_host", "akr_host_sobol_dim1", "akr_host_fastmod", "akr_host_tri_pretest",
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
     "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2", "akr_host_denoise", "akr_probe_denoise_times",
-    "akr_host_pt_launch_plan",
+    "akr_host_pt_launch_plan", "akr_host_denoise_variance", "akr_probe_denoise_variance_times",
 ]
 
 
@@ -210,6 +210,9 @@ def lib() -> C.CDLL:
     proto("akr_denoise", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp)
     proto("akr_host_denoise", C.POINTER(abi.DenoiseConfig), u32, u32, fp, f32, fp, f32, fp, f32, fp)
     proto("akr_probe_denoise_times", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, i32, fp)
+    proto("akr_denoise_variance", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, vp)
+    proto("akr_host_denoise_variance", C.POINTER(abi.DenoiseConfig), u32, u32, fp, f32, fp, fp, f32, fp, f32, fp)
+    proto("akr_probe_denoise_variance_times", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, vp, i32, fp)
     _lib = L
     return L
 
@@ -487,7 +490,7 @@ class Scene:
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step)."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes)."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 
@@ -888,6 +891,40 @@ def host_denoise(width: int, height: int, color: np.ndarray, albedo: Optional[np
     out = np.zeros(3 * width * height, dtype=np.float32)
     ptr = [_fp(f) if f is not None else None for f in films]
     check(lib().akr_host_denoise(C.byref(c), width, height, ptr[0], splat_scales[0], ptr[1], splat_scales[1], ptr[2], splat_scales[2], _fp(out)))
+    return out.reshape(height, width, 3)
+
+
+def denoise_variance(ctx: Context, color: Film, half: Film, albedo: Optional[Film], normal: Optional[Film], out: Film, cfg: Optional[abi.DenoiseConfig] = None) -> None:
+    """akr_denoise_variance: akr_denoise with per-pixel colour weights from the variance between `half` (the colour film after a subset of
+    its samples) and the rest of `color` (DESIGN.md 4.10 "Variance guide"). out may be `color`, not `half`."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    check(lib().akr_denoise_variance(ctx.h, C.byref(c), color.h, half.h if half is not None else None, albedo.h if albedo is not None else None,
+                                     normal.h if normal is not None else None, out.h))
+
+
+def denoise_variance_times(ctx: Context, color: Film, half: Film, albedo: Optional[Film], normal: Optional[Film], out: Film, kernel: int,
+                           cfg: Optional[abi.DenoiseConfig] = None) -> dict:
+    """akr_probe_denoise_variance_times (test hook): akr_denoise_variance under level kernel `kernel`, its parts timed by HIP events (ms); "prepare" includes the prefilter."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    t = np.zeros(11, dtype=np.float32)
+    check(lib().akr_probe_denoise_variance_times(ctx.h, C.byref(c), color.h, half.h, albedo.h if albedo is not None else None,
+                                                 normal.h if normal is not None else None, out.h, kernel, _fp(t)))
+    return {"prepare": float(t[0]), "levels": [float(v) for v in t[1:1 + c.iterations]], "finish": float(t[9]), "total": float(t[10])}
+
+
+def host_denoise_variance(width: int, height: int, color: np.ndarray, half: np.ndarray, albedo: Optional[np.ndarray] = None, normal: Optional[np.ndarray] = None,
+                          cfg: Optional[abi.DenoiseConfig] = None, splat_scales=(1.0, 1.0, 1.0)) -> np.ndarray:
+    """akr_host_denoise_variance (test hook): akr_denoise_variance's arithmetic on the host; `half` a raw film accumulator like `color`. -> (H, W, 3)."""
+    c = cfg if cfg is not None else abi.DenoiseConfig.default()
+    films = []
+    for f in (color, half, albedo, normal):
+        if f is not None:
+            f = np.ascontiguousarray(f, dtype=np.float32).reshape(-1)
+            assert f.size == 7 * width * height
+        films.append(f)
+    out = np.zeros(3 * width * height, dtype=np.float32)
+    ptr = [_fp(f) if f is not None else None for f in films]
+    check(lib().akr_host_denoise_variance(C.byref(c), width, height, ptr[0], splat_scales[0], ptr[1], ptr[2], splat_scales[1], ptr[3], splat_scales[2], _fp(out)))
     return out.reshape(height, width, 3)
 
 

@@ -97,6 +97,127 @@ __global__ void __launch_bounds__(256) k_denoise_finish(const float4* __restrict
     film[6 * n + i] = 1.0f;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// akr_denoise_variance (DESIGN.md 4.10 "Variance guide"): records {x.rgb, v | -1}, {n.xyz, r | -1}, {a.rgb, -} (device/ddenoise.h)
+__global__ void __launch_bounds__(256) k_denoise_prepare_var(const float* __restrict__ color, float color_scale, const float* __restrict__ half,
+                                                             const float* __restrict__ albedo, float albedo_scale, const float* __restrict__ normal,
+                                                             float normal_scale, uint64_t n, uint32_t demodulate, float albedo_floor, DenoiseRecords rec) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float4 x, nn, a;
+    dn_prepare_pixel_var(color, color_scale, half, albedo, albedo_scale, normal, normal_scale, n, i, demodulate != 0, albedo_floor, x, nn, a);
+    rec.x[i] = x;
+    rec.n[i] = nn;
+    rec.a[i] = a;
+}
+
+// The lane-to-pixel mapping of the tiled kernels: column = lane & 15, and the row such that each of the four 16-lane groups that serve a
+// 16-byte LDS read lies in one tile row (k_denoise_level_tiled's comment)
+__device__ __forceinline__ void dn_tile_lane(int& lx, int& ly) {
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, quad = (lane >> 2) & 7;
+    lx = lane & 15;
+    ly = wave * 4 + ((lane >> 5) << 1) + ((((quad + 1) >> 1) & 1) ^ (quad >> 2));
+}
+
+// The prefilter: v0 = the 7 x 7 guide-weighted mean of the two-half estimates, written into x.w of every valid pixel. A workgroup takes
+// 16 x 16 pixels, loads their n and a records and a halo of 3 -- 22 x 22 x 2 records, 15 488 bytes -- and reads every tap from LDS, lanes
+// laid over the tile as in k_denoise_level_tiled. A record outside the image is stored without an estimate.
+constexpr int kDnVarHalo = 3, kDnVarPitch = kDnTile + 2 * kDnVarHalo;
+__global__ void __launch_bounds__(256) k_denoise_variance(DenoiseLevel lv, float4* __restrict__ xs, const float4* __restrict__ ns, const float4* __restrict__ as,
+                                                          uint32_t tiles_x) {
+    __shared__ float4 sn[kDnVarPitch * kDnVarPitch], sa[kDnVarPitch * kDnVarPitch];
+    const int W = (int)lv.width, H = (int)lv.height;
+    const int x0 = (int)(blockIdx.x % tiles_x) * kDnTile, y0 = (int)(blockIdx.x / tiles_x) * kDnTile;
+    for (int t = (int)threadIdx.x; t < kDnVarPitch * kDnVarPitch; t += 256) {
+        const int j = t / kDnVarPitch, i = t - j * kDnVarPitch;
+        const int X = x0 + i - kDnVarHalo, Y = y0 + j - kDnVarHalo;
+        float4 n = make_float4(0.0f, 0.0f, 0.0f, -1.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (X >= 0 && Y >= 0 && X < W && Y < H) {
+            const size_t q = (size_t)Y * W + X;
+            n = ns[q];
+            a = as[q];
+        }
+        sn[t] = n;
+        sa[t] = a;
+    }
+    __syncthreads();
+    int lx, ly;
+    dn_tile_lane(lx, ly);
+    const int px = x0 + lx, py = y0 + ly;
+    if (px >= W || py >= H) return;
+    const size_t p = (size_t)py * W + px;
+    float4 x = xs[p];
+    if (!dn_var_valid(x)) return;
+    const int centre = (ly + kDnVarHalo) * kDnVarPitch + lx + kDnVarHalo;
+    x.w = dn_prefilter_pixel(px, py, lv, [&](int dx, int dy, float4& nq, float4& aq) {
+        const int q = centre + dy * kDnVarPitch + dx;
+        nq = sn[q];
+        aq = sa[q];
+        return !(nq.w < 0.0f);
+    });
+    xs[p] = x;
+}
+
+// k_denoise_level with the variance-guided level
+__global__ void __launch_bounds__(256) k_denoise_level_var(DenoiseLevel lv, const float4* __restrict__ xs, const float4* __restrict__ ns,
+                                                           const float4* __restrict__ as, float4* __restrict__ x_out, uint32_t blocks_x) {
+    const uint32_t bx = blockIdx.x % blocks_x, by = blockIdx.x / blocks_x;
+    const int px = (int)(bx * 32 + (threadIdx.x & 31)), py = (int)(by * 8 + (threadIdx.x >> 5));
+    if (px >= (int)lv.width || py >= (int)lv.height) return;
+    const int s = (int)lv.step, W = (int)lv.width;
+    const float4 y = dn_level_pixel_var(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
+        const size_t q = (size_t)(py + s * dy) * W + (px + s * dx);
+        xq = xs[q];
+        nq = ns[q];
+        aq = as[q];
+        return dn_var_valid(xq);
+    });
+    x_out[(size_t)py * W + px] = y;
+}
+
+// k_denoise_level_tiled with the variance-guided level: the same residue-class tiles, the same 19 200 bytes, the same lane mapping; the 3 x 3
+// taps of g lie inside the 5 x 5 of the tile. A record outside the image is stored invalid (x.w = -1).
+__global__ void __launch_bounds__(256) k_denoise_level_var_tiled(DenoiseLevel lv, const float4* __restrict__ xs, const float4* __restrict__ ns,
+                                                                 const float4* __restrict__ as, float4* __restrict__ x_out, uint32_t tiles_x) {
+    __shared__ float4 sx[kDnPitch * kDnPitch], sn[kDnPitch * kDnPitch], sa[kDnPitch * kDnPitch];
+    const int s = (int)lv.step, W = (int)lv.width, H = (int)lv.height;
+    uint32_t b = blockIdx.x;
+    const int rx = (int)(b % lv.step);
+    b /= lv.step;
+    const int ry = (int)(b % lv.step);
+    b /= lv.step;
+    const int cx0 = (int)(b % tiles_x) * kDnTile, cy0 = (int)(b / tiles_x) * kDnTile;  // the tile's origin in class coordinates
+    if (rx + s * cx0 >= W || ry + s * cy0 >= H) return;  // a class with fewer tiles than the widest one (the whole workgroup leaves)
+    for (int t = (int)threadIdx.x; t < kDnPitch * kDnPitch; t += 256) {
+        const int j = t / kDnPitch, i = t - j * kDnPitch;
+        const int X = rx + s * (cx0 + i - kDnHalo), Y = ry + s * (cy0 + j - kDnHalo);
+        float4 x = make_float4(0.0f, 0.0f, 0.0f, -1.0f), n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = n;
+        if (X >= 0 && Y >= 0 && X < W && Y < H) {
+            const size_t q = (size_t)Y * W + X;
+            x = xs[q];
+            n = ns[q];
+            a = as[q];
+        }
+        sx[t] = x;
+        sn[t] = n;
+        sa[t] = a;
+    }
+    __syncthreads();
+    int lx, ly;
+    dn_tile_lane(lx, ly);
+    const int px = rx + s * (cx0 + lx), py = ry + s * (cy0 + ly);
+    if (px >= W || py >= H) return;
+    const int centre = (ly + kDnHalo) * kDnPitch + lx + kDnHalo;
+    const float4 y = dn_level_pixel_var(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
+        const int q = centre + dy * kDnPitch + dx;
+        xq = sx[q];
+        nq = sn[q];
+        aq = sa[q];
+        return dn_var_valid(xq);
+    });
+    x_out[(size_t)py * W + px] = y;
+}
+
 hipError_t launch_denoise_prepare(const float* color, float color_scale, const float* albedo, float albedo_scale, const float* normal, float normal_scale,
                                   uint64_t n, uint32_t demodulate, float albedo_floor, DenoiseRecords rec, hipStream_t stream) {
     launch_kernel(k_denoise_prepare, (uint32_t)((n + 255) / 256), 0, stream, color, color_scale, albedo, albedo_scale, normal, normal_scale, n, demodulate, albedo_floor, rec);
@@ -110,6 +231,27 @@ hipError_t launch_denoise_level(const DenoiseLevel& lv, DenoiseRecords rec, floa
     } else {
         const uint32_t blocks_x = (lv.width + 31) / 32, blocks_y = (lv.height + 7) / 8;
         launch_kernel(k_denoise_level, blocks_x * blocks_y, 0, stream, lv, (const float4*)rec.x, (const float4*)rec.n, (const float4*)rec.a, x_out, blocks_x);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_denoise_prepare_var(const float* color, float color_scale, const float* half, const float* albedo, float albedo_scale, const float* normal,
+                                      float normal_scale, uint64_t n, uint32_t demodulate, float albedo_floor, DenoiseRecords rec, hipStream_t stream) {
+    launch_kernel(k_denoise_prepare_var, (uint32_t)((n + 255) / 256), 0, stream, color, color_scale, half, albedo, albedo_scale, normal, normal_scale, n, demodulate, albedo_floor, rec);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_variance(const DenoiseLevel& lv, DenoiseRecords rec, hipStream_t stream) {
+    const uint32_t tiles_x = (lv.width + kDnTile - 1) / kDnTile, tiles_y = (lv.height + kDnTile - 1) / kDnTile;
+    launch_kernel(k_denoise_variance, tiles_x * tiles_y, 0, stream, lv, rec.x, (const float4*)rec.n, (const float4*)rec.a, tiles_x);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_level_var(const DenoiseLevel& lv, DenoiseRecords rec, float4* x_out, bool tiled, hipStream_t stream) {
+    if (tiled) {
+        const uint32_t cw = (lv.width + lv.step - 1) / lv.step, ch = (lv.height + lv.step - 1) / lv.step;  // the largest class
+        const uint32_t tiles_x = (cw + kDnTile - 1) / kDnTile, tiles_y = (ch + kDnTile - 1) / kDnTile;
+        launch_kernel(k_denoise_level_var_tiled, tiles_x * tiles_y * lv.step * lv.step, 0, stream, lv, (const float4*)rec.x, (const float4*)rec.n, (const float4*)rec.a, x_out, tiles_x);
+    } else {
+        const uint32_t blocks_x = (lv.width + 31) / 32, blocks_y = (lv.height + 7) / 8;
+        launch_kernel(k_denoise_level_var, blocks_x * blocks_y, 0, stream, lv, (const float4*)rec.x, (const float4*)rec.n, (const float4*)rec.a, x_out, blocks_x);
     }
     return hipGetLastError();
 }

@@ -100,6 +100,108 @@ AKR_HD void dn_prepare_pixel(const float* color, float color_scale, const float*
     x.w = valid ? 1.0f : 0.0f;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The variance guide of akr_denoise_variance (DESIGN.md 4.10 "Variance guide"). The records differ from the ones above in their fourth
+// components: x = {x.rgb, v} with v the variance of the pixel's colour, and -1 for an invalid pixel (valid <=> !(x.w < 0));
+// n = {n.xyz, r} with r the pixel's own two-half estimate, and -1 where there is none. A level reads lv.kc as kv = 1 / sigma_variance^2.
+AKR_HD bool dn_var_valid(const float4& x) { return !(x.w < 0.0f); }
+
+// dn_prepare_pixel plus the two-half estimate r = |xA - xB|^2 (wA wB) / (C.w C.w) of `half`, the colour film as it stood after a subset
+// of the samples (its splat plane is not read)
+AKR_HD void dn_prepare_pixel_var(const float* color, float color_scale, const float* half, const float* albedo, float albedo_scale, const float* normal,
+                                 float normal_scale, uint64_t n, uint64_t i, bool demodulate, float albedo_floor, float4& x, float4& nn, float4& a) {
+    dn_prepare_pixel(color, color_scale, albedo, albedo_scale, normal, normal_scale, n, i, demodulate, albedo_floor, x, nn, a);
+    const bool valid = x.w != 0.0f;
+    const float4 d = dn_divisor(a, demodulate, albedo_floor);
+    const float wc = color[6 * n + i];
+    const float wa = half[6 * n + i], wb = wc - wa;
+    float4 xa, xb;
+    xa.x = (half[3 * i + 0] / wa) / d.x;
+    xa.y = (half[3 * i + 1] / wa) / d.y;
+    xa.z = (half[3 * i + 2] / wa) / d.z;
+    xb.x = ((color[3 * i + 0] - half[3 * i + 0]) / wb) / d.x;
+    xb.y = ((color[3 * i + 1] - half[3 * i + 1]) / wb) / d.y;
+    xb.z = ((color[3 * i + 2] - half[3 * i + 2]) / wb) / d.z;
+    xa.w = xb.w = 0.0f;
+    const float f = (wa * wb) / (wc * wc);
+    const float r = dn_dist2(xa, xb) * f;
+    const bool est = valid && wa > 0.0f && wb > 0.0f && dn_finite(r);
+    x.w = valid ? 0.0f : -1.0f;
+    nn.w = est ? r : -1.0f;
+}
+
+// v0 of the valid pixel (px, py): the 7 x 7 guide-weighted mean of the estimates r. fetch(dx, dy, nq, aq) -> bool reads the n and a records
+// of the in-image pixel (px, py) + (dx, dy) and says whether it carries an estimate (nq.w, then)
+template <class Fetch>
+AKR_HD float dn_prefilter_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& fetch) {
+    float4 np_, ap;
+    (void)fetch(0, 0, np_, ap);
+    float num = 0.0f, den = 0.0f;
+    for (int dy = -3; dy <= 3; dy++) {
+        const int qy = py + dy;
+        for (int dx = -3; dx <= 3; dx++) {
+            const int qx = px + dx;
+            if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
+            float4 nq, aq;
+            if (!fetch(dx, dy, nq, aq)) continue;
+            const float m = exp_f(-(dn_dist2(np_, nq) * lv.kn + dn_dist2(ap, aq) * lv.ka));
+            num = num + m * nq.w;
+            den = den + m;
+        }
+    }
+    return den > 0.0f ? num / den : 0.0f;
+}
+
+// G = {1/4, 1/2, 1/4}
+AKR_HD float dn_g3(int d) { return d == 0 ? 0.5f : 0.25f; }
+
+// The record x = {y.rgb, v'} of pixel (px, py) after one variance-guided level; fetch as for dn_level_pixel, valid <=> dn_var_valid(xq)
+template <class Fetch>
+AKR_HD float4 dn_level_pixel_var(int px, int py, const DenoiseLevel& lv, Fetch&& fetch) {
+    float4 xp, np_, ap;
+    if (!fetch(0, 0, xp, np_, ap)) return xp;  // an invalid centre passes through unchanged
+    const int s = (int)lv.step;
+    // g: the variance smoothed over the 3 x 3 taps of the level's own lattice
+    float gn = 0.0f, gd = 0.0f;
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = py + s * dy;
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = px + s * dx;
+            if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
+            float4 xq, nq, aq;
+            if (!fetch(dx, dy, xq, nq, aq)) continue;
+            const float gw = dn_g3(dx) * dn_g3(dy);
+            gn = gn + gw * xq.w;
+            gd = gd + gw;
+        }
+    }
+    const float g = gn / gd;
+    DenoiseLevel lp = lv;
+    lp.kc = lv.kc / (g + 1e-10f);
+    float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, vacc = 0.0f, wsum = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = py + s * dy;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = px + s * dx;
+            if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
+            float4 xq, nq, aq;
+            if (!fetch(dx, dy, xq, nq, aq)) continue;
+            const float w = dn_tap_weight(dn_b3(dx) * dn_b3(dy), xp, np_, ap, xq, nq, aq, lp);
+            acc0 = acc0 + w * xq.x;
+            acc1 = acc1 + w * xq.y;
+            acc2 = acc2 + w * xq.z;
+            vacc = vacc + (w * w) * xq.w;
+            wsum = wsum + w;
+        }
+    }
+    float4 y;
+    y.x = acc0 / wsum;
+    y.y = acc1 / wsum;
+    y.z = acc2 / wsum;
+    y.w = vacc / (wsum * wsum);
+    return y;
+}
+
 // out = y d
 AKR_HD void dn_finish_pixel(const float4& y, const float4& a, bool demodulate, float albedo_floor, float out[3]) {
     const float4 d = dn_divisor(a, demodulate, albedo_floor);

@@ -23,6 +23,15 @@ void check_config(const akr_denoise_config& c) {
         throw std::invalid_argument("akr_denoise: a sigma is too small: 1 / sigma^2 (sigma_color at the last level: sigma_color 2^-(iterations - 1)) is not finite in f32");
 }
 
+// akr_denoise_variance: akr_denoise's refusals and those of sigma_variance. kv / (g + 1e-10f) has to stay finite for g = 0
+void check_config_variance(const akr_denoise_config& c) {
+    check_config(c);
+    if (!(c.sigma_variance > 0.0f && c.sigma_variance <= 3.4028235e38f)) throw std::invalid_argument("akr_denoise_variance: sigma_variance must be finite and > 0");
+    const float kv = 1.0f / (c.sigma_variance * c.sigma_variance);
+    if (!(kv / 1e-10f <= 3.4028235e38f))
+        throw std::invalid_argument("akr_denoise_variance: sigma_variance is too small: (1 / sigma_variance^2) / 1e-10 is not finite in f32");
+}
+
 // k = 1 / sigma^2 in f32; a sigma of exactly 0 switches the term off
 float inv_sigma2(float sigma) { return sigma == 0.0f ? 0.0f : 1.0f / (sigma * sigma); }
 
@@ -37,15 +46,27 @@ DenoiseLevel level_params(const akr_denoise_config& c, uint32_t w, uint32_t h, u
     return lv;
 }
 
+// The same for a variance-guided level: kc = kv = 1 / sigma_variance^2 at every level (the variance shrinks by itself)
+DenoiseLevel level_params_variance(const akr_denoise_config& c, uint32_t w, uint32_t h, uint32_t i, bool have_albedo, bool have_normal) {
+    DenoiseLevel lv = level_params(c, w, h, i, have_albedo, have_normal);
+    lv.kc = 1.0f / (c.sigma_variance * c.sigma_variance);
+    return lv;
+}
+
 // Which level kernel runs step s when option denoise_kernel leaves it to the library ("Cost": at 1920 x 1080 the tiled
 // kernel takes 0.47 / 0.49 / 0.59 of the gathering kernel's time at steps 1 / 2 / 4, 1.16 at step 8, the same at step 16)
 bool tiled_by_default(uint32_t step) { return step <= 4; }
 
 // The whole stage on the context's stream. kernel: -1 the library decides per step, 0 the gathering kernel, 1 the tiled one.
 // times (or nullptr): milliseconds of prepare, the levels [8], finish, the whole call [11] -- HIP events on the stream.
-void denoise_run(akr_context* ctx, const akr_denoise_config& cfg, akr_film* color, akr_film* albedo, akr_film* normal, akr_film* out, int kernel, float* times) {
-    check_config(cfg);
-    for (akr_film* f : {albedo, normal, out}) {
+// half = nullptr: akr_denoise. Else akr_denoise_variance: prepare is followed by the prefilter (both in times[0]) and the levels are the
+// variance-guided ones.
+void denoise_run(akr_context* ctx, const akr_denoise_config& cfg, akr_film* color, akr_film* half, akr_film* albedo, akr_film* normal, akr_film* out, int kernel,
+                 float* times) {
+    if (half) check_config_variance(cfg);
+    else check_config(cfg);
+    if (half && half == out) throw std::invalid_argument("akr_denoise_variance: the half film cannot be the output film");
+    for (akr_film* f : {half, albedo, normal, out}) {
         if (!f) continue;
         if (f->ctx != ctx || color->ctx != ctx) throw std::invalid_argument("akr_denoise: every film must belong to the context");
         if (f->width != color->width || f->height != color->height) throw std::invalid_argument("akr_denoise: the films differ in size");
@@ -74,13 +95,19 @@ void denoise_run(akr_context* ctx, const akr_denoise_config& cfg, akr_film* colo
     DenoiseRecords rec{bx0.as<float4>(), bn.as<float4>(), ba.as<float4>()};
     float4* other = bx1.as<float4>();
     mark();
-    HIP_CHECK(launch_denoise_prepare(color->data, color->splat_scale, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
-                                     normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
+    if (half) {
+        HIP_CHECK(launch_denoise_prepare_var(color->data, color->splat_scale, half->data, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
+                                             normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
+        HIP_CHECK(launch_denoise_variance(level_params_variance(cfg, w, h, 0, albedo != nullptr, normal != nullptr), rec, ctx->stream));
+    } else {
+        HIP_CHECK(launch_denoise_prepare(color->data, color->splat_scale, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
+                                         normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
+    }
     mark();
     for (uint32_t i = 0; i < cfg.iterations; i++) {
-        const DenoiseLevel lv = level_params(cfg, w, h, i, albedo != nullptr, normal != nullptr);
+        const DenoiseLevel lv = half ? level_params_variance(cfg, w, h, i, albedo != nullptr, normal != nullptr) : level_params(cfg, w, h, i, albedo != nullptr, normal != nullptr);
         const bool tiled = kernel < 0 ? tiled_by_default(lv.step) : kernel != 0;
-        HIP_CHECK(launch_denoise_level(lv, rec, other, tiled, ctx->stream));
+        HIP_CHECK(half ? launch_denoise_level_var(lv, rec, other, tiled, ctx->stream) : launch_denoise_level(lv, rec, other, tiled, ctx->stream));
         std::swap(rec.x, other);
         mark();
     }
@@ -111,12 +138,19 @@ AKR_API int32_t akr_denoise_config_default(akr_denoise_config* c) {
     c->sigma_normal = 0.125f;
     c->sigma_albedo = 0.0625f;
     c->albedo_floor = 1e-3f;
+    c->sigma_variance = 8.0f;  // the lowest point of DESIGN.md 4.10's sigma_variance table (read by akr_denoise_variance alone)
     return AKR_OK;
 }
 
 AKR_API int32_t akr_denoise(akr_context* ctx, const akr_denoise_config* cfg, akr_film* color, akr_film* albedo, akr_film* normal, akr_film* out) {
     if (!ctx || !cfg || !color || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_denoise: NULL argument");
-    return guarded([&] { denoise_run(ctx, *cfg, color, albedo, normal, out, tuning().denoise_kernel, nullptr); });
+    return guarded([&] { denoise_run(ctx, *cfg, color, nullptr, albedo, normal, out, tuning().denoise_kernel, nullptr); });
+}
+
+AKR_API int32_t akr_denoise_variance(akr_context* ctx, const akr_denoise_config* cfg, akr_film* color, akr_film* half, akr_film* albedo, akr_film* normal,
+                                     akr_film* out) {
+    if (!ctx || !cfg || !color || !half || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_denoise_variance: NULL argument");
+    return guarded([&] { denoise_run(ctx, *cfg, color, half, albedo, normal, out, tuning().denoise_kernel, nullptr); });
 }
 
 #if defined(AKR_TEST_HOOKS) && AKR_TEST_HOOKS
@@ -124,7 +158,14 @@ AKR_TEST_API int32_t akr_probe_denoise_times(akr_context* ctx, const akr_denoise
                                              int32_t kernel, float* times11) {
     if (!ctx || !cfg || !color || !out || !times11) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_denoise_times: NULL argument");
     if (kernel < -1 || kernel > 1) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_denoise_times: kernel is -1, 0 or 1");
-    return guarded([&] { denoise_run(ctx, *cfg, color, albedo, normal, out, kernel, times11); });
+    return guarded([&] { denoise_run(ctx, *cfg, color, nullptr, albedo, normal, out, kernel, times11); });
+}
+
+AKR_TEST_API int32_t akr_probe_denoise_variance_times(akr_context* ctx, const akr_denoise_config* cfg, akr_film* color, akr_film* half, akr_film* albedo,
+                                                      akr_film* normal, akr_film* out, int32_t kernel, float* times11) {
+    if (!ctx || !cfg || !color || !half || !out || !times11) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_denoise_variance_times: NULL argument");
+    if (kernel < -1 || kernel > 1) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_denoise_variance_times: kernel is -1, 0 or 1");
+    return guarded([&] { denoise_run(ctx, *cfg, color, half, albedo, normal, out, kernel, times11); });
 }
 
 AKR_TEST_API int32_t akr_host_denoise(const akr_denoise_config* cfg, uint32_t width, uint32_t height, const float* color_film, float color_splat_scale,
@@ -149,6 +190,48 @@ AKR_TEST_API int32_t akr_host_denoise(const akr_denoise_config* cfg, uint32_t wi
                         nq = nn[q];
                         aq = a[q];
                         return xq.w != 0.0f;
+                    });
+            x.swap(y);
+        }
+        for (uint64_t i = 0; i < n; i++) dn_finish_pixel(x[i], a[i], demodulate, cfg->albedo_floor, out_rgb + 3 * i);
+    });
+}
+
+AKR_TEST_API int32_t akr_host_denoise_variance(const akr_denoise_config* cfg, uint32_t width, uint32_t height, const float* color_film, float color_splat_scale,
+                                               const float* half_film, const float* albedo_film, float albedo_splat_scale, const float* normal_film,
+                                               float normal_splat_scale, float* out_rgb) {
+    if (!cfg || !color_film || !half_film || !out_rgb || !width || !height) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_denoise_variance: bad argument");
+    return guarded([&] {
+        check_config_variance(*cfg);
+        const uint64_t n = (uint64_t)width * height;
+        const bool demodulate = cfg->demodulate && albedo_film;
+        std::vector<float4> x(n), y(n), nn(n), a(n);
+        for (uint64_t i = 0; i < n; i++)
+            dn_prepare_pixel_var(color_film, color_splat_scale, half_film, albedo_film, albedo_splat_scale, normal_film, normal_splat_scale, n, i, demodulate,
+                                 cfg->albedo_floor, x[i], nn[i], a[i]);
+        const DenoiseLevel lv0 = level_params_variance(*cfg, width, height, 0, albedo_film != nullptr, normal_film != nullptr);
+        for (int py = 0; py < (int)height; py++)
+            for (int px = 0; px < (int)width; px++) {
+                const size_t p = (size_t)py * width + px;
+                if (!dn_var_valid(x[p])) continue;
+                x[p].w = dn_prefilter_pixel(px, py, lv0, [&](int dx, int dy, float4& nq, float4& aq) {
+                    const size_t q = (size_t)(py + dy) * width + (px + dx);
+                    nq = nn[q];
+                    aq = a[q];
+                    return !(nq.w < 0.0f);
+                });
+            }
+        for (uint32_t it = 0; it < cfg->iterations; it++) {
+            const DenoiseLevel lv = level_params_variance(*cfg, width, height, it, albedo_film != nullptr, normal_film != nullptr);
+            const int s = (int)lv.step;
+            for (int py = 0; py < (int)height; py++)
+                for (int px = 0; px < (int)width; px++)
+                    y[(size_t)py * width + px] = dn_level_pixel_var(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
+                        const size_t q = (size_t)(py + s * dy) * width + (px + s * dx);
+                        xq = x[q];
+                        nq = nn[q];
+                        aq = a[q];
+                        return dn_var_valid(xq);
                     });
             x.swap(y);
         }

@@ -20,7 +20,8 @@ std::string denoised_path(const std::string& out) {
 
 // Option "denoise" (DESIGN.md 4.10): the feature passes of a finished pt task -- albedo and ns (not remapped) at `spp` samples with the task's
 // sampler, seed, filter and colour pipeline, through the scene's lens if it has one -- then akr_denoise with its defaults, in place in `film`.
-void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, akr_film* film, uint32_t spp, bool verbose) {
+// half (option "denoise_variance"): the film after the first half of the task's passes; the filter is akr_denoise_variance then.
+void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, akr_film* film, akr_film* half, uint32_t spp, bool verbose) {
     auto check = [](int32_t rc) { if (rc != AKR_OK) throw std::runtime_error(std::string(g_last_error)); };
     akr_aov_config ac;
     check(akr_aov_config_default(&ac));
@@ -41,7 +42,7 @@ void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, 
     check(akr_aov_render(ctx, scene, &ac, normal.f, &sn));
     akr_denoise_config dc;
     check(akr_denoise_config_default(&dc));
-    check(akr_denoise(ctx, &dc, film, albedo.f, normal.f, film));
+    check(half ? akr_denoise_variance(ctx, &dc, film, half, albedo.f, normal.f, film) : akr_denoise(ctx, &dc, film, albedo.f, normal.f, film));
     if (verbose) std::fprintf(stderr, "[akari_hip] Denoised (feature passes of %u spp: %.2fms)\n", spp, sa.kernel_ms + sn.kernel_ms);
 }
 }  // namespace
@@ -54,7 +55,9 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
     akr_render_session ses{0, 0, nullptr, 0, 0};
     if (session) ses = *session;
     const std::string name = ses.name ? ses.name : "default";
-    const int denoise_spp = tuning().denoise;  // read once, like a session's options
+    const TuningOptions opts = tuning();  // read once, like a session's options
+    const int denoise_spp = opts.denoise;
+    const bool denoise_variance = denoise_spp > 0 && opts.denoise_variance != 0;
     return guarded([&] {
         std::vector<ParsedTask> tasks = parse_render_tasks(method_json_text, ses.override_sampler_independent != 0);
         const uint32_t w = scene->flat.camera.width, h = scene->flat.camera.height;
@@ -133,13 +136,37 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
                 if (stats_out) *stats_out = st;
                 continue;
             }
+            // option "denoise_variance": the film after the first floor(n_passes / 2) passes is kept as the half film of the denoise step
+            FilmHolder half;
+            uint32_t half_spp = 0;  // the sample count at which the half is taken; 0 = no half
+            if (denoise_variance) {
+                if (task.cfg.spp_per_pass == 0 || task.cfg.spp <= task.cfg.spp_per_pass) {
+                    akr_film_destroy(film);
+                    throw std::invalid_argument("akr_render_task: option denoise_variance needs a task of at least two passes: spp = " + std::to_string(task.cfg.spp) +
+                                                " is one pass at spp_per_pass = " + std::to_string(task.cfg.spp_per_pass));
+                }
+                const uint32_t n_passes = (task.cfg.spp + task.cfg.spp_per_pass - 1) / task.cfg.spp_per_pass;
+                half_spp = (n_passes / 2) * task.cfg.spp_per_pass;
+                check(akr_film_create(ctx, w, h, &half.f));
+            }
+            auto take_half = [&] {  // device to device, in the stream's order after the passes so far
+                check(guarded([&] {
+                    HIP_CHECK(hipMemcpyAsync(half.f->data, film->data, film->n_floats() * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                }));
+            };
             check(akr_pt_begin(ctx, scene, &task.cfg, film, &se));
             std::string stats_json = "{\"intermediate\":[";
             uint32_t cnt = 0;
             bool first = true;
+            if (half_spp && !ses.save_intermediate) {
+                check(akr_pt_passes(se, half_spp / task.cfg.spp_per_pass, 1, &cnt));
+                take_half();
+            }
             while (cnt < task.cfg.spp) {  // pt.rs:1126-1149
                 if (ses.save_intermediate) {
                     check(akr_pt_passes(se, 1, 1, &cnt));
+                    if (half_spp && cnt == half_spp) take_half();
                     akr_pt_stats st;
                     check(akr_pt_get_stats(se, &st));
                     check(akr_film_resolve(film, rgb.data()));
@@ -172,7 +199,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
             write_image(task.film_out, rgb.data(), w, h);  // util::write_image(&output_image, &config.film.out), lib.rs:192
             if (stats_out) *stats_out = st;
             if (denoise_spp > 0) {  // option "denoise": film.out is written as ever, the denoised image next to it
-                denoise_step(ctx, scene, task.cfg, done.f, (uint32_t)denoise_spp, ses.verbose != 0);
+                denoise_step(ctx, scene, task.cfg, done.f, half.f, (uint32_t)denoise_spp, ses.verbose != 0);
                 check(akr_film_resolve(done.f, rgb.data()));
                 write_image(denoised_path(task.film_out), rgb.data(), w, h);
             }

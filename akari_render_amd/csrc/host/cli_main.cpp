@@ -1,11 +1,12 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]]
+//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
 // with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 // --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
+// --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,7 +18,7 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
               "  -m, --method <METHOD>    Render method config file (\"type\": \"pt\")\n"
               "  -d, --device <DEVICE>    HIP device ordinal (default 0)\n"
@@ -26,7 +27,8 @@ static void usage() {
               "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files\n"
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
-              "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)");
+              "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
+              "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)");
 }
 
 // akari-cli --spec-compile <header file> <out.co> <arch> <flags> <min waves>: the library's helper process for per-scene kernels
@@ -52,7 +54,7 @@ int main(int argc, char** argv) {
     unsigned w = 0, h = 0;
     int dof = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
-    int denoise = 0;
+    int denoise = 0, denoise_variance = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(1); } return argv[++i]; };
@@ -76,6 +78,7 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        else if (a == "--denoise-variance") denoise_variance = 1;
         else if (a == "--lens-radius" || a == "--focal-distance") {
             const char* text = next();
             char* end = nullptr;
@@ -104,6 +107,8 @@ int main(int argc, char** argv) {
     if (akr_context_create(device, &ctx) != AKR_OK) die("device");
     if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
     if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
+    if (denoise_variance && !denoise) { std::fputs("akari-cli: --denoise-variance needs --denoise\n", stderr); return 1; }
+    if (denoise_variance && akr_option_set("denoise_variance", 1) != AKR_OK) die("option denoise_variance");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
     if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
         akr_lens_desc lens;

@@ -830,6 +830,7 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_REBRAID")) g_tuning.rebraid = std::max(1, std::min(64, std::atoi(e)));
     if (const char* e = std::getenv("AKR_ARITH")) g_tuning.arith = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE")) g_tuning.denoise = std::max(0, std::min(65536, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_DENOISE_VARIANCE")) g_tuning.denoise_variance = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE_KERNEL")) g_tuning.denoise_kernel = std::max(-1, std::min(1, std::atoi(e)));
 }
 int* tuning_field(const char* name) {
@@ -853,6 +854,7 @@ int* tuning_field(const char* name) {
     if (n == "sched_trial") return &g_tuning.sched_trial;
     if (n == "pad_percent") return &g_tuning.pad_percent;
     if (n == "denoise") return &g_tuning.denoise;
+    if (n == "denoise_variance") return &g_tuning.denoise_variance;
     if (n == "denoise_kernel") return &g_tuning.denoise_kernel;
     return nullptr;
 }
@@ -882,6 +884,7 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.wavefront && (value < -1 || value > 1)) return false;
     if (f == &g_tuning.pad_percent && (value < 1 || value > 10000)) return false;
     if (f == &g_tuning.denoise && (value < 0 || value > 65536)) return false;
+    if (f == &g_tuning.denoise_variance && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.denoise_kernel && (value < -1 || value > 1)) return false;
     *f = value;
     return true;

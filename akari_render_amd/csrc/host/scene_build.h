@@ -235,6 +235,7 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   sched_trial  AKR_SCHED_TRIAL=<v>      flattened scenes, option wavefront = -1: -1 (default) = a long render of a large frame of a large untextured scene starts with two passes
 //                                         under each schedule and goes on with the faster; 0 = never (the megakernel); 1 = every pt session on a scene with a tree (tests)
 //   denoise      AKR_DENOISE=<n>          akr_render_task: n > 0 = every pt task is followed by albedo + ns aov passes of n spp and akr_denoise, "{stem}.denoised{ext}" written
+//   denoise_variance AKR_DENOISE_VARIANCE=1  akr_render_task with denoise > 0: the step is akr_denoise_variance, its half film the task's film after floor(n_passes / 2) passes
 //   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
 //   max_fused_passes (no environment hook)     most passes akr_pt_passes fuses into one launch: 0 = adaptive (16, up to 64 once a pass has been timed), else 1..64
 struct TuningOptions {
@@ -255,6 +256,7 @@ struct TuningOptions {
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
+    int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
     int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
     int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
 };

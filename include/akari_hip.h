@@ -543,7 +543,8 @@ typedef struct {
     uint32_t demodulate;     /* 1: divide the colour by the albedo before filtering, multiply afterwards (needs an albedo film) */
     float sigma_color, sigma_normal, sigma_albedo;   /* >= 0, finite */
     float albedo_floor;      /* 1e-3; > 0: the least divisor of the demodulation */
-    uint32_t _pad[2];
+    float sigma_variance;    /* > 0, finite: read by akr_denoise_variance alone (akr_denoise ignores it) */
+    uint32_t _pad;
 } akr_denoise_config;
 AKR_API int32_t akr_denoise_config_default(akr_denoise_config *cfg);
 /* color -> out. albedo and / or normal may be NULL (that term is dropped; without albedo there is no demodulation). All films have one
@@ -552,6 +553,14 @@ AKR_API int32_t akr_denoise_config_default(akr_denoise_config *cfg);
  * `out` receives rgb = the result, splat = 0, weight = 1, so akr_film_resolve(out) returns the result exactly; out may be `color`.
  * Enqueued on the context's stream, blocks until the result is complete; work buffers (64 bytes per pixel) live for the call. */
 AKR_API int32_t akr_denoise(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *albedo, akr_film *normal, akr_film *out);
+/* The same filter with per-pixel colour weights from the render's own noise (DESIGN.md 4.10 "Variance guide"). `half` is the colour film as
+ * it stood after a subset of its samples (same layout, size and context; e.g. read after the first half of a session's passes): the two
+ * halves give a per-pixel variance estimate, a 7 x 7 guide-weighted prefilter smooths it, and every level divides the colour distance by
+ * the variance, which it filters along: kc = (1 / sigma_variance^2) / (g + 1e-10), g the 3 x 3 smoothed variance. sigma_color is not read.
+ * Refused like akr_denoise, and: half NULL, of another size or context, half == out, sigma_variance not finite and > 0 or so small that
+ * (1 / sigma_variance^2) / 1e-10 is not finite in f32. out may be `color`. */
+AKR_API int32_t akr_denoise_variance(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *half, akr_film *albedo, akr_film *normal,
+                                     akr_film *out);
 
 /* ---------------------------------------------------------------------------------------------------
  * `gpt` integrator (Method::GradientPathTracer, akari_integrator/src/gpt.rs; "type": "gpt"): gradient-domain path tracing.
@@ -727,7 +736,10 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *                                           integrator at n spp (the task's sampler, seed, filter and colour pipeline), akr_denoise runs with its
  *                                           default configuration and "{stem}.denoised{ext}" is written next to film.out; 0 (default) = off. Other
  *                                           method types ignore it. n <= 65536.
- *   "denoise_kernel" (AKR_DENOISE_KERNEL=v) akr_denoise's level kernel: 0 = one thread per pixel gathering from global memory, 1 = the LDS-tiled
+ *   "denoise_variance" (AKR_DENOISE_VARIANCE=1)  akr_render_task with "denoise" > 0: 1 = the denoise step is akr_denoise_variance, its half film the
+ *                                           task's film after the first floor(n_passes / 2) passes (film.out is unchanged); a task of a single pass
+ *                                           (spp <= spp_per_pass) is refused. 0 (default) = akr_denoise.
+ *   "denoise_kernel" (AKR_DENOISE_KERNEL=v) akr_denoise's / akr_denoise_variance's level kernel: 0 = one thread per pixel gathering from global memory, 1 = the LDS-tiled
  *                                           kernel, -1 (default) = the library decides per step. Same bits either way.
  * Values out of an option's range fail with AKR_ERR_INVALID_ARGUMENT.
  * A session reads the options once, when it begins (akr_pt_begin / akr_gpt_begin / ...): a later akr_option_set does not change it.

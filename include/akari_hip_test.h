@@ -127,6 +127,14 @@ AKR_TEST_API int32_t akr_host_denoise(const akr_denoise_config *cfg, uint32_t wi
 AKR_TEST_API int32_t akr_probe_denoise_times(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *albedo, akr_film *normal, akr_film *out,
                                         int32_t kernel, float *times11);
 
+/* akr_denoise_variance on the host and timed: the twins of the two hooks above. half_film = the colour film after a subset of its samples
+ * (its splat plane is not read); times11[0] = prepare + prefilter. */
+AKR_TEST_API int32_t akr_host_denoise_variance(const akr_denoise_config *cfg, uint32_t width, uint32_t height, const float *color_film, float color_splat_scale,
+                                          const float *half_film, const float *albedo_film, float albedo_splat_scale, const float *normal_film,
+                                          float normal_splat_scale, float *out_rgb);
+AKR_TEST_API int32_t akr_probe_denoise_variance_times(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *half, akr_film *albedo,
+                                                 akr_film *normal, akr_film *out, int32_t kernel, float *times11);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);

@@ -3,8 +3,10 @@ of finish and of the whole call, and the same under the schedule akr_denoise shi
 -- warm-up calls first, then repeated calls, median / min / max reported -- next to the level's byte floor
 (48 B read + 16 B written per pixel) and to the kernel time of one 16-spp C2 render (scenes/cbox, force_diffuse: bench.py's headline
 configuration) of the same frame. One JSON line per kernel, appended to profiles/denoise_bench.jsonl.
+--variance times akr_denoise_variance instead (rows "mode": "variance"): the frame is rendered in two passes of 8 spp, the film after the
+first is the half film, and "prepare" is prepare + the variance prefilter.
 
-    python tools/denoise_bench.py [--quick] [--out FILE] [--runs N]
+    python tools/denoise_bench.py [--quick] [--variance] [--out FILE] [--runs N]
 """
 import argparse
 import json
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "denoise_bench.jsonl"))
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--variance", action="store_true", help="time akr_denoise_variance (half film = the frame after the first of two passes)")
     args = ap.parse_args()
     w, h = (256, 144) if args.quick else (1920, 1080)
     ctx = capi.Context(0)
@@ -41,6 +44,16 @@ def main():
     capi.pt_render(ctx, scene, cfg, color)  # warm-up of the render itself
     color.clear()
     frame_ms = capi.pt_render(ctx, scene, cfg, color)["kernel_ms"]
+    half = None
+    if args.variance:  # the same 16 spp in two passes of 8, the film after the first kept as the half
+        color.clear()
+        cfg.spp_per_pass = 8
+        half = capi.Film(ctx, w, h)
+        se = capi.PtSession(ctx, scene, cfg, color)
+        se.passes(1, blocking=True)
+        half.write(color.read())
+        se.passes(1, blocking=True)
+        frame_ms = se.end()["kernel_ms"]
     feature_ms = 0.0
     for film, aov in ((albedo, abi.AOV_ALBEDO), (normal, abi.AOV_NS)):
         ac = abi.AovConfig.default()
@@ -49,12 +62,17 @@ def main():
     dc = abi.DenoiseConfig.default()
     floor_ms = 64.0 * w * h / HBM_BYTES_PER_S * 1e3
     results = []
+    def times(kernel):
+        if half is not None:
+            return capi.denoise_variance_times(ctx, color, half, albedo, normal, out, kernel, dc)
+        return capi.denoise_times(ctx, color, albedo, normal, out, kernel, dc)
+
     for kernel, name in ((0, "gather"), (1, "tiled"), (-1, "auto")):
         for _ in range(args.warmup):
-            capi.denoise_times(ctx, color, albedo, normal, out, kernel, dc)
-        runs = [capi.denoise_times(ctx, color, albedo, normal, out, kernel, dc) for _ in range(args.runs)]
+            times(kernel)
+        runs = [times(kernel) for _ in range(args.runs)]
         results.append(out.resolve())
-        row = {"kernel": name, "width": w, "height": h, "runs": args.runs, "warmup": args.warmup, "device": ctx.device_info()["name"],
+        row = {"mode": "variance" if half is not None else "fixed", "kernel": name, "width": w, "height": h, "runs": args.runs, "warmup": args.warmup, "device": ctx.device_info()["name"],
                "prepare_ms": spread([r["prepare"] for r in runs]), "finish_ms": spread([r["finish"] for r in runs]),
                "total_ms": spread([r["total"] for r in runs]),
                "level_ms": {str(1 << i): spread([r["levels"][i] for r in runs]) for i in range(dc.iterations)},
