@@ -313,6 +313,18 @@ MARKOV_STATE_DTYPE = [("cur_pixel", "<u4", (2,)), ("chain_id", "<u4"), ("cur_f",
                       ("n_mutations", "<u4"), ("cur_iter", "<u4"), ("last_large_iter", "<u4")]
 
 
+class AdaptiveConfig(_Struct):
+    """akr_adaptive_config: when a tile of akr_pt_adaptive_render retires."""
+
+    _fields_ = [("threshold", C.c_float), ("min_spp", C.c_uint32), ("round_passes", C.c_uint32), ("_pad", C.c_uint32)]
+
+    @staticmethod
+    def default() -> "AdaptiveConfig":
+        c = AdaptiveConfig()
+        c.threshold, c.min_spp, c.round_passes = 0.0625, 16, 1
+        return c
+
+
 class PtStats(C.Structure):
     _fields_ = [
         ("n_samples", C.c_uint64),
@@ -328,6 +340,16 @@ class PtStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
+
+
+class AdaptiveStats(C.Structure):
+    """akr_adaptive_stats: what akr_pt_adaptive_render did."""
+
+    _fields_ = [("rounds", C.c_uint32), ("tiles_retired", C.c_uint32), ("samples_drawn", C.c_uint64), ("samples_uniform", C.c_uint64), ("pt", PtStats)]
+
+    def as_dict(self):
+        return {"rounds": self.rounds, "tiles_retired": self.tiles_retired, "samples_drawn": self.samples_drawn, "samples_uniform": self.samples_uniform,
+                "pt": self.pt.as_dict()}
 
 
 class KernelInfo(C.Structure):

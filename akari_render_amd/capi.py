@@ -43,6 +43,7 @@ EXPORTS = [
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
     "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
     "akr_denoise_config_default", "akr_denoise", "akr_denoise_variance",
+    "akr_pt_set_active_tiles", "akr_film_tile_error", "akr_adaptive_config_default", "akr_pt_adaptive_render",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -54,6 +55,7 @@ TEST_EXPORTS = [
     "akr_probe_env_sample", "akr_probe_env_pdf", "akr_host_lens_ray", "akr_probe_camera_rays",
     "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2", "akr_host_denoise", "akr_probe_denoise_times",
     "akr_host_pt_launch_plan", "akr_host_denoise_variance", "akr_probe_denoise_variance_times",
+    "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
 ]
 
 
@@ -92,6 +94,9 @@ def lib() -> C.CDLL:
     for sid, cls in enumerate((abi.MeshDesc, abi.InstanceDesc, abi.MaterialDesc, abi.CameraDesc, abi.SceneDesc, abi.PtConfig, abi.PtStats, abi.SceneInfo,
                                abi.KernelInfo, abi.AovConfig, abi.GptConfig, abi.McmcConfig, abi.McmcResult, abi.McmcPartial,
                                abi.EnvironmentDesc, abi.LensDesc, abi.DenoiseConfig), start=1):
+        if L.akr_struct_size(sid) != C.sizeof(cls):
+            raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
+    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats)):  # (id 18 is not assigned)
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -213,6 +218,13 @@ def lib() -> C.CDLL:
     proto("akr_denoise_variance", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, vp)
     proto("akr_host_denoise_variance", C.POINTER(abi.DenoiseConfig), u32, u32, fp, f32, fp, fp, f32, fp, f32, fp)
     proto("akr_probe_denoise_variance_times", vp, C.POINTER(abi.DenoiseConfig), vp, vp, vp, vp, vp, i32, fp)
+    proto("akr_pt_set_active_tiles", vp, up, u32)
+    proto("akr_film_tile_error", vp, vp, vp, u32, u32, up, u32, fp)
+    proto("akr_adaptive_config_default", C.POINTER(abi.AdaptiveConfig))
+    proto("akr_pt_adaptive_render", vp, vp, C.POINTER(abi.PtConfig), C.POINTER(abi.AdaptiveConfig), vp, vp, up, C.POINTER(abi.AdaptiveStats))
+    proto("akr_host_tile_error", u32, u32, fp, fp, u32, u32, up, u32, fp)
+    proto("akr_host_half_bracket", u32, u32, fp, fp, u32, u32, up, u32, i32)
+    proto("akr_probe_adapt_times", vp, vp, vp, u32, u32, up, u32, fp)
     _lib = L
     return L
 
@@ -490,7 +502,7 @@ class Scene:
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes)."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes, "adaptive" = n: render_task renders pt tasks adaptively with threshold n / 1024, "adaptive_min_spp")."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 
@@ -638,6 +650,15 @@ class PtSession:
         done = C.c_uint32()
         check(lib().akr_pt_passes(self.h, n, 1 if blocking else 0, C.byref(done)))
         return done.value
+
+    def set_active_tiles(self, tiles) -> None:
+        """akr_pt_set_active_tiles: the passes from now on render only `tiles` (row-major ids on the session's tile grid, a duplicate-free
+        subset of the session's own, any order; an empty list renders nothing); None restores the session's own set."""
+        if tiles is None:
+            check(lib().akr_pt_set_active_tiles(self.h, None, 0))
+            return
+        t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+        check(lib().akr_pt_set_active_tiles(self.h, _up(t) if t.size else C.cast(C.pointer(C.c_uint32(0)), C.POINTER(C.c_uint32)), t.size))
 
     def sampler_states(self, n_pixels: int) -> np.ndarray:
         st = np.zeros(2 * n_pixels, dtype=np.uint64)
@@ -926,6 +947,56 @@ def host_denoise_variance(width: int, height: int, color: np.ndarray, half: np.n
     ptr = [_fp(f) if f is not None else None for f in films]
     check(lib().akr_host_denoise_variance(C.byref(c), width, height, ptr[0], splat_scales[0], ptr[1], ptr[2], splat_scales[1], ptr[3], splat_scales[2], _fp(out)))
     return out.reshape(height, width, 3)
+
+
+def film_tile_error(ctx: Context, film: Film, half: Film, tile_w: int, tile_h: int, tiles) -> np.ndarray:
+    """akr_film_tile_error: the error estimate of each listed tile from a pt film and its A-half -> f32[len(tiles)]."""
+    t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+    err = np.zeros(t.size, dtype=np.float32)
+    check(lib().akr_film_tile_error(ctx.h, film.h, half.h if half is not None else None, tile_w, tile_h, _up(t), t.size, _fp(err)))
+    return err
+
+
+def host_tile_error(width: int, height: int, film: np.ndarray, half: np.ndarray, tile_w: int, tile_h: int, tiles) -> np.ndarray:
+    """akr_host_tile_error (test hook): akr_film_tile_error's arithmetic on the host, over raw film accumulators."""
+    film, half = np.ascontiguousarray(film, dtype=np.float32), np.ascontiguousarray(half, dtype=np.float32)
+    assert film.size == half.size == 7 * width * height
+    t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+    err = np.zeros(t.size, dtype=np.float32)
+    check(lib().akr_host_tile_error(width, height, _fp(film), _fp(half), tile_w, tile_h, _up(t), t.size, _fp(err)))
+    return err
+
+
+def host_half_bracket(width: int, height: int, film: np.ndarray, half: np.ndarray, tile_w: int, tile_h: int, tiles, close: bool) -> np.ndarray:
+    """akr_host_half_bracket (test hook): k_half_open (close = False: half - film) or k_half_close (half + film) over the listed tiles -> the new half film."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    out = np.array(half, dtype=np.float32, copy=True)
+    assert film.size == out.size == 7 * width * height
+    t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+    check(lib().akr_host_half_bracket(width, height, _fp(film), _fp(out), tile_w, tile_h, _up(t), t.size, 1 if close else 0))
+    return out
+
+
+def adapt_times(ctx: Context, film: Film, half: Film, tile_w: int, tile_h: int, tiles) -> dict:
+    """akr_probe_adapt_times (test hook): k_tile_error, k_half_open and k_half_close over the listed tiles, each timed by HIP events (ms)."""
+    t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+    ms = np.zeros(3, dtype=np.float32)
+    check(lib().akr_probe_adapt_times(ctx.h, film.h, half.h, tile_w, tile_h, _up(t), t.size, _fp(ms)))
+    return {"tile_error": float(ms[0]), "half_open": float(ms[1]), "half_close": float(ms[2])}
+
+
+def pt_adaptive_render(ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film, acfg: Optional[abi.AdaptiveConfig] = None, half: Optional[Film] = None,
+                       want_tile_spp: bool = True):
+    """akr_pt_adaptive_render: pt with cfg.spp as the most a pixel gets; tiles retire by their error estimate.
+    -> (stats dict, tile_spp u32[tiles_y, tiles_x] or None)."""
+    c, a = cfg.copy(), (acfg if acfg is not None else abi.AdaptiveConfig.default())
+    tw, th = c.tile_w or 32, c.tile_h or 32
+    tiles_x, tiles_y = (film.width + tw - 1) // tw, (film.height + th - 1) // th
+    tile_spp = np.zeros(tiles_x * tiles_y, dtype=np.uint32) if want_tile_spp else None
+    st = abi.AdaptiveStats()
+    check(lib().akr_pt_adaptive_render(ctx.h, scene.h, C.byref(c), C.byref(a), film.h, half.h if half is not None else None,
+                                       _up(tile_spp) if tile_spp is not None else None, C.byref(st)))
+    return st.as_dict(), (tile_spp.reshape(tiles_y, tiles_x) if tile_spp is not None else None)
 
 
 def gpt_render(ctx: Context, scene: Scene, cfg: abi.GptConfig, film: Film, want_aux: bool = False):

@@ -279,6 +279,10 @@ struct akr_pt_session : RenderBase {
     int spec_waves = 3;
     std::shared_ptr<SpecKernel> spec;
     std::string spec_status = "not requested";
+    // akr_pt_set_active_tiles: the list the passes render instead of the session's own tiles (params.owned_tiles points at it, params.shard_count
+    // is at least 2 so that item_to_pixel reads it, params.n_items counts its pixels); room for every tile of the grid, allocated at the first call
+    DevBuf active_tiles;
+    bool active_set = false;
 };
 
 namespace akr_api {

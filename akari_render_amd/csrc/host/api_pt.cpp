@@ -209,6 +209,24 @@ static bool choose_wavefront(const akr_pt_session* se) {
     return scene->cs.instanced.on && se->grid.n_items >= wf_auto_items(scene);
 }
 
+// The groups' shares of the slots [0, n_active): the session's slots, or the shorter range of an active-tile list (akr_pt_set_active_tiles;
+// the buffers stay as they were allocated, for the session's own n_items)
+static void wf_set_range(WavefrontState& ws, uint32_t n_active) {
+    const uint32_t groups = (uint32_t)ws.group.size();
+    const WfBuffers& w = ws.buf;
+    for (uint32_t g = 0; g < groups; g++) {
+        WfBuffers& wg = ws.group[g];
+        // boundaries on whole 1024-slot tiles
+        auto bound = [&](uint32_t k) { return k >= groups ? n_active : (uint32_t)(((uint64_t)n_active * k / groups) & ~1023ull); };
+        wg.slot_base = bound(g);
+        wg.slot_end = bound(g + 1);
+        for (int k = 0; k < 2; k++) {  // a group's queues: its share of the session's
+            wg.queue_closest[k] = w.queue_closest[k] + wg.slot_base;
+            wg.queue_shadow[k] = w.queue_shadow[k] + wg.slot_base;
+        }
+    }
+}
+
 // The wavefront schedule's buffers for the session: a slot per item of the session's parameter block
 static std::unique_ptr<WavefrontState> wf_allocate(const akr_pt_session* se, bool sort) {
     auto ws = std::make_unique<WavefrontState>();
@@ -270,18 +288,11 @@ static std::unique_ptr<WavefrontState> wf_allocate(const akr_pt_session* se, boo
     ws->ctrl.alloc((size_t)groups * 8 * sizeof(uint32_t));  // per group: qcount[4], qhead, n_active
     for (uint32_t g = 0; g < groups; g++) {
         WfBuffers wg = w;
-        // boundaries on whole 1024-slot tiles
-        auto bound = [&](uint32_t k) { return k >= groups ? n_slots : (uint32_t)(((uint64_t)n_slots * k / groups) & ~1023ull); };
-        wg.slot_base = bound(g);
-        wg.slot_end = bound(g + 1);
-        for (int k = 0; k < 2; k++) {  // a group's queues: its share of the session's
-            wg.queue_closest[k] = w.queue_closest[k] + wg.slot_base;
-            wg.queue_shadow[k] = w.queue_shadow[k] + wg.slot_base;
-        }
         uint32_t* c = (uint32_t*)ws->ctrl.p + 8 * g;
         wg.qcount = c; wg.qhead = c + 4; wg.n_active = c + 5;
         ws->group.push_back(wg);
     }
+    wf_set_range(*ws, n_slots);
     if (groups > 1) {
         for (uint32_t g = 0; g < groups; g++) {
             hipStream_t st = nullptr;
@@ -614,7 +625,8 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             }
             set_launch_passes(se, fused, last);
             LaunchTimer timer(se);
-            if (se->wf) wf_run(se);
+            if (se->active_set && se->params.n_items == 0) {}  // an empty active-tile list: the passes are counted, nothing runs
+            else if (se->wf) wf_run(se);
             else HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr, se->arith_relaxed));
             timer.stop();
             se->spp_done = done;
@@ -653,6 +665,45 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
         while (left > 0 && se->spp_done < total) launch(kMaxFusedPasses);
         if (blocking) HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
         if (spp_done) *spp_done = se->spp_done;
+    });
+}
+// The tiles the session's passes render from now on (include/akari_hip.h). Host only: the kernels already map items through PtParams.owned_tiles
+// whenever shard_count > 1 (device/dpath.h item_to_pixel) and read shard_count nowhere else, and film and sampler state are per pixel.
+AKR_API int32_t akr_pt_set_active_tiles(akr_pt_session* se, const uint32_t* tiles, uint32_t n) {
+    if (!se) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_set_active_tiles: session is NULL");
+    return guarded([&] {
+        se->ctx->bind();
+        PtParams& p = se->params;
+        const akr_pt_config& c = se->cfg;
+        const uint32_t n_tiles = se->grid.tiles_x * se->grid.tiles_y, tile_px = se->grid.tile_w * se->grid.tile_h;
+        const uint32_t count = c.shard_count > 1 ? c.shard_count : 1, rank = c.shard_count > 1 ? c.shard_rank : 0;
+        if (tiles) {
+            std::vector<uint8_t> seen(n_tiles, 0);
+            for (uint32_t j = 0; j < n; j++) {
+                const uint32_t t = tiles[j];
+                if (t >= n_tiles) throw std::invalid_argument("akr_pt_set_active_tiles: tile " + std::to_string(t) + " is out of range (the grid has " + std::to_string(n_tiles) + " tiles)");
+                if (tile_owner(t % se->grid.tiles_x, t / se->grid.tiles_x, count) != rank)
+                    throw std::invalid_argument("akr_pt_set_active_tiles: tile " + std::to_string(t) + " is not owned by this session (shard " + std::to_string(rank) + " of " + std::to_string(count) + ")");
+                if (seen[t]) throw std::invalid_argument("akr_pt_set_active_tiles: duplicate tile " + std::to_string(t));
+                seen[t] = 1;
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(se->ctx->stream));  // launches in flight read the list
+        se->sched_trial = se->sched_trial == 1 ? 0 : se->sched_trial;  // no timed schedule trial for a session that ever set a list
+        if (!tiles) {
+            se->active_set = false;
+            p.shard_count = count;
+            p.owned_tiles = se->owned_tiles.as<uint32_t>();
+            p.n_items = se->grid.n_items;
+        } else {
+            if (!se->active_tiles.p) se->active_tiles.alloc((size_t)std::max(1u, n_tiles) * sizeof(uint32_t));
+            if (n) HIP_CHECK(hipMemcpy(se->active_tiles.p, tiles, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            se->active_set = true;
+            p.shard_count = std::max(2u, count);  // item_to_pixel's list branch
+            p.owned_tiles = se->active_tiles.as<uint32_t>();
+            p.n_items = n * tile_px;
+        }
+        if (se->wf) wf_set_range(*se->wf, p.n_items);  // (never more than the slots allocated: a subset of the session's tiles)
     });
 }
 AKR_API int32_t akr_pt_read_sampler_states(akr_pt_session* se, uint64_t* dst) {

@@ -58,6 +58,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
     const TuningOptions opts = tuning();  // read once, like a session's options
     const int denoise_spp = opts.denoise;
     const bool denoise_variance = denoise_spp > 0 && opts.denoise_variance != 0;
+    const int adaptive = opts.adaptive;
     return guarded([&] {
         std::vector<ParsedTask> tasks = parse_render_tasks(method_json_text, ses.override_sampler_independent != 0);
         const uint32_t w = scene->flat.camera.width, h = scene->flat.camera.height;
@@ -134,6 +135,40 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
                 }
                 write_image(task.film_out, rgb.data(), w, h);
                 if (stats_out) *stats_out = st;
+                continue;
+            }
+            if (adaptive > 0) {  // option "adaptive" (DESIGN.md 4.11): the task's spp is the most a pixel gets, tiles retire by their error estimate
+                if (ses.save_intermediate || denoise_variance) {
+                    akr_film_destroy(film);
+                    throw Unsupported(std::string("unsupported: option adaptive together with ") + (ses.save_intermediate ? "--save-intermediate" : "option denoise_variance"));
+                }
+                akr_adaptive_config ac;
+                check(akr_adaptive_config_default(&ac));
+                ac.threshold = (float)adaptive / 1024.0f;
+                if (opts.adaptive_min_spp > 0) ac.min_spp = (uint32_t)opts.adaptive_min_spp;
+                akr_adaptive_stats as;
+                check(akr_pt_adaptive_render(ctx, scene, &task.cfg, &ac, film, nullptr, nullptr, &as));
+                const akr_pt_stats& st = as.pt;
+                if (ses.save_stats) {
+                    std::string path = name + ".json";
+                    FILE* f = std::fopen(path.c_str(), "wb");
+                    if (!f) throw std::runtime_error("cannot open '" + path + "' for writing");
+                    std::fputs("{\"intermediate\":[]}", f);
+                    std::fclose(f);
+                }
+                if (ses.verbose)
+                    std::fprintf(stderr, "[akari_hip] Rendering finished in %.2fs (%.1f Msamples/s); adaptive: %u rounds, %llu of %llu samples drawn, %u tiles retired\n", st.kernel_ms * 1e-3,
+                                 st.n_samples / (st.kernel_ms * 1e3), as.rounds, (unsigned long long)as.samples_drawn, (unsigned long long)as.samples_uniform, as.tiles_retired);
+                check(akr_film_resolve(film, rgb.data()));
+                FilmHolder done(film);
+                film = nullptr;
+                write_image(task.film_out, rgb.data(), w, h);
+                if (stats_out) *stats_out = st;
+                if (denoise_spp > 0) {
+                    denoise_step(ctx, scene, task.cfg, done.f, nullptr, (uint32_t)denoise_spp, ses.verbose != 0);
+                    check(akr_film_resolve(done.f, rgb.data()));
+                    write_image(denoised_path(task.film_out), rgb.data(), w, h);
+                }
                 continue;
             }
             // option "denoise_variance": the film after the first floor(n_passes / 2) passes is kept as the half film of the denoise step

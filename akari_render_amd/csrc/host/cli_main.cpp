@@ -1,12 +1,15 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
 //             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance]
+//             [--adaptive [X]] [--adaptive-min-spp N]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
 // with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 // --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
 // --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
+// --adaptive [X] (library option "adaptive" = X * 1024; the library's default threshold when X is left out): pt tasks render adaptively, the task's spp the most a pixel
+// gets; --adaptive-min-spp N (option "adaptive_min_spp"): the samples a tile receives before it may retire.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +22,7 @@
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
               "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance]\n"
+              "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
               "  -m, --method <METHOD>    Render method config file (\"type\": \"pt\")\n"
               "  -d, --device <DEVICE>    HIP device ordinal (default 0)\n"
@@ -28,7 +32,9 @@ static void usage() {
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
               "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
-              "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)");
+              "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)\n"
+              "      --adaptive [<X>]     pt tasks render adaptively: tiles whose error estimate is <= X stop receiving samples, spp is the most a pixel gets\n"
+              "      --adaptive-min-spp <N>  with --adaptive: samples a tile receives before it may retire");
 }
 
 // akari-cli --spec-compile <header file> <out.co> <arch> <flags> <min waves>: the library's helper process for per-scene kernels
@@ -55,6 +61,7 @@ int main(int argc, char** argv) {
     int dof = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
     int denoise = 0, denoise_variance = 0;
+    int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(1); } return argv[++i]; };
@@ -79,6 +86,28 @@ int main(int argc, char** argv) {
             }
         }
         else if (a == "--denoise-variance") denoise_variance = 1;
+        else if (a == "--adaptive") {  // the threshold is optional: taken only if the next argument is a number
+            akr_adaptive_config ac;
+            akr_adaptive_config_default(&ac);
+            float t = ac.threshold;
+            if (i + 1 < argc) {
+                char* end = nullptr;
+                const float v = std::strtof(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == 0) {
+                    if (!(v * 1024.0f >= 1.0f && v <= 1024.0f)) { std::fprintf(stderr, "akari-cli: --adaptive wants a threshold in 1/1024 .. 1024, got '%s'\n", argv[i + 1]); return 1; }
+                    t = v;
+                    i++;
+                }
+            }
+            adaptive = (int)(t * 1024.0f + 0.5f);
+        }
+        else if (a == "--adaptive-min-spp") {
+            const char* text = next();
+            char* end = nullptr;
+            const long v = std::strtol(text, &end, 10);
+            if (end == text || *end != 0 || v < 1 || v > 65536) { std::fprintf(stderr, "akari-cli: --adaptive-min-spp wants 1 .. 65536 samples, got '%s'\n", text); return 1; }
+            adaptive_min_spp = (int)v;
+        }
         else if (a == "--lens-radius" || a == "--focal-distance") {
             const char* text = next();
             char* end = nullptr;
@@ -109,6 +138,9 @@ int main(int argc, char** argv) {
     if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
     if (denoise_variance && !denoise) { std::fputs("akari-cli: --denoise-variance needs --denoise\n", stderr); return 1; }
     if (denoise_variance && akr_option_set("denoise_variance", 1) != AKR_OK) die("option denoise_variance");
+    if (adaptive_min_spp && !adaptive) { std::fputs("akari-cli: --adaptive-min-spp needs --adaptive\n", stderr); return 1; }
+    if (adaptive && akr_option_set("adaptive", adaptive) != AKR_OK) die("option adaptive");
+    if (adaptive_min_spp && akr_option_set("adaptive_min_spp", adaptive_min_spp) != AKR_OK) die("option adaptive_min_spp");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
     if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
         akr_lens_desc lens;

@@ -832,6 +832,8 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_DENOISE")) g_tuning.denoise = std::max(0, std::min(65536, std::atoi(e)));
     if (const char* e = std::getenv("AKR_DENOISE_VARIANCE")) g_tuning.denoise_variance = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE_KERNEL")) g_tuning.denoise_kernel = std::max(-1, std::min(1, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_ADAPTIVE")) g_tuning.adaptive = std::max(0, std::min(1 << 20, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_ADAPTIVE_MIN_SPP")) g_tuning.adaptive_min_spp = std::max(0, std::min(65536, std::atoi(e)));
 }
 int* tuning_field(const char* name) {
     const std::string n = name ? name : "";
@@ -856,6 +858,8 @@ int* tuning_field(const char* name) {
     if (n == "denoise") return &g_tuning.denoise;
     if (n == "denoise_variance") return &g_tuning.denoise_variance;
     if (n == "denoise_kernel") return &g_tuning.denoise_kernel;
+    if (n == "adaptive") return &g_tuning.adaptive;
+    if (n == "adaptive_min_spp") return &g_tuning.adaptive_min_spp;
     return nullptr;
 }
 }  // namespace
@@ -886,6 +890,8 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.denoise && (value < 0 || value > 65536)) return false;
     if (f == &g_tuning.denoise_variance && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.denoise_kernel && (value < -1 || value > 1)) return false;
+    if (f == &g_tuning.adaptive && (value < 0 || value > (1 << 20))) return false;
+    if (f == &g_tuning.adaptive_min_spp && (value < 0 || value > 65536)) return false;
     *f = value;
     return true;
 }

@@ -237,6 +237,8 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   denoise      AKR_DENOISE=<n>          akr_render_task: n > 0 = every pt task is followed by albedo + ns aov passes of n spp and akr_denoise, "{stem}.denoised{ext}" written
 //   denoise_variance AKR_DENOISE_VARIANCE=1  akr_render_task with denoise > 0: the step is akr_denoise_variance, its half film the task's film after floor(n_passes / 2) passes
 //   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
+//   adaptive     AKR_ADAPTIVE=<n>         akr_render_task: n > 0 = pt tasks render through akr_pt_adaptive_render with threshold n / 1024 (api_adapt.cpp); 0 = off
+//   adaptive_min_spp AKR_ADAPTIVE_MIN_SPP=<n>  ... with this min_spp; 0 = akr_adaptive_config_default's
 //   max_fused_passes (no environment hook)     most passes akr_pt_passes fuses into one launch: 0 = adaptive (16, up to 64 once a pass has been timed), else 1..64
 struct TuningOptions {
     int force_bvh = 0, bvh_balanced = 0, defer_metal = -1, wavefront = -1, simple_kernels = 1;
@@ -258,6 +260,8 @@ struct TuningOptions {
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
     int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
     int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
+    int adaptive = 0;  // akr_render_task: > 0 = pt tasks render adaptively, threshold = adaptive / 1024.0f; 0 = uniformly
+    int adaptive_min_spp = 0;  // ... min_spp of those renders; 0 = the default configuration's
     int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
 };
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it

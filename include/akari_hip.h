@@ -563,6 +563,48 @@ AKR_API int32_t akr_denoise_variance(akr_context *ctx, const akr_denoise_config 
                                      akr_film *out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Adaptive sampling for `pt` (no reference counterpart): tiles whose error estimate is low stop receiving samples. A pixel
+ * that received n samples holds, bit for bit, what n samples of akr_pt_render give it: film and sampler state are per pixel, and a tile
+ * that sits out a pass resumes with exactly the sample it would have drawn.
+ * ------------------------------------------------------------------------------------------------- */
+/* The passes after this call render only the listed tiles: row-major ids on the session's tile_w x tile_h grid, a duplicate-free subset of
+ * the tiles the session owns (all of them for one rank, the Morton share of a shard), in any order; anything else is
+ * AKR_ERR_INVALID_ARGUMENT. tiles == NULL restores the session's own set. n == 0 with a list is legal: passes then render nothing and
+ * spp_done still advances. Waits for the session's launches in flight. Both schedules (megakernel, wavefront), every sampler. */
+AKR_API int32_t akr_pt_set_active_tiles(akr_pt_session *se, const uint32_t *tiles, uint32_t n);
+/* err_out_host[j] = the error of tile tiles[j] (host arrays; row-major ids on the tile_w x tile_h grid over the film, each below the tile
+ * count) from `film` and `half`, the film's A-half (same size and context, half != film): per pixel e = (d f) / sqrt(l + 0.01) with d the
+ * L1 distance of the two halves' means, f = sqrt(wA wB / w^2) and l the sum of the mean's channels; the tile's error is the mean of e over
+ * its pixels that have an estimate (both halves hold samples, e finite), +inf if none has. Defined to the bit.
+ * tile_w, tile_h: multiples of 8 (0 = 32) with tile_w * tile_h <= 4096. Blocks until the result is there. */
+AKR_API int32_t akr_film_tile_error(akr_context *ctx, akr_film *film, akr_film *half, uint32_t tile_w, uint32_t tile_h, const uint32_t *tiles, uint32_t n,
+                                    float *err_out_host);
+typedef struct {
+    float threshold;         /* a tile retires when its error is <= threshold (>= 0; +inf: every tile retires at min_spp) */
+    uint32_t min_spp;        /* ... and it has received at least this many samples */
+    uint32_t round_passes;   /* passes (of cfg.spp_per_pass samples) per round, >= 1 */
+    uint32_t _pad;
+} akr_adaptive_config;
+typedef struct {
+    uint32_t rounds;             /* rounds rendered */
+    uint32_t tiles_retired;      /* tiles that stopped before cfg.spp */
+    uint64_t samples_drawn;      /* sum over the session's in-frame pixels of the samples they received */
+    uint64_t samples_uniform;    /* the same pixels x cfg.spp: what akr_pt_render draws */
+    akr_pt_stats pt;             /* the session's counters (akr_pt_end) */
+} akr_adaptive_stats;
+AKR_API int32_t akr_adaptive_config_default(akr_adaptive_config *cfg);
+/* akr_pt_render with cfg.spp as the MAXIMUM per pixel. Rounds of acfg.round_passes passes alternate A, B, A, B, ...; the samples of the
+ * A-rounds are accumulated in the half film as well. After every full B-round short of cfg.spp the errors of the tiles still active are
+ * computed (akr_film_tile_error) and a tile retires iff it has min_spp samples and its error is finite and <= threshold; the render ends
+ * when no tile is left or cfg.spp is reached. film: as for akr_pt_render (clear it first). half (or NULL): a film of the same size and
+ * context, != film; cleared by the call, afterwards the A-half of every pixel -- directly the `half` of akr_denoise_variance. tile_spp
+ * (or NULL): host array of tiles_x * tiles_y counts, the samples each tile's pixels received (0 for tiles of other ranks).
+ * Refused: a task of a single round (cfg.spp <= round_passes * spp_per_pass), a sample range, tile_w * tile_h > 4096, a NaN or negative
+ * threshold, round_passes = 0. Shards compose: a rank adapts inside its own tiles. */
+AKR_API int32_t akr_pt_adaptive_render(akr_context *ctx, akr_scene *scene, const akr_pt_config *cfg, const akr_adaptive_config *acfg, akr_film *film,
+                                       akr_film *half, uint32_t *tile_spp, akr_adaptive_stats *stats);
+
+/* ---------------------------------------------------------------------------------------------------
  * `gpt` integrator (Method::GradientPathTracer, akari_integrator/src/gpt.rs; "type": "gpt"): gradient-domain path tracing.
  * Per sample one base path and four offset paths through the neighbouring pixels (stride apart, mirrored at the border)
  * on the same random numbers; the offset paths rejoin the base path through the reconnection shift mapping of
@@ -689,7 +731,9 @@ typedef enum {
     AKR_STRUCT_MESH_DESC = 1, AKR_STRUCT_INSTANCE_DESC, AKR_STRUCT_MATERIAL_DESC, AKR_STRUCT_CAMERA_DESC, AKR_STRUCT_SCENE_DESC,
     AKR_STRUCT_PT_CONFIG, AKR_STRUCT_PT_STATS, AKR_STRUCT_SCENE_INFO, AKR_STRUCT_KERNEL_INFO, AKR_STRUCT_AOV_CONFIG, AKR_STRUCT_GPT_CONFIG,
     AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC, AKR_STRUCT_LENS_DESC,
-    AKR_STRUCT_DENOISE_CONFIG
+    AKR_STRUCT_DENOISE_CONFIG,
+    /* (18 stays unknown: callers of earlier versions probe it as the first id past the list) */
+    AKR_STRUCT_ADAPTIVE_CONFIG = 19, AKR_STRUCT_ADAPTIVE_STATS
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
@@ -741,6 +785,10 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *                                           (spp <= spp_per_pass) is refused. 0 (default) = akr_denoise.
  *   "denoise_kernel" (AKR_DENOISE_KERNEL=v) akr_denoise's / akr_denoise_variance's level kernel: 0 = one thread per pixel gathering from global memory, 1 = the LDS-tiled
  *                                           kernel, -1 (default) = the library decides per step. Same bits either way.
+ *   "adaptive"     (AKR_ADAPTIVE=n)         akr_render_task: n > 0 = `pt` tasks render through akr_pt_adaptive_render with threshold = n / 1024 (the
+ *                                           other fields: akr_adaptive_config_default, min_spp from "adaptive_min_spp"); 0 (default) = off, film.out
+ *                                           byte-identical to earlier versions. Refused together with --save-intermediate and "denoise_variance".
+ *   "adaptive_min_spp" (AKR_ADAPTIVE_MIN_SPP=n)  akr_render_task with "adaptive" > 0: min_spp; 0 (default) = akr_adaptive_config_default's
  * Values out of an option's range fail with AKR_ERR_INVALID_ARGUMENT.
  * A session reads the options once, when it begins (akr_pt_begin / akr_gpt_begin / ...): a later akr_option_set does not change it.
  * "wavefront" = 1 on a scene without a BVH renders with the megakernel. Unknown names fail with AKR_ERR_INVALID_ARGUMENT. */

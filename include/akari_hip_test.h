@@ -135,6 +135,18 @@ AKR_TEST_API int32_t akr_host_denoise_variance(const akr_denoise_config *cfg, ui
 AKR_TEST_API int32_t akr_probe_denoise_variance_times(akr_context *ctx, const akr_denoise_config *cfg, akr_film *color, akr_film *half, akr_film *albedo,
                                                  akr_film *normal, akr_film *out, int32_t kernel, float *times11);
 
+/* Adaptive sampling on the host (no GPU): the text of csrc/device/dadapt.h compiled for the host, over host film arrays [rgb 3N | splat 3N | weight N].
+ * akr_host_tile_error = akr_film_tile_error; akr_host_half_bracket runs k_half_open (close = 0: half <- half - film) or k_half_close
+ * (close = 1: half <- half + film) over the rgb and weight planes of the listed tiles' pixels, in place in half_film. Same refusals. */
+AKR_TEST_API int32_t akr_host_tile_error(uint32_t width, uint32_t height, const float *film, const float *half_film, uint32_t tile_w, uint32_t tile_h,
+                                    const uint32_t *tiles, uint32_t n, float *err_out);
+AKR_TEST_API int32_t akr_host_half_bracket(uint32_t width, uint32_t height, const float *film, float *half_film, uint32_t tile_w, uint32_t tile_h,
+                                      const uint32_t *tiles, uint32_t n, int32_t close);
+/* The three kernels over the listed tiles, timed by HIP events on the context's stream: times3 = milliseconds of k_tile_error, k_half_open,
+ * k_half_close (tools/adaptive_bench.py). half is left as it was up to the rounding of (half - film) + film. */
+AKR_TEST_API int32_t akr_probe_adapt_times(akr_context *ctx, akr_film *film, akr_film *half, uint32_t tile_w, uint32_t tile_h, const uint32_t *tiles, uint32_t n,
+                                      float *times3);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);
