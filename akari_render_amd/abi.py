@@ -325,6 +325,36 @@ class AdaptiveConfig(_Struct):
         return c
 
 
+DISPLAY_LINEAR, DISPLAY_REINHARD, DISPLAY_ACES, DISPLAY_HABLE = 1, 2, 3, 4
+DISPLAY_CURVE_NAMES = {DISPLAY_LINEAR: "linear", DISPLAY_REINHARD: "reinhard", DISPLAY_ACES: "aces", DISPLAY_HABLE: "hable"}
+
+
+class DisplayConfig(_Struct):
+    """akr_display_config: exposure, bloom and tone curve of akr_display_transform."""
+
+    _fields_ = [
+        ("curve", C.c_uint32),
+        ("auto_exposure", C.c_uint32),
+        ("exposure_ev", C.c_float),
+        ("key", C.c_float),
+        ("low_permille", C.c_uint32),
+        ("high_permille", C.c_uint32),
+        ("white", C.c_float),
+        ("bloom_strength", C.c_float),
+        ("bloom_threshold", C.c_float),
+        ("bloom_levels", C.c_uint32),
+        ("_pad", C.c_uint32 * 2),
+    ]
+
+    @staticmethod
+    def default() -> "DisplayConfig":
+        c = DisplayConfig()
+        c.curve, c.auto_exposure, c.exposure_ev, c.key = DISPLAY_ACES, 0, 0.0, 0.18
+        c.low_permille, c.high_permille, c.white = 50, 20, 0.0
+        c.bloom_strength, c.bloom_threshold, c.bloom_levels = 0.0, 1.0, 5
+        return c
+
+
 class PtStats(C.Structure):
     _fields_ = [
         ("n_samples", C.c_uint64),

@@ -44,6 +44,7 @@ EXPORTS = [
     "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
     "akr_denoise_config_default", "akr_denoise", "akr_denoise_variance",
     "akr_pt_set_active_tiles", "akr_film_tile_error", "akr_adaptive_config_default", "akr_pt_adaptive_render",
+    "akr_display_config_default", "akr_film_luminance_histogram", "akr_display_exposure", "akr_display_transform",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -56,6 +57,7 @@ TEST_EXPORTS = [
     "akr_probe_div", "akr_probe_intersect_pair", "akr_probe_math2", "akr_host_denoise", "akr_probe_denoise_times",
     "akr_host_pt_launch_plan", "akr_host_denoise_variance", "akr_probe_denoise_variance_times",
     "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
+    "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
 ]
 
 
@@ -96,7 +98,7 @@ def lib() -> C.CDLL:
                                abi.EnvironmentDesc, abi.LensDesc, abi.DenoiseConfig), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
-    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats)):  # (id 18 is not assigned)
+    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats), (22, abi.DisplayConfig)):  # (ids 18 and 21 are not assigned)
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -221,6 +223,13 @@ def lib() -> C.CDLL:
     proto("akr_pt_set_active_tiles", vp, up, u32)
     proto("akr_film_tile_error", vp, vp, vp, u32, u32, up, u32, fp)
     proto("akr_adaptive_config_default", C.POINTER(abi.AdaptiveConfig))
+    proto("akr_display_config_default", C.POINTER(abi.DisplayConfig))
+    proto("akr_film_luminance_histogram", vp, vp, up, up)
+    proto("akr_display_exposure", C.POINTER(abi.DisplayConfig), up, fp)
+    proto("akr_display_transform", vp, C.POINTER(abi.DisplayConfig), vp, vp, fp)
+    proto("akr_host_display_transform", C.POINTER(abi.DisplayConfig), u32, u32, fp, f32, fp, fp)
+    proto("akr_host_luminance_histogram", u32, u32, fp, f32, up, up)
+    proto("akr_probe_display_times", vp, C.POINTER(abi.DisplayConfig), vp, vp, i32, fp)
     proto("akr_pt_adaptive_render", vp, vp, C.POINTER(abi.PtConfig), C.POINTER(abi.AdaptiveConfig), vp, vp, up, C.POINTER(abi.AdaptiveStats))
     proto("akr_host_tile_error", u32, u32, fp, fp, u32, u32, up, u32, fp)
     proto("akr_host_half_bracket", u32, u32, fp, fp, u32, u32, up, u32, i32)
@@ -502,7 +511,7 @@ class Scene:
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes, "adaptive" = n: render_task renders pt tasks adaptively with threshold n / 1024, "adaptive_min_spp")."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes, "adaptive" = n: render_task renders pt tasks adaptively with threshold n / 1024, "adaptive_min_spp", "display" = 1..4: render_task also writes {stem}.display.png through the display transform with that curve, "display_auto_exposure", "display_exposure" = EV x 1024, "display_bloom" = strength x 1024, "display_kernel")."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 
@@ -997,6 +1006,59 @@ def pt_adaptive_render(ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film
     check(lib().akr_pt_adaptive_render(ctx.h, scene.h, C.byref(c), C.byref(a), film.h, half.h if half is not None else None,
                                        _up(tile_spp) if tile_spp is not None else None, C.byref(st)))
     return st.as_dict(), (tile_spp.reshape(tiles_y, tiles_x) if tile_spp is not None else None)
+
+
+def display_transform(ctx: Context, film: Film, out: Film, cfg: Optional[abi.DisplayConfig] = None) -> float:
+    """akr_display_transform: exposure, bloom and tone curve of `film` into `out` (which may be `film`); the result is linear,
+    display-referred, in [0, 1]. cfg None = akr_display_config_default. -> the exposure k that was used."""
+    c = cfg if cfg is not None else abi.DisplayConfig.default()
+    k = C.c_float()
+    check(lib().akr_display_transform(ctx.h, C.byref(c), film.h, out.h, C.byref(k)))
+    return k.value
+
+
+def film_luminance_histogram(ctx: Context, film: Film):
+    """akr_film_luminance_histogram -> (counts uint32[256] of 1/8-EV log-luminance bins over [-20, 12), the number of pixels below 2^-20)."""
+    counts, skipped = np.zeros(256, dtype=np.uint32), C.c_uint32()
+    check(lib().akr_film_luminance_histogram(ctx.h, film.h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(skipped)))
+    return counts, skipped.value
+
+
+def display_exposure(cfg: abi.DisplayConfig, counts: np.ndarray) -> float:
+    """akr_display_exposure (host only, pure): the auto-exposure k of `cfg` for a histogram of 256 counts."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert counts.size == 256
+    k = C.c_float()
+    check(lib().akr_display_exposure(C.byref(cfg), counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(k)))
+    return k.value
+
+
+def host_display_transform(width: int, height: int, film: np.ndarray, cfg: Optional[abi.DisplayConfig] = None, splat_scale: float = 1.0):
+    """akr_host_display_transform (test hook): akr_display_transform's arithmetic on the host. film = a raw film accumulator (7 W H floats).
+    -> ((H, W, 3), the exposure k): what Film.resolve() of akr_display_transform's output film returns."""
+    c = cfg if cfg is not None else abi.DisplayConfig.default()
+    film = np.ascontiguousarray(film, dtype=np.float32).reshape(-1)
+    assert film.size == 7 * width * height
+    out, k = np.zeros(3 * width * height, dtype=np.float32), C.c_float()
+    check(lib().akr_host_display_transform(C.byref(c), width, height, _fp(film), splat_scale, _fp(out), C.byref(k)))
+    return out.reshape(height, width, 3), k.value
+
+
+def host_luminance_histogram(width: int, height: int, film: np.ndarray, splat_scale: float = 1.0):
+    """akr_host_luminance_histogram (test hook): akr_film_luminance_histogram of a host film -> (counts uint32[256], skipped)."""
+    film = np.ascontiguousarray(film, dtype=np.float32).reshape(-1)
+    assert film.size == 7 * width * height
+    counts, skipped = np.zeros(256, dtype=np.uint32), C.c_uint32()
+    check(lib().akr_host_luminance_histogram(width, height, _fp(film), splat_scale, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(skipped)))
+    return counts, skipped.value
+
+
+def display_times(ctx: Context, film: Film, out: Film, kernel: int, cfg: Optional[abi.DisplayConfig] = None) -> dict:
+    """akr_probe_display_times (test hook): akr_display_transform under blur `kernel` (0 gathering passes, 1 through LDS, -1 the library's choice), its parts timed by HIP events (ms)."""
+    c = cfg if cfg is not None else abi.DisplayConfig.default()
+    t = np.zeros(8, dtype=np.float32)
+    check(lib().akr_probe_display_times(ctx.h, C.byref(c), film.h, out.h, kernel, _fp(t)))
+    return dict(zip(("histogram", "source", "down", "blur", "up", "apply", "total", "blur_level1"), (float(v) for v in t)))
 
 
 def gpt_render(ctx: Context, scene: Scene, cfg: abi.GptConfig, film: Film, want_aux: bool = False):

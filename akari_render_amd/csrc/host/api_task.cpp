@@ -45,6 +45,30 @@ void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, 
     check(half ? akr_denoise_variance(ctx, &dc, film, half, albedo.f, normal.f, film) : akr_denoise(ctx, &dc, film, albedo.f, normal.f, film));
     if (verbose) std::fprintf(stderr, "[akari_hip] Denoised (feature passes of %u spp: %.2fms)\n", spp, sa.kernel_ms + sn.kernel_ms);
 }
+
+// "{stem}.display.png" of film.out
+std::string display_path(const std::string& out) {
+    const size_t slash = out.find_last_of("/\\"), dot = out.find_last_of('.');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return out + ".display.png";
+    return out.substr(0, dot) + ".display.png";
+}
+
+// Option "display" (DESIGN.md 4.12): akr_display_transform of a finished pt task's film (the denoised one when the denoise step ran), in
+// place, with the default configuration but for the fields the options carry; the result goes through the PNG writer's OETF
+void display_step(akr_context* ctx, const TuningOptions& opts, akr_film* film, const std::string& out, std::vector<float>& rgb, bool verbose) {
+    auto check = [](int32_t rc) { if (rc != AKR_OK) throw std::runtime_error(std::string(g_last_error)); };
+    akr_display_config dc;
+    check(akr_display_config_default(&dc));
+    dc.curve = (uint32_t)opts.display;
+    dc.auto_exposure = opts.display_auto_exposure != 0 ? 1u : 0u;
+    dc.exposure_ev = (float)opts.display_exposure / 1024.0f;
+    dc.bloom_strength = (float)opts.display_bloom / 1024.0f;
+    float k = 0.0f;
+    check(akr_display_transform(ctx, &dc, film, film, &k));
+    check(akr_film_resolve(film, rgb.data()));
+    write_image(display_path(out), rgb.data(), film->width, film->height);
+    if (verbose) std::fprintf(stderr, "[akari_hip] Display transform (curve %u, exposure %g)\n", dc.curve, (double)k);
+}
 }  // namespace
 
 extern "C" {
@@ -169,6 +193,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
                     check(akr_film_resolve(done.f, rgb.data()));
                     write_image(denoised_path(task.film_out), rgb.data(), w, h);
                 }
+                if (opts.display > 0) display_step(ctx, opts, done.f, task.film_out, rgb, ses.verbose != 0);
                 continue;
             }
             // option "denoise_variance": the film after the first floor(n_passes / 2) passes is kept as the half film of the denoise step
@@ -238,6 +263,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
                 check(akr_film_resolve(done.f, rgb.data()));
                 write_image(denoised_path(task.film_out), rgb.data(), w, h);
             }
+            if (opts.display > 0) display_step(ctx, opts, done.f, task.film_out, rgb, ses.verbose != 0);
         }
     });
 }

@@ -1,7 +1,7 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
 //             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance]
-//             [--adaptive [X]] [--adaptive-min-spp N]
+//             [--adaptive [X]] [--adaptive-min-spp N] [--display [linear|reinhard|aces|hable]] [--exposure EV] [--auto-exposure] [--bloom [X]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
 // with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
@@ -10,6 +10,10 @@
 // --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
 // --adaptive [X] (library option "adaptive" = X * 1024; the library's default threshold when X is left out): pt tasks render adaptively, the task's spp the most a pixel
 // gets; --adaptive-min-spp N (option "adaptive_min_spp"): the samples a tile receives before it may retire.
+// --display [CURVE] (library option "display"; aces when CURVE is left out): every pt task also writes {stem}.display.png, its film (the denoised one with --denoise)
+// through akr_display_transform; --exposure EV, --auto-exposure, --bloom [X] (options "display_exposure" = EV * 1024, "display_auto_exposure",
+// "display_bloom" = X * 1024, 0.25 when X is left out) set that transform's fields and imply --display.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +27,7 @@ static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
               "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance]\n"
               "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
+              "                 [--display [linear|reinhard|aces|hable]] [--exposure <EV>] [--auto-exposure] [--bloom [<X>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
               "  -m, --method <METHOD>    Render method config file (\"type\": \"pt\")\n"
               "  -d, --device <DEVICE>    HIP device ordinal (default 0)\n"
@@ -34,7 +39,9 @@ static void usage() {
               "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
               "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)\n"
               "      --adaptive [<X>]     pt tasks render adaptively: tiles whose error estimate is <= X stop receiving samples, spp is the most a pixel gets\n"
-              "      --adaptive-min-spp <N>  with --adaptive: samples a tile receives before it may retire");
+              "      --adaptive-min-spp <N>  with --adaptive: samples a tile receives before it may retire\n"
+              "      --display [<CURVE>]  pt tasks also write {stem}.display.png: exposure, bloom and a tone curve (linear, reinhard, aces (default), hable)\n"
+              "      --exposure <EV>, --auto-exposure, --bloom [<X>]  with --display: exposure in stops, exposure from the luminance histogram, bloom of strength X (default 0.25)");
 }
 
 // akari-cli --spec-compile <header file> <out.co> <arch> <flags> <min waves>: the library's helper process for per-scene kernels
@@ -62,6 +69,7 @@ int main(int argc, char** argv) {
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
     int denoise = 0, denoise_variance = 0;
     int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
+    int display = 0, display_exposure = 0, display_auto = 0, display_bloom = 0, display_fields = 0;  // the options' values; display_fields: one of the three others was given
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(1); } return argv[++i]; };
@@ -100,6 +108,39 @@ int main(int argc, char** argv) {
                 }
             }
             adaptive = (int)(t * 1024.0f + 0.5f);
+        }
+        else if (a == "--display") {  // the curve is optional: taken only if the next argument names one
+            display = 3;
+            static const char* const names[] = {"linear", "reinhard", "aces", "hable"};
+            for (int c = 0; i + 1 < argc && c < 4; c++)
+                if (std::strcmp(argv[i + 1], names[c]) == 0) {
+                    display = c + 1;
+                    i++;
+                    break;
+                }
+        }
+        else if (a == "--auto-exposure") display_auto = display_fields = 1;
+        else if (a == "--exposure") {
+            const char* text = next();
+            char* end = nullptr;
+            const float v = std::strtof(text, &end);
+            if (end == text || *end != 0 || !(v >= -64.0f && v <= 64.0f)) { std::fprintf(stderr, "akari-cli: --exposure wants -64 .. 64 stops, got '%s'\n", text); return 1; }
+            display_exposure = (int)std::lround(v * 1024.0f);
+            display_fields = 1;
+        }
+        else if (a == "--bloom") {  // the strength is optional: taken only if the next argument is a number
+            float s = 0.25f;
+            if (i + 1 < argc) {
+                char* end = nullptr;
+                const float v = std::strtof(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == 0) {
+                    if (!(v >= 0.0f && v <= 64.0f)) { std::fprintf(stderr, "akari-cli: --bloom wants a strength in 0 .. 64, got '%s'\n", argv[i + 1]); return 1; }
+                    s = v;
+                    i++;
+                }
+            }
+            display_bloom = (int)std::lround(s * 1024.0f);
+            display_fields = 1;
         }
         else if (a == "--adaptive-min-spp") {
             const char* text = next();
@@ -141,6 +182,10 @@ int main(int argc, char** argv) {
     if (adaptive_min_spp && !adaptive) { std::fputs("akari-cli: --adaptive-min-spp needs --adaptive\n", stderr); return 1; }
     if (adaptive && akr_option_set("adaptive", adaptive) != AKR_OK) die("option adaptive");
     if (adaptive_min_spp && akr_option_set("adaptive_min_spp", adaptive_min_spp) != AKR_OK) die("option adaptive_min_spp");
+    if (display_fields && !display) display = 3;
+    if (display && (akr_option_set("display", display) != AKR_OK || akr_option_set("display_auto_exposure", display_auto) != AKR_OK ||
+                    akr_option_set("display_exposure", display_exposure) != AKR_OK || akr_option_set("display_bloom", display_bloom) != AKR_OK))
+        die("option display");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
     if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
         akr_lens_desc lens;

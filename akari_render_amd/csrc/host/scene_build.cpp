@@ -833,6 +833,11 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_DENOISE_VARIANCE")) g_tuning.denoise_variance = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE_KERNEL")) g_tuning.denoise_kernel = std::max(-1, std::min(1, std::atoi(e)));
     if (const char* e = std::getenv("AKR_ADAPTIVE")) g_tuning.adaptive = std::max(0, std::min(1 << 20, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_DISPLAY")) g_tuning.display = std::max(0, std::min(4, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_DISPLAY_AUTO_EXPOSURE")) g_tuning.display_auto_exposure = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("AKR_DISPLAY_EXPOSURE")) g_tuning.display_exposure = std::max(-65536, std::min(65536, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_DISPLAY_BLOOM")) g_tuning.display_bloom = std::max(0, std::min(65536, std::atoi(e)));
+    if (const char* e = std::getenv("AKR_DISPLAY_KERNEL")) g_tuning.display_kernel = std::max(-1, std::min(1, std::atoi(e)));
     if (const char* e = std::getenv("AKR_ADAPTIVE_MIN_SPP")) g_tuning.adaptive_min_spp = std::max(0, std::min(65536, std::atoi(e)));
 }
 int* tuning_field(const char* name) {
@@ -860,6 +865,11 @@ int* tuning_field(const char* name) {
     if (n == "denoise_kernel") return &g_tuning.denoise_kernel;
     if (n == "adaptive") return &g_tuning.adaptive;
     if (n == "adaptive_min_spp") return &g_tuning.adaptive_min_spp;
+    if (n == "display") return &g_tuning.display;
+    if (n == "display_auto_exposure") return &g_tuning.display_auto_exposure;
+    if (n == "display_exposure") return &g_tuning.display_exposure;
+    if (n == "display_bloom") return &g_tuning.display_bloom;
+    if (n == "display_kernel") return &g_tuning.display_kernel;
     return nullptr;
 }
 }  // namespace
@@ -892,6 +902,11 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.denoise_kernel && (value < -1 || value > 1)) return false;
     if (f == &g_tuning.adaptive && (value < 0 || value > (1 << 20))) return false;
     if (f == &g_tuning.adaptive_min_spp && (value < 0 || value > 65536)) return false;
+    if (f == &g_tuning.display && (value < 0 || value > 4)) return false;
+    if (f == &g_tuning.display_auto_exposure && (value < 0 || value > 1)) return false;
+    if (f == &g_tuning.display_exposure && (value < -65536 || value > 65536)) return false;
+    if (f == &g_tuning.display_bloom && (value < 0 || value > 65536)) return false;
+    if (f == &g_tuning.display_kernel && (value < -1 || value > 1)) return false;
     *f = value;
     return true;
 }

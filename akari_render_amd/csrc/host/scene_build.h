@@ -239,6 +239,9 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
 //   adaptive     AKR_ADAPTIVE=<n>         akr_render_task: n > 0 = pt tasks render through akr_pt_adaptive_render with threshold n / 1024 (api_adapt.cpp); 0 = off
 //   adaptive_min_spp AKR_ADAPTIVE_MIN_SPP=<n>  ... with this min_spp; 0 = akr_adaptive_config_default's
+//   display      AKR_DISPLAY=<c>          akr_render_task: c = 1..4 (linear, reinhard, aces, hable) = every pt task also writes "{stem}.display.png" through akr_display_transform; 0 = off
+//   display_auto_exposure, display_exposure (EV x 1024), display_bloom (strength x 1024): AKR_DISPLAY_AUTO_EXPOSURE / _EXPOSURE / _BLOOM, the fields of that transform
+//   display_kernel AKR_DISPLAY_KERNEL=<v> akr_display_transform's blur: 0 = two gathering passes, 1 = through LDS, -1 = the library decides (api_display.cpp)
 //   max_fused_passes (no environment hook)     most passes akr_pt_passes fuses into one launch: 0 = adaptive (16, up to 64 once a pass has been timed), else 1..64
 struct TuningOptions {
     int force_bvh = 0, bvh_balanced = 0, defer_metal = -1, wavefront = -1, simple_kernels = 1;
@@ -262,6 +265,9 @@ struct TuningOptions {
     int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
     int adaptive = 0;  // akr_render_task: > 0 = pt tasks render adaptively, threshold = adaptive / 1024.0f; 0 = uniformly
     int adaptive_min_spp = 0;  // ... min_spp of those renders; 0 = the default configuration's
+    int display = 0;  // akr_render_task: 1..4 = the curve of the display transform that follows every pt task; 0 = no such step
+    int display_auto_exposure = 0, display_exposure = 0, display_bloom = 0;  // ... its auto_exposure, exposure_ev x 1024, bloom_strength x 1024
+    int display_kernel = -1;  // akr_display_transform: which blur (0 gathering passes, 1 through LDS, -1 the library's choice); same bits either way
     int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
 };
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it

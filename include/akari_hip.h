@@ -605,6 +605,43 @@ AKR_API int32_t akr_pt_adaptive_render(akr_context *ctx, akr_scene *scene, const
                                        akr_film *half, uint32_t *tile_spp, akr_adaptive_stats *stats);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Display transform (no reference counterpart: write_image_ldr clips at 1): what lies between a film and an 8-bit file --
+ * exposure (manual, or the key-value rule over a trimmed log-luminance histogram), bloom (a bright pass, a pyramid of 2 x 2 boxes blurred
+ * with [1 4 6 4 1] / 16, recombined bilinearly) and a tone curve per channel, then a clamp to [0, 1]. Every pixel is resolved as
+ * akr_film_resolve does and sanitised with clamp(x, 0, 65504): NaN and negatives read as 0, +inf as 65504. The arithmetic is defined to
+ * the bit like the integrators'. The result is linear and display-referred: the PNG writer's sRGB OETF follows, unchanged.
+ * The defaults are choices, not measurements.
+ * ------------------------------------------------------------------------------------------------- */
+typedef enum { AKR_DISPLAY_LINEAR = 1, AKR_DISPLAY_REINHARD = 2, AKR_DISPLAY_ACES = 3, AKR_DISPLAY_HABLE = 4 } akr_display_curve;
+typedef struct {
+    uint32_t curve;            /* AKR_DISPLAY_ACES; linear = the clamp alone, reinhard (extended, `white`), aces (Narkowicz's fit), hable (`white`) */
+    uint32_t auto_exposure;    /* 0; 1: k = key / 2^(average log2 luminance of the trimmed histogram) * 2^exposure_ev */
+    float exposure_ev;         /* 0; finite. Manual exposure: k = 2^exposure_ev */
+    float key;                 /* 0.18; finite, > 0 (auto exposure) */
+    uint32_t low_permille, high_permille;  /* 50, 20: the share of the histogram's samples dropped at the bottom / top; their sum < 1000 */
+    float white;               /* 0 = the curve's default (reinhard 4, hable 11.2); finite, >= 0 */
+    float bloom_strength;      /* 0 = no bloom (nothing is allocated or launched); finite, >= 0 */
+    float bloom_threshold;     /* 1; finite, >= 0: luminance (after exposure) above which a pixel feeds the bloom */
+    uint32_t bloom_levels;     /* 5; 1..8 when bloom_strength > 0 */
+    uint32_t _pad[2];
+} akr_display_config;
+AKR_API int32_t akr_display_config_default(akr_display_config *cfg);
+/* counts256[i] = the pixels of `film` whose luminance L = (0.2126 r + 0.7152 g) + 0.0722 b (resolved, sanitised) falls into bin
+ * i = clamp(floor((log2 L + 20) 8), 0, 255) -- 1/8 EV each over [-20, 12) --, *skipped (may be NULL) = the pixels with L < 2^-20.
+ * Host arrays. Integer atomics: exact and independent of the order. Blocks until the result is there. */
+AKR_API int32_t akr_film_luminance_histogram(akr_context *ctx, akr_film *film, uint32_t *counts256, uint32_t *skipped);
+/* Host only, pure: the exposure k of `cfg` for a histogram. floor(N low_permille / 1000) samples are dropped from the bottom and
+ * floor(N high_permille / 1000) from the top (a split bin keeps its remainder), avg = mean bin centre / 8 - 20,
+ * k = key 2^-avg 2^exposure_ev; with nothing left (or auto_exposure's histogram empty) k = 2^exposure_ev. cfg->auto_exposure is not read. */
+AKR_API int32_t akr_display_exposure(const akr_display_config *cfg, const uint32_t *counts256, float *k);
+/* film -> out: rgb = the result, splat = 0, weight = 1, so akr_film_resolve(out) returns the result exactly; out may be `film`.
+ * *exposure_used (may be NULL) = k. AKR_ERR_INVALID_ARGUMENT: an unknown curve, bloom_levels outside 1..8 with bloom_strength > 0, a negative
+ * or non-finite strength or threshold, a non-finite exposure_ev, key or white, key <= 0, white < 0 (or so small that the curve's
+ * normalisation is not finite), low_permille + high_permille >= 1000, an exposure k beyond 2^100, films of different size or context.
+ * Enqueued on the context's stream, blocks until the result is complete; the bloom's work buffers (about 15 bytes per pixel) live for the call. */
+AKR_API int32_t akr_display_transform(akr_context *ctx, const akr_display_config *cfg, akr_film *film, akr_film *out, float *exposure_used);
+
+/* ---------------------------------------------------------------------------------------------------
  * `gpt` integrator (Method::GradientPathTracer, akari_integrator/src/gpt.rs; "type": "gpt"): gradient-domain path tracing.
  * Per sample one base path and four offset paths through the neighbouring pixels (stride apart, mirrored at the border)
  * on the same random numbers; the offset paths rejoin the base path through the reconnection shift mapping of
@@ -733,7 +770,9 @@ typedef enum {
     AKR_STRUCT_MCMC_CONFIG, AKR_STRUCT_MCMC_RESULT, AKR_STRUCT_MCMC_PARTIAL, AKR_STRUCT_ENVIRONMENT_DESC, AKR_STRUCT_LENS_DESC,
     AKR_STRUCT_DENOISE_CONFIG,
     /* (18 stays unknown: callers of earlier versions probe it as the first id past the list) */
-    AKR_STRUCT_ADAPTIVE_CONFIG = 19, AKR_STRUCT_ADAPTIVE_STATS
+    AKR_STRUCT_ADAPTIVE_CONFIG = 19, AKR_STRUCT_ADAPTIVE_STATS,
+    /* (21 stays unknown for the same reason) */
+    AKR_STRUCT_DISPLAY_CONFIG = 22
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
@@ -789,6 +828,15 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *                                           other fields: akr_adaptive_config_default, min_spp from "adaptive_min_spp"); 0 (default) = off, film.out
  *                                           byte-identical to earlier versions. Refused together with --save-intermediate and "denoise_variance".
  *   "adaptive_min_spp" (AKR_ADAPTIVE_MIN_SPP=n)  akr_render_task with "adaptive" > 0: min_spp; 0 (default) = akr_adaptive_config_default's
+ *   "display"      (AKR_DISPLAY=c)          akr_render_task: c = 1..4 (an akr_display_curve) = after a `pt` task has written film.out (and the denoised
+ *                                           image), akr_display_transform runs on the denoised film when "denoise" is on, else on the task's film,
+ *                                           and "{stem}.display.png" is written next to film.out; 0 (default) = off, every output byte-identical to
+ *                                           earlier versions. The other fields are akr_display_config_default's but for the three options below.
+ *   "display_auto_exposure" (AKR_DISPLAY_AUTO_EXPOSURE=1)  ... with auto_exposure = 1
+ *   "display_exposure" (AKR_DISPLAY_EXPOSURE=n)  ... with exposure_ev = n / 1024, -65536 <= n <= 65536
+ *   "display_bloom" (AKR_DISPLAY_BLOOM=n)   ... with bloom_strength = n / 1024, 0 <= n <= 65536
+ *   "display_kernel" (AKR_DISPLAY_KERNEL=v) akr_display_transform's blur: 0 = two gathering passes, 1 = one kernel whose horizontal pass stays in
+ *                                           LDS, -1 (default) = the library decides. Same bits either way.
  * Values out of an option's range fail with AKR_ERR_INVALID_ARGUMENT.
  * A session reads the options once, when it begins (akr_pt_begin / akr_gpt_begin / ...): a later akr_option_set does not change it.
  * "wavefront" = 1 on a scene without a BVH renders with the megakernel. Unknown names fail with AKR_ERR_INVALID_ARGUMENT. */

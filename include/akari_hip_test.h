@@ -147,6 +147,18 @@ AKR_TEST_API int32_t akr_host_half_bracket(uint32_t width, uint32_t height, cons
 AKR_TEST_API int32_t akr_probe_adapt_times(akr_context *ctx, akr_film *film, akr_film *half, uint32_t tile_w, uint32_t tile_h, const uint32_t *tiles, uint32_t n,
                                       float *times3);
 
+/* akr_display_transform on the host (no GPU): the text of csrc/device/ddisplay.h compiled for the host, over a host array. film = an accumulator in the
+ * reference layout [rgb 3N | splat 3N | weight N] with its splat scale. out_rgb = 3 N floats, what akr_film_resolve returns for akr_display_transform's
+ * output film; *exposure_used (may be NULL) = k. Same refusals as akr_display_transform. */
+AKR_TEST_API int32_t akr_host_display_transform(const akr_display_config *cfg, uint32_t width, uint32_t height, const float *film, float splat_scale, float *out_rgb,
+                                           float *exposure_used);
+/* akr_film_luminance_histogram on the host: counts256 and *skipped of a host film. */
+AKR_TEST_API int32_t akr_host_luminance_histogram(uint32_t width, uint32_t height, const float *film, float splat_scale, uint32_t *counts256, uint32_t *skipped);
+/* akr_display_transform under one blur (0 = gathering passes, 1 = LDS; -1 = the library's choice) with its parts timed by HIP events on the context's stream:
+ * times8 = milliseconds of the histogram kernel, the bloom source, all downsamples, all blurs, all upsamples, the apply pass, the whole call (the histogram's read-back included),
+ * the blur of level 1 alone (tools/display_bench.py). */
+AKR_TEST_API int32_t akr_probe_display_times(akr_context *ctx, const akr_display_config *cfg, akr_film *film, akr_film *out, int32_t kernel, float *times8);
+
 /* SurfaceInteraction of (inst, prim, u, v): out 19 floats / item = p, ng, n, t, s, uv, area, material. */
 /* The tables of the pmj02bn sampler as the library uses them: sets = u32[5 * 65536 * 2], bluenoise = u16[48 * 128 * 128]. */
 AKR_TEST_API int32_t akr_host_pmj02bn_tables(uint32_t *sets, uint16_t *bluenoise);
