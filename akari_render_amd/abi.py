@@ -430,6 +430,23 @@ class PtLaunchPlan(C.Structure):
         return d
 
 
+class PtFeaturesPlan(C.Structure):
+    """akr_pt_features_plan (include/akari_hip_test.h): akr_pt_launch_plan of a session that may collect the denoiser's guides, and the sizes of its layout."""
+
+    _fields_ = [
+        ("plan", PtLaunchPlan),
+        ("feat", C.c_uint32), ("kernel_compiled", C.c_uint32), ("park_slots", C.c_uint32), ("park_slots_feat", C.c_uint32),
+        ("required_bytes", C.c_uint32), ("lds_budget", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        d = self.plan.as_dict()
+        d["variant"]["feat"] = int(self.feat)
+        for k in ("kernel_compiled", "park_slots", "park_slots_feat", "required_bytes", "lds_budget"):
+            d[k] = int(getattr(self, k))
+        return d
+
+
 class SceneInfo(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),

@@ -34,6 +34,7 @@ EXPORTS = [
     "akr_scene_get_array", "akr_scene_get_image_count", "akr_scene_get_image", "akr_scene_get_material_graph", "akr_film_create",
     "akr_film_wrap", "akr_film_destroy", "akr_film_clear", "akr_film_read", "akr_film_write", "akr_film_resolve",
     "akr_film_device_ptr", "akr_pt_config_default", "akr_pt_config_from_json", "akr_pt_render", "akr_pt_begin", "akr_pt_passes",
+    "akr_pt_begin_features", "akr_pt_render_features",
     "akr_pt_end", "akr_pt_get_stats", "akr_render_task", "akr_image_write", "akr_aov_config_default", "akr_aov_render",
     "akr_gpt_config_default", "akr_gpt_render", "akr_gpt_begin", "akr_gpt_sample", "akr_gpt_sums", "akr_gpt_sums_read",
     "akr_gpt_sums_write", "akr_gpt_finish", "akr_gpt_abort", "akr_gpt_reduce", "akr_mcmc_config_default", "akr_mcmc_render",
@@ -58,6 +59,7 @@ TEST_EXPORTS = [
     "akr_host_pt_launch_plan", "akr_host_denoise_variance", "akr_probe_denoise_variance_times",
     "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
+    "akr_host_pt_features_plan",
 ]
 
 
@@ -126,6 +128,7 @@ def lib() -> C.CDLL:
     proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
     proto("akr_host_pt_launch_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, C.POINTER(abi.PtLaunchPlan))
+    proto("akr_host_pt_features_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, i32, i32, i32, C.POINTER(abi.PtFeaturesPlan))
     proto("akr_probe_env_sample", vp, vp, u32, fp, fp)
     proto("akr_probe_env_pdf", vp, vp, u32, fp, fp)
     proto("akr_scene_get_ggx_table", vp, fp)
@@ -188,6 +191,8 @@ def lib() -> C.CDLL:
     proto("akr_pt_render", vp, vp, C.POINTER(abi.PtConfig), vp, C.POINTER(abi.PtStats))
     proto("akr_pt_begin", vp, vp, C.POINTER(abi.PtConfig), vp, vpp)
     proto("akr_pt_passes", vp, u32, i32, up)
+    proto("akr_pt_begin_features", vp, vp, C.POINTER(abi.PtConfig), vp, vp, vp, vpp)
+    proto("akr_pt_render_features", vp, vp, C.POINTER(abi.PtConfig), vp, vp, vp, C.POINTER(abi.PtStats))
     proto("akr_pt_end", vp, C.POINTER(abi.PtStats))
     proto("akr_pt_get_stats", vp, C.POINTER(abi.PtStats))
     proto("akr_render_task", vp, vp, C.c_char_p, C.POINTER(RenderSession), C.POINTER(abi.PtStats))
@@ -339,6 +344,15 @@ class Scene:
         of a pt session of this scene and `cfg` under the given options; spec_waves != 0: with a per-scene kernel of that many waves."""
         out = abi.PtLaunchPlan()
         check(lib().akr_host_pt_launch_plan(self.h, C.byref(cfg), defer_metal, simple_kernels, defer_on, spec_waves, C.byref(out)))
+        return out.as_dict()
+
+    def features_plan(self, cfg: abi.PtConfig, feat: bool = True, defer_metal: int = -1, simple_kernels: int = 1, defer_on: int = 0, spec_waves: int = 0,
+                      wavefront: int = -1, arith: int = 0) -> dict:
+        """akr_host_pt_features_plan (test hook, no GPU): launch_plan for a session that collects the denoiser's guides (feat; variant["feat"]),
+        with the layout's park columns, required bytes and budget. Raises AkariError(ERR_UNSUPPORTED) where akr_pt_begin_features would refuse
+        under options wavefront / arith of the values given."""
+        out = abi.PtFeaturesPlan()
+        check(lib().akr_host_pt_features_plan(self.h, C.byref(cfg), defer_metal, simple_kernels, defer_on, spec_waves, 1 if feat else 0, wavefront, arith, C.byref(out)))
         return out.as_dict()
 
     def material_folded_host(self, material: int, uv: np.ndarray):
@@ -511,7 +525,7 @@ class Scene:
 
 
 def set_option(name: str, value: int) -> None:
-    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes, "adaptive" = n: render_task renders pt tasks adaptively with threshold n / 1024, "adaptive_min_spp", "display" = 1..4: render_task also writes {stem}.display.png through the display transform with that curve, "display_auto_exposure", "display_exposure" = EV x 1024, "display_bloom" = strength x 1024, "display_kernel")."""
+    """akr_option_set: process-wide tuning switches / test hooks ("force_bvh", "bvh_balanced", "defer_metal", "defer_on", "wavefront", "simple_kernels", "lens": akr_scene_load applies the file's focal_distance / fstop, "denoise": render_task follows every pt task with a denoise step, "denoise_variance": that step is akr_denoise_variance on the film after half the passes, "denoise_features": that step's guides are collected by the pt task's own session, "adaptive" = n: render_task renders pt tasks adaptively with threshold n / 1024, "adaptive_min_spp", "display" = 1..4: render_task also writes {stem}.display.png through the display transform with that curve, "display_auto_exposure", "display_exposure" = EV x 1024, "display_bloom" = strength x 1024, "display_kernel")."""
     check(lib().akr_option_set(name.encode(), int(value)))
 
 
@@ -647,13 +661,19 @@ class Film:
 
 
 class PtSession:
-    """akr_pt_begin / akr_pt_passes / akr_pt_end (the reference's `while cnt < spp` loop, pt.rs:1126-1149)."""
+    """akr_pt_begin / akr_pt_passes / akr_pt_end (the reference's `while cnt < spp` loop, pt.rs:1126-1149). With albedo and normal (both or
+    neither) akr_pt_begin_features: the session also accumulates the denoiser's guides into those two films from the samples it takes."""
 
-    def __init__(self, ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film):
+    def __init__(self, ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film, albedo: Optional[Film] = None, normal: Optional[Film] = None):
         self.ctx = ctx
         self.h = C.c_void_p()
         self._cfg = cfg.copy()
-        check(lib().akr_pt_begin(ctx.h, scene.h, C.byref(self._cfg), film.h, C.byref(self.h)))
+        if albedo is None and normal is None:
+            check(lib().akr_pt_begin(ctx.h, scene.h, C.byref(self._cfg), film.h, C.byref(self.h)))
+        else:  # (one of the two alone: the library refuses it)
+            self._guides = (albedo, normal)  # kept alive as long as the session
+            check(lib().akr_pt_begin_features(ctx.h if ctx is not None else None, scene.h, C.byref(self._cfg), film.h if film is not None else None,
+                                              albedo.h if albedo is not None else None, normal.h if normal is not None else None, C.byref(self.h)))
 
     def passes(self, n: int = 1, blocking: bool = False) -> int:
         done = C.c_uint32()
@@ -705,6 +725,15 @@ def pt_render(ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film) -> dict
     st = abi.PtStats()
     c = cfg.copy()
     check(lib().akr_pt_render(ctx.h, scene.h, C.byref(c), film.h, C.byref(st)))
+    return st.as_dict()
+
+
+def pt_render_features(ctx: Context, scene: Scene, cfg: abi.PtConfig, film: Film, albedo: Film, normal: Film) -> dict:
+    """akr_pt_render_features: pt_render that also accumulates the denoiser's albedo and shading-normal guides from the same samples."""
+    st = abi.PtStats()
+    c = cfg.copy()
+    check(lib().akr_pt_render_features(ctx.h if ctx is not None else None, scene.h, C.byref(c), film.h if film is not None else None,
+                                       albedo.h if albedo is not None else None, normal.h if normal is not None else None, C.byref(st)))
     return st.as_dict()
 
 

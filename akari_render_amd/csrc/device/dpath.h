@@ -452,6 +452,8 @@ struct PathRegs {
     Sampler smp;
     vec3 film_rgb;
     float film_w;
+    // FEAT sessions: the accumulators of the two guide films, albedo and shading normal of every sample's first hit (their weight is film_w)
+    vec3 feat_a, feat_n;
     uint32_t c_samples, c_closest, c_shadow, c_shaded;
     bool carry;  // BVH kernels: the lane's rays of the last intersection phase are still being traced (pt_pass.h: AKR_PT_STRAGGLERS)
     // a vertex whose shading was put off by one iteration (pt_pass.h: conductor hits are shaded on even iterations only)
@@ -468,12 +470,15 @@ struct PathRegs {
 // conflicts). path_step<.., PARK> writes the cold fields there before it shades a vertex and reads them back after: two LDS
 // instructions per field and iteration instead of a scratch store and load, and the registers are free in between. The pixel
 // of the lane (pix, sx, sy: constant for the launch) lives there for the whole launch.
-enum : uint32_t { PK_PIX = 0, PK_SX, PK_SY, PK_FILM, PK_FILM_W = PK_FILM + 3, PK_CNT, PK_SPP = PK_CNT + 3, PK_DEFER = PK_SPP + 3, PK_END = PK_DEFER + 3 };
+enum : uint32_t { PK_PIX = 0, PK_SX, PK_SY, PK_FILM, PK_FILM_W = PK_FILM + 3, PK_CNT, PK_SPP = PK_CNT + 3, PK_DEFER = PK_SPP + 3, PK_END = PK_DEFER + 3,
+                  // FEAT kernels (never DEFER: the columns of its fields are theirs): the guide accumulators, which live here for the whole launch
+                  PK_FEAT_A = PK_DEFER, PK_FEAT_N = PK_FEAT_A + 3, PK_END_FEAT = PK_FEAT_N + 3 };
 static_assert(PK_END <= kParkSlots, "park column too small");
+static_assert(PK_DEFER == kParkSlotsNoDefer && PK_END_FEAT <= kParkSlotsFeat, "park column of a FEAT kernel too small");
 AKR_D void park_put(uint32_t* park, uint32_t slot, uint32_t v) { park[slot * 256u] = v; }
 AKR_D uint32_t park_get(const uint32_t* park, uint32_t slot) { return park[slot * 256u]; }
 
-template <bool PMJ = false, bool LENS = false>
+template <bool PMJ = false, bool LENS = false, bool FEAT = false>
 AKR_D void path_regs_init(PathRegs& r, const PtParams& p, bool active, uint32_t pix, uint32_t sx, uint32_t sy) {
     const size_t N = (size_t)p.width * p.height;
     r.ro = mk3(0, 0, 0); r.rd = mk3(0, 0, 1); r.ray_ex0 = kInvalid;
@@ -490,10 +495,15 @@ AKR_D void path_regs_init(PathRegs& r, const PtParams& p, bool active, uint32_t 
     r.c_closest = 0; r.c_shadow = 0; r.c_shaded = 0;
     r.smp.pcg = Pcg32{0, 1}; r.smp.dim = 0;
     r.film_rgb = mk3(0, 0, 0); r.film_w = 0.0f;
+    r.feat_a = mk3(0, 0, 0); r.feat_n = mk3(0, 0, 0);
     if (active) {
         r.smp.pcg = p.states[pix];  // SamplerCreator::create, sampler/mod.rs:317-327
         r.film_rgb = mk3(p.film[3 * (size_t)pix + 0], p.film[3 * (size_t)pix + 1], p.film[3 * (size_t)pix + 2]);
         r.film_w = p.film[6 * N + pix];
+        if (FEAT) {
+            r.feat_a = mk3(p.feat_albedo[3 * (size_t)pix + 0], p.feat_albedo[3 * (size_t)pix + 1], p.feat_albedo[3 * (size_t)pix + 2]);
+            r.feat_n = mk3(p.feat_normal[3 * (size_t)pix + 0], p.feat_normal[3 * (size_t)pix + 1], p.feat_normal[3 * (size_t)pix + 2]);
+        }
         sampler_start<PMJ>(p, r.smp);  // sampler.start()
         generate_ray<PMJ, LENS>(p, sx, sy, r.smp, r.ro, r.rd);
     }
@@ -514,7 +524,10 @@ AKR_D void shifted_pixel(const PtParams& p, uint32_t px, uint32_t py, uint32_t& 
 // FD: 1 / 0 = force_diffuse known at compile time (the reference's JIT also specialises the kernel on it: the branch
 // at pt.rs:268 is taken while tracing the kernel, so a force_diffuse kernel contains no Principled code); -1 = read
 // p.force_diffuse at run time.
-template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
+// FEAT: the session collects the denoiser's guides. At a sample's depth-0 vertex the value k_aov (aov_kernel.h) computes
+// for the sample's camera ray -- albedo + emission, shading normal; a miss adds nothing -- goes to the lane's guide accumulators: registers, or
+// with PARK their LDS columns (PK_FEAT_*), where they stay from the first iteration to the lane's last store. No random number is drawn for it.
+template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
 AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found, bool occluded, uint32_t pix_in, uint32_t sx_in, uint32_t sy_in,
                      uint32_t* park = nullptr) {
     const bool force_diffuse = FD < 0 ? (p.force_diffuse != 0) : (FD != 0);
@@ -552,6 +565,20 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
             p.film[3 * (size_t)pix + 1] = r.film_rgb.y;
             p.film[3 * (size_t)pix + 2] = r.film_rgb.z;
             p.film[6 * N + pix] = r.film_w;
+            if (FEAT) {
+                if (PARK) {
+                    r.feat_a = mk3(u2f(park_get(park, PK_FEAT_A + 0)), u2f(park_get(park, PK_FEAT_A + 1)), u2f(park_get(park, PK_FEAT_A + 2)));
+                    r.feat_n = mk3(u2f(park_get(park, PK_FEAT_N + 0)), u2f(park_get(park, PK_FEAT_N + 1)), u2f(park_get(park, PK_FEAT_N + 2)));
+                }
+                p.feat_albedo[3 * (size_t)pix + 0] = r.feat_a.x;
+                p.feat_albedo[3 * (size_t)pix + 1] = r.feat_a.y;
+                p.feat_albedo[3 * (size_t)pix + 2] = r.feat_a.z;
+                p.feat_albedo[6 * N + pix] = r.film_w;
+                p.feat_normal[3 * (size_t)pix + 0] = r.feat_n.x;
+                p.feat_normal[3 * (size_t)pix + 1] = r.feat_n.y;
+                p.feat_normal[3 * (size_t)pix + 2] = r.feat_n.z;
+                p.feat_normal[6 * N + pix] = r.film_w;
+            }
         }
     }
     // ---- shade the vertex the closest-hit ray found ----
@@ -583,6 +610,29 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
             // TEX kernels, texture-fed inputs -- a per-hit record (graph evaluated at si.uv, folded here). Two instantiations
             // in the TEX kernels: lanes on constant materials keep the register-only path and no 256-byte private copy.
             auto shade_vertex = [&](const DMaterial& mat) {
+            if (FEAT && r.depth == 0) {
+                // k_aov's sample (aov_kernel.h): its ShadePoint has force_diffuse = false whatever the session shades with; a lean one gives shade_ns the same frame
+                ShadePoint fsp;
+                shade_point_init(fsp, mat, si.frame, si.ng, false, /*lean=*/true);
+                vec3 fa = shade_albedo_plus_emission(mat), fn = shade_ns(fsp, mat);
+                if (is_nan(fa.x) || is_nan(fa.y) || is_nan(fa.z)) fa = mk3(0, 0, 0);
+                if (is_nan(fn.x) || is_nan(fn.y) || is_nan(fn.z)) fn = mk3(0, 0, 0);
+                fa = fa * 1.0f;
+                fn = fn * 1.0f;
+                if (p.color & COLOR_REPR_ACES) {
+                    fa = cs_convert(fa, true, false);
+                    fn = cs_convert(fn, true, false);
+                }
+                if (PARK) {
+                    park_put(park, PK_FEAT_A + 0, f2u(u2f(park_get(park, PK_FEAT_A + 0)) + fa.x)); park_put(park, PK_FEAT_A + 1, f2u(u2f(park_get(park, PK_FEAT_A + 1)) + fa.y));
+                    park_put(park, PK_FEAT_A + 2, f2u(u2f(park_get(park, PK_FEAT_A + 2)) + fa.z));
+                    park_put(park, PK_FEAT_N + 0, f2u(u2f(park_get(park, PK_FEAT_N + 0)) + fn.x)); park_put(park, PK_FEAT_N + 1, f2u(u2f(park_get(park, PK_FEAT_N + 1)) + fn.y));
+                    park_put(park, PK_FEAT_N + 2, f2u(u2f(park_get(park, PK_FEAT_N + 2)) + fn.z));
+                } else {
+                    r.feat_a = mk3(r.feat_a.x + fa.x, r.feat_a.y + fa.y, r.feat_a.z + fa.z);
+                    r.feat_n = mk3(r.feat_n.x + fn.x, r.feat_n.y + fn.y, r.feat_n.z + fn.z);
+                }
+            }
             {  // handle_surface_light, pt.rs:230-258
                 vec3 direct = mk3(0, 0, 0);
                 float w = 0.0f;

@@ -44,8 +44,9 @@ using PairWalkOpt = WalkOpt<!TEX>;
 // INST: the scene is kept as meshes + instances (two-level traversal, dinst_trav.h).
 // ENV: the scene has an environment light (device/denv.h).
 // LENS: the camera has a thin lens (dpath.h generate_ray).
+// FEAT: the session collects the denoiser's albedo and normal guides from its own samples (dpath.h path_step).
 // Which combinations of the flags exist as kernels: kernels.h pt_variant_compiled.
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false>
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false>
 AKR_D void pt_pass_body(const PtParams& p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];  // BVH: kBvhStackDepth x 256 words; else: staged tables
     TraceCtx tc;
@@ -82,13 +83,17 @@ AKR_D void pt_pass_body(const PtParams& p) {
     shifted_pixel(p, px, py, sx, sy);
     if (PMJ && p.bn_offset != 0) pmj_bluenoise_stage(p, px, py);  // before the first draw (path_regs_init generates the first camera ray)
     PathRegs r;
-    path_regs_init<PMJ, LENS>(r, q, in_frame, pix, sx, sy);
+    path_regs_init<PMJ, LENS, FEAT>(r, q, in_frame, pix, sx, sy);
     constexpr bool PARK = !FD && TEX;  // cold path state in LDS while a vertex is shaded (dpath.h: PARK)
     uint32_t* park = lds_stack + p.park_offset + threadIdx.x;
     if (PARK) {
         park_put(park, PK_PIX, pix);
         park_put(park, PK_SX, sx);
         park_put(park, PK_SY, sy);
+        if (FEAT) {  // the guide accumulators' home for the launch (dpath.h PK_FEAT_*)
+            park_put(park, PK_FEAT_A + 0, f2u(r.feat_a.x)); park_put(park, PK_FEAT_A + 1, f2u(r.feat_a.y)); park_put(park, PK_FEAT_A + 2, f2u(r.feat_a.z));
+            park_put(park, PK_FEAT_N + 0, f2u(r.feat_n.x)); park_put(park, PK_FEAT_N + 1, f2u(r.feat_n.y)); park_put(park, PK_FEAT_N + 2, f2u(r.feat_n.z));
+        }
     }
 
     uint32_t iteration = 0;
@@ -213,8 +218,8 @@ AKR_D void pt_pass_body(const PtParams& p) {
             }
             if (STRAG > 0 && r.carry) {
                 // still tracing: nothing to resolve or shade yet
-            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV, LENS>(q, r, hit, found, occluded, 0, 0, 0, park);
-            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS>(q, r, hit, found, occluded, pix, sx, sy);
+            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV, LENS, FEAT>(q, r, hit, found, occluded, 0, 0, 0, park);
+            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS, FEAT>(q, r, hit, found, occluded, pix, sx, sy);
         }
     }
     flush_counters(p, r, tc.cnt, BVH);

@@ -220,6 +220,8 @@ struct RenderBase {
     PtVariant variant{};  // which instantiation of the pt kernel the session runs (session_params; kernels.h)
     PtParams params;  // the session's constant block (session_params); a launch sets n_passes / last_pass_spp (set_launch_passes)
     bool holds_scene = false;  // counted in scene->sessions (base_begin)
+    // a pt session begun by akr_pt_begin_features: the two guide films its FEAT kernels accumulate into; else null
+    akr_film *feat_albedo = nullptr, *feat_normal = nullptr;
     void fold_events(bool all) {  // all: the stream has been synchronised
         size_t keep = 0;
         for (size_t i = 0; i < pending.size(); i++) {
@@ -331,7 +333,11 @@ struct PtPlan {
     uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
     uint32_t stage_bytes[13], stage_total, tex_slots;
 };
-PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves);
+// feat: the session collects the denoiser's guides (akr_pt_begin_features): the FEAT kernels, which exclude DEFER and SIMPLE as ENV and LENS do.
+PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves, bool feat = false);
+// Why a pt session of (scene, options) cannot collect guides -- "" when it can. The ONE statement of akr_pt_begin_features' refusals that need no
+// device: kept scenes, a forced wavefront schedule, the relaxed arithmetic tier (akr_host_pt_features_plan asks it for host-only scenes).
+std::string pt_features_refusal(const akr_scene* s, const TuningOptions& t);
 // the part of the variant that is a fact of the scene and the config: bvh, fd, tex, pmj, inst, env, lens
 PtVariant pt_scene_facts(const akr_scene* s, const akr_pt_config& c);
 // DScene.bvh_stack_depth / n_nodes of a compiled scene (scene_finish fills them in; a host-only scene has no DScene)

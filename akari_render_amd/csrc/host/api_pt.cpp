@@ -17,13 +17,21 @@ PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
     return PtVariant{cs.has_tree(), c.force_diffuse != 0, cs.has_textures, c.sampler_type != AKR_SAMPLER_INDEPENDENT, false, false, false,
                      cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f};
 }
-PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves) {
+std::string akr_api::pt_features_refusal(const akr_scene* s, const TuningOptions& t) {
+    if (s->cs.instanced.on)
+        return "unsupported: akr_pt_begin_features: the scene is kept as meshes + instances (option instancing); its kernels collect no guides -- render them with akr_aov_render";
+    if (t.wavefront == 1) return "unsupported: akr_pt_begin_features: the wavefront schedule is forced (option wavefront = 1); only the megakernel collects guides";
+    if (t.arith == 1) return "unsupported: akr_pt_begin_features: the relaxed arithmetic tier (option arith = 1) has no kernels that collect guides";
+    return "";
+}
+PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves, bool feat) {
     const CompiledScene& cs = s->cs;
     PtPlan pl{};
     PtVariant& v = pl.v = pt_scene_facts(s, c);
+    v.feat = feat;
     // The exclusion rules, applied here and nowhere else (kernels.h pt_variant_compiled states them): no DEFER and no SIMPLE kernels with an
-    // environment light or a lens; a kept scene has neither, and its kernels stage no tables.
-    const bool plain = !v.env && !v.lens;
+    // environment light, a lens or collected guides; a kept scene has neither, and its kernels stage no tables.
+    const bool plain = !v.env && !v.lens && !v.feat;
     {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
         // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
         // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
@@ -141,7 +149,7 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, b
         }
     }
     {   // which kernel, which tables staged in LDS: decided from the scene and the config (pt_plan), kept with the session
-        const PtPlan plan = pt_plan(s, c, se->defer_metal_option, se->simple_kernels_option, se->defer_on_option, spec_active, spec_waves);
+        const PtPlan plan = pt_plan(s, c, se->defer_metal_option, se->simple_kernels_option, se->defer_on_option, spec_active, spec_waves, se->feat_albedo != nullptr);
         se->variant = plan.v;
         std::memcpy(p.stage_bytes, plan.stage_bytes, sizeof p.stage_bytes);
         p.stage_total = plan.stage_total;
@@ -164,6 +172,8 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, b
     p.tiles_y = se->grid.tiles_y;
     p.owned_tiles = se->owned_tiles.as<uint32_t>();  // (null unless shard_count > 1: base_begin)
     p.n_items = se->grid.n_items;
+    p.feat_albedo = se->feat_albedo ? se->feat_albedo->data : nullptr;
+    p.feat_normal = se->feat_normal ? se->feat_normal->data : nullptr;
 }
 std::vector<uint32_t> akr_api::owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count) {
     std::vector<std::pair<uint32_t, uint32_t>> mine;  // (Morton code, tile)
@@ -413,6 +423,7 @@ static bool schedule_trial_eligible(const akr_pt_session* se) {
     const TuningOptions t = tuning();
     const akr_scene* sc = se->scene;
     if (t.wavefront != -1 || t.sched_trial == 0 || se->wf || se->arith_relaxed || se->spec_active) return false;
+    if (se->feat_albedo) return false;  // a session that collects guides stays on the megakernel
     if (sc->cs.instanced.on || !sc->cs.has_tree() || t.wf_sort != 0) return false;
     if (t.sched_trial == 1) return true;
     const uint64_t passes = (session_samples(se->cfg) + se->cfg.spp_per_pass - 1) / se->cfg.spp_per_pass;
@@ -536,14 +547,16 @@ int32_t akr_api::render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_c
         *out = se.release();
     });
 }
-extern "C" {
-AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out) {
-    if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: NULL argument");
+// akr_pt_begin, and with the two guide films akr_pt_begin_features (whose refusals the caller has already made)
+static int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, akr_pt_session** out) {
     *out = nullptr;
     return guarded([&] {
         auto se = std::make_unique<akr_pt_session>();
         base_begin(se.get(), ctx, scene, cfg, film);
-        const bool wavefront = choose_wavefront(se.get());
+        se->feat_albedo = albedo;
+        se->feat_normal = normal;
+        const bool features = albedo != nullptr;
+        const bool wavefront = !features && choose_wavefront(se.get());
         const bool wf_sort = wavefront && tuning().wf_sort != 0;
         {
             const TuningOptions t = tuning();
@@ -558,13 +571,15 @@ AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_co
             // kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
             // Which sessions it takes is decided here and nowhere else: its translation unit holds the variants without inst, env and lens.
             const PtVariant facts = pt_scene_facts(scene, *cfg);
-            se->arith_relaxed = t.arith == 1 && !facts.inst && !wavefront;
+            se->arith_relaxed = t.arith == 1 && !facts.inst && !wavefront && !features;
             if (se->arith_relaxed && facts.env)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
             if (se->arith_relaxed && facts.lens)
                 throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)");
             if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
             else if (wavefront) se->spec_status = "wavefront schedule";
+            else if (features) se->spec_status = scene->cs.has_textures && t.specialise == 1 ? "guides are collected by the interpreter kernels: no per-scene kernel (option specialise ignored)"
+                                                                                            : "guides are collected by the precompiled kernels";
             else if (!scene->cs.has_textures) se->spec_status = "the scene has no texture-fed material";
             else if (t.specialise == 0) se->spec_status = "option specialise = 0";
             else if (cfg->force_diffuse) se->spec_status = "force_diffuse kernels evaluate no surface graphs";
@@ -594,6 +609,30 @@ AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_co
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         *out = se.release();
     });
+}
+extern "C" {
+AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_session** out) {
+    if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin: NULL argument");
+    return pt_begin(ctx, scene, cfg, film, nullptr, nullptr, out);
+}
+// A pt session whose kernels also accumulate the denoiser's guides (include/akari_hip.h). Everything it cannot do is refused
+// here, before a byte is allocated or written.
+AKR_API int32_t akr_pt_begin_features(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, akr_pt_session** out) {
+    if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: NULL argument");
+    *out = nullptr;
+    if (!ctx || (scene && !scene->ctx))
+        return fail(AKR_ERR_UNSUPPORTED, "unsupported: akr_pt_begin_features: guides are collected by GPU kernels; a host-only scene (no device context) cannot render them");
+    if (!scene || !cfg || !film) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: NULL argument");
+    if (!albedo || !normal) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: both guide films are required (albedo and normal)");
+    if (albedo == normal || albedo == film || normal == film) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: film, albedo and normal must be three different films");
+    for (const akr_film* g : {albedo, normal}) {
+        if (g->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: a guide film belongs to another context");
+        if (g->width != scene->flat.camera.width || g->height != scene->flat.camera.height)
+            return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: a guide film's resolution does not match the scene camera");
+    }
+    const std::string why = pt_features_refusal(scene, tuning());
+    if (!why.empty()) return fail(AKR_ERR_UNSUPPORTED, why);
+    return pt_begin(ctx, scene, cfg, film, albedo, normal, out);
 }
 AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blocking, uint32_t* spp_done) {
     if (!se) return fail(AKR_ERR_INVALID_ARGUMENT, "session is NULL");
@@ -756,7 +795,7 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         info->specialised = se->spec_active ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
         const PtVariant& v = se->variant;  // (bit 0: the flattened scene's tree; a kept scene's two-level traversal does not set it)
-        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u);
+        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;
@@ -777,6 +816,14 @@ AKR_API int32_t akr_pt_end(akr_pt_session* se, akr_pt_stats* stats) { return bas
 AKR_API int32_t akr_pt_render(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_stats* stats) {
     akr_pt_session* se = nullptr;
     int32_t rc = akr_pt_begin(ctx, scene, cfg, film, &se);
+    if (rc != AKR_OK) return rc;
+    uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
+    rc = akr_pt_passes(se, n_passes, 1, nullptr);
+    return end_keeping_first_error(rc, [&] { return akr_pt_end(se, stats); });
+}
+AKR_API int32_t akr_pt_render_features(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, akr_pt_stats* stats) {
+    akr_pt_session* se = nullptr;
+    int32_t rc = akr_pt_begin_features(ctx, scene, cfg, film, albedo, normal, &se);
     if (rc != AKR_OK) return rc;
     uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
     rc = akr_pt_passes(se, n_passes, 1, nullptr);

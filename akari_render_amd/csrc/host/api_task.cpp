@@ -21,8 +21,17 @@ std::string denoised_path(const std::string& out) {
 // Option "denoise" (DESIGN.md 4.10): the feature passes of a finished pt task -- albedo and ns (not remapped) at `spp` samples with the task's
 // sampler, seed, filter and colour pipeline, through the scene's lens if it has one -- then akr_denoise with its defaults, in place in `film`.
 // half (option "denoise_variance"): the film after the first half of the task's passes; the filter is akr_denoise_variance then.
-void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, akr_film* film, akr_film* half, uint32_t spp, bool verbose) {
+// own_albedo / own_normal (option "denoise_features"): the guides the task's own session collected; no feature passes then.
+void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, akr_film* film, akr_film* half, uint32_t spp, bool verbose, akr_film* own_albedo = nullptr,
+                  akr_film* own_normal = nullptr) {
     auto check = [](int32_t rc) { if (rc != AKR_OK) throw std::runtime_error(std::string(g_last_error)); };
+    akr_denoise_config dc;
+    check(akr_denoise_config_default(&dc));
+    if (own_albedo && own_normal) {
+        check(half ? akr_denoise_variance(ctx, &dc, film, half, own_albedo, own_normal, film) : akr_denoise(ctx, &dc, film, own_albedo, own_normal, film));
+        if (verbose) std::fprintf(stderr, "[akari_hip] Denoised (guides collected by the task's own %u spp)\n", cfg.spp);
+        return;
+    }
     akr_aov_config ac;
     check(akr_aov_config_default(&ac));
     ac.spp = spp;
@@ -40,8 +49,6 @@ void denoise_step(akr_context* ctx, akr_scene* scene, const akr_pt_config& cfg, 
     check(akr_aov_render(ctx, scene, &ac, albedo.f, &sa));
     ac.aov = AKR_AOV_NS;
     check(akr_aov_render(ctx, scene, &ac, normal.f, &sn));
-    akr_denoise_config dc;
-    check(akr_denoise_config_default(&dc));
     check(half ? akr_denoise_variance(ctx, &dc, film, half, albedo.f, normal.f, film) : akr_denoise(ctx, &dc, film, albedo.f, normal.f, film));
     if (verbose) std::fprintf(stderr, "[akari_hip] Denoised (feature passes of %u spp: %.2fms)\n", spp, sa.kernel_ms + sn.kernel_ms);
 }
@@ -80,7 +87,10 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
     if (session) ses = *session;
     const std::string name = ses.name ? ses.name : "default";
     const TuningOptions opts = tuning();  // read once, like a session's options
-    const int denoise_spp = opts.denoise;
+    // option "denoise_features" implies the denoise step; where its guides cannot come from the task's session (a session that refuses them, an
+    // adaptive task) they come from aov passes as ever, of "denoise" spp if that is set, else 16
+    const bool denoise_features = opts.denoise_features != 0;
+    const int denoise_spp = opts.denoise > 0 ? opts.denoise : (denoise_features ? 16 : 0);
     const bool denoise_variance = denoise_spp > 0 && opts.denoise_variance != 0;
     const int adaptive = opts.adaptive;
     return guarded([&] {
@@ -215,7 +225,17 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
                     HIP_CHECK(hipStreamSynchronize(ctx->stream));
                 }));
             };
-            check(akr_pt_begin(ctx, scene, &task.cfg, film, &se));
+            FilmHolder own_albedo, own_normal;  // option "denoise_features": the guide films of the task's session
+            bool own_guides = false;
+            if (denoise_features) {
+                check(akr_film_create(ctx, w, h, &own_albedo.f));
+                check(akr_film_create(ctx, w, h, &own_normal.f));
+                const int32_t rc = akr_pt_begin_features(ctx, scene, &task.cfg, film, own_albedo.f, own_normal.f, &se);
+                if (rc == AKR_OK) own_guides = true;
+                else if (rc != AKR_ERR_UNSUPPORTED) check(rc);
+                else if (ses.verbose) std::fprintf(stderr, "[akari_hip] denoise_features: %s; the guides come from aov passes of %d spp\n", g_last_error.c_str(), denoise_spp);
+            }
+            if (!own_guides) check(akr_pt_begin(ctx, scene, &task.cfg, film, &se));
             std::string stats_json = "{\"intermediate\":[";
             uint32_t cnt = 0;
             bool first = true;
@@ -259,7 +279,7 @@ AKR_API int32_t akr_render_task(akr_context* ctx, akr_scene* scene, const char* 
             write_image(task.film_out, rgb.data(), w, h);  // util::write_image(&output_image, &config.film.out), lib.rs:192
             if (stats_out) *stats_out = st;
             if (denoise_spp > 0) {  // option "denoise": film.out is written as ever, the denoised image next to it
-                denoise_step(ctx, scene, task.cfg, done.f, half.f, (uint32_t)denoise_spp, ses.verbose != 0);
+                denoise_step(ctx, scene, task.cfg, done.f, half.f, (uint32_t)denoise_spp, ses.verbose != 0, own_guides ? own_albedo.f : nullptr, own_guides ? own_normal.f : nullptr);
                 check(akr_film_resolve(done.f, rgb.data()));
                 write_image(denoised_path(task.film_out), rgb.data(), w, h);
             }

@@ -1,6 +1,6 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance]
+//             [--resolution WxH] [--independent-sampler] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
 //             [--adaptive [X]] [--adaptive-min-spp N] [--display [linear|reinhard|aces|hable]] [--exposure EV] [--auto-exposure] [--bloom [X]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
@@ -8,6 +8,8 @@
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 // --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
 // --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
+// --denoise-features (library option "denoise_features"; implies the denoise step): the filter's albedo / normal guides are collected by the pt task's own samples,
+// not by passes of their own; N of --denoise then only matters where the session cannot collect them.
 // --adaptive [X] (library option "adaptive" = X * 1024; the library's default threshold when X is left out): pt tasks render adaptively, the task's spp the most a pixel
 // gets; --adaptive-min-spp N (option "adaptive_min_spp"): the samples a tile receives before it may retire.
 // --display [CURVE] (library option "display"; aces when CURVE is left out): every pt task also writes {stem}.display.png, its film (the denoised one with --denoise)
@@ -25,7 +27,7 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
               "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
               "                 [--display [linear|reinhard|aces|hable]] [--exposure <EV>] [--auto-exposure] [--bloom [<X>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
@@ -38,6 +40,7 @@ static void usage() {
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
               "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
               "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)\n"
+              "      --denoise-features   the denoise step (implied) takes its albedo / normal guides from the pt task's own samples instead of from passes of their own\n"
               "      --adaptive [<X>]     pt tasks render adaptively: tiles whose error estimate is <= X stop receiving samples, spp is the most a pixel gets\n"
               "      --adaptive-min-spp <N>  with --adaptive: samples a tile receives before it may retire\n"
               "      --display [<CURVE>]  pt tasks also write {stem}.display.png: exposure, bloom and a tone curve (linear, reinhard, aces (default), hable)\n"
@@ -67,7 +70,7 @@ int main(int argc, char** argv) {
     unsigned w = 0, h = 0;
     int dof = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
-    int denoise = 0, denoise_variance = 0;
+    int denoise = 0, denoise_variance = 0, denoise_features = 0;
     int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
     int display = 0, display_exposure = 0, display_auto = 0, display_bloom = 0, display_fields = 0;  // the options' values; display_fields: one of the three others was given
     for (int i = 1; i < argc; i++) {
@@ -94,6 +97,7 @@ int main(int argc, char** argv) {
             }
         }
         else if (a == "--denoise-variance") denoise_variance = 1;
+        else if (a == "--denoise-features") denoise_features = 1;
         else if (a == "--adaptive") {  // the threshold is optional: taken only if the next argument is a number
             akr_adaptive_config ac;
             akr_adaptive_config_default(&ac);
@@ -177,7 +181,8 @@ int main(int argc, char** argv) {
     if (akr_context_create(device, &ctx) != AKR_OK) die("device");
     if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
     if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
-    if (denoise_variance && !denoise) { std::fputs("akari-cli: --denoise-variance needs --denoise\n", stderr); return 1; }
+    if (denoise_features && akr_option_set("denoise_features", 1) != AKR_OK) die("option denoise_features");
+    if (denoise_variance && !denoise && !denoise_features) { std::fputs("akari-cli: --denoise-variance needs --denoise or --denoise-features\n", stderr); return 1; }
     if (denoise_variance && akr_option_set("denoise_variance", 1) != AKR_OK) die("option denoise_variance");
     if (adaptive_min_spp && !adaptive) { std::fputs("akari-cli: --adaptive-min-spp needs --adaptive\n", stderr); return 1; }
     if (adaptive && akr_option_set("adaptive", adaptive) != AKR_OK) die("option adaptive");

@@ -831,6 +831,7 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_ARITH")) g_tuning.arith = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE")) g_tuning.denoise = std::max(0, std::min(65536, std::atoi(e)));
     if (const char* e = std::getenv("AKR_DENOISE_VARIANCE")) g_tuning.denoise_variance = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("AKR_DENOISE_FEATURES")) g_tuning.denoise_features = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_DENOISE_KERNEL")) g_tuning.denoise_kernel = std::max(-1, std::min(1, std::atoi(e)));
     if (const char* e = std::getenv("AKR_ADAPTIVE")) g_tuning.adaptive = std::max(0, std::min(1 << 20, std::atoi(e)));
     if (const char* e = std::getenv("AKR_DISPLAY")) g_tuning.display = std::max(0, std::min(4, std::atoi(e)));
@@ -862,6 +863,7 @@ int* tuning_field(const char* name) {
     if (n == "pad_percent") return &g_tuning.pad_percent;
     if (n == "denoise") return &g_tuning.denoise;
     if (n == "denoise_variance") return &g_tuning.denoise_variance;
+    if (n == "denoise_features") return &g_tuning.denoise_features;
     if (n == "denoise_kernel") return &g_tuning.denoise_kernel;
     if (n == "adaptive") return &g_tuning.adaptive;
     if (n == "adaptive_min_spp") return &g_tuning.adaptive_min_spp;
@@ -899,6 +901,7 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.pad_percent && (value < 1 || value > 10000)) return false;
     if (f == &g_tuning.denoise && (value < 0 || value > 65536)) return false;
     if (f == &g_tuning.denoise_variance && (value < 0 || value > 1)) return false;
+    if (f == &g_tuning.denoise_features && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.denoise_kernel && (value < -1 || value > 1)) return false;
     if (f == &g_tuning.adaptive && (value < 0 || value > (1 << 20))) return false;
     if (f == &g_tuning.adaptive_min_spp && (value < 0 || value > 65536)) return false;

@@ -236,6 +236,7 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //                                         under each schedule and goes on with the faster; 0 = never (the megakernel); 1 = every pt session on a scene with a tree (tests)
 //   denoise      AKR_DENOISE=<n>          akr_render_task: n > 0 = every pt task is followed by albedo + ns aov passes of n spp and akr_denoise, "{stem}.denoised{ext}" written
 //   denoise_variance AKR_DENOISE_VARIANCE=1  akr_render_task with denoise > 0: the step is akr_denoise_variance, its half film the task's film after floor(n_passes / 2) passes
+//   denoise_features AKR_DENOISE_FEATURES=1  akr_render_task: a pt task's denoise step takes its guides from the task's own session (akr_pt_begin_features), not from aov passes
 //   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
 //   adaptive     AKR_ADAPTIVE=<n>         akr_render_task: n > 0 = pt tasks render through akr_pt_adaptive_render with threshold n / 1024 (api_adapt.cpp); 0 = off
 //   adaptive_min_spp AKR_ADAPTIVE_MIN_SPP=<n>  ... with this min_spp; 0 = akr_adaptive_config_default's
@@ -262,6 +263,7 @@ struct TuningOptions {
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
     int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
+    int denoise_features = 0;  // akr_render_task: 1 = the denoise step's guides come from the pt task's own session (akr_pt_begin_features), not from aov passes
     int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
     int adaptive = 0;  // akr_render_task: > 0 = pt tasks render adaptively, threshold = adaptive / 1024.0f; 0 = uniformly
     int adaptive_min_spp = 0;  // ... min_spp of those renders; 0 = the default configuration's

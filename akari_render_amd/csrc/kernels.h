@@ -14,21 +14,24 @@
 // outside the namespace: the relaxed tier's translation unit compiles this header inside another one (pt_kernels_relaxed.hip).
 struct PtVariant {
     bool bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens;
+    bool feat;  // the session collects the denoiser's guides (device/dpath.h FEAT). Last: aggregate initialisers without it mean feat = false
 };
 // The combinations that exist as precompiled kernels -- the one statement of the exclusion rules: the exhaustive kernels always stage;
 // DEFER only in full-graph kernels, of BVH scenes those with textures; SIMPLE only in full-graph kernels of scenes without textures;
-// neither with an environment light or a lens; a kept scene runs the BVH kernel without staged tables, DEFER or SIMPLE.
+// neither with an environment light, a lens or collected guides; a kept scene runs the BVH kernel without staged tables, DEFER or SIMPLE, and
+// collects no guides.
 constexpr bool pt_variant_compiled(const PtVariant& v) {
-    return (v.bvh || v.stage) && !(v.defer && (v.fd || (v.bvh && !v.tex))) && !(v.simple && (v.fd || v.tex)) && !((v.env || v.lens) && (v.defer || v.simple)) &&
-           !(v.inst && !(v.bvh && !v.stage && !v.defer && !v.simple));
+    return (v.bvh || v.stage) && !(v.defer && (v.fd || (v.bvh && !v.tex))) && !(v.simple && (v.fd || v.tex)) && !((v.env || v.lens || v.feat) && (v.defer || v.simple)) &&
+           !(v.inst && !(v.bvh && !v.stage && !v.defer && !v.simple && !v.feat));
 }
 // The flags of a per-scene kernel request as one integer: akr_host_spec_compile(_text), the helper process's command line (fd = false,
 // tex = true, no SIMPLE: a per-scene kernel is the full-graph kernel of a scene with textures).
 constexpr uint32_t pt_variant_bits(const PtVariant& v) {
-    return (v.bvh ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (v.inst ? 16u : 0u) | (v.env ? 32u : 0u) | (v.lens ? 64u : 0u);
+    return (v.bvh ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (v.inst ? 16u : 0u) | (v.env ? 32u : 0u) | (v.lens ? 64u : 0u) |
+           (v.feat ? 128u : 0u);  // (never set in a per-scene kernel's request: a FEAT session runs the interpreter kernels)
 }
 constexpr PtVariant pt_variant_from_bits(uint32_t f) {
-    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0};
+    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0, (f & 128u) != 0};
 }
 // pt_lds_layout (below): what it is given ...
 struct PtLdsSizes {
@@ -60,6 +63,7 @@ namespace akr {
 // LDS columns per lane (one word per slot, slot s of lane i at word s * 256 + i): cold path state parked while a vertex is shaded
 // (dpath.h: PARK), and a traversal carried over to the next intersection phase (device/pt_pass.h).
 constexpr uint32_t kParkSlots = 16, kParkSlotsNoDefer = 13;  // dpath.h: PK_*
+constexpr uint32_t kParkSlotsFeat = 19;                      // FEAT kernels (never DEFER): the 13 and the two guide accumulators (PK_FEAT_*)
 // The columns of a carried traversal (device/pt_pass.h, dinst_trav.h trace_pair_inst): best hit so far | place in the tree | which of the vertex's
 // two rays | the first ray's hit | kept scenes (dinst_trav.h): TLAS leaf of the instance the ray is in, the candidate waiting for its exact test.
 // A carried ray of the wavefront schedule (wf_kernels.hip, WfBuffers::carry) keeps the same groups of four (carry_best, carry_place, carry_inst).
@@ -83,7 +87,7 @@ inline PtLdsLayout pt_lds_layout(const PtVariant& v, const PtLdsSizes& s, bool p
     PtLdsLayout L{};
     const size_t slots = v.tex ? (size_t)s.tex_slots * kTexValStride * sizeof(TexVal) : 0;
     const int stragglers = v.inst ? AKR_PT_STRAGGLERS_INST : (v.tex ? AKR_PT_STRAGGLERS_TEX : AKR_PT_STRAGGLERS);
-    const size_t park = (!v.fd && v.tex) ? (size_t)(v.defer || plan_larger_park ? kParkSlots : kParkSlotsNoDefer) * 256 * 4 : 0;
+    const size_t park = (!v.fd && v.tex) ? (size_t)(v.feat ? kParkSlotsFeat : (v.defer || plan_larger_park ? kParkSlots : kParkSlotsNoDefer)) * 256 * 4 : 0;
     const size_t carry = (v.bvh && stragglers > 0) ? (size_t)(v.inst ? kCarrySlotsInstanced : kCarrySlots) * 256 * 4 : 0;
     auto align = [](size_t b) { return (b + 15) & ~(size_t)15; };
     size_t base = v.bvh ? (size_t)s.stack_depth * 256 * 4 : 0;
@@ -171,6 +175,8 @@ struct PtParams {
     const uint32_t* owned_tiles;  // shard_count > 1: the tiles (row-major ids) this rank owns, in Morton order (tile_owner below); else null
     // thin lens (dpath.h generate_ray_lens_from): radius > 0 = the session runs the LENS kernels, which alone read these
     float lens_radius, lens_focal;
+    // FEAT kernels alone read these: the accumulators (7 N floats, the film's layout) of the albedo and the shading-normal guide
+    float *feat_albedo, *feat_normal;
 };
 
 // Which rank owns tile (tx, ty) of a frame shared by `count` ranks: its position on the Z-order (Morton) curve, modulo the ranks

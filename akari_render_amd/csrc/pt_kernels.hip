@@ -197,14 +197,19 @@ __global__ void k_probe_material(PtParams p, uint32_t material, uint32_t n, cons
 extern "C" hipError_t akr_launch_pt_pass_relaxed(const void* params, const PtVariant* v, uint32_t blocks, size_t lds, hipStream_t stream);
 namespace akr {
 static hipError_t pt_pass_entry_plain(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) { return pt_pass_entry_t<false, false>(q, v, blocks, lds, stream); }
-// the translation unit that holds the kernels of a variant, by [inst][env][lens]
+// the translation unit that holds the kernels of a variant, by [inst][env][lens]; those that collect the denoiser's guides by [env][lens]
 static constexpr PtPassEntry kPtPassEntry[2][2][2] = {{{pt_pass_entry_plain, pt_pass_entry_lens}, {pt_pass_entry_env, pt_pass_entry_lens_env}},
                                                       {{pt_pass_entry_inst, pt_pass_entry_inst_lens}, {pt_pass_entry_inst_env, pt_pass_entry_inst_lens_env}}};
+static constexpr PtPassEntry kPtPassEntryFeat[2][2] = {{pt_pass_entry_feat, pt_pass_entry_feat_lens}, {pt_pass_entry_feat_env, pt_pass_entry_feat_lens_env}};
 hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t stream, hipFunction_t spec_fn, bool relaxed) {
     const uint32_t blocks = (p.n_items + 255u) / 256u;
     if (blocks == 0) return hipSuccess;
     const PtLdsLayout L = pt_lds_layout(v, pt_lds_sizes(p));
     const PtParams q = pt_params_with_layout(p, L);
+    if (v.feat) {  // precompiled kernels of flattened scenes on the contract, nothing else (host/api_pt.cpp akr_pt_begin_features refuses the rest)
+        if (spec_fn || relaxed || v.inst) return hipErrorInvalidValue;
+        return kPtPassEntryFeat[v.env][v.lens](q, v, blocks, L.total_bytes, stream);
+    }
     if (spec_fn) {  // the scene's own kernel (host/specialise.cpp) wraps the body of whatever the variant is: same parameter block, same LDS layout
         if (L.total_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)spec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total_bytes);
         void* args[] = {(void*)&q};

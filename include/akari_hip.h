@@ -448,6 +448,21 @@ AKR_API int32_t akr_pt_render(akr_context *ctx, akr_scene *scene, const akr_pt_c
 AKR_API int32_t akr_pt_begin(akr_context *ctx, akr_scene *scene, const akr_pt_config *cfg, akr_film *film,
                              akr_pt_session **out);
 AKR_API int32_t akr_pt_passes(akr_pt_session *session, uint32_t n_passes, int32_t blocking, uint32_t *spp_done);
+/* akr_pt_begin / akr_pt_render for a session that also collects the denoiser's guides from the samples it takes: for every
+ * sample, what akr_aov_render computes for that sample's camera ray -- AKR_AOV_ALBEDO into `albedo`, AKR_AOV_NS (not remapped) into `normal`,
+ * (0, 0, 0) where the ray leaves the scene -- is added to the guide film as a radiance sample is added to `film`; a guide's weight plane is
+ * written with the colour film's. The vertex is recorded whatever max_depth, force_diffuse, indirect_only and debug_depth say, and draws no
+ * random number: `film`, the sampler states and the counters are bit for bit those of akr_pt_begin's session. Both guide films are required:
+ * films of this context with the frame's size, different from each other and from `film` (clear them first; they go through akr_film_resolve,
+ * akr_film_reduce and akr_denoise like any film). akr_pt_passes, akr_pt_set_active_tiles, akr_pt_get_stats, akr_pt_kernel_info (kernel_flags bit 6)
+ * and akr_pt_end work on the session unchanged; tile shards and sample ranges as well.
+ * Refused with AKR_ERR_UNSUPPORTED, before anything is allocated or written: a scene kept as meshes + instances, option "wavefront" = 1, option
+ * "arith" = 1, a host-only scene or a NULL context. The automatic schedule choice and the timed schedule trial stay on the megakernel; option
+ * "specialise" falls back to the interpreter kernels (akr_kernel_info.status says so). */
+AKR_API int32_t akr_pt_begin_features(akr_context *ctx, akr_scene *scene, const akr_pt_config *cfg, akr_film *film, akr_film *albedo, akr_film *normal,
+                                      akr_pt_session **out);
+AKR_API int32_t akr_pt_render_features(akr_context *ctx, akr_scene *scene, const akr_pt_config *cfg, akr_film *film, akr_film *albedo, akr_film *normal,
+                                       akr_pt_stats *stats);
 AKR_API int32_t akr_pt_end(akr_pt_session *session, akr_pt_stats *stats);
 /* Waits for the queued passes and returns the counters accumulated so far (the session stays open). */
 AKR_API int32_t akr_pt_get_stats(akr_pt_session *session, akr_pt_stats *stats);
@@ -467,7 +482,7 @@ typedef struct {
     uint32_t absent_mask;     /* lobes no material of the scene can have: 1 coat, 2 transmission, 4 normal map, 8 glass, 16 conductor */
     uint32_t min_waves;       /* waves per SIMD the kernel was compiled for */
     uint32_t vgprs, scratch_bytes;
-    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens) */
+    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features) */
     uint32_t _pad;
     double compile_ms;        /* hiprtc compile at akr_pt_begin (0 on a cache hit) */
     double load_ms;           /* cache lookup + module load */
@@ -822,6 +837,11 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *   "denoise_variance" (AKR_DENOISE_VARIANCE=1)  akr_render_task with "denoise" > 0: 1 = the denoise step is akr_denoise_variance, its half film the
  *                                           task's film after the first floor(n_passes / 2) passes (film.out is unchanged); a task of a single pass
  *                                           (spp <= spp_per_pass) is refused. 0 (default) = akr_denoise.
+ *   "denoise_features" (AKR_DENOISE_FEATURES=1)  akr_render_task: 1 = a `pt` task's denoise step takes its guides from the task's own session
+ *                                           (akr_pt_begin_features: the task's samples, its full spp) instead of from aov passes. Implies the denoise
+ *                                           step, and decides where the guides come from whatever "denoise" = n says; composes with "denoise_variance".
+ *                                           Where the session refuses guides the step falls back to the aov passes (n = "denoise" if set, else 16
+ *                                           spp); adaptive tasks keep the aov passes. 0 (default) = off.
  *   "denoise_kernel" (AKR_DENOISE_KERNEL=v) akr_denoise's / akr_denoise_variance's level kernel: 0 = one thread per pixel gathering from global memory, 1 = the LDS-tiled
  *                                           kernel, -1 (default) = the library decides per step. Same bits either way.
  *   "adaptive"     (AKR_ADAPTIVE=n)         akr_render_task: n > 0 = `pt` tasks render through akr_pt_adaptive_render with threshold = n / 1024 (the

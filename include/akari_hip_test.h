@@ -115,6 +115,19 @@ typedef struct akr_pt_launch_plan {
 } akr_pt_launch_plan;
 AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
                                         int32_t spec_waves, akr_pt_launch_plan *out);
+/* The same for a session that may collect the denoiser's guides (feat = 1: what akr_pt_begin_features decides; feat = 0: exactly the plan above).
+ * wavefront, arith: the values of the options of those names to decide for (not the process's). feat = 1 where akr_pt_begin_features refuses --
+ * a kept scene, wavefront = 1, arith = 1 -- fails with AKR_ERR_UNSUPPORTED and that call's message. A feature session gets no per-scene kernel.
+ *   plan            as above (variant[] has no entry for feat: it is `feat` here)
+ *   kernel_compiled 1 = the variant exists as a precompiled kernel (kernels.h pt_variant_compiled)
+ *   park_slots      LDS columns per lane of parked path state in the layout (0: the kernel parks nothing); park_slots_feat: kParkSlotsFeat
+ *   required_bytes  the layout's LDS without the blocks that only take what is left; lds_budget: the workgroup's share (pt_lds_budget) */
+typedef struct akr_pt_features_plan {
+    akr_pt_launch_plan plan;
+    uint32_t feat, kernel_compiled, park_slots, park_slots_feat, required_bytes, lds_budget;
+} akr_pt_features_plan;
+AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
+                                               int32_t spec_waves, int32_t feat, int32_t wavefront, int32_t arith, akr_pt_features_plan *out);
 
 /* akr_denoise on the host (no GPU): the text of csrc/device/ddenoise.h compiled for the host, over host arrays. Each film is an accumulator
  * in the reference layout [rgb 3N | splat 3N | weight N] with its splat scale; albedo_film / normal_film may be NULL. out_rgb = 3 N floats,
