@@ -59,7 +59,7 @@ TEST_EXPORTS = [
     "akr_host_pt_launch_plan", "akr_host_denoise_variance", "akr_probe_denoise_variance_times",
     "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
-    "akr_host_pt_features_plan",
+    "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
 ]
 
 
@@ -202,6 +202,8 @@ def lib() -> C.CDLL:
     proto("akr_host_chacha_block", up, u64, u64, i32, up)
     proto("akr_host_pcg32_states", u64, u64, u64p)
     proto("akr_host_pcg_start", u64p, u64)
+    proto("akr_host_pcg_end_pass", u64p, u64, u32)
+    proto("akr_probe_pcg_end_pass", vp, u32, u64p, u64p, up, u64p, u64p)
     proto("akr_host_alias_table", fp, u32, up, fp, fp)
     proto("akr_probe_math", vp, u32, fp, fp, fp, fp)
     proto("akr_probe_math2", vp, u32, fp, fp)
@@ -786,6 +788,13 @@ def host_pcg_start(state: int, inc: int) -> int:
     return s.value
 
 
+def host_pcg_end_pass(state: int, inc: int, dim: int) -> int:
+    """advance(-dim) by the closed form the kernels use at the end of a pass of the independent sampler (drng.h pcg_end_pass), on the host."""
+    s = C.c_uint64(state)
+    check(lib().akr_host_pcg_end_pass(C.byref(s), inc, dim))
+    return s.value
+
+
 def host_tri_pretest(rays8: np.ndarray, tris9: np.ndarray, plane_shift: float = 0.0):
     """(may_hit, exact_accept, exact_t) per (ray, triangle) pair: dinst.h tri_may_hit and the exact Woop test on the host."""
     rays8 = np.ascontiguousarray(rays8, dtype=np.float32).reshape(-1, 8)
@@ -829,6 +838,19 @@ def probe_div(ctx: Context, a: np.ndarray, b: np.ndarray):
     fast, ieee = np.zeros_like(a), np.zeros_like(a)
     check(lib().akr_probe_div(ctx.h, a.size, _fp(a), _fp(b), _fp(fast), _fp(ieee)))
     return fast, ieee
+
+
+def probe_pcg_end_pass(ctx: Context, state: np.ndarray, inc: np.ndarray, dim: np.ndarray):
+    """advance(-dim) of the generators (state, inc) on the device: (the kernels' closed form, the defining loop), u64 each."""
+    state = np.ascontiguousarray(state, dtype=np.uint64)
+    inc = np.ascontiguousarray(inc, dtype=np.uint64)
+    dim = np.ascontiguousarray(dim, dtype=np.uint32)
+    assert state.shape == inc.shape == dim.shape
+    closed, loop = np.zeros_like(state), np.zeros_like(state)
+    u64p = C.POINTER(C.c_uint64)
+    check(lib().akr_probe_pcg_end_pass(ctx.h, state.size, state.ctypes.data_as(u64p), inc.ctypes.data_as(u64p), _up(dim),
+                                       closed.ctypes.data_as(u64p), loop.ctypes.data_as(u64p)))
+    return closed, loop
 
 
 def probe_bsdf(ctx: Context, m: abi.MaterialData, mode: int, wo, data: np.ndarray, table: Optional[np.ndarray] = None) -> np.ndarray:

@@ -188,7 +188,7 @@ AKR_D void sampler_start(const PtParams& p, Sampler& s) {
 template <bool PMJ>
 AKR_D void sampler_end_pass(const PtParams& p, Sampler& s) {
     if (!PMJ) {
-        pcg_advance(s.pcg, -(int64_t)s.dim);
+        pcg_end_pass(s.pcg, s.dim);  // advance(-dim) without its 64 trips
         s.dim = 0;
     }  // pmj02bn: the state is stored as it is; dim is reset by the next start()
 }

@@ -52,14 +52,73 @@ AKR_HD void pcg_advance(Pcg32& p, int64_t idelta) {
     p.state = acc_mult * p.state + acc_plus;
 }
 
-// advance(16384) in closed form. 16384 = 1 << 14 has one set bit, so the loop above reduces to
-//   state' = A * state + (A + C * inc),  A = MULT^(2^14),  C = prod_{k<14} (MULT^(2^k) + 1)   (mod 2^64)
-// A and C are constants of the generator; they are computed once on the host with the loop itself
-// (host/scene_build.cpp: pcg_start_constants) and checked against pcg_advance in the tests.
+// The two advances the independent sampler makes have closed forms. With M_k = MULT^(2^k), C_0 = 1, C_{k+1} = (M_k + 1) * C_k
+// (mod 2^64) -- cur_mult and cur_plus / inc of the loop above at trip k -- and S the set bits of delta, the loop returns
+//   state' = (prod_{k in S} M_k) * state + sum_{k in S} M_k + inc * sum_{k in S} C_k                      (mod 2^64)
+// M_k and C_k are constants of the generator; both forms take them from the loop's own recurrences and are checked against
+// pcg_advance in the tests.
+//
+// pcg_start: advance(16384). 16384 = 1 << 14 has one set bit, so
+//   state' = A * state + (A + C * inc),  A = M_14,  C = C_14 = prod_{k<14} (M_k + 1)
+// A and C are computed once on the host with the loop itself (host/scene_build.cpp: pcg_start_constants).
 struct PcgStartConsts {
     uint64_t A, C;
 };
 AKR_HD void pcg_start(Pcg32& p, PcgStartConsts k) { p.state = k.A * p.state + (k.A + k.C * p.inc); }
+
+// pcg_end_pass: advance(-dim), the Drop of the sampler. delta = 2^64 - dim has bit 63 set for every dim >= 1, so the loop always
+// runs its 64 trips -- for the one or two lanes of a wave that end a pass in an iteration. The product and the two sums of the
+// closed form decompose over any chunking of delta's bits: bits 32 .. 63 of 2^64 - dim are set for every 32-bit dim >= 1 (one
+// constant triple), the low 32 bits are ~(dim - 1), looked up four bits at a time in 8 tables of 16 triples (3 KB; compile-time
+// constants of this header, so the per-scene kernels get them with the text).
+struct PcgJump {
+    uint64_t mult, sum_m, sum_c;  // prod M_k, sum M_k, sum C_k over a set of bits
+};
+constexpr int kPcgJumpChunkBits = 4, kPcgJumpChunks = 32 / kPcgJumpChunkBits, kPcgJumpChunkValues = 1 << kPcgJumpChunkBits;
+struct PcgEndPassTables {
+    PcgJump low[kPcgJumpChunks][kPcgJumpChunkValues];  // low[j][v]: the bits of v << (kPcgJumpChunkBits * j)
+    PcgJump high;                                      // bits 32 .. 63, all set
+};
+constexpr PcgEndPassTables pcg_end_pass_tables() {
+    PcgEndPassTables t{};
+    for (int j = 0; j < kPcgJumpChunks; j++)
+        for (int v = 0; v < kPcgJumpChunkValues; v++) t.low[j][v] = PcgJump{1, 0, 0};
+    t.high = PcgJump{1, 0, 0};
+    uint64_t cur_mult = kPcgMult, cur_c = 1;  // the loop's cur_mult, and its cur_plus for inc = 1
+    for (int k = 0; k < 64; k++) {
+        if (k < 32) {
+            for (int v = 0; v < kPcgJumpChunkValues; v++) {
+                if (!((v >> (k % kPcgJumpChunkBits)) & 1)) continue;
+                PcgJump& e = t.low[k / kPcgJumpChunkBits][v];
+                e.mult *= cur_mult;
+                e.sum_m += cur_mult;
+                e.sum_c += cur_c;
+            }
+        } else {
+            t.high.mult *= cur_mult;
+            t.high.sum_m += cur_mult;
+            t.high.sum_c += cur_c;
+        }
+        cur_c = (cur_mult + 1) * cur_c;
+        cur_mult *= cur_mult;
+    }
+    return t;
+}
+inline constexpr PcgEndPassTables kPcgEndPass = pcg_end_pass_tables();
+
+AKR_HD void pcg_end_pass(Pcg32& p, uint32_t dim) {
+    if (dim == 0) return;  // advance(0): the loop makes no trip
+    const uint32_t low = 0u - dim;
+    uint64_t mult = kPcgEndPass.high.mult, sum_m = kPcgEndPass.high.sum_m, sum_c = kPcgEndPass.high.sum_c;
+#pragma unroll
+    for (int j = 0; j < kPcgJumpChunks; j++) {
+        const PcgJump& e = kPcgEndPass.low[j][(low >> (kPcgJumpChunkBits * j)) & (uint32_t)(kPcgJumpChunkValues - 1)];
+        mult *= e.mult;
+        sum_m += e.sum_m;
+        sum_c += e.sum_c;
+    }
+    p.state = mult * p.state + (sum_m + sum_c * p.inc);
+}
 
 AKR_HD float pcg_next_1d(Pcg32& p) {  // sampler/mod.rs:194-198; can return exactly 1.0
     uint32_t n = pcg_gen_u32(p);

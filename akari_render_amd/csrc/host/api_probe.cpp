@@ -38,6 +38,14 @@ AKR_TEST_API int32_t akr_host_pcg_start(uint64_t* state, uint64_t inc) {
     *state = p.state;
     return AKR_OK;
 }
+// device/drng.h pcg_end_pass on the host: the closed form the kernels use for the Drop of the independent sampler = advance(-dim)
+AKR_TEST_API int32_t akr_host_pcg_end_pass(uint64_t* state, uint64_t inc, uint32_t dim) {
+    if (!state) return fail(AKR_ERR_INVALID_ARGUMENT, "state is NULL");
+    Pcg32 p{*state, inc};
+    pcg_end_pass(p, dim);
+    *state = p.state;
+    return AKR_OK;
+}
 // device/drng.h on the host: reverse_bits32(sobol_dim1(i)) by the defining loop and by the five-step butterfly the kernels use
 AKR_TEST_API int32_t akr_host_sobol_dim1(uint32_t n, const uint32_t* index, uint32_t* by_loop, uint32_t* by_butterfly) {
     if (!index || !by_loop || !by_butterfly) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_sobol_dim1: NULL argument");
@@ -125,6 +133,23 @@ AKR_TEST_API int32_t akr_probe_div(akr_context* ctx, uint32_t n, const float* a,
         if (n) {
             HIP_CHECK(hipMemcpy(out_fast, df.p, (size_t)n * 4, hipMemcpyDeviceToHost));
             HIP_CHECK(hipMemcpy(out_ieee, di.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+AKR_TEST_API int32_t akr_probe_pcg_end_pass(akr_context* ctx, uint32_t n, const uint64_t* state, const uint64_t* inc, const uint32_t* dim, uint64_t* out_closed, uint64_t* out_loop) {
+    if (!ctx || !state || !inc || !dim || !out_closed || !out_loop) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_pcg_end_pass: NULL argument");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf ds, di, dd, dc, dl;
+        ds.upload(std::vector<uint64_t>(state, state + n));
+        di.upload(std::vector<uint64_t>(inc, inc + n));
+        dd.upload(std::vector<uint32_t>(dim, dim + n));
+        dc.alloc((size_t)n * 8); dl.alloc((size_t)n * 8);
+        if (n) HIP_CHECK(launch_probe_pcg_end_pass(n, ds.as<uint64_t>(), di.as<uint64_t>(), dd.as<uint32_t>(), dc.as<uint64_t>(), dl.as<uint64_t>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) {
+            HIP_CHECK(hipMemcpy(out_closed, dc.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(out_loop, dl.p, (size_t)n * 8, hipMemcpyDeviceToHost));
         }
     });
 }

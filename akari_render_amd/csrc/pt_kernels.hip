@@ -88,6 +88,17 @@ __global__ void k_probe_div(uint32_t n, const float* __restrict__ a, const float
     out_fast[i] = div_f_unscaled(a[i], b[i]);
     out_ieee[i] = div_f(a[i], b[i]);
 }
+// the end of a pass of the independent sampler, advance(-dim): by the closed form the kernels use (drng.h pcg_end_pass) and by the loop that defines it
+__global__ void k_probe_pcg_end_pass(uint32_t n, const uint64_t* __restrict__ state, const uint64_t* __restrict__ inc, const uint32_t* __restrict__ dim,
+                                     uint64_t* __restrict__ out_closed, uint64_t* __restrict__ out_loop) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Pcg32 a{state[i], inc[i]}, b = a;
+    pcg_end_pass(a, dim[i]);
+    pcg_advance(b, -(int64_t)dim[i]);
+    out_closed[i] = a.state;
+    out_loop[i] = b.state;
+}
 __global__ void k_probe_bsdf(const DMaterial* __restrict__ m, const float* __restrict__ table, int mode, vec3 wo, uint32_t n,
                              const float* __restrict__ in, float* __restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -250,6 +261,10 @@ hipError_t launch_probe_math2(uint32_t n, const float* xy, float* out, hipStream
 }
 hipError_t launch_probe_div(uint32_t n, const float* a, const float* b, float* out_fast, float* out_ieee, hipStream_t stream) {
     hipLaunchKernelGGL(k_probe_div, dim3((n + 255) / 256), dim3(256), 0, stream, n, a, b, out_fast, out_ieee);
+    return hipGetLastError();
+}
+hipError_t launch_probe_pcg_end_pass(uint32_t n, const uint64_t* state, const uint64_t* inc, const uint32_t* dim, uint64_t* out_closed, uint64_t* out_loop, hipStream_t stream) {
+    hipLaunchKernelGGL(k_probe_pcg_end_pass, dim3((n + 255) / 256), dim3(256), 0, stream, n, state, inc, dim, out_closed, out_loop);
     return hipGetLastError();
 }
 hipError_t launch_probe_intersect_pair(const PtParams& p, uint32_t n, const float* rays, const uint32_t* excl, uint32_t* out, float* out_tuv, hipStream_t stream) {

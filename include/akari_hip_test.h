@@ -23,6 +23,7 @@ extern "C" {
  *   akr_host_chacha_block    one ChaCha block with `rounds` rounds (RFC 7539 / zero-key vectors pin the core)
  *   akr_host_pcg32_states    init_pcg32_buffer_with_seed on the host: 2 x u64 (state, inc) per entry
  *   akr_host_pcg_start       the closed form the kernels use for sampler.start() = advance(16384)
+ *   akr_host_pcg_end_pass    the closed form the kernels use for the Drop of the independent sampler = advance(-dim)
  *   akr_host_alias_table     AliasTable::new (util/distribution.rs:35-78) */
 AKR_TEST_API int32_t akr_host_stdrng_u64(uint64_t seed, uint32_t n, uint64_t *out);
 
@@ -31,6 +32,8 @@ AKR_TEST_API int32_t akr_host_chacha_block(const uint32_t *key8, uint64_t counte
 AKR_TEST_API int32_t akr_host_pcg32_states(uint64_t seed, uint64_t n, uint64_t *out2n);
 
 AKR_TEST_API int32_t akr_host_pcg_start(uint64_t *state, uint64_t inc);
+
+AKR_TEST_API int32_t akr_host_pcg_end_pass(uint64_t *state, uint64_t inc, uint32_t dim);
 
 AKR_TEST_API int32_t akr_host_sobol_dim1(uint32_t n, const uint32_t *index, uint32_t *by_loop, uint32_t *by_butterfly);
 
@@ -58,6 +61,11 @@ AKR_TEST_API int32_t akr_probe_math2(akr_context *ctx, uint32_t n, const float *
 
 /* a / b for n pairs: by the pair walk's division without range scaling (csrc/device/dmath.h div_f_unscaled) and by the contract's a / b. */
 AKR_TEST_API int32_t akr_probe_div(akr_context *ctx, uint32_t n, const float *a, const float *b, float *out_fast, float *out_ieee);
+
+/* advance(-dim) of n generators (state, inc): by the closed form the kernels use at the end of a pass of the independent sampler
+ * (csrc/device/drng.h pcg_end_pass) and by the loop that defines it (pcg_advance), both on the device. */
+AKR_TEST_API int32_t akr_probe_pcg_end_pass(akr_context *ctx, uint32_t n, const uint64_t *state, const uint64_t *inc, const uint32_t *dim, uint64_t *out_closed,
+                                       uint64_t *out_loop);
 
 /* BSDF of material `m` on a flat surface (normal +z, world == local; cf. akari_test.rs:16-439):
  * mode 0: in = wi (3 floats / item)  -> out = f.rgb, pdf (4 floats / item)
