@@ -107,6 +107,15 @@ class EnvironmentDesc(C.Structure):
                 ("color", C.c_float * 3), ("strength", C.c_float), ("rotation", C.c_float * 9), ("_pad2", C.c_uint32)]
 
 
+LIGHT_POINT, LIGHT_SPOT, LIGHT_SUN = 0, 1, 2  # akr_light_type
+
+
+class PunctualLightDesc(C.Structure):
+    """akr_punctual_light_desc: a point, spot or sun light."""
+    _fields_ = [("type", C.c_uint32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("color", C.c_float * 3), ("strength", C.c_float),
+                ("cone_angle", C.c_float), ("blend", C.c_float)]
+
+
 class LensDesc(C.Structure):
     """akr_lens_desc: the camera's thin lens (radius 0 = a pinhole)."""
     _fields_ = [("radius", C.c_float), ("focal_distance", C.c_float)]
@@ -420,11 +429,13 @@ class PtLaunchPlan(C.Structure):
         ("lds_bytes", C.c_uint32), ("blocks", C.c_uint32),
         ("specialised", C.c_uint32),
         ("wrapper", C.c_char * 600),
+        ("punct", C.c_uint32),
     ]
 
     def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("variant", "stage_bytes", "wrapper")}
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("variant", "stage_bytes", "wrapper", "punct")}
         d["variant"] = {n: int(self.variant[i]) for i, n in enumerate(self.VARIANT)}
+        d["variant"]["punct"] = int(self.punct)  # (the PUNCT kernels: the struct's last field, not one of the ten)
         d["stage_bytes"] = [int(b) for b in self.stage_bytes]
         d["wrapper"] = self.wrapper.decode()
         return d
@@ -587,6 +598,33 @@ class EnvironmentData:
 
 
 @dataclass
+class PunctualLightData:
+    """A point, spot or sun light of a scene (akr_punctual_light_desc): `type` LIGHT_POINT / LIGHT_SPOT / LIGHT_SUN, `position` (point, spot), `direction` the
+    light points / travels along (spot, sun), `color` x `strength` = radiant intensity (point, spot) or irradiance (sun), `cone_angle` = the spot's outer
+    HALF-angle in radians, `blend` in [0, 1] the part of it over which the light falls off."""
+    type: int
+    position: tuple = (0.0, 0.0, 0.0)
+    direction: tuple = (0.0, 0.0, 0.0)
+    color: tuple = (1.0, 1.0, 1.0)
+    strength: float = 1.0
+    cone_angle: float = 0.0
+    blend: float = 0.0
+
+    def to_desc(self) -> PunctualLightDesc:
+        d = PunctualLightDesc()
+        d.type = int(self.type)
+        for k in range(3):
+            d.position[k], d.direction[k], d.color[k] = float(self.position[k]), float(self.direction[k]), float(self.color[k])
+        d.strength, d.cone_angle, d.blend = float(self.strength), float(self.cone_angle), float(self.blend)
+        return d
+
+    @staticmethod
+    def from_desc(d: PunctualLightDesc) -> "PunctualLightData":
+        return PunctualLightData(int(d.type), tuple(float(v) for v in d.position), tuple(float(v) for v in d.direction), tuple(float(v) for v in d.color),
+                                 float(d.strength), float(d.cone_angle), float(d.blend))
+
+
+@dataclass
 class LensData:
     """The thin lens of a scene's camera: a disk of `radius` in the camera's x / y plane, focused `focal_distance` along the optical axis
     (lens_radius and focal_length of the reference's PerspectiveCamera)."""
@@ -614,6 +652,7 @@ class SceneData:
     images: List["ImageData"] = field(default_factory=list)
     environment: Optional[EnvironmentData] = None  # set by capi.Scene through akr_scene_set_environment (not part of akr_scene_desc)
     lens: Optional[LensData] = None  # set by capi.Scene through akr_scene_set_lens (not part of akr_scene_desc / akr_camera_desc)
+    lights: List["PunctualLightData"] = field(default_factory=list)  # added by capi.Scene through akr_scene_add_punctual_light (not part of akr_scene_desc)
 
     def n_triangles(self) -> int:
         return sum(self.meshes[i.mesh].indices.shape[0] for i in self.instances)

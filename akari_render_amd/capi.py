@@ -22,8 +22,10 @@ ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED
  ARRAY_LIGHT_PDF, ARRAY_AREA_ENTRIES, ARRAY_AREA_PDF, ARRAY_INST_TRI_OFFSET, ARRAY_R2C, ARRAY_C2W,
  ARRAY_TEX_NODES, ARRAY_TEX_IMAGES, ARRAY_TEX_TEXELS, ARRAY_MAT_INPUTS,
  ARRAY_INST_LEAVES, ARRAY_MESH_TRIS, ARRAY_MESH_POS, ARRAY_MESH_META, ARRAY_MESH_NORMALS,
- ARRAY_ENV_MARGINAL_ENTRIES, ARRAY_ENV_MARGINAL_PDF, ARRAY_ENV_CONDITIONAL_ENTRIES, ARRAY_ENV_CONDITIONAL_PDF, ARRAY_ENV_TEXELS) = range(27)
+ ARRAY_ENV_MARGINAL_ENTRIES, ARRAY_ENV_MARGINAL_PDF, ARRAY_ENV_CONDITIONAL_ENTRIES, ARRAY_ENV_CONDITIONAL_PDF, ARRAY_ENV_TEXELS,
+ ARRAY_PUNCTUAL_LIGHTS) = range(28)
 ENV_LIGHT_INSTANCE = 0xFFFFFFFF  # akr_scene_get_light's instance of the environment light
+PUNCTUAL_LIGHT_INSTANCE = 0xFFFFFFFE  # ... of a point, spot or sun light
 
 # every symbol include/akari_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
@@ -46,6 +48,7 @@ EXPORTS = [
     "akr_denoise_config_default", "akr_denoise", "akr_denoise_variance",
     "akr_pt_set_active_tiles", "akr_film_tile_error", "akr_adaptive_config_default", "akr_pt_adaptive_render",
     "akr_display_config_default", "akr_film_luminance_histogram", "akr_display_exposure", "akr_display_transform",
+    "akr_scene_add_punctual_light", "akr_scene_clear_punctual_lights", "akr_scene_punctual_light_count", "akr_scene_get_punctual_light",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -60,6 +63,7 @@ TEST_EXPORTS = [
     "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
     "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
+    "akr_host_light_sample", "akr_probe_light_sample",
 ]
 
 
@@ -100,7 +104,7 @@ def lib() -> C.CDLL:
                                abi.EnvironmentDesc, abi.LensDesc, abi.DenoiseConfig), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
-    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats), (22, abi.DisplayConfig)):  # (ids 18 and 21 are not assigned)
+    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats), (22, abi.DisplayConfig), (24, abi.PunctualLightDesc)):  # (ids 18, 21 and 23 are not assigned)
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -125,6 +129,12 @@ def lib() -> C.CDLL:
     proto("akr_scene_get_environment", vp, C.POINTER(abi.EnvironmentDesc))
     proto("akr_scene_set_lens", vp, C.POINTER(abi.LensDesc))
     proto("akr_scene_get_lens", vp, C.POINTER(abi.LensDesc))
+    proto("akr_scene_add_punctual_light", vp, C.POINTER(abi.PunctualLightDesc))
+    proto("akr_scene_clear_punctual_lights", vp)
+    proto("akr_scene_punctual_light_count", vp, up)
+    proto("akr_scene_get_punctual_light", vp, u32, C.POINTER(abi.PunctualLightDesc))
+    proto("akr_host_light_sample", vp, u32, fp, fp, up)
+    proto("akr_probe_light_sample", vp, vp, u32, fp, fp, up)
     proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
     proto("akr_host_pt_launch_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, C.POINTER(abi.PtLaunchPlan))
@@ -307,6 +317,8 @@ class Scene:
             lens = getattr(source, "lens", None)
             if lens is not None:
                 self.set_lens(lens.radius, lens.focal_distance)
+            for light in getattr(source, "lights", None) or ():
+                self.add_punctual_light(light)
 
     def close(self):
         if self.h:
@@ -393,6 +405,44 @@ class Scene:
             im = np.ctypeslib.as_array(d.texels, shape=(n,)).astype(np.float32, copy=True).reshape(d.height, d.width, 4)
             return abi.EnvironmentData(image=im, strength=float(d.strength), rotation=rot, filter=int(d.filter))
         return abi.EnvironmentData(color=tuple(float(c) for c in d.color), strength=float(d.strength), rotation=rot)
+
+    def add_punctual_light(self, light: Optional[abi.PunctualLightData] = None, **fields):
+        """akr_scene_add_punctual_light: appends a point, spot or sun light (an abi.PunctualLightData, or its fields as keywords). A light of strength 0 or
+        an all-zero colour is accepted and not added."""
+        if light is None:
+            light = abi.PunctualLightData(**fields)
+        d = light.to_desc()
+        check(lib().akr_scene_add_punctual_light(self.h, C.byref(d)))
+
+    def clear_punctual_lights(self):
+        """akr_scene_clear_punctual_lights."""
+        check(lib().akr_scene_clear_punctual_lights(self.h))
+
+    def punctual_lights(self) -> list:
+        """akr_scene_punctual_light_count / akr_scene_get_punctual_light: the lights the scene holds, as abi.PunctualLightData."""
+        n = C.c_uint32()
+        check(lib().akr_scene_punctual_light_count(self.h, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            d = abi.PunctualLightDesc()
+            check(lib().akr_scene_get_punctual_light(self.h, i, C.byref(d)))
+            out.append(abi.PunctualLightData.from_desc(d))
+        return out
+
+    def _light_sample(self, fn, head, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 7)
+        n = rows.shape[0]
+        out, light = np.zeros((n, 13), np.float32), np.zeros(n, np.uint32)
+        check(fn(*head, n, _fp(rows), _fp(out), _up(light)))
+        return out, light
+
+    def host_light_sample(self, rows):
+        """akr_host_light_sample (test hook, no GPU): rows (n, 7) = p, n, u_select -> ((n, 13) = li, wi, pdf, ro, tmax, valid, delta; (n,) the light chosen)."""
+        return self._light_sample(lib().akr_host_light_sample, (self.h,), rows)
+
+    def probe_light_sample(self, rows):
+        """akr_probe_light_sample (test hook): the same on the device."""
+        return self._light_sample(lib().akr_probe_light_sample, (self.ctx.h, self.h), rows)
 
     def set_lens(self, radius: Optional[float] = None, focal_distance: float = 0.0):
         """akr_scene_set_lens: a thin lens of `radius`, focused `focal_distance` along the optical axis. radius None or 0: removes the lens."""
@@ -523,7 +573,7 @@ class Scene:
         c = abi.CameraDesc()
         check(lib().akr_scene_get_camera(self.h, C.byref(c)))
         cam = abi.CameraData(np.array(list(c.c2w), dtype=np.float32), float(c.fov), c.width, c.height)
-        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment(), lens=self.lens())
+        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment(), lens=self.lens(), lights=self.punctual_lights())
 
 
 def set_option(name: str, value: int) -> None:

@@ -67,7 +67,7 @@ struct AliasPacked {
     uint32_t j;
     float t, pdf_i, pdf_j;
 };
-AKR_D uint32_t alias_sample_and_remap(const AliasPacked* __restrict__ entries, uint32_t n, float u, float& pdf, float& remapped) {
+AKR_HD uint32_t alias_sample_and_remap(const AliasPacked* __restrict__ entries, uint32_t n, float u, float& pdf, float& remapped) {
     float u1;
     uint32_t idx = uniform_discrete_choice_and_remap(n, u, u1);
     AliasPacked e = entries[idx];

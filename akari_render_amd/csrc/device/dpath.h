@@ -4,6 +4,7 @@
 // film.rs, sampler/mod.rs, light/{mod,area}.rs of the reference; file:line cited per function.
 #pragma once
 #include "denv.h"
+#include "dpunct.h"
 #include "dinst_trav.h"
 #include "drng.h"
 #include "../kernels.h"
@@ -297,11 +298,14 @@ struct LightSample {
     float tmax;
     uint32_t ex1;
     bool valid;
+    bool delta;  // a punctual light's sample (dpunct.h): no BSDF-sampled ray finds the light, so path_step weighs it with 1 instead of the MIS weight
 };
 // LightAggregate::sample_direct (light/mod.rs:115-132) + AreaLight::sample_direct (light/area.rs:51-107).
 // ENV: the scene has an environment light, the last entry of the light table (denv.h); a choice of it draws its direction from the
 // environment's tables with the u_sample a triangle would use -- no dimension more -- and its shadow ray is an unbounded one.
-template <bool TEX, bool INST = false, bool ENV = false>
+// PUNCT: the scene has punctual lights, entries of the light table whose LightRec says kPunctInst (dpunct.h); a choice of
+// one consumes u_select as every choice does and ignores u_sample.
+template <bool TEX, bool INST = false, bool ENV = false, bool PUNCT = false>
 AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_select, vec2 u_sample, uint32_t color = 0) {
     LightSample s;
     s.li = mk3(0, 0, 0);
@@ -311,6 +315,7 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
     s.tmax = 0.0f;
     s.ex1 = kInvalid;
     s.valid = false;
+    s.delta = false;
     if (sc.n_lights == 0) return s;
     float light_choice_pdf, u_sel2, pdf_prim, u_unused;
     uint32_t light = alias_sample_and_remap(sc.light_alias, sc.n_lights, u_select, light_choice_pdf, u_sel2);
@@ -329,6 +334,18 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
         return s;
     }
     const LightRec L = sc.lights[light];
+    if (PUNCT && L.inst == kPunctInst) {
+        const PunctSample ps = punct_sample(sc.punct[L.first_gid], pn_p, pn_n);
+        s.li = ps.li;
+        s.wi = ps.wi;
+        s.ro = ps.ro;
+        s.tmax = ps.tmax;
+        s.ex1 = kInvalid;
+        s.valid = ps.valid;
+        s.pdf = light_choice_pdf;
+        s.delta = true;
+        return s;
+    }
     uint32_t prim = alias_sample_and_remap(sc.area_alias + L.tri_offset, L.n_tris, u_sel2, pdf_prim, u_unused);
     uint32_t gid = L.first_gid + prim;
     vec2 bary = uniform_sample_triangle(u_sample);
@@ -527,7 +544,8 @@ AKR_D void shifted_pixel(const PtParams& p, uint32_t px, uint32_t py, uint32_t& 
 // FEAT: the session collects the denoiser's guides. At a sample's depth-0 vertex the value k_aov (aov_kernel.h) computes
 // for the sample's camera ray -- albedo + emission, shading normal; a miss adds nothing -- goes to the lane's guide accumulators: registers, or
 // with PARK their LDS columns (PK_FEAT_*), where they stay from the first iteration to the lane's last store. No random number is drawn for it.
-template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
+// PUNCT: the scene has punctual lights (sample_direct above); nothing changes on a hit or a miss.
+template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false, bool PUNCT = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
 AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found, bool occluded, uint32_t pix_in, uint32_t sx_in, uint32_t sy_in,
                      uint32_t* park = nullptr) {
     const bool force_diffuse = FD < 0 ? (p.force_diffuse != 0) : (FD != 0);
@@ -656,7 +674,7 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
                 LightSample dl;
                 dl.valid = false;
                 if (p.use_nee && (!p.indirect_only || r.depth > 1))
-                    dl = sample_direct<TEX, INST, ENV>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z), p.color);
+                    dl = sample_direct<TEX, INST, ENV, PUNCT>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z), p.color);
                 vec3 u_bsdf = next_3d<PMJ>(p, r.smp);
                 // sample_surface_and_shade_direct, pt.rs:297-323
                 ShadePoint sp;
@@ -664,7 +682,7 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
                 if (FD != 1) shade_point_cache_wo(sp, mat, sc.ggx_table, wo);
                 if (dl.valid) {
                     BsdfEval e = shade_evaluate(sp, mat, sc.ggx_table, wo, dl.wi);
-                    float w = mis_weight(dl.pdf, e.pdf);
+                    float w = (PUNCT && dl.delta) ? 1.0f : mis_weight(dl.pdf, e.pdf);
                     vec3 direct = div_s((dl.li * e.f) * w, dl.pdf);
                     // the shadow ray is traced in the next intersection phase; what it would add is fixed now
                     // (radiance += beta * direct with the beta of THIS vertex, pt.rs:134-138,508)

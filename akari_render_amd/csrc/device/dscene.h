@@ -71,6 +71,20 @@ struct DEnv {
     uint32_t w, h, filter, light;               // light: the environment's entry in the light table (the last one)
 };
 
+// A punctual light (host/scene_punct.cpp folds it, device/dpunct.h samples it): a point or spot light at q, or a sun whose light
+// travels along a. One 64-byte record in HBM, read by the PUNCT kernels only. Its entry in the light table is a LightRec with inst = kPunctInst and
+// first_gid = the record's index.
+enum : uint32_t { PUNCT_POINT = 0, PUNCT_SPOT = 1, PUNCT_SUN = 2 };
+constexpr uint32_t kPunctInst = 0xfffffffeu;
+struct DPunct {
+    vec3 q;       uint32_t kind;    // position (POINT, SPOT)
+    vec3 a;       float cos_o;      // unit axis / direction of travel (SPOT, SUN); cosine of the outer half-angle
+    vec3 c;       float cos_i;      // colour x strength in the session's colour pipeline; cosine of the inner half-angle
+    float inv_span;                 // 1 / (cos_i - cos_o), 0 = the step falloff
+    uint32_t _pad[3];
+};
+static_assert(sizeof(DPunct) == 64, "DPunct layout");
+
 struct DScene {
     const float4* __restrict__ woop;        // 3 float4 per triangle (exhaustive path) or 4 (BVH path: + global id)
     const uint32_t* __restrict__ tri_gid;   // traversal order -> global id (host-side tests; the BVH path reads the id from the record)
@@ -99,6 +113,9 @@ struct DScene {
     uint64_t plane_share_mask;                      // exhaustive path: bit k = record k carries the plane row of record k-1
     TexScene tex;                                   // textures + shader-graph node lists (all nullptr without textures)
     DInst in2;                                      // meshes + instances kept as they are (in2.on; else all zero)
+    // The punctual lights (DPunct above), or nullptr: a scene with some runs the PUNCT kernels. Last: everything before keeps its offset.
+    const DPunct* __restrict__ punct;
+    uint32_t n_punct, _pad_punct;
 };
 
 struct SurfacePoint {  // interaction.rs:15-48, minus what this path never reads

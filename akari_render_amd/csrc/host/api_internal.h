@@ -169,11 +169,13 @@ struct akr_scene {
         light_n_tris, area_entries, area_pdf, inst_tri_offset, bvh_nodes, tex_nodes, tex_images, tex_texels, tex_mat_inputs;
     DevBuf in2_tlas_leaves, in2_mesh_tris, in2_mesh_pos, in2_mesh_meta, in2_mesh_normals, in2_inst_mats, in2_share_bits;  // meshes + instances (scene_inst.cpp)
     DevBuf env_texels, env_marginal, env_conditional, env_rec;  // the environment light (scene_env.cpp; DScene.env points at env_rec)
-    std::atomic<int> sessions{0};  // pt / aov / gpt / mcmc_opt sessions that hold the scene (akr_scene_set_environment is refused meanwhile)
+    DevBuf punct;  // the punctual lights' records under the default colour pipeline (scene_punct.cpp; DScene.punct)
+    std::atomic<int> sessions{0};  // pt / aov / gpt / mcmc_opt sessions that hold the scene (akr_scene_set_environment and the punctual lights' setters are refused meanwhile)
     std::vector<float> ggx_host;
     // materials / node lists / raw inputs re-compiled for a non-default colour pipeline (akr_pt_config.color), by pipeline
     struct ColorSet {
         DevBuf materials, tex_nodes, mat_inputs;
+        DevBuf punct;  // the punctual lights' records: their colour goes through the pipeline on the host, as an Emission material's
     };
     std::map<uint32_t, std::unique_ptr<ColorSet>> color_sets;
     std::mutex color_sets_mutex;  // sessions of several host threads may begin on one scene; entries are never removed before the scene dies
@@ -338,8 +340,11 @@ PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_optio
 // Why a pt session of (scene, options) cannot collect guides -- "" when it can. The ONE statement of akr_pt_begin_features' refusals that need no
 // device: kept scenes, a forced wavefront schedule, the relaxed arithmetic tier (akr_host_pt_features_plan asks it for host-only scenes).
 std::string pt_features_refusal(const akr_scene* s, const TuningOptions& t);
-// the part of the variant that is a fact of the scene and the config: bvh, fd, tex, pmj, inst, env, lens
+// the part of the variant that is a fact of the scene and the config: bvh, fd, tex, pmj, inst, env, lens, punct
 PtVariant pt_scene_facts(const akr_scene* s, const akr_pt_config& c);
+// Why a pt session of (scene, options) cannot render the scene's punctual lights -- "" when it can, or has none. The ONE statement of akr_pt_begin's
+// refusals for such a scene: a forced wavefront schedule, the relaxed arithmetic tier (kept scenes are refused when the scene is compiled).
+std::string pt_punctual_refusal(const akr_scene* s, const TuningOptions& t);
 // DScene.bvh_stack_depth / n_nodes of a compiled scene (scene_finish fills them in; a host-only scene has no DScene)
 inline uint32_t scene_stack_depth(const CompiledScene& cs) {
     // one pending group per tree level at most (disect.h); a kept scene: two levels + the three words that remember the TLAS position
@@ -363,6 +368,8 @@ uint32_t session_samples(const akr_pt_config& c);
 std::vector<uint32_t> owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count);
 // api_scene.cpp
 void scene_finish(akr_scene* s);
+// the light tables packed as the kernels read them (dgeom.h AliasPacked, dscene.h LightRec): what upload_lights uploads and akr_host_light_sample samples
+void packed_light_tables(const CompiledScene& cs, std::vector<AliasPacked>& light_alias, std::vector<AliasPacked>& area_alias, std::vector<LightRec>& lights);
 void scene_spec_header(akr_scene* scene, std::string& out);
 // api_aux.cpp: shard_count > 1 = this rank's share (akr_mcmc_render_shard); on_pass: akr_render_task's progress hook
 int32_t mcmc_render_impl(akr_context* ctx, akr_scene* scene, const akr_mcmc_config* cfg, akr_film* film, akr_mcmc_result* result, uint32_t* chain_states,

@@ -238,6 +238,33 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context* ctx, akr_scene* scene, ui
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context* ctx, akr_scene* scene, uint32_t n, const float* dirs3, float* out4) {
     return probe_env(ctx, scene, 1, n, dirs3, out4, "akr_probe_env_pdf");
 }
+// next-event estimation with punctual lights (device/dpunct.h): the selection and the lights' branch of sample_direct, row by row
+AKR_TEST_API int32_t akr_host_light_sample(const akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
+    if (!scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_light_sample: NULL argument");
+    return guarded([&] {
+        std::vector<AliasPacked> la, aa;
+        std::vector<LightRec> lr;
+        packed_light_tables(scene->cs, la, aa, lr);
+        for (uint32_t i = 0; i < n; i++) punct_probe_row(la.data(), lr.data(), scene->cs.punct.data(), scene->cs.n_lights, rows7 + 7ull * i, out13 + 13ull * i, light + i);
+    });
+}
+AKR_TEST_API int32_t akr_probe_light_sample(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
+    if (!ctx || !scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: NULL argument");
+    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: the scene was not created on this context");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf din, dout, dl;
+        din.upload(std::vector<float>(rows7, rows7 + 7ull * n));
+        dout.alloc(13ull * n * 4);
+        dl.alloc(4ull * n);
+        if (n) HIP_CHECK(launch_probe_light_sample(probe_params(scene), n, din.as<float>(), dout.as<float>(), dl.as<uint32_t>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) {
+            HIP_CHECK(hipMemcpy(out13, dout.p, 13ull * n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(light, dl.p, 4ull * n, hipMemcpyDeviceToHost));
+        }
+    });
+}
 // the camera's ray generation (device/dpath.h): the parameter block's camera part, filled by the sessions' own function
 static PtParams probe_camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {
     PtParams p;
@@ -265,7 +292,7 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_t
 static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves, bool feat,
                                                           akr_pt_launch_plan* out) {
         const CompiledScene& cs = scene->cs;
-        const bool spec = !feat && spec_waves != 0 && cs.has_textures && !cfg->force_diffuse;  // (where akr_pt_begin asks for a per-scene kernel)
+        const bool spec = !feat && spec_waves != 0 && cs.has_textures && !cfg->force_diffuse && cs.punct.empty();  // (where akr_pt_begin asks for a per-scene kernel)
         const PtPlan pl = pt_plan(scene, *cfg, defer_metal, simple_kernels, defer_on, spec, spec ? spec_waves : 3, feat);
         const PtVariant& v = pl.v;
         const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, pl.stage_total, cfg->sampler_type == AKR_SAMPLER_PMJ02BN};
@@ -282,6 +309,7 @@ static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, cons
         out->lds_bytes = (uint32_t)L.total_bytes;
         out->blocks = (grid.n_items + 255u) / 256u;
         out->specialised = spec ? 1u : 0u;
+        out->punct = v.punct ? 1u : 0u;
         if (spec) std::snprintf(out->wrapper, sizeof out->wrapper, "%s", spec_wrapper_source(v, spec_waves).c_str());
         return {v, L};
 }

@@ -15,13 +15,22 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
 PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
     const CompiledScene& cs = s->cs;  // (stage, defer, simple: pt_plan)
     return PtVariant{cs.has_tree(), c.force_diffuse != 0, cs.has_textures, c.sampler_type != AKR_SAMPLER_INDEPENDENT, false, false, false,
-                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f};
+                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f, false, !cs.punct.empty()};
+}
+std::string akr_api::pt_punctual_refusal(const akr_scene* s, const TuningOptions& t) {
+    if (s->cs.punct.empty()) return "";
+    const std::string who = "a " + punctual_light_name(s->cs);
+    if (t.wavefront == 1) return "unsupported: the scene has " + who + " and the wavefront schedule is forced (option wavefront = 1); only the megakernel samples punctual lights";
+    if (t.arith == 1) return "unsupported: the scene has " + who + "; the relaxed arithmetic tier (option arith = 1) has no kernels that sample punctual lights";
+    return "";
 }
 std::string akr_api::pt_features_refusal(const akr_scene* s, const TuningOptions& t) {
     if (s->cs.instanced.on)
         return "unsupported: akr_pt_begin_features: the scene is kept as meshes + instances (option instancing); its kernels collect no guides -- render them with akr_aov_render";
     if (t.wavefront == 1) return "unsupported: akr_pt_begin_features: the wavefront schedule is forced (option wavefront = 1); only the megakernel collects guides";
     if (t.arith == 1) return "unsupported: akr_pt_begin_features: the relaxed arithmetic tier (option arith = 1) has no kernels that collect guides";
+    if (!s->cs.punct.empty())
+        return "unsupported: akr_pt_begin_features: the scene has a " + punctual_light_name(s->cs) + "; the kernels that sample punctual lights collect no guides -- render them with akr_aov_render";
     return "";
 }
 PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves, bool feat) {
@@ -30,8 +39,8 @@ PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_me
     PtVariant& v = pl.v = pt_scene_facts(s, c);
     v.feat = feat;
     // The exclusion rules, applied here and nowhere else (kernels.h pt_variant_compiled states them): no DEFER and no SIMPLE kernels with an
-    // environment light, a lens or collected guides; a kept scene has neither, and its kernels stage no tables.
-    const bool plain = !v.env && !v.lens && !v.feat;
+    // environment light, a lens, collected guides or punctual lights; a kept scene has neither, and its kernels stage no tables.
+    const bool plain = !v.env && !v.lens && !v.feat && !v.punct;
     {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
         // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
         // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
@@ -134,6 +143,7 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves, b
             p.sc.tex.nodes = set.tex_nodes.as<DNode>();
             p.sc.tex.mat_inputs = set.mat_inputs.as<MatInputs>();
         }
+        if (!s->cs.punct.empty()) p.sc.punct = set.punct.as<DPunct>();
     }
     p.sampler = c.sampler_type;
     if (c.sampler_type == AKR_SAMPLER_PMJ02BN || c.sampler_type == AKR_SAMPLER_SOBOL) {  // Pmj02BnSamplerCreator::new (sampler/mod.rs:376-395)
@@ -424,6 +434,7 @@ static bool schedule_trial_eligible(const akr_pt_session* se) {
     const akr_scene* sc = se->scene;
     if (t.wavefront != -1 || t.sched_trial == 0 || se->wf || se->arith_relaxed || se->spec_active) return false;
     if (se->feat_albedo) return false;  // a session that collects guides stays on the megakernel
+    if (!sc->cs.punct.empty()) return false;  // ... and so does a scene with punctual lights
     if (sc->cs.instanced.on || !sc->cs.has_tree() || t.wf_sort != 0) return false;
     if (t.sched_trial == 1) return true;
     const uint64_t passes = (session_samples(se->cfg) + se->cfg.spp_per_pass - 1) / se->cfg.spp_per_pass;
@@ -504,6 +515,11 @@ void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, con
         }
         scene->color_sets[cfg->color] = std::move(set);
     }
+    if (cfg->color != 0 && !scene->cs.punct.empty() && !scene->color_sets.at(cfg->color)->punct.p) {  // (dropped when the lights change: api_scene.cpp)
+        std::vector<DPunct> recs;
+        for (const akr_punctual_light_desc& d : scene->flat.punct) recs.push_back(fold_punctual(d, cfg->color));
+        scene->color_sets.at(cfg->color)->punct.upload(recs);
+    }
     if (cfg->color != 0) se->color_set = scene->color_sets.at(cfg->color).get();  // stable: the map owns it through a unique_ptr
     color_lock.unlock();
     const uint64_t n = (uint64_t)film->width * film->height;
@@ -552,6 +568,10 @@ static int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config*
     *out = nullptr;
     return guarded([&] {
         auto se = std::make_unique<akr_pt_session>();
+        if (scene) {  // what a scene with punctual lights cannot do, before a byte is allocated
+            const std::string why = pt_punctual_refusal(scene, tuning());
+            if (!why.empty()) throw Unsupported(why);
+        }
         base_begin(se.get(), ctx, scene, cfg, film);
         se->feat_albedo = albedo;
         se->feat_normal = normal;
@@ -581,6 +601,7 @@ static int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config*
             else if (features) se->spec_status = scene->cs.has_textures && t.specialise == 1 ? "guides are collected by the interpreter kernels: no per-scene kernel (option specialise ignored)"
                                                                                             : "guides are collected by the precompiled kernels";
             else if (!scene->cs.has_textures) se->spec_status = "the scene has no texture-fed material";
+            else if (facts.punct) se->spec_status = "punctual lights are sampled by the interpreter kernels: no per-scene kernel (option specialise ignored)";
             else if (t.specialise == 0) se->spec_status = "option specialise = 0";
             else if (cfg->force_diffuse) se->spec_status = "force_diffuse kernels evaluate no surface graphs";
             else {
@@ -795,7 +816,7 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         info->specialised = se->spec_active ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
         const PtVariant& v = se->variant;  // (bit 0: the flattened scene's tree; a kept scene's two-level traversal does not set it)
-        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u);
+        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u) | (v.punct ? 128u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;

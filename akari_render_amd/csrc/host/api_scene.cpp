@@ -31,8 +31,27 @@ static void ensure_ggx_table(akr_scene* s) {
     s->ggx_table.upload(s->ggx_host);
 }
 
-// the light tables (and the environment's record and tables) on the device, and their pointers in s->dscene: at scene creation and after
-// akr_scene_set_environment
+static void pack_alias(const std::vector<AliasEntry>& e, const std::vector<float>& pdf, size_t first, size_t n, std::vector<AliasPacked>& out) {
+    for (size_t i = 0; i < n; i++) out.push_back(AliasPacked{e[first + i].j, e[first + i].t, pdf[first + i], pdf[first + e[first + i].j]});
+}
+void akr_api::packed_light_tables(const CompiledScene& cs, std::vector<AliasPacked>& la, std::vector<AliasPacked>& aa, std::vector<LightRec>& lr) {
+    pack_alias(cs.light_entries, cs.light_pdf, 0, cs.n_lights, la);
+    uint32_t n_punct = 0;
+    for (uint32_t l = 0; l < cs.n_lights; l++) {
+        if (cs.light_inst[l] == 0xffffffffu) {  // the environment (no triangles)
+            lr.push_back(LightRec{cs.light_tri_offset[l], 0u, 0u, 0xffffffffu});
+            continue;
+        }
+        if (cs.light_inst[l] == kPunctInst) {  // a punctual light (no triangles): first_gid = its record in DScene.punct
+            lr.push_back(LightRec{cs.light_tri_offset[l], 0u, n_punct++, kPunctInst});
+            continue;
+        }
+        pack_alias(cs.area_entries, cs.area_pdf, cs.light_tri_offset[l], cs.light_n_tris[l], aa);
+        lr.push_back(LightRec{cs.light_tri_offset[l], cs.light_n_tris[l], cs.inst_tri_offset[cs.light_inst[l]], cs.light_inst[l]});
+    }
+}
+// the light tables (and the environment's record and tables, and the punctual lights' records) on the device, and their pointers in s->dscene: at scene
+// creation and after akr_scene_set_environment / akr_scene_add_punctual_light / akr_scene_clear_punctual_lights
 static void upload_lights(akr_scene* s) {
     const CompiledScene& cs = s->cs;
     s->light_entries.upload(cs.light_entries);
@@ -40,21 +59,12 @@ static void upload_lights(akr_scene* s) {
     s->light_inst.upload(cs.light_inst);
     s->light_tri_offset.upload(cs.light_tri_offset);
     s->light_n_tris.upload(cs.light_n_tris);
+    s->punct.upload(cs.punct);
     {  // the light tables once more, packed so that each level of light sampling is ONE gather (device/dgeom.h, dscene.h)
-        auto pack = [](const std::vector<AliasEntry>& e, const std::vector<float>& pdf, size_t first, size_t n, std::vector<AliasPacked>& out) {
-            for (size_t i = 0; i < n; i++) out.push_back(AliasPacked{e[first + i].j, e[first + i].t, pdf[first + i], pdf[first + e[first + i].j]});
-        };
+        auto pack = pack_alias;
         std::vector<AliasPacked> la, aa;
         std::vector<LightRec> lr;
-        pack(cs.light_entries, cs.light_pdf, 0, cs.n_lights, la);
-        for (uint32_t l = 0; l < cs.n_lights; l++) {
-            if (cs.light_inst[l] == 0xffffffffu) {  // the environment (no triangles)
-                lr.push_back(LightRec{cs.light_tri_offset[l], 0u, 0u, 0xffffffffu});
-                continue;
-            }
-            pack(cs.area_entries, cs.area_pdf, cs.light_tri_offset[l], cs.light_n_tris[l], aa);
-            lr.push_back(LightRec{cs.light_tri_offset[l], cs.light_n_tris[l], cs.inst_tri_offset[cs.light_inst[l]], cs.light_inst[l]});
-        }
+        packed_light_tables(cs, la, aa, lr);
         s->light_alias.upload(la);
         s->area_alias.upload(aa);
         s->lights.upload(lr);
@@ -100,6 +110,8 @@ static void upload_lights(akr_scene* s) {
     d.lights = s->lights.as<LightRec>();
     d.n_lights = cs.n_lights;
     d.env = cs.env.on ? s->env_rec.as<DEnv>() : nullptr;
+    d.punct = s->punct.as<DPunct>();
+    d.n_punct = (uint32_t)cs.punct.size();
 }
 static void count_device_bytes(akr_scene* s) {
     s->device_bytes = 0;
@@ -107,7 +119,7 @@ static void count_device_bytes(akr_scene* s) {
                             &s->light_pdf, &s->light_inst, &s->light_tri_offset, &s->light_n_tris, &s->area_entries, &s->area_pdf,
                             &s->inst_tri_offset, &s->light_alias, &s->area_alias, &s->lights, &s->bvh_nodes, &s->tex_nodes, &s->tex_images, &s->tex_texels, &s->tex_mat_inputs,
                             &s->in2_tlas_leaves, &s->in2_mesh_tris, &s->in2_mesh_pos, &s->in2_mesh_meta, &s->in2_mesh_normals, &s->in2_inst_mats, &s->in2_share_bits,
-                            &s->env_texels, &s->env_marginal, &s->env_conditional, &s->env_rec})
+                            &s->env_texels, &s->env_marginal, &s->env_conditional, &s->env_rec, &s->punct})
         s->device_bytes += b->bytes;
 }
 
@@ -158,6 +170,7 @@ static void check_lens_reach(const akr_scene* s, const HostLens& lens) {
 void akr_api::scene_finish(akr_scene* s) {
     akr_context* ctx = s->ctx;
     compile_scene(s->flat, s->cs);
+    compile_punctual(s->flat, s->cs);
     compile_environment(s->flat, s->cs);
     check_lens_reach(s, s->flat.lens);  // (a lens from the file, option `lens`)
     CompiledScene& cs = s->cs;
@@ -251,6 +264,7 @@ static uint64_t compiled_scene_bytes(const CompiledScene& cs) {
                  b(cs.light_inst) + b(cs.light_tri_offset) + b(cs.light_n_tris) + b(cs.area_entries) + b(cs.area_pdf) + b(cs.inst_tri_offset) +
                  16ull * (cs.light_entries.size() + cs.area_entries.size() + cs.n_lights) + b(cs.bvh_nodes) + b(cs.tex_nodes) + b(cs.images) + b(cs.texels) +
                  b(cs.mat_inputs);
+    n += b(cs.punct);
     n += b(cs.env.texels) + 16ull * (cs.env.marginal_entries.size() + cs.env.conditional_entries.size()) + (cs.env.on ? sizeof(DEnv) : 0u);
     const CompiledScene::Instanced& is = cs.instanced;
     return n + b(is.nodes) + b(is.tlas_leaves) + b(is.mesh_tris) + b(is.mesh_pos) + b(is.mesh_meta) + b(is.mesh_normals) + b(is.inst_mats) + (is.on ? std::max<uint64_t>(((uint64_t)cs.n_tris + 31u) / 32u, 1u) * 4u : 0u);
@@ -349,6 +363,52 @@ AKR_API int32_t akr_scene_get_environment(const akr_scene* s, akr_environment_de
     out->texels = e.texels.empty() ? nullptr : e.texels.data();
     for (int c = 0; c < 3; c++) out->color[c] = e.color[c];
     out->strength = e.strength;
+    return AKR_OK;
+}
+// the punctual lights changed: light table and records compiled again (the change is taken back if that is refused), uploaded, the colour sets' copies dropped
+static void punctual_lights_changed(akr_scene* s, std::vector<akr_punctual_light_desc>& before) {
+    try {
+        compile_punctual(s->flat, s->cs);
+    } catch (...) {
+        std::swap(s->flat.punct, before);  // (compile_punctual refuses before it changes anything)
+        throw;
+    }
+    if (s->ctx) {
+        s->ctx->bind();
+        upload_lights(s);
+        count_device_bytes(s);
+        std::lock_guard<std::mutex> lock(s->color_sets_mutex);
+        for (auto& kv : s->color_sets) kv.second->punct.release();  // folded again by the next session of that pipeline (api_pt.cpp base_begin)
+    }
+}
+AKR_API int32_t akr_scene_add_punctual_light(akr_scene* s, const akr_punctual_light_desc* desc) {
+    if (!s || !desc) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_add_punctual_light: NULL argument");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_add_punctual_light: a session holds the scene (end it first)");
+        akr_punctual_light_desc checked;
+        if (!punctual_from_desc(*desc, checked)) return;  // no light
+        std::vector<akr_punctual_light_desc> before = s->flat.punct;
+        s->flat.punct.push_back(checked);
+        punctual_lights_changed(s, before);
+    });
+}
+AKR_API int32_t akr_scene_clear_punctual_lights(akr_scene* s) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_clear_punctual_lights: scene is NULL");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_clear_punctual_lights: a session holds the scene (end it first)");
+        std::vector<akr_punctual_light_desc> before = s->flat.punct;
+        s->flat.punct.clear();
+        punctual_lights_changed(s, before);
+    });
+}
+AKR_API int32_t akr_scene_punctual_light_count(const akr_scene* s, uint32_t* count) {
+    if (!s || !count) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_punctual_light_count: NULL argument");
+    *count = (uint32_t)s->flat.punct.size();
+    return AKR_OK;
+}
+AKR_API int32_t akr_scene_get_punctual_light(const akr_scene* s, uint32_t index, akr_punctual_light_desc* out) {
+    if (!s || !out || index >= s->flat.punct.size()) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_punctual_light: bad argument");
+    *out = s->flat.punct[index];
     return AKR_OK;
 }
 AKR_API int32_t akr_scene_set_lens(akr_scene* s, const akr_lens_desc* desc) {
@@ -478,6 +538,7 @@ AKR_API int32_t akr_scene_get_array(const akr_scene* s, int32_t which, const voi
         case AKR_ARRAY_ENV_CONDITIONAL_ENTRIES: set(cs.env.conditional_entries.data(), cs.env.conditional_entries.size() * sizeof(AliasEntry)); break;
         case AKR_ARRAY_ENV_CONDITIONAL_PDF: set(cs.env.conditional_pdf.data(), cs.env.conditional_pdf.size() * 4); break;
         case AKR_ARRAY_ENV_TEXELS: set(cs.env.texels.data(), cs.env.texels.size() * 4); break;
+        case AKR_ARRAY_PUNCTUAL_LIGHTS: set(cs.punct.data(), cs.punct.size() * sizeof(DPunct)); break;
         default: return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: unknown array id");
     }
     return AKR_OK;

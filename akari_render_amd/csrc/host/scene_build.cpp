@@ -748,11 +748,7 @@ void compile_scene(const FlatScene& flat, CompiledScene& out) {
     const TuningOptions tune = tuning();
     const uint32_t kExhaustiveMax = tune.force_bvh ? 0u : 64u;
     // the exhaustive kernels stage the shading tables in LDS (device/pt_pass.h: STAGE): a tiny mesh with a huge material list goes the BVH way
-    size_t stage = 0;
-    for (size_t b : {out.shade.size() * 4, out.normals.size() * 4, out.inst.size() * 4, out.materials.size() * sizeof(DMaterial),
-                     (size_t)out.n_lights * 32, out.area_entries.size() * 16, out.light_pdf.size() * 4, out.area_pdf.size() * 4,
-                     out.tex_nodes.size() * sizeof(DNode), out.images.size() * sizeof(DImage), out.mat_inputs.size() * sizeof(MatInputs)})
-        stage += (b + 15) & ~(size_t)15;
+    const size_t stage = exhaustive_stage_bytes(out, out.n_lights);
     if (n_tris > kExhaustiveMax || stage > kStageMaxBytes) {
         const float pad_scale = 0.01f * (float)tune.pad_percent;  // (test hook: 100)
         const float pad = pad_scale * bvh_box_padding(out.scene_lo, out.scene_hi, flat.camera.c2w);
@@ -806,6 +802,15 @@ void compile_scene(const FlatScene& flat, CompiledScene& out) {
     out.woop.resize(out.woop.size() + 32, 0.0f);
 }
 
+size_t exhaustive_stage_bytes(const CompiledScene& out, size_t n_lights) {
+    size_t stage = 0;
+    for (size_t b : {out.shade.size() * 4, out.normals.size() * 4, out.inst.size() * 4, out.materials.size() * sizeof(DMaterial),
+                     n_lights * 32 /* AliasPacked + LightRec */, out.area_entries.size() * 16, n_lights * 4, out.area_pdf.size() * 4,
+                     out.tex_nodes.size() * sizeof(DNode), out.images.size() * sizeof(DImage), out.mat_inputs.size() * sizeof(MatInputs)})
+        stage += (b + 15) & ~(size_t)15;
+    return stage;
+}
+
 namespace {
 std::mutex g_tuning_mutex;
 bool g_tuning_init = false;
@@ -823,6 +828,7 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_SPECIALISE_WAVES")) g_tuning.specialise_waves = std::atoi(e);
     if (const char* e = std::getenv("AKR_WF_SORT")) g_tuning.wf_sort = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_LENS")) g_tuning.lens = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("AKR_PUNCTUAL_LIGHTS")) g_tuning.punctual_lights = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_INSTANCING")) g_tuning.instancing = std::atoi(e);
     if (const char* e = std::getenv("AKR_WF_GROUPS")) g_tuning.wf_groups = std::max(0, std::min(32, std::atoi(e)));
     if (const char* e = std::getenv("AKR_WF_CARRY")) g_tuning.wf_carry = std::max(0, std::min(1 << 30, std::atoi(e)));
@@ -854,6 +860,7 @@ int* tuning_field(const char* name) {
     if (n == "max_fused_passes") return &g_tuning.max_fused_passes;
     if (n == "wf_sort") return &g_tuning.wf_sort;
     if (n == "lens") return &g_tuning.lens;
+    if (n == "punctual_lights") return &g_tuning.punctual_lights;
     if (n == "instancing") return &g_tuning.instancing;
     if (n == "arith") return &g_tuning.arith;
     if (n == "rebraid") return &g_tuning.rebraid;
@@ -891,6 +898,7 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.max_fused_passes && (value < 0 || value > 64)) return false;
     if (f == &g_tuning.wf_sort && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.lens && (value < 0 || value > 1)) return false;
+    if (f == &g_tuning.punctual_lights && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.instancing && (value < -1 || value > 1)) return false;
     if (f == &g_tuning.arith && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.rebraid && (value < 1 || value > 64)) return false;

@@ -68,6 +68,7 @@ struct FlatScene {
     std::vector<HostImage> images;
     std::vector<HostGraph> graphs;  // empty, or one per material
     HostEnvironment env;
+    std::vector<akr_punctual_light_desc> punct;  // akr_scene_add_punctual_light / scene.json "lights": checked, as given (scene_punct.cpp; not part of akr_scene_desc)
     HostLens lens;  // akr_scene_set_lens, or the file's focal_distance / fstop under option `lens` (not part of akr_scene_desc)
     static FlatScene from_desc(const akr_scene_desc& d);
 };
@@ -136,6 +137,9 @@ struct CompiledScene {
         float rot_t[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // world -> environment (R^T), row-major
         float power = 0.0f;                             // selection weight 4 pi R^2 Lbar
     } env;
+    // the punctual lights' records under the default colour pipeline (scene_punct.cpp; device/dscene.h DPunct): their entries in the light table come after
+    // the emissive instances' and before the environment's, light_inst = kPunctInst
+    std::vector<DPunct> punct;
     bool has_textures = false;
     bool has_alpha = false;
     bool needs_ggx_table = false;
@@ -227,6 +231,7 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //                                         sin / cos / log / exp and contraction instead of the bit-exact contract
 //   pad_percent  (no environment hook)    test hook: box padding in percent of the derived value (100)
 //   lens         AKR_LENS=1               akr_scene_load gives the camera the thin lens of the file's focal_distance and fstop (the reference reads both and renders a pinhole)
+//   punctual_lights AKR_PUNCTUAL_LIGHTS=0 akr_scene_load drops the file's point / spot / sun lights (the reference's lights collection has no implementation)
 //   wf_sort      AKR_WF_SORT=1            wavefront schedule: ray queues sorted by origin cell + direction octant before each trace launch
 //   wf_groups    AKR_WF_GROUPS=<g>        wavefront schedule: the slots run as g groups with queues and streams of their own (api_pt.cpp wf_run); 0 = the library decides
 //   wf_carry     AKR_WF_CARRY=0           wavefront schedule: 0 = every trace launch traces its rays to the end (1, default: a wave that finds the queue empty and
@@ -260,6 +265,7 @@ struct TuningOptions {
     int wf_carry = 1;  // wavefront schedule: 1 = the last rays of a trace launch are carried into the next one (wf_kernels.hip), 0 = every launch traces to the end
     int sched_trial = -1;  // flattened scenes under option wavefront = -1: a timed trial of both schedules at the start of a long render (api_pt.cpp schedule_trial):
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
+    int punctual_lights = 1;  // akr_scene_load: 1 = the file's point / spot / sun lights light the scene; 0 = dropped, as the reference renders every file
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
     int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
@@ -278,11 +284,23 @@ bool tuning_set(const char* name, int value);    // false: unknown name
 bool tuning_get(const char* name, int* value);
 
 void compile_scene(const FlatScene& flat, CompiledScene& out);
+// What the exhaustive kernels stage in LDS (device/pt_pass.h: STAGE) of a compiled scene whose light list has n_lights entries, in bytes, each table padded to 16:
+// the ONE sum that compile_scene (exhaustive or BVH?), compile_environment and compile_punctual (does the scene still fit with the entry added?) compare
+// with kStageMaxBytes. A table staged in future is added here.
+size_t exhaustive_stage_bytes(const CompiledScene& out, size_t n_lights);
+// "point light" / "spot light" / "sun light" of the scene's first punctual light: what a refusal names
+std::string punctual_light_name(const CompiledScene& cs);
 // scene_env.cpp: the environment light of `flat` into `out` (tables, light-table entry); replaces the one `out` has. After compile_scene.
 constexpr uint32_t kEnvConstW = 32, kEnvConstH = 16;  // the image a constant colour is stored as
 void compile_environment(const FlatScene& flat, CompiledScene& out);
 // an akr_environment_desc checked and copied (throws std::invalid_argument); the result's `set` is false for "no environment"
 HostEnvironment environment_from_desc(const akr_environment_desc& d);
+void rebuild_light_alias(CompiledScene& out);  // n_lights and the selection table from light_power
+// scene_punct.cpp: an akr_punctual_light_desc checked and copied to `out` (throws std::invalid_argument); false = "no light" (strength 0 or an all-zero colour)
+bool punctual_from_desc(const akr_punctual_light_desc& d, akr_punctual_light_desc& out);
+DPunct fold_punctual(const akr_punctual_light_desc& d, uint32_t color);  // the record under the colour pipeline `color`
+// the punctual lights of `flat` into `out` (records, light-table entries); replaces those `out` has. After compile_scene; the environment's entry stays last.
+void compile_punctual(const FlatScene& flat, CompiledScene& out);
 float triangle_emission_power(const CompiledScene& out, const TexScene& host_tex, uint32_t material, uint32_t prim, vec2 uv0, vec2 uv1, vec2 uv2, float area);
 bool instance_may_emit(const CompiledScene& out, const std::vector<akr_material_desc>& descs, const HostInstance& in);
 // scene_inst.cpp: does this scene take the two-level route, and its geometry + light tables if so (materials and the instance table

@@ -63,26 +63,18 @@ HostEnvironment environment_from_desc(const akr_environment_desc& d) {
     return e;
 }
 
-namespace {
 void rebuild_light_alias(CompiledScene& out) {
     out.n_lights = (uint32_t)out.light_inst.size();
     out.light_entries.clear();
     out.light_pdf.clear();
     if (out.n_lights > 0) build_alias_table(out.light_power, out.light_entries, out.light_pdf);
 }
-}  // namespace
 
 void compile_environment(const FlatScene& flat, CompiledScene& out) {
     if (!flat.env.set && !out.env.on) return;  // (a scene without one keeps its tables exactly as compile_scene made them)
     if (flat.env.set && out.bvh_nodes.empty() && !out.instanced.on) {
         // the exhaustive kernels read the light tables from LDS: scene_build.cpp sized the fit without this entry
-        const size_t n_lights = out.light_inst.size() + (out.env.on ? 0 : 1);
-        size_t stage = 0;
-        for (size_t b : {out.shade.size() * 4, out.normals.size() * 4, out.inst.size() * 4, out.materials.size() * sizeof(DMaterial),
-                         n_lights * 32, out.area_entries.size() * 16, n_lights * 4, out.area_pdf.size() * 4,
-                         out.tex_nodes.size() * sizeof(DNode), out.images.size() * sizeof(DImage), out.mat_inputs.size() * sizeof(MatInputs)})
-            stage += (b + 15) & ~(size_t)15;
-        if (stage > kStageMaxBytes) throw std::runtime_error("unsupported: the scene's shading tables with an environment light pass the exhaustive kernels' LDS budget");
+        if (exhaustive_stage_bytes(out, out.light_inst.size() + (out.env.on ? 0 : 1)) > kStageMaxBytes) throw std::runtime_error("unsupported: the scene's shading tables with an environment light pass the exhaustive kernels' LDS budget");
     }
     if (out.env.on) {  // the previous environment: the last light
         out.light_inst.pop_back();

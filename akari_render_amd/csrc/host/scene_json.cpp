@@ -42,12 +42,13 @@ bool file_exists(const std::string& p) {
 std::string base64_decode(const std::string& in) {
     static const std::string tbl = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
     std::string out;
-    int val = 0, bits = -8;
+    uint32_t val = 0;  // (unsigned: the bits shifted out at the top are meant to go)
+    int bits = -8;
     for (unsigned char c : in) {
         if (c == '=' || c == '\n' || c == '\r') continue;
         size_t p = tbl.find((char)c);
         if (p == std::string::npos) throw std::runtime_error("bad base64 buffer");
-        val = (val << 6) + (int)p;
+        val = (val << 6) + (uint32_t)p;
         bits += 6;
         if (bits >= 0) {
             out.push_back((char)((val >> bits) & 0xFF));
@@ -536,6 +537,38 @@ FlatScene load_scene_json(const std::string& path) {
                 for (int col = 0; col < 3; col++) d.rotation[3 * row + col] = t.m[col * 4 + row];
         }
         flat.env = environment_from_desc(d);
+    }
+    if (scene.has("lights") && tuning().punctual_lights != 0) {
+        // optional punctual lights: {name: {"type": "point" | "spot" | "sun", "data": {position, direction, color, strength, spot_size, spot_blend}}}. An entry
+        // whose data is empty is the reference's own `Light::Point(PointLight {})` (akari_scenegraph/src/scene.rs), which lights nothing: ignored.
+        for (const auto& kv : scene.at("lights").obj) {
+            const JsonValue& lj = *kv.second;
+            if (!lj.has("data") || lj.at("data").obj.empty()) continue;
+            try {
+                const std::string type = lj.at("type").as_string();
+                const JsonValue& dj = lj.at("data");
+                akr_punctual_light_desc d;
+                std::memset(&d, 0, sizeof d);
+                if (type == "point") d.type = AKR_LIGHT_POINT;
+                else if (type == "spot") d.type = AKR_LIGHT_SPOT;
+                else if (type == "sun") d.type = AKR_LIGHT_SUN;
+                else throw std::runtime_error("unknown light type '" + type + "'");
+                if (d.type != AKR_LIGHT_SUN)
+                    for (int k = 0; k < 3; k++) d.position[k] = dj.at("position").at(k).as_f32();
+                if (d.type != AKR_LIGHT_POINT)
+                    for (int k = 0; k < 3; k++) d.direction[k] = dj.at("direction").at(k).as_f32();
+                for (int c = 0; c < 3; c++) d.color[c] = dj.has("color") ? dj.at("color").at(c).as_f32() : 1.0f;
+                d.strength = dj.has("strength") ? dj.at("strength").as_f32() : 1.0f;
+                if (d.type == AKR_LIGHT_SPOT) {
+                    d.cone_angle = dj.at("spot_size").as_f32() * 0.5f;  // spot_size is the full cone angle
+                    d.blend = dj.has("spot_blend") ? dj.at("spot_blend").as_f32() : 0.0f;
+                }
+                akr_punctual_light_desc checked;
+                if (punctual_from_desc(d, checked)) flat.punct.push_back(checked);
+            } catch (const std::exception& e) {
+                throw std::runtime_error("light '" + kv.first + "': " + e.what());
+            }
+        }
     }
     if (!scene.has("camera")) throw std::runtime_error("scene has no camera");
     const JsonValue& cam = scene.at("camera");

@@ -1,0 +1,133 @@
+// scene_punct.cpp -- the punctual lights on the host: the description checked, the 64-byte record the kernels read
+// (device/dscene.h DPunct; folded in double, each value rounded once) and the lights' entries in the light table, between the emissive instances and
+// the environment.
+#include <cmath>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+#include "scene_build.h"
+
+namespace akr {
+
+static const char* punct_kind_name(uint32_t type) { return type == AKR_LIGHT_POINT ? "point" : (type == AKR_LIGHT_SPOT ? "spot" : "sun"); }
+
+std::string punctual_light_name(const CompiledScene& cs) {
+    if (cs.punct.empty()) return "";
+    return cs.punct[0].kind == PUNCT_POINT ? "point light" : (cs.punct[0].kind == PUNCT_SPOT ? "spot light" : "sun light");
+}
+
+bool punctual_from_desc(const akr_punctual_light_desc& d, akr_punctual_light_desc& out) {
+    if (d.type > AKR_LIGHT_SUN) throw std::invalid_argument("punctual light: unknown type " + std::to_string(d.type));
+    const std::string who = std::string(punct_kind_name(d.type)) + " light: ";
+    if (!std::isfinite(d.strength) || d.strength < 0.0f) throw std::invalid_argument(who + "strength must be finite and >= 0");
+    bool any = false;
+    for (int c = 0; c < 3; c++) {
+        if (!std::isfinite(d.color[c]) || d.color[c] < 0.0f) throw std::invalid_argument(who + "colour must be finite and >= 0");
+        any = any || d.color[c] > 0.0f;
+    }
+    if (d.type != AKR_LIGHT_SUN)
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(d.position[k])) throw std::invalid_argument(who + "position must be finite");
+    if (d.type != AKR_LIGHT_POINT) {
+        double l2 = 0.0;
+        for (int k = 0; k < 3; k++) {
+            if (!std::isfinite(d.direction[k])) throw std::invalid_argument(who + "direction must be finite");
+            l2 += (double)d.direction[k] * d.direction[k];
+        }
+        if (!(l2 > 0.0)) throw std::invalid_argument(who + "direction must not be zero");
+    }
+    if (d.type == AKR_LIGHT_SPOT) {
+        // (pi/2 as the f32 nearest to it: what a caller can pass)
+        if (!std::isfinite(d.cone_angle) || !(d.cone_angle > 0.0f) || d.cone_angle > 1.57079637f) throw std::invalid_argument(who + "cone_angle (the outer half-angle) must be in (0, pi/2]");
+        if (!std::isfinite(d.blend) || d.blend < 0.0f || d.blend > 1.0f) throw std::invalid_argument(who + "blend must be in [0, 1]");
+    }
+    out = d;
+    // what the kind does not read is stored as zero: two descriptions of the same light compare equal
+    if (d.type == AKR_LIGHT_SUN) out.position[0] = out.position[1] = out.position[2] = 0.0f;
+    if (d.type == AKR_LIGHT_POINT) out.direction[0] = out.direction[1] = out.direction[2] = 0.0f;
+    if (d.type != AKR_LIGHT_SPOT) out.cone_angle = out.blend = 0.0f;
+    return any && d.strength > 0.0f;  // a strength of 0 or an all-zero colour: no light, as for the environment
+}
+
+DPunct fold_punctual(const akr_punctual_light_desc& d, uint32_t color) {
+    DPunct r;
+    std::memset(&r, 0, sizeof r);
+    r.kind = d.type == AKR_LIGHT_POINT ? PUNCT_POINT : (d.type == AKR_LIGHT_SPOT ? PUNCT_SPOT : PUNCT_SUN);
+    if (d.type != AKR_LIGHT_SUN) r.q = mk3(d.position[0], d.position[1], d.position[2]);
+    if (d.type != AKR_LIGHT_POINT) {
+        const double x = d.direction[0], y = d.direction[1], z = d.direction[2];
+        const double len = std::sqrt((x * x + y * y) + z * z);
+        r.a = mk3((float)(x / len), (float)(y / len), (float)(z / len));
+    }
+    if (d.type == AKR_LIGHT_SPOT) {
+        r.cos_o = (float)std::cos((double)d.cone_angle);
+        r.cos_i = (float)std::cos((double)d.cone_angle * (1.0 - (double)d.blend));
+        r.inv_span = r.cos_i == r.cos_o ? 0.0f : 1.0f / (r.cos_i - r.cos_o);
+    }
+    // colour x strength, then the way of an Emission material's constant colour into the session's pipeline (dbsdf.h convert_color_inputs: here, on the host)
+    r.c = color_input(mk3(d.color[0] * d.strength, d.color[1] * d.strength, d.color[2] * d.strength), false, color);
+    return r;
+}
+
+// the selection weight: "radiant power" on the scale of the triangle lights' estimate -- 4 pi I for a point light, the cone's solid angle (at the mean of
+// its two cosines) x I for a spot, pi R^2 E for a sun over the scene's bounding sphere (R as scene_env.cpp computes it)
+static float punctual_power(const DPunct& r, double R) {
+    const double m = (double)max3(r.c);
+    if (r.kind == PUNCT_POINT) return (float)((4.0 * M_PI) * m);
+    if (r.kind == PUNCT_SPOT) return (float)(((2.0 * M_PI) * (1.0 - 0.5 * ((double)r.cos_i + (double)r.cos_o))) * m);
+    return (float)(((M_PI * R) * R) * m);
+}
+
+void compile_punctual(const FlatScene& flat, CompiledScene& out) {
+    if (flat.punct.empty() && out.punct.empty()) return;  // (a scene without one keeps its tables exactly as compile_scene made them)
+    if (!flat.punct.empty()) {
+        const std::string who = std::string(punct_kind_name(flat.punct[0].type)) + " light";
+        if (out.instanced.on)
+            throw std::runtime_error("unsupported: the scene has a " + who + " and is kept as meshes + instances (option instancing); the kernels of kept scenes sample no punctual lights");
+        if (out.bvh_nodes.empty()) {  // the exhaustive kernels read the light tables from LDS: scene_build.cpp sized the fit without these entries
+            if (exhaustive_stage_bytes(out, out.light_inst.size() - out.punct.size() + flat.punct.size()) > kStageMaxBytes) throw std::runtime_error("unsupported: the scene's shading tables with its " + who + "s pass the exhaustive kernels' LDS budget");
+        }
+    }
+    // the environment's entry is the last: taken off, put back behind the punctual lights
+    const bool env = out.env.on;
+    uint32_t env_entry[3] = {0, 0, 0};
+    float env_power = 0.0f;
+    auto pop = [&] {
+        out.light_inst.pop_back();
+        out.light_power.pop_back();
+        out.light_tri_offset.pop_back();
+        out.light_n_tris.pop_back();
+    };
+    if (env) {
+        env_entry[0] = out.light_inst.back(); env_entry[1] = out.light_tri_offset.back(); env_entry[2] = out.light_n_tris.back();
+        env_power = out.light_power.back();
+        pop();
+    }
+    for (size_t k = 0; k < out.punct.size(); k++) pop();
+    out.punct.clear();
+    double r2 = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double ext = (double)out.scene_hi[a] - (double)out.scene_lo[a];
+        r2 += ext * ext;
+    }
+    double R = 0.5 * std::sqrt(r2);
+    if (!(R > 0.0) || !std::isfinite(R)) R = 1.0;
+    for (const akr_punctual_light_desc& d : flat.punct) {
+        const DPunct r = fold_punctual(d, 0);
+        out.punct.push_back(r);
+        out.light_inst.push_back(kPunctInst);
+        out.light_power.push_back(punctual_power(r, R));
+        out.light_tri_offset.push_back((uint32_t)out.area_entries.size());
+        out.light_n_tris.push_back(0);
+    }
+    if (env) {
+        out.light_inst.push_back(env_entry[0]);
+        out.light_power.push_back(env_power);
+        out.light_tri_offset.push_back(env_entry[1]);
+        out.light_n_tris.push_back(env_entry[2]);
+    }
+    rebuild_light_alias(out);
+}
+
+}  // namespace akr

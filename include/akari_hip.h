@@ -307,6 +307,34 @@ AKR_API int32_t akr_scene_set_environment(akr_scene *scene, const akr_environmen
 /* The environment as decoded (texels owned by the scene); width = height = 0 and strength = 0 when there is none. A constant
  * colour comes back as width = height = 0 with its colour. */
 AKR_API int32_t akr_scene_get_environment(const akr_scene *scene, akr_environment_desc *out);
+/* Punctual lights of a scene (pt integrator): point, spot and sun lights, sampled by next-event estimation. All three are delta
+ * lights -- no radius, no angular size, hard shadows -- and invisible: no camera or BSDF-sampled ray ever hits one, so a render with use_nee = 0 gets
+ * nothing from them, and aov renders the scene as if they were not there.
+ *   AKR_LIGHT_POINT  at `position`; color x strength = radiant intensity I per channel (W/sr in the units emission uses): Li = I / dist^2
+ *   AKR_LIGHT_SPOT   at `position`, pointing along `direction`; cone_angle = the cone's outer HALF-angle in (0, pi/2]; blend in [0, 1] = the part of
+ *                    that angle over which the light falls off, smoothstep in the cosine (0 = a hard edge): Li = I f / dist^2
+ *   AKR_LIGHT_SUN    light travelling along `direction`; color x strength = irradiance E on a surface facing it: Li = E
+ * `direction` is normalised by the library when it folds the light. A light with strength 0 or an all-zero colour is no light: it is accepted and not added. In the light list
+ * (akr_scene_get_light) the punctual lights come after the emissive instances, in the order given, with instance 0xFFFFFFFE; the environment stays
+ * last. Refused with AKR_ERR_UNSUPPORTED: gpt, mcmc_opt, the relaxed arithmetic tier, option "wavefront" = 1, akr_pt_begin_features, and scenes kept
+ * as meshes + instances. Scenes with texture-fed materials render with the interpreter kernels (no per-scene kernel). Not part of akr_scene_desc. */
+typedef enum { AKR_LIGHT_POINT = 0, AKR_LIGHT_SPOT = 1, AKR_LIGHT_SUN = 2 } akr_light_type;
+typedef struct {
+    uint32_t type;        /* akr_light_type */
+    float position[3];    /* POINT, SPOT */
+    float direction[3];   /* SPOT, SUN: the way the light points / travels; any length > 0 */
+    float color[3];       /* linear RGB in the scene's RGB colour space, >= 0 */
+    float strength;       /* >= 0 */
+    float cone_angle;     /* SPOT: outer half-angle, radians, in (0, pi/2] */
+    float blend;          /* SPOT: in [0, 1] */
+} akr_punctual_light_desc;
+/* Appends a light / removes them all. Refused while a session holds the scene; AKR_ERR_INVALID_ARGUMENT for an unknown type, a zero or
+ * non-finite direction, non-finite or negative values, a cone_angle or blend out of range. */
+AKR_API int32_t akr_scene_add_punctual_light(akr_scene *scene, const akr_punctual_light_desc *desc);
+AKR_API int32_t akr_scene_clear_punctual_lights(akr_scene *scene);
+/* The lights the scene holds (those that were "no light" are not among them), as given. */
+AKR_API int32_t akr_scene_punctual_light_count(const akr_scene *scene, uint32_t *count);
+AKR_API int32_t akr_scene_get_punctual_light(const akr_scene *scene, uint32_t index, akr_punctual_light_desc *out);
 /* Thin lens of the scene's camera (pt and aov integrators): depth of field. A camera ray starts at a point of a disk of
  * `radius` around the camera position, in the camera's x / y plane, and passes through the point where the pinhole ray of the same film
  * sample meets the plane of focus, `focal_distance` along the optical axis. The sample weight is the filter's: no vignetting. A host that
@@ -370,7 +398,8 @@ typedef enum {
     AKR_ARRAY_ENV_MARGINAL_PDF = 23,        /* f32[env height] */
     AKR_ARRAY_ENV_CONDITIONAL_ENTRIES = 24, /* {u32 j, f32 t}[env height * env width], row by row */
     AKR_ARRAY_ENV_CONDITIONAL_PDF = 25,     /* f32[env height * env width] */
-    AKR_ARRAY_ENV_TEXELS = 26               /* f32[4 * env width * env height]: what the kernels look up (strength applied) */
+    AKR_ARRAY_ENV_TEXELS = 26,              /* f32[4 * env width * env height]: what the kernels look up (strength applied) */
+    AKR_ARRAY_PUNCTUAL_LIGHTS = 27          /* the punctual lights' folded records (default colour pipeline), 64 B each: csrc/device/dscene.h DPunct */
 } akr_array_id;
 AKR_API int32_t akr_scene_get_array(const akr_scene *scene, int32_t which, const void **ptr, uint64_t *bytes);
 
@@ -482,7 +511,7 @@ typedef struct {
     uint32_t absent_mask;     /* lobes no material of the scene can have: 1 coat, 2 transmission, 4 normal map, 8 glass, 16 conductor */
     uint32_t min_waves;       /* waves per SIMD the kernel was compiled for */
     uint32_t vgprs, scratch_bytes;
-    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features) */
+    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features), 7 samples punctual lights (the PUNCT kernels; akr_scene_add_punctual_light) */
     uint32_t _pad;
     double compile_ms;        /* hiprtc compile at akr_pt_begin (0 on a cache hit) */
     double load_ms;           /* cache lookup + module load */
@@ -787,7 +816,9 @@ typedef enum {
     /* (18 stays unknown: callers of earlier versions probe it as the first id past the list) */
     AKR_STRUCT_ADAPTIVE_CONFIG = 19, AKR_STRUCT_ADAPTIVE_STATS,
     /* (21 stays unknown for the same reason) */
-    AKR_STRUCT_DISPLAY_CONFIG = 22
+    AKR_STRUCT_DISPLAY_CONFIG = 22,
+    /* (23 stays unknown for the same reason) */
+    AKR_STRUCT_PUNCTUAL_LIGHT_DESC = 24
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
@@ -830,6 +861,8 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *   "lens"         (AKR_LENS=1)             akr_scene_load: 1 = the camera gets the thin lens of the file's focal_distance and fstop, radius =
  *                                           focal_distance / (2 fstop) (load.rs:177-179); 0 (default) = a pinhole, which is how the reference
  *                                           renders every file -- its exporter writes the pair whether or not depth of field is on
+ *   "punctual_lights" (AKR_PUNCTUAL_LIGHTS=0)  akr_scene_load: 1 (default) = the file's point, spot and sun lights light the scene; 0 = they are dropped,
+ *                                           which is how the reference renders every file (its lights collection has no implementation)
  *   "denoise"      (AKR_DENOISE=n)          akr_render_task: n > 0 = after a `pt` task has written film.out, albedo and ns are rendered with the aov
  *                                           integrator at n spp (the task's sampler, seed, filter and colour pipeline), akr_denoise runs with its
  *                                           default configuration and "{stem}.denoised{ext}" is written next to film.out; 0 (default) = off. Other

@@ -94,6 +94,16 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context *ctx, akr_scene *scene, ui
 
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context *ctx, akr_scene *scene, uint32_t n, const float *dirs3, float *out4);
 
+/* Next-event estimation of a scene with punctual lights (csrc/device/dpunct.h; default colour pipeline) for n rows
+ * rows7 = p.xyz, n.xyz (the surface point and its geometric normal), u_select: the light the alias table picks and, if it is a punctual one, its sample.
+ * out13 = li.rgb, wi.xyz, pdf, ro.xyz, tmax, valid, delta (the last two 0 or 1); light = the index chosen. A choice of an emissive instance or
+ * of the environment comes back with pdf = its selection probability and everything else 0.
+ *   akr_host_light_sample    the shared text on the host (no GPU; works on a host-only scene)
+ *   akr_probe_light_sample   the same through a kernel of one thread per row */
+AKR_TEST_API int32_t akr_host_light_sample(const akr_scene *scene, uint32_t n, const float *rows7, float *out13, uint32_t *light);
+
+AKR_TEST_API int32_t akr_probe_light_sample(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rows7, float *out13, uint32_t *light);
+
 /* The camera ray of the scene's camera and lens (csrc/device/dpath.h generate_ray_from / generate_ray_lens_from) for n items:
  * pixels2 = (x, y) as u32, u4 = u_filter.xy, u_lens.xy (u_lens is ignored without a lens), out6 = o.xyz, d.xyz in world space.
  *   akr_host_lens_ray       the shared text on the host (no GPU; works on a host-only scene)
@@ -108,7 +118,7 @@ AKR_TEST_API int32_t akr_probe_camera_rays(akr_context *ctx, akr_scene *scene, u
  * host-only scene): what akr_pt_begin decides, without the session. The options are the process-wide ones a session snapshots when it
  * begins (defer_metal -1 = the library decides, simple_kernels, defer_on); spec_waves = 0: no per-scene kernel, else the per-scene kernel
  * of that many waves per SIMD is taken to have compiled (where the session would ask for one: texture-fed materials, no force_diffuse).
- *   variant[10]     the instantiation: bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens
+ *   variant[10]     the instantiation: bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens; punct (the struct's last field): the PUNCT kernels
  *   simple_scene .. stage_total, tile_offset .. val_offset_words   the fields of the kernel parameter block of the same names
  *   lds_bytes, blocks   dynamic LDS and workgroups of a launch
  *   specialised     1 = a per-scene kernel; wrapper is then the text that instantiates it (part of the kernel cache's key), else "" */
@@ -120,6 +130,7 @@ typedef struct akr_pt_launch_plan {
     uint32_t lds_bytes, blocks;
     uint32_t specialised;
     char wrapper[600];
+    uint32_t punct;
 } akr_pt_launch_plan;
 AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
                                         int32_t spec_waves, akr_pt_launch_plan *out);
