@@ -111,9 +111,9 @@ LIGHT_POINT, LIGHT_SPOT, LIGHT_SUN = 0, 1, 2  # akr_light_type
 
 
 class PunctualLightDesc(C.Structure):
-    """akr_punctual_light_desc: a point, spot or sun light (DESIGN.md 4.14)."""
+    """akr_punctual_light_desc: a point, spot or sun light (DESIGN.md 4.14, 4.15)."""
     _fields_ = [("type", C.c_uint32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("color", C.c_float * 3), ("strength", C.c_float),
-                ("cone_angle", C.c_float), ("blend", C.c_float)]
+                ("cone_angle", C.c_float), ("blend", C.c_float), ("radius", C.c_float), ("angle", C.c_float)]
 
 
 class LensDesc(C.Structure):
@@ -601,7 +601,8 @@ class EnvironmentData:
 class PunctualLightData:
     """A point, spot or sun light of a scene (akr_punctual_light_desc): `type` LIGHT_POINT / LIGHT_SPOT / LIGHT_SUN, `position` (point, spot), `direction` the
     light points / travels along (spot, sun), `color` x `strength` = radiant intensity (point, spot) or irradiance (sun), `cone_angle` = the spot's outer
-    HALF-angle in radians, `blend` in [0, 1] the part of it over which the light falls off."""
+    HALF-angle in radians, `blend` in [0, 1] the part of it over which the light falls off; `radius` (point, spot) the radius of the emitting disk and
+    `angle` (sun) the FULL angular diameter in radians -- soft shadows; 0, the default, is a delta light."""
     type: int
     position: tuple = (0.0, 0.0, 0.0)
     direction: tuple = (0.0, 0.0, 0.0)
@@ -609,6 +610,8 @@ class PunctualLightData:
     strength: float = 1.0
     cone_angle: float = 0.0
     blend: float = 0.0
+    radius: float = 0.0
+    angle: float = 0.0
 
     def to_desc(self) -> PunctualLightDesc:
         d = PunctualLightDesc()
@@ -616,12 +619,13 @@ class PunctualLightData:
         for k in range(3):
             d.position[k], d.direction[k], d.color[k] = float(self.position[k]), float(self.direction[k]), float(self.color[k])
         d.strength, d.cone_angle, d.blend = float(self.strength), float(self.cone_angle), float(self.blend)
+        d.radius, d.angle = float(self.radius), float(self.angle)
         return d
 
     @staticmethod
     def from_desc(d: PunctualLightDesc) -> "PunctualLightData":
         return PunctualLightData(int(d.type), tuple(float(v) for v in d.position), tuple(float(v) for v in d.direction), tuple(float(v) for v in d.color),
-                                 float(d.strength), float(d.cone_angle), float(d.blend))
+                                 float(d.strength), float(d.cone_angle), float(d.blend), float(d.radius), float(d.angle))
 
 
 @dataclass

@@ -63,7 +63,7 @@ TEST_EXPORTS = [
     "akr_host_tile_error", "akr_host_half_bracket", "akr_probe_adapt_times",
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
     "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
-    "akr_host_light_sample", "akr_probe_light_sample",
+    "akr_host_light_sample", "akr_probe_light_sample", "akr_host_light_sample_soft", "akr_probe_light_sample_soft",
 ]
 
 
@@ -135,6 +135,8 @@ def lib() -> C.CDLL:
     proto("akr_scene_get_punctual_light", vp, u32, C.POINTER(abi.PunctualLightDesc))
     proto("akr_host_light_sample", vp, u32, fp, fp, up)
     proto("akr_probe_light_sample", vp, vp, u32, fp, fp, up)
+    proto("akr_host_light_sample_soft", vp, u32, fp, fp, up)
+    proto("akr_probe_light_sample_soft", vp, vp, u32, fp, fp, up)
     proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
     proto("akr_host_pt_launch_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, C.POINTER(abi.PtLaunchPlan))
@@ -407,8 +409,8 @@ class Scene:
         return abi.EnvironmentData(color=tuple(float(c) for c in d.color), strength=float(d.strength), rotation=rot)
 
     def add_punctual_light(self, light: Optional[abi.PunctualLightData] = None, **fields):
-        """akr_scene_add_punctual_light: appends a point, spot or sun light (an abi.PunctualLightData, or its fields as keywords). A light of strength 0 or
-        an all-zero colour is accepted and not added."""
+        """akr_scene_add_punctual_light: appends a point, spot or sun light (an abi.PunctualLightData, or its fields as keywords, `radius=` and `angle=`
+        among them: soft shadows). A light of strength 0 or an all-zero colour is accepted and not added."""
         if light is None:
             light = abi.PunctualLightData(**fields)
         d = light.to_desc()
@@ -429,8 +431,8 @@ class Scene:
             out.append(abi.PunctualLightData.from_desc(d))
         return out
 
-    def _light_sample(self, fn, head, rows):
-        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 7)
+    def _light_sample(self, fn, head, rows, cols=7):
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, cols)
         n = rows.shape[0]
         out, light = np.zeros((n, 13), np.float32), np.zeros(n, np.uint32)
         check(fn(*head, n, _fp(rows), _fp(out), _up(light)))
@@ -443,6 +445,15 @@ class Scene:
     def probe_light_sample(self, rows):
         """akr_probe_light_sample (test hook): the same on the device."""
         return self._light_sample(lib().akr_probe_light_sample, (self.ctx.h, self.h), rows)
+
+    def host_light_sample_soft(self, rows):
+        """akr_host_light_sample_soft (test hook, no GPU): rows (n, 9) = p, n, u_select, u_sample -> the same pair; a light with a size draws its point
+        from u_sample."""
+        return self._light_sample(lib().akr_host_light_sample_soft, (self.h,), rows, 9)
+
+    def probe_light_sample_soft(self, rows):
+        """akr_probe_light_sample_soft (test hook): the same on the device."""
+        return self._light_sample(lib().akr_probe_light_sample_soft, (self.ctx.h, self.h), rows, 9)
 
     def set_lens(self, radius: Optional[float] = None, focal_distance: float = 0.0):
         """akr_scene_set_lens: a thin lens of `radius`, focused `focal_distance` along the optical axis. radius None or 0: removes the lens."""

@@ -12,6 +12,23 @@ AKR_HD vec2 uniform_sample_disk(vec2 u) {  // sampling.rs:5-9 (polar)
     sincos_f(phi, s, c);
     return mk2(r * c, r * s);
 }
+// Shirley-Chiu, unit square -> unit disk: the thin lens (dpath.h generate_ray_lens_from) and the soft point / spot lights (dpunct.h)
+AKR_HD vec2 concentric_disk(vec2 u) {
+    const float sx = 2.0f * u.x - 1.0f, sy = 2.0f * u.y - 1.0f;
+    if (sx == 0.0f && sy == 0.0f) return mk2(0.0f, 0.0f);
+    const float kPiOver4 = 0.785398163397448310f, kPiOver2 = 1.570796326794896619f;
+    float r, theta;
+    if (abs_f(sx) > abs_f(sy)) {
+        r = sx;
+        theta = kPiOver4 * (sy / sx);
+    } else {
+        r = sy;
+        theta = kPiOver2 - kPiOver4 * (sx / sy);
+    }
+    float sn, cs;
+    sincos_f(theta, sn, cs);
+    return mk2(r * cs, r * sn);
+}
 AKR_HD vec3 cos_sample_hemisphere(vec2 u) {  // sampling.rs:17-21
     vec2 d = uniform_sample_disk(u);
     float z = __builtin_sqrtf(max_f(1.0f - d.x * d.x - d.y * d.y, 0.0f));

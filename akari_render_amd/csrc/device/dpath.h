@@ -218,23 +218,7 @@ AKR_HD void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 
     }
 }
 // The thin lens (the reference stores lens_radius and focal_length in PerspectiveCameraData, camera/mod.rs:105-118,
-// and leaves them unused). concentric_disk: Shirley-Chiu, unit square -> unit disk.
-AKR_HD vec2 concentric_disk(vec2 u) {
-    const float sx = 2.0f * u.x - 1.0f, sy = 2.0f * u.y - 1.0f;
-    if (sx == 0.0f && sy == 0.0f) return mk2(0.0f, 0.0f);
-    const float kPiOver4 = 0.785398163397448310f, kPiOver2 = 1.570796326794896619f;
-    float r, theta;
-    if (abs_f(sx) > abs_f(sy)) {
-        r = sx;
-        theta = kPiOver4 * (sy / sx);
-    } else {
-        r = sy;
-        theta = kPiOver2 - kPiOver4 * (sx / sy);
-    }
-    float sn, cs;
-    sincos_f(theta, sn, cs);
-    return mk2(r * cs, r * sn);
-}
+// and leaves them unused). The lens point comes from dgeom.h concentric_disk.
 // generate_ray_from with a lens of radius p.lens_radius > 0 focused at distance p.lens_focal along the optical axis: the pinhole
 // direction dc in camera space meets the plane of focus at dc * ft; the ray leaves the lens point l towards that point.
 AKR_HD void generate_ray_lens_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& o, vec3& d) {
@@ -304,7 +288,8 @@ struct LightSample {
 // ENV: the scene has an environment light, the last entry of the light table (denv.h); a choice of it draws its direction from the
 // environment's tables with the u_sample a triangle would use -- no dimension more -- and its shadow ray is an unbounded one.
 // PUNCT: the scene has punctual lights, entries of the light table whose LightRec says kPunctInst (dpunct.h); a choice of
-// one consumes u_select as every choice does and ignores u_sample.
+// one consumes u_select as every choice does; a delta light ignores u_sample, a soft one (a radius, an angle: section 4.15) draws its point from it -- no
+// dimension more.
 template <bool TEX, bool INST = false, bool ENV = false, bool PUNCT = false>
 AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_select, vec2 u_sample, uint32_t color = 0) {
     LightSample s;
@@ -335,7 +320,7 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
     }
     const LightRec L = sc.lights[light];
     if (PUNCT && L.inst == kPunctInst) {
-        const PunctSample ps = punct_sample(sc.punct[L.first_gid], pn_p, pn_n);
+        const PunctSample ps = punct_sample(sc.punct[L.first_gid], pn_p, pn_n, u_sample, (sc.n_punct & kPunctSoftBit) != 0);
         s.li = ps.li;
         s.wi = ps.wi;
         s.ro = ps.ro;

@@ -71,7 +71,7 @@ struct DEnv {
     uint32_t w, h, filter, light;               // light: the environment's entry in the light table (the last one)
 };
 
-// A punctual light (host/scene_punct.cpp folds it, device/dpunct.h samples it): a point or spot light at q, or a sun whose light
+// A punctual light (DESIGN.md sections 4.14 and 4.15; host/scene_punct.cpp folds it, device/dpunct.h samples it): a point or spot light at q, or a sun whose light
 // travels along a. One 64-byte record in HBM, read by the PUNCT kernels only. Its entry in the light table is a LightRec with inst = kPunctInst and
 // first_gid = the record's index.
 enum : uint32_t { PUNCT_POINT = 0, PUNCT_SPOT = 1, PUNCT_SUN = 2 };
@@ -81,9 +81,15 @@ struct DPunct {
     vec3 a;       float cos_o;      // unit axis / direction of travel (SPOT, SUN); cosine of the outer half-angle
     vec3 c;       float cos_i;      // colour x strength in the session's colour pipeline; cosine of the inner half-angle
     float inv_span;                 // 1 / (cos_i - cos_o), 0 = the step falloff
-    uint32_t _pad[3];
+    // the soft size (section 4.15), in what was padding: zeros = a delta light, which takes the code it always took
+    float radius;                   // POINT, SPOT: radius of the emitting disk at q that faces the shading point
+    float cos_max;                  // SUN: cosine of half the angular diameter
+    float k;                        // SUN: 2 / (1 + cos_max), radiance over the cap's pdf per unit of c
 };
 static_assert(sizeof(DPunct) == 64, "DPunct layout");
+// DScene.n_punct: the number of records in its low bits and, in its top bit, "one of them has a size". The same for every lane of a launch: a scene of delta
+// lights branches around the soft sampling text on a scalar (section 4.15, cost).
+constexpr uint32_t kPunctSoftBit = 0x80000000u;
 
 struct DScene {
     const float4* __restrict__ woop;        // 3 float4 per triangle (exhaustive path) or 4 (BVH path: + global id)
@@ -115,7 +121,7 @@ struct DScene {
     DInst in2;                                      // meshes + instances kept as they are (in2.on; else all zero)
     // The punctual lights (DPunct above), or nullptr: a scene with some runs the PUNCT kernels. Last: everything before keeps its offset.
     const DPunct* __restrict__ punct;
-    uint32_t n_punct, _pad_punct;
+    uint32_t n_punct, _pad_punct;                   // n_punct: count | kPunctSoftBit
 };
 
 struct SurfacePoint {  // interaction.rs:15-48, minus what this path never reads

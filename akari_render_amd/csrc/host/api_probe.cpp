@@ -238,23 +238,36 @@ AKR_TEST_API int32_t akr_probe_env_sample(akr_context* ctx, akr_scene* scene, ui
 AKR_TEST_API int32_t akr_probe_env_pdf(akr_context* ctx, akr_scene* scene, uint32_t n, const float* dirs3, float* out4) {
     return probe_env(ctx, scene, 1, n, dirs3, out4, "akr_probe_env_pdf");
 }
-// next-event estimation with punctual lights (device/dpunct.h): the selection and the lights' branch of sample_direct, row by row
-AKR_TEST_API int32_t akr_host_light_sample(const akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
-    if (!scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_light_sample: NULL argument");
+// next-event estimation with punctual lights (device/dpunct.h): the selection and the lights' branch of sample_direct, row by row.
+// The seven-column hooks are the nine-column ones with u_sample = (0.5, 0.5).
+static std::vector<float> rows9_of_rows7(uint32_t n, const float* rows7) {
+    std::vector<float> r(9ull * n);
+    for (uint32_t i = 0; i < n; i++) {
+        for (int k = 0; k < 7; k++) r[9ull * i + k] = rows7[7ull * i + k];
+        r[9ull * i + 7] = r[9ull * i + 8] = 0.5f;
+    }
+    return r;
+}
+AKR_TEST_API int32_t akr_host_light_sample_soft(const akr_scene* scene, uint32_t n, const float* rows9, float* out13, uint32_t* light) {
+    if (!scene || !rows9 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_light_sample_soft: NULL argument");
     return guarded([&] {
         std::vector<AliasPacked> la, aa;
         std::vector<LightRec> lr;
         packed_light_tables(scene->cs, la, aa, lr);
-        for (uint32_t i = 0; i < n; i++) punct_probe_row(la.data(), lr.data(), scene->cs.punct.data(), scene->cs.n_lights, rows7 + 7ull * i, out13 + 13ull * i, light + i);
+        for (uint32_t i = 0; i < n; i++) punct_probe_row(la.data(), lr.data(), scene->cs.punct.data(), scene->cs.n_lights, rows9 + 9ull * i, out13 + 13ull * i, light + i);
     });
 }
-AKR_TEST_API int32_t akr_probe_light_sample(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
-    if (!ctx || !scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: NULL argument");
-    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: the scene was not created on this context");
+AKR_TEST_API int32_t akr_host_light_sample(const akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
+    if (!scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_light_sample: NULL argument");
+    return akr_host_light_sample_soft(scene, n, rows9_of_rows7(n, rows7).data(), out13, light);
+}
+AKR_TEST_API int32_t akr_probe_light_sample_soft(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rows9, float* out13, uint32_t* light) {
+    if (!ctx || !scene || !rows9 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample_soft: NULL argument");
+    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample_soft: the scene was not created on this context");
     return guarded([&] {
         ctx->bind();
         DevBuf din, dout, dl;
-        din.upload(std::vector<float>(rows7, rows7 + 7ull * n));
+        din.upload(std::vector<float>(rows9, rows9 + 9ull * n));
         dout.alloc(13ull * n * 4);
         dl.alloc(4ull * n);
         if (n) HIP_CHECK(launch_probe_light_sample(probe_params(scene), n, din.as<float>(), dout.as<float>(), dl.as<uint32_t>(), ctx->stream));
@@ -264,6 +277,10 @@ AKR_TEST_API int32_t akr_probe_light_sample(akr_context* ctx, akr_scene* scene, 
             HIP_CHECK(hipMemcpy(light, dl.p, 4ull * n, hipMemcpyDeviceToHost));
         }
     });
+}
+AKR_TEST_API int32_t akr_probe_light_sample(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rows7, float* out13, uint32_t* light) {
+    if (!ctx || !scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: NULL argument");
+    return akr_probe_light_sample_soft(ctx, scene, n, rows9_of_rows7(n, rows7).data(), out13, light);
 }
 // the camera's ray generation (device/dpath.h): the parameter block's camera part, filled by the sessions' own function
 static PtParams probe_camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {

@@ -112,6 +112,8 @@ static void upload_lights(akr_scene* s) {
     d.env = cs.env.on ? s->env_rec.as<DEnv>() : nullptr;
     d.punct = s->punct.as<DPunct>();
     d.n_punct = (uint32_t)cs.punct.size();
+    for (const DPunct& r : cs.punct)  // (the size is not a matter of the colour pipeline: the colour sets' records have it where these do)
+        if (r.radius != 0.0f || r.cos_max != 0.0f) d.n_punct |= kPunctSoftBit;
 }
 static void count_device_bytes(akr_scene* s) {
     s->device_bytes = 0;

@@ -1,12 +1,13 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
+//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
 //             [--adaptive [X]] [--adaptive-min-spp N] [--display [linear|reinhard|aces|hable]] [--exposure EV] [--auto-exposure] [--bloom [X]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
 // with the independent sampler and the same seed. --depth-of-field (no reference counterpart: its camera ignores the lens it loads) renders
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 // --no-punctual-lights (library option "punctual_lights" = 0): the scene file's point, spot and sun lights are dropped, which is how the reference renders it.
+// --no-soft-lights (library option "soft_lights" = 0): the file's lights are loaded with radius 0 and angle 0, so every shadow they cast has a hard edge.
 // --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
 // --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
 // --denoise-features (library option "denoise_features"; implies the denoise step): the filter's albedo / normal guides are collected by the pt task's own samples,
@@ -28,7 +29,7 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler] [--no-punctual-lights] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
               "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
               "                 [--display [linear|reinhard|aces|hable]] [--exposure <EV>] [--auto-exposure] [--bloom [<X>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
@@ -38,6 +39,7 @@ static void usage() {
               "      --save-intermediate  write {name}-{spp}.exr after every pass\n"
               "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files\n"
               "      --no-punctual-lights drop the scene file's point, spot and sun lights (default: they light the scene)\n"
+              "      --no-soft-lights     load the scene file's lights with radius 0 and angle 0: hard shadows (default: soft shadows where the file gives a size)\n"
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
               "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
@@ -70,7 +72,7 @@ int main(int argc, char** argv) {
     std::string scene, method, name;
     int device = 0, verbose = 0, save_intermediate = 0, save_stats = 0, indep = 0;
     unsigned w = 0, h = 0;
-    int dof = 0, no_punctual = 0;
+    int dof = 0, no_punctual = 0, no_soft = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
     int denoise = 0, denoise_variance = 0, denoise_features = 0;
     int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
@@ -87,6 +89,7 @@ int main(int argc, char** argv) {
         else if (a == "--independent-sampler") indep = 1;
         else if (a == "--depth-of-field") dof = 1;
         else if (a == "--no-punctual-lights") no_punctual = 1;
+        else if (a == "--no-soft-lights") no_soft = 1;
         else if (a == "--denoise") {  // the number is optional: taken only if the next argument is one
             denoise = 16;
             if (i + 1 < argc) {
@@ -184,6 +187,7 @@ int main(int argc, char** argv) {
     if (akr_context_create(device, &ctx) != AKR_OK) die("device");
     if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
     if (no_punctual && akr_option_set("punctual_lights", 0) != AKR_OK) die("option punctual_lights");
+    if (no_soft && akr_option_set("soft_lights", 0) != AKR_OK) die("option soft_lights");
     if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
     if (denoise_features && akr_option_set("denoise_features", 1) != AKR_OK) die("option denoise_features");
     if (denoise_variance && !denoise && !denoise_features) { std::fputs("akari-cli: --denoise-variance needs --denoise or --denoise-features\n", stderr); return 1; }

@@ -232,6 +232,7 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   pad_percent  (no environment hook)    test hook: box padding in percent of the derived value (100)
 //   lens         AKR_LENS=1               akr_scene_load gives the camera the thin lens of the file's focal_distance and fstop (the reference reads both and renders a pinhole)
 //   punctual_lights AKR_PUNCTUAL_LIGHTS=0 akr_scene_load drops the file's point / spot / sun lights (the reference's lights collection has no implementation)
+//   soft_lights  AKR_SOFT_LIGHTS=0        akr_scene_load loads every light with radius 0 and angle 0: delta lights, hard shadows
 //   wf_sort      AKR_WF_SORT=1            wavefront schedule: ray queues sorted by origin cell + direction octant before each trace launch
 //   wf_groups    AKR_WF_GROUPS=<g>        wavefront schedule: the slots run as g groups with queues and streams of their own (api_pt.cpp wf_run); 0 = the library decides
 //   wf_carry     AKR_WF_CARRY=0           wavefront schedule: 0 = every trace launch traces its rays to the end (1, default: a wave that finds the queue empty and
@@ -266,6 +267,7 @@ struct TuningOptions {
     int sched_trial = -1;  // flattened scenes under option wavefront = -1: a timed trial of both schedules at the start of a long render (api_pt.cpp schedule_trial):
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
     int punctual_lights = 1;  // akr_scene_load: 1 = the file's point / spot / sun lights light the scene; 0 = dropped, as the reference renders every file
+    int soft_lights = 1;  // akr_scene_load: 1 = the file's lights keep their radius / angle; 0 = every light is loaded as a delta light
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
     int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise

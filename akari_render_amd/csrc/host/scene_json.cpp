@@ -539,7 +539,7 @@ FlatScene load_scene_json(const std::string& path) {
         flat.env = environment_from_desc(d);
     }
     if (scene.has("lights") && tuning().punctual_lights != 0) {
-        // optional punctual lights: {name: {"type": "point" | "spot" | "sun", "data": {position, direction, color, strength, spot_size, spot_blend}}}. An entry
+        // optional punctual lights: {name: {"type": "point" | "spot" | "sun", "data": {position, direction, color, strength, spot_size, spot_blend, radius (point, spot), angle (sun)}}}. An entry
         // whose data is empty is the reference's own `Light::Point(PointLight {})` (akari_scenegraph/src/scene.rs), which lights nothing: ignored.
         for (const auto& kv : scene.at("lights").obj) {
             const JsonValue& lj = *kv.second;
@@ -562,6 +562,10 @@ FlatScene load_scene_json(const std::string& path) {
                 if (d.type == AKR_LIGHT_SPOT) {
                     d.cone_angle = dj.at("spot_size").as_f32() * 0.5f;  // spot_size is the full cone angle
                     d.blend = dj.has("spot_blend") ? dj.at("spot_blend").as_f32() : 0.0f;
+                }
+                if (tuning().soft_lights != 0) {  // the soft size; option soft_lights = 0: every light a delta light
+                    if (d.type != AKR_LIGHT_SUN && dj.has("radius")) d.radius = dj.at("radius").as_f32();
+                    if (d.type == AKR_LIGHT_SUN && dj.has("angle")) d.angle = dj.at("angle").as_f32();
                 }
                 akr_punctual_light_desc checked;
                 if (punctual_from_desc(d, checked)) flat.punct.push_back(checked);

@@ -1,4 +1,4 @@
-// scene_punct.cpp -- the punctual lights on the host: the description checked, the 64-byte record the kernels read
+// scene_punct.cpp -- the punctual lights on the host (DESIGN.md sections 4.14 and 4.15): the description checked, the 64-byte record the kernels read
 // (device/dscene.h DPunct; folded in double, each value rounded once) and the lights' entries in the light table, between the emissive instances and
 // the environment.
 #include <cmath>
@@ -42,11 +42,16 @@ bool punctual_from_desc(const akr_punctual_light_desc& d, akr_punctual_light_des
         if (!std::isfinite(d.cone_angle) || !(d.cone_angle > 0.0f) || d.cone_angle > 1.57079637f) throw std::invalid_argument(who + "cone_angle (the outer half-angle) must be in (0, pi/2]");
         if (!std::isfinite(d.blend) || d.blend < 0.0f || d.blend > 1.0f) throw std::invalid_argument(who + "blend must be in [0, 1]");
     }
+    // the soft size (section 4.15): a radius of a point / spot light, the full angular diameter of a sun; what the kind does not read is not looked at
+    if (d.type != AKR_LIGHT_SUN && (!std::isfinite(d.radius) || d.radius < 0.0f)) throw std::invalid_argument(who + "radius must be finite and >= 0");
+    if (d.type == AKR_LIGHT_SUN && (!std::isfinite(d.angle) || d.angle < 0.0f || (double)d.angle >= M_PI)) throw std::invalid_argument(who + "angle (the full angular diameter) must be in [0, pi)");
     out = d;
     // what the kind does not read is stored as zero: two descriptions of the same light compare equal
     if (d.type == AKR_LIGHT_SUN) out.position[0] = out.position[1] = out.position[2] = 0.0f;
     if (d.type == AKR_LIGHT_POINT) out.direction[0] = out.direction[1] = out.direction[2] = 0.0f;
     if (d.type != AKR_LIGHT_SPOT) out.cone_angle = out.blend = 0.0f;
+    if (d.type == AKR_LIGHT_SUN || d.radius == 0.0f) out.radius = 0.0f;  // (and a -0 becomes the +0 whose bits say "delta")
+    if (d.type != AKR_LIGHT_SUN || d.angle == 0.0f) out.angle = 0.0f;
     return any && d.strength > 0.0f;  // a strength of 0 or an all-zero colour: no light, as for the environment
 }
 
@@ -64,6 +69,14 @@ DPunct fold_punctual(const akr_punctual_light_desc& d, uint32_t color) {
         r.cos_o = (float)std::cos((double)d.cone_angle);
         r.cos_i = (float)std::cos((double)d.cone_angle * (1.0 - (double)d.blend));
         r.inv_span = r.cos_i == r.cos_o ? 0.0f : 1.0f / (r.cos_i - r.cos_o);
+    }
+    // the soft size: zeros (a delta light) unless the light has one. cos_max > 0 for every angle < pi, so 0 can say "no angle".
+    if (d.type != AKR_LIGHT_SUN) {
+        r.radius = d.radius;
+    } else if (d.angle > 0.0f) {
+        const double cm = std::cos(0.5 * (double)d.angle);
+        r.cos_max = (float)cm;
+        r.k = (float)(2.0 / (1.0 + cm));
     }
     // colour x strength, then the way of an Emission material's constant colour into the session's pipeline (dbsdf.h convert_color_inputs: here, on the host)
     r.c = color_input(mk3(d.color[0] * d.strength, d.color[1] * d.strength, d.color[2] * d.strength), false, color);

@@ -291,7 +291,7 @@ inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds
 #if !defined(__HIPCC_RTC__)
 hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_inst_kernels.hip: once per kept scene (DInst::share_bits)
 hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
-hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows7, float* out13, uint32_t* light, hipStream_t stream);  // pt_punct_kernels.hip: test hook
+hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, hipStream_t stream);  // pt_punct_kernels.hip: test hook
 // pt_lens_kernels.hip, test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
 hipError_t launch_probe_camera_rays(const PtParams& p, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6, hipStream_t stream);
 // One pass launch of a pt session: lays the LDS out (pt_lds_layout) and goes to the translation unit that holds the variant's kernel

@@ -42,7 +42,7 @@ template <bool ENV, bool LENS, bool FEAT = false, bool PUNCT = false>
 hipError_t pt_pass_entry_t(const PtParams& q, const PtVariant& v, uint32_t blocks, size_t lds, hipStream_t stream) {
     if (v.inst || v.env != ENV || v.lens != LENS || v.feat != FEAT || v.punct != PUNCT || !pt_variant_compiled(v)) return hipErrorInvalidValue;
     if (FEAT && (q.feat_albedo == nullptr || q.feat_normal == nullptr)) return hipErrorInvalidValue;
-    if (PUNCT && (q.sc.punct == nullptr || q.sc.n_punct == 0)) return hipErrorInvalidValue;
+    if (PUNCT && (q.sc.punct == nullptr || (q.sc.n_punct & ~kPunctSoftBit) == 0)) return hipErrorInvalidValue;
     dispatch_bools([&](auto B, auto F, auto T, auto P, auto S, auto D, auto X) {
         if constexpr (pt_variant_compiled(PtVariant{B(), F(), T(), P(), S(), D(), X(), false, ENV, LENS, FEAT, PUNCT}))
             launch_kernel<true>(k_pt_pass<B(), F(), T(), P(), S(), D(), X(), ENV, LENS, FEAT, PUNCT>, blocks, lds, stream, q);

@@ -8,14 +8,14 @@ hipError_t pt_pass_entry_punct(const PtParams& q, const PtVariant& v, uint32_t b
 
 // ---------------------------------------------------------------------------------------------------- test hook
 __global__ void k_probe_light_sample(const AliasPacked* __restrict__ light_alias, const LightRec* __restrict__ lights, const DPunct* __restrict__ punct, uint32_t n_lights, uint32_t n,
-                                     const float* __restrict__ rows7, float* __restrict__ out13, uint32_t* __restrict__ light) {
+                                     const float* __restrict__ rows9, float* __restrict__ out13, uint32_t* __restrict__ light) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    punct_probe_row(light_alias, lights, punct, n_lights, rows7 + 7 * (size_t)i, out13 + 13 * (size_t)i, light + i);
+    punct_probe_row(light_alias, lights, punct, n_lights, rows9 + 9 * (size_t)i, out13 + 13 * (size_t)i, light + i);
 }
-hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows7, float* out13, uint32_t* light, hipStream_t stream) {
+hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_probe_light_sample, dim3((n + 255) / 256), dim3(256), 0, stream, p.sc.light_alias, p.sc.lights, p.sc.punct, p.sc.n_lights, n, rows7, out13, light);
+    hipLaunchKernelGGL(k_probe_light_sample, dim3((n + 255) / 256), dim3(256), 0, stream, p.sc.light_alias, p.sc.lights, p.sc.punct, p.sc.n_lights, n, rows9, out13, light);
     return hipGetLastError();
 }
 

@@ -307,9 +307,13 @@ AKR_API int32_t akr_scene_set_environment(akr_scene *scene, const akr_environmen
 /* The environment as decoded (texels owned by the scene); width = height = 0 and strength = 0 when there is none. A constant
  * colour comes back as width = height = 0 with its colour. */
 AKR_API int32_t akr_scene_get_environment(const akr_scene *scene, akr_environment_desc *out);
-/* Punctual lights of a scene (pt integrator): point, spot and sun lights, sampled by next-event estimation. All three are delta
- * lights -- no radius, no angular size, hard shadows -- and invisible: no camera or BSDF-sampled ray ever hits one, so a render with use_nee = 0 gets
- * nothing from them, and aov renders the scene as if they were not there.
+/* Punctual lights of a scene (pt integrator): point, spot and sun lights, sampled by next-event estimation. Without a size
+ * (radius = 0, angle = 0) they are delta lights with hard shadows. With one they cast soft shadows: a point or spot light of `radius` > 0 is a
+ * uniformly emitting disk of that radius at `position` that faces the point it lights, Li = I cos / dist^2 towards a point drawn on it (I / dist^2 as
+ * radius -> 0); a sun of `angle` > 0 is a uniformly radiant cap of directions of that FULL angular diameter around -direction, which still gives a
+ * surface facing it the irradiance E. With or without a size they are invisible: no camera or BSDF-sampled ray ever hits one, so a render with
+ * use_nee = 0 gets nothing from them, a mirror shows no highlight of them, and aov renders the scene as if they were not there. A radius given to a
+ * sun and an angle given to a point or spot light are ignored and read back as 0.
  *   AKR_LIGHT_POINT  at `position`; color x strength = radiant intensity I per channel (W/sr in the units emission uses): Li = I / dist^2
  *   AKR_LIGHT_SPOT   at `position`, pointing along `direction`; cone_angle = the cone's outer HALF-angle in (0, pi/2]; blend in [0, 1] = the part of
  *                    that angle over which the light falls off, smoothstep in the cosine (0 = a hard edge): Li = I f / dist^2
@@ -327,9 +331,11 @@ typedef struct {
     float strength;       /* >= 0 */
     float cone_angle;     /* SPOT: outer half-angle, radians, in (0, pi/2] */
     float blend;          /* SPOT: in [0, 1] */
+    float radius;         /* POINT, SPOT: >= 0; 0 = a delta light (hard shadows) */
+    float angle;          /* SUN: the FULL angular diameter, radians, in [0, pi); 0 = a delta light */
 } akr_punctual_light_desc;
 /* Appends a light / removes them all. Refused while a session holds the scene; AKR_ERR_INVALID_ARGUMENT for an unknown type, a zero or
- * non-finite direction, non-finite or negative values, a cone_angle or blend out of range. */
+ * non-finite direction, non-finite or negative values, a cone_angle or blend out of range, an angle >= pi. */
 AKR_API int32_t akr_scene_add_punctual_light(akr_scene *scene, const akr_punctual_light_desc *desc);
 AKR_API int32_t akr_scene_clear_punctual_lights(akr_scene *scene);
 /* The lights the scene holds (those that were "no light" are not among them), as given. */
@@ -399,7 +405,7 @@ typedef enum {
     AKR_ARRAY_ENV_CONDITIONAL_ENTRIES = 24, /* {u32 j, f32 t}[env height * env width], row by row */
     AKR_ARRAY_ENV_CONDITIONAL_PDF = 25,     /* f32[env height * env width] */
     AKR_ARRAY_ENV_TEXELS = 26,              /* f32[4 * env width * env height]: what the kernels look up (strength applied) */
-    AKR_ARRAY_PUNCTUAL_LIGHTS = 27          /* the punctual lights' folded records (default colour pipeline), 64 B each: csrc/device/dscene.h DPunct */
+    AKR_ARRAY_PUNCTUAL_LIGHTS = 27          /* the punctual lights' folded records (default colour pipeline), 64 B each: csrc/device/dscene.h DPunct (words 13 - 15: radius, cos_max, k) */
 } akr_array_id;
 AKR_API int32_t akr_scene_get_array(const akr_scene *scene, int32_t which, const void **ptr, uint64_t *bytes);
 
@@ -863,6 +869,8 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *                                           renders every file -- its exporter writes the pair whether or not depth of field is on
  *   "punctual_lights" (AKR_PUNCTUAL_LIGHTS=0)  akr_scene_load: 1 (default) = the file's point, spot and sun lights light the scene; 0 = they are dropped,
  *                                           which is how the reference renders every file (its lights collection has no implementation)
+ *   "soft_lights"  (AKR_SOFT_LIGHTS=0)      akr_scene_load: 1 (default) = the file's lights keep their "radius" / "angle" (soft shadows);
+ *                                           0 = every light is loaded with radius 0 and angle 0: the delta lights and hard shadows of 4.14
  *   "denoise"      (AKR_DENOISE=n)          akr_render_task: n > 0 = after a `pt` task has written film.out, albedo and ns are rendered with the aov
  *                                           integrator at n spp (the task's sampler, seed, filter and colour pipeline), akr_denoise runs with its
  *                                           default configuration and "{stem}.denoised{ext}" is written next to film.out; 0 (default) = off. Other

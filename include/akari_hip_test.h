@@ -104,6 +104,12 @@ AKR_TEST_API int32_t akr_host_light_sample(const akr_scene *scene, uint32_t n, c
 
 AKR_TEST_API int32_t akr_probe_light_sample(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rows7, float *out13, uint32_t *light);
 
+/* The same with the two numbers a light with a size draws its point from: rows9 = p.xyz, n.xyz, u_select, u_sample.xy; out13 and
+ * light as above. A delta light ignores u_sample; the two hooks above are these with u_sample = (0.5, 0.5). */
+AKR_TEST_API int32_t akr_host_light_sample_soft(const akr_scene *scene, uint32_t n, const float *rows9, float *out13, uint32_t *light);
+
+AKR_TEST_API int32_t akr_probe_light_sample_soft(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rows9, float *out13, uint32_t *light);
+
 /* The camera ray of the scene's camera and lens (csrc/device/dpath.h generate_ray_from / generate_ray_lens_from) for n items:
  * pixels2 = (x, y) as u32, u4 = u_filter.xy, u_lens.xy (u_lens is ignored without a lens), out6 = o.xyz, d.xyz in world space.
  *   akr_host_lens_ray       the shared text on the host (no GPU; works on a host-only scene)
