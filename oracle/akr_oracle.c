@@ -12,6 +12,8 @@
  *   akari_integrator/src/aov.rs, gpt.rs (+ the shift-mapping branches of pt.rs:329-900), mcmc_opt.rs (+ mcmc.rs,
  *   sampler/mcmc.rs, util/distribution.rs:92-115), sampler/mod.rs:329-700 (pmj02bn; the two tables are handed in by the tests).
  *   The environment light has no reference counterpart (hit_envmap returns zero): or_env.h restates DESIGN.md 4.8.
+ *   Neither have the punctual lights (light/point.rs is a struct and nothing else) nor the thin lens (generate_ray never uses the
+ *   lens fields): or_punct.h restates DESIGN.md 4.14 and 4.15, or_camera_ray below restates 4.9.
  *
  * Parity status: the reference cannot be built or run here (no Rust toolchain; LuisaCompute is an
  * un-vendored path dependency) and its tests hold no numeric fixtures for this path, so
@@ -31,6 +33,7 @@
 #include "or_tex.h"
 #include "or_geom.h"
 #include "or_env.h"
+#include "or_punct.h"
 #include "or_math.h"
 #include "or_rng.h"
 #include <pthread.h>
@@ -82,6 +85,12 @@ typedef struct {
     uint32_t color;              /* ColorPipeline of the render in progress (OR_COLOR_*), set by the render entry points; 0 during
                                   * scene creation: the light tables come from the sRGB pipeline (load.rs:316-319) */
     or_env *env;                 /* the environment light (or_env.h) or NULL; it is light n_lights - 1 */
+    /* the punctual lights (or_punct.h, DESIGN.md 4.14 "Light list"): lights n_emit .. n_emit + n_punct - 1, in the order given,
+     * between the emissive instances and the environment */
+    uint32_t n_emit, n_punct;
+    or_punctual_light_desc *punct_desc; /* as accepted (normalised); those that were "no light" are not among them */
+    or_punct *punct[4];                 /* the folded records per colour pipeline (index = the OR_COLOR_* bits) */
+    float lens_radius, lens_focal;      /* the thin lens; radius 0 = the pinhole */
 } or_scene;
 
 typedef struct { v3 o, d; float t_min, t_max; uint32_t ex0_inst, ex0_prim, ex1_inst, ex1_prim; } or_ray;
@@ -412,7 +421,7 @@ static v3 or_material_emission(const or_scene *sc, const or_si *si, v3 wo) {
 /* ---------------------------------- lights ------------------------------------------------------- */
 static float or_mis_weight(float a, float b) { float pa = 1.0f * a, pb = 1.0f * b; return pa / (pa + pb); } /* pt.rs:962-973, power 1 */
 
-typedef struct { v3 li, wi; float pdf; or_ray shadow_ray; int valid; } or_light_sample;
+typedef struct { v3 li, wi; float pdf; or_ray shadow_ray; int valid; int delta; } or_light_sample;
 /* light/mod.rs:115-132 + light/area.rs:51-107 */
 static or_light_sample or_sample_direct(const or_scene *sc, v3 pn_p, v3 pn_n, float u_select, v2 u_sample) {
     or_light_sample s;
@@ -432,6 +441,18 @@ static or_light_sample or_sample_direct(const or_scene *sc, v3 pn_p, v3 pn_n, fl
         s.wi = wi;
         s.valid = ok;
         s.pdf = pdf * light_choice_pdf;
+        return s;
+    }
+    if (sc->light_inst[light_idx] == OR_PUNCT_INST) { /* a punctual light (4.14 / 4.15 Sampling): NEE only, pdf = the choice's */
+        const or_punct *L = &sc->punct[sc->color & 3u][light_idx - sc->n_emit];
+        const or_punct_ls ps = or_punct_sample(L, pn_p, pn_n, u_sample);
+        s.li = ps.li; s.wi = ps.wi;
+        s.shadow_ray.o = ps.ro; s.shadow_ray.d = ps.wi; s.shadow_ray.t_min = 0.0f; s.shadow_ray.t_max = ps.tmax;
+        s.shadow_ray.ex0_inst = OR_INVALID; s.shadow_ray.ex0_prim = OR_INVALID;
+        s.shadow_ray.ex1_inst = OR_INVALID; s.shadow_ray.ex1_prim = OR_INVALID;
+        s.valid = ps.valid;
+        s.pdf = light_choice_pdf;
+        s.delta = 1;
         return s;
     }
     uint32_t inst_id = sc->light_inst[light_idx];
@@ -612,6 +633,7 @@ OR_EXPORT or_scene *or_scene_create(const or_scene_desc *d) {
         }
         free(powers);
     }
+    sc->n_emit = sc->n_lights;
     if (sc->n_lights > 0) or_alias_build(&sc->light_dist, sc->light_power, sc->n_lights);
     return sc;
 }
@@ -635,6 +657,8 @@ OR_EXPORT void or_scene_destroy(or_scene *sc) {
     free(sc->woop); free(sc->tri_inst); free(sc->tri_prim);
     free(sc->light_inst); free(sc->light_power);
     or_env_free(sc->env);
+    free(sc->punct_desc);
+    for (int k = 0; k < 4; k++) free(sc->punct[k]);
     or_scene_free_bvh(sc);
     free(sc);
 }
@@ -752,9 +776,11 @@ static v2 or_filter_sample(const or_pt_config *cfg, v2 u) { /* film.rs:32-49 */
     v2 off = V2((r * cs) * sigma, (r * sn) * sigma);
     return V2(or_clamp(off.x, -width, width), or_clamp(off.y, -width, width));
 }
-static or_ray or_generate_ray(const or_scene *sc, const or_pt_config *cfg, uint32_t px, uint32_t py, or_sampler *smp) { /* camera/mod.rs:70-103 */
+/* The camera ray of a film sample for given numbers (camera/mod.rs:70-103; with a lens DESIGN.md 4.9 steps 2 - 5: u_lens -> the point l of
+ * the lens disk, the pinhole direction's point on the plane of focus, the ray from l through it; the weight stays the filter's) */
+static or_ray or_camera_ray(const or_scene *sc, const or_pt_config *cfg, uint32_t px, uint32_t py, v2 u_filter, v2 u_lens) {
     v2 fpixel = V2((float)px + 0.5f, (float)py + 0.5f);
-    v2 offset = or_filter_sample(cfg, smp_2d(smp));
+    v2 offset = or_filter_sample(cfg, u_filter);
     v2 pf = V2(fpixel.x + offset.x, fpixel.y + offset.y);
     const float *m = sc->r2c;
     /* r2c.transform_point((x,y,0)): M * (x,y,0,1), then / w */
@@ -764,14 +790,35 @@ static or_ray or_generate_ray(const or_scene *sc, const or_pt_config *cfg, uint3
     float qw = ((m[3] * pf.x + m[7] * pf.y) + m[11] * 0.0f) + m[15] * 1.0f;
     v3 d = v3normalize(v3divs(V3(qx, qy, qz), qw));
     v3 o = V3(0, 0, 0);
-    if (!sc->c2w_identity) {
-        const float *c = sc->c2w;
+    const float *c = sc->c2w;
+    if (sc->lens_radius > 0.0f) {
+        const v2 ab = or_concentric_disk(u_lens);                            /* step 2 */
+        const v3 l = V3(sc->lens_radius * ab.x, sc->lens_radius * ab.y, 0.0f); /* step 3 */
+        const float ft = sc->lens_focal / (-d.z);
+        const v3 p_focus = v3scale(d, ft);
+        d = v3normalize(v3sub(p_focus, l));
+        o = l;
+        if (!sc->c2w_identity) {                                             /* step 4 */
+            const float r0 = ((c[0] * l.x + c[4] * l.y) + c[8] * l.z) + c[12] * 1.0f;
+            const float r1 = ((c[1] * l.x + c[5] * l.y) + c[9] * l.z) + c[13] * 1.0f;
+            const float r2 = ((c[2] * l.x + c[6] * l.y) + c[10] * l.z) + c[14] * 1.0f;
+            const float r3 = ((c[3] * l.x + c[7] * l.y) + c[11] * l.z) + c[15] * 1.0f;
+            o = v3divs(V3(r0, r1, r2), r3);
+            d = V3((c[0] * d.x + c[4] * d.y) + c[8] * d.z, (c[1] * d.x + c[5] * d.y) + c[9] * d.z, (c[2] * d.x + c[6] * d.y) + c[10] * d.z);
+        }
+    } else if (!sc->c2w_identity) {
         float ow = c[15];
         o = v3divs(V3(c[12], c[13], c[14]), ow); /* M * (0,0,0,1) */
         d = V3((c[0] * d.x + c[4] * d.y) + c[8] * d.z, (c[1] * d.x + c[5] * d.y) + c[9] * d.z, (c[2] * d.x + c[6] * d.y) + c[10] * d.z);
     }
     or_ray r = {o, d, 0.0f, 1e20f, OR_INVALID, OR_INVALID, OR_INVALID, OR_INVALID};
     return r;
+}
+/* 4.9 step 1: the lens draws u_lens = next_2d right after the filter's next_2d; the pinhole draws nothing */
+static or_ray or_generate_ray(const or_scene *sc, const or_pt_config *cfg, uint32_t px, uint32_t py, or_sampler *smp) {
+    const v2 u_filter = smp_2d(smp);
+    const v2 u_lens = sc->lens_radius > 0.0f ? smp_2d(smp) : V2(0.0f, 0.0f);
+    return or_camera_ray(sc, cfg, px, py, u_filter, u_lens);
 }
 
 /* ---------------------------------- the path tracer, pt.rs:329-900 ------------------------------- */
@@ -830,7 +877,7 @@ static v3 or_radiance(const or_scene *sc, const or_pt_config *cfg, or_ray ray, o
         if (dl.valid) {
             v3 f; float pdf;
             or_surf_evaluate(closure, wo, dl.wi, &f, &pdf);
-            float w = or_mis_weight(dl.pdf, pdf);
+            float w = dl.delta ? 1.0f : or_mis_weight(dl.pdf, pdf); /* 4.14: no ray ever hits a punctual light, no MIS partner */
             direct = v3divs(v3scale(v3mul(dl.li, f), w), dl.pdf);
         }
         or_bsdf_sample bs = or_closure_sample(closure, wo, u_bsdf.x, V2(u_bsdf.y, u_bsdf.z));
@@ -1390,6 +1437,7 @@ static int or_gpt_sources(int32_t cp, int32_t o, uint32_t r, uint32_t out[3]) {
  * [primal 3N | Gx 3(W+1)(H+1) | Gy 3(W+1)(H+1)] = the accumulated sums of gpt.rs:441-455 (divide by spp for the mean). */
 OR_EXPORT int or_gpt_render(const or_scene *sc, const or_gpt_config *g, float *film, float *aux, uint32_t n_threads) {
     if (sc->env) return -5; /* no environment in gpt (refused) */
+    if (sc->n_punct || sc->lens_radius > 0.0f) return -5; /* nor a punctual light (4.14) or a lens (4.9) */
     ((or_scene *)sc)->color = g->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H, NG = (uint64_t)(W + 1) * (H + 1);
@@ -1623,6 +1671,7 @@ static or_mcmc_eval or_mcmc_evaluate(const or_scene *sc, const or_mcmc_config *c
  * acceptance rate, splat scale as f32 bits, contribution as f32 bits} (doubles / reinterpreted), chain_states (10 u32 each). */
 OR_EXPORT int or_mcmc_render(const or_scene *sc, const or_mcmc_config *c, float *film, double *result, uint32_t *chain_states, uint32_t n_threads) {
     if (sc->env) return -5; /* no environment in mcmc_opt (refused) */
+    if (sc->n_punct || sc->lens_radius > 0.0f) return -5; /* nor a punctual light (4.14) or a lens (4.9) */
     ((or_scene *)sc)->color = c->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H;
@@ -1913,34 +1962,144 @@ OR_EXPORT void or_bsdf_eval_many(const or_material_desc *m, const float *table, 
     for (uint32_t i = 0; i < n; i++) or_bsdf_probe(m, table, 0, wo_, wi + 3 * i, out + 4 * i);
 }
 /* ---------------------------------- the environment light (or_env.h) -------------- */
+static void or_world_bounds(const or_scene *sc, float lo[3], float hi[3]) { /* over every triangle corner (lo > hi: no geometry) */
+    for (int a = 0; a < 3; a++) { lo[a] = INFINITY; hi[a] = -INFINITY; }
+    for (uint32_t i = 0; i < sc->n_instances; i++) {
+        const or_instance *in = &sc->instances[i];
+        const or_mesh_desc *g = &sc->meshes[in->mesh].d;
+        for (uint32_t k = 0; k < 3 * g->n_triangles; k++) {
+            v3 p = xf_point(&in->xf, ld3(g->vertices, g->indices[k]));
+            lo[0] = or_min(lo[0], p.x); lo[1] = or_min(lo[1], p.y); lo[2] = or_min(lo[2], p.z);
+            hi[0] = or_max(hi[0], p.x); hi[1] = or_max(hi[1], p.y); hi[2] = or_max(hi[2], p.z);
+        }
+    }
+}
+/* The light list (4.14): the emissive instances as or_scene_create found them, the punctual lights in the order given, the environment
+ * last; the alias table rebuilt over all of them. */
+static void or_rebuild_light_list(or_scene *sc) {
+    if (sc->n_lights > 0) or_alias_free(&sc->light_dist);
+    const uint32_t cap = sc->n_emit + sc->n_punct + 1;
+    sc->light_inst = (uint32_t *)realloc(sc->light_inst, 4ull * cap);
+    sc->light_power = (float *)realloc(sc->light_power, 4ull * cap);
+    uint32_t n = sc->n_emit;
+    if (sc->n_punct) {
+        float lo[3], hi[3];
+        or_world_bounds(sc, lo, hi);
+        const double R = or_punct_bounds_radius(lo, hi);
+        for (uint32_t k = 0; k < sc->n_punct; k++) {
+            sc->light_inst[n] = OR_PUNCT_INST;
+            sc->light_power[n] = or_punct_power(&sc->punct[0][k], R);
+            n++;
+        }
+    }
+    if (sc->env) {
+        sc->light_inst[n] = OR_INVALID;
+        sc->light_power[n] = sc->env->power;
+        n++;
+    }
+    sc->n_lights = n;
+    if (sc->n_lights > 0) or_alias_build(&sc->light_dist, sc->light_power, sc->n_lights);
+}
 /* Sets (desc = NULL: removes) the scene's environment: the last entry of the light table, weight 4 pi R^2 Lbar. Returns 0, or -1 for a
  * description akr_scene_set_environment refuses (the scene is left as it was). */
 OR_EXPORT int or_scene_set_environment(or_scene *sc, const or_environment_desc *d) {
     or_env *e = 0;
     if (d) {
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t i = 0; i < sc->n_instances; i++) { /* world bounds over every triangle corner */
-            const or_instance *in = &sc->instances[i];
-            const or_mesh_desc *g = &sc->meshes[in->mesh].d;
-            for (uint32_t k = 0; k < 3 * g->n_triangles; k++) {
-                v3 p = xf_point(&in->xf, ld3(g->vertices, g->indices[k]));
-                lo[0] = or_min(lo[0], p.x); lo[1] = or_min(lo[1], p.y); lo[2] = or_min(lo[2], p.z);
-                hi[0] = or_max(hi[0], p.x); hi[1] = or_max(hi[1], p.y); hi[2] = or_max(hi[2], p.z);
-            }
-        }
+        float lo[3], hi[3];
+        or_world_bounds(sc, lo, hi);
         if (or_env_create(d, lo, hi, &e) != 0) return -1;
     }
-    if (sc->n_lights > 0) or_alias_free(&sc->light_dist);
-    if (sc->env) { sc->n_lights--; or_env_free(sc->env); sc->env = 0; }
-    if (e) {
-        sc->env = e;
-        sc->light_inst[sc->n_lights] = OR_INVALID;
-        sc->light_power[sc->n_lights] = e->power;
-        sc->n_lights++;
-    }
-    if (sc->n_lights > 0) or_alias_build(&sc->light_dist, sc->light_power, sc->n_lights);
+    or_env_free(sc->env);
+    sc->env = e;
+    or_rebuild_light_list(sc);
     return 0;
 }
+/* ---------------------------------- punctual lights (or_punct.h) and the lens (4.9) -------------- */
+/* Replaces the scene's punctual lights by the n given (NULL or 0: removes them). Returns 0, or -1 when akr_scene_add_punctual_light
+ * would refuse one of them (the scene is left as it was). A light of strength 0 or an all-zero colour is accepted and is no light. */
+OR_EXPORT int or_scene_set_punctual_lights(or_scene *sc, const or_punctual_light_desc *lights, uint32_t n) {
+    if (!lights) n = 0;
+    or_punctual_light_desc *keep = (or_punctual_light_desc *)malloc(sizeof(or_punctual_light_desc) * (n ? n : 1));
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const int rc = or_punct_check(&lights[i], &keep[m]);
+        if (rc < 0) { free(keep); return -1; }
+        if (rc > 0) m++;
+    }
+    free(sc->punct_desc);
+    sc->punct_desc = keep;
+    sc->n_punct = m;
+    for (uint32_t color = 0; color < 4; color++) {
+        free(sc->punct[color]);
+        sc->punct[color] = (or_punct *)malloc(sizeof(or_punct) * (m ? m : 1));
+        for (uint32_t k = 0; k < m; k++) sc->punct[color][k] = or_punct_fold(&keep[k], color);
+    }
+    or_rebuild_light_list(sc);
+    return 0;
+}
+/* The folded records under the ColorPipeline bits `color`, 16 words each (may be NULL), and the descriptions as held (may be NULL);
+ * returns the count. */
+OR_EXPORT uint32_t or_scene_punctual_records(const or_scene *sc, uint32_t color, uint32_t *words16, or_punctual_light_desc *descs) {
+    if (words16 && sc->n_punct) memcpy(words16, sc->punct[color & 3u], sizeof(or_punct) * sc->n_punct);
+    if (descs && sc->n_punct) memcpy(descs, sc->punct_desc, sizeof(or_punctual_light_desc) * sc->n_punct);
+    return sc->n_punct;
+}
+/* The light table's alias entries ({j, t} records) and pdfs, n_lights each */
+OR_EXPORT void or_scene_light_table(const or_scene *sc, or_alias_entry *entries, float *pdf) {
+    if (!sc->n_lights) return;
+    memcpy(entries, sc->light_dist.table, sizeof(or_alias_entry) * sc->n_lights);
+    memcpy(pdf, sc->light_dist.pdf, 4ull * sc->n_lights);
+}
+/* Known-answer call with the rows of akr_host_light_sample_soft: rows9 = p, n, u_select, u_sample -> out13 = li, wi, pdf, ro, tmax, valid,
+ * delta and the light chosen. An emitter or the environment answers the choice's pdf alone. Uses the records of the pipeline set by
+ * or_scene_set_color (0 after creation). Returns -1 for a scene without lights. */
+OR_EXPORT int or_punct_sample_many(const or_scene *sc, uint32_t n, const float *rows9, float *out13, uint32_t *light) {
+    if (!sc->n_lights) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = rows9 + 9ull * i;
+        float *o = out13 + 13ull * i;
+        float pdf, rest;
+        const uint32_t idx = or_alias_sample_and_remap(&sc->light_dist, r[6], &pdf, &rest);
+        memset(o, 0, 13 * sizeof(float));
+        o[6] = pdf;
+        light[i] = idx;
+        if (sc->light_inst[idx] != OR_PUNCT_INST) continue;
+        const or_punct_ls s = or_punct_sample(&sc->punct[sc->color & 3u][idx - sc->n_emit], V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), V2(r[7], r[8]));
+        o[0] = s.li.x; o[1] = s.li.y; o[2] = s.li.z; o[3] = s.wi.x; o[4] = s.wi.y; o[5] = s.wi.z;
+        o[7] = s.ro.x; o[8] = s.ro.y; o[9] = s.ro.z; o[10] = s.tmax; o[11] = s.valid ? 1.0f : 0.0f; o[12] = 1.0f;
+    }
+    return 0;
+}
+/* Sets (NULL or radius 0: removes) the camera's lens. Returns -1 for what akr_scene_set_lens refuses on the values alone: a non-finite
+ * or negative value, a radius > 0 without a focal distance > 0. (The library's further test against the padding of its acceleration
+ * structure is the library's own concern: the oracle has no padded boxes.) */
+OR_EXPORT int or_scene_set_lens(or_scene *sc, const or_lens_desc *d) {
+    if (d) {
+        if (!or_isfinite(d->radius) || !or_isfinite(d->focal_distance) || d->radius < 0.0f || d->focal_distance < 0.0f) return -1;
+        if (d->radius > 0.0f && !(d->focal_distance > 0.0f)) return -1;
+    }
+    sc->lens_radius = (d && d->radius > 0.0f) ? d->radius : 0.0f;
+    sc->lens_focal = (d && d->radius > 0.0f) ? d->focal_distance : 0.0f;
+    return 0;
+}
+OR_EXPORT void or_scene_get_lens(const or_scene *sc, or_lens_desc *out) { out->radius = sc->lens_radius; out->focal_distance = sc->lens_focal; }
+/* Known-answer call with the rows of akr_host_lens_ray: pixels2 = x, y; u4 = u_filter, u_lens -> out6 = o, d */
+OR_EXPORT int or_lens_ray_many(const or_scene *sc, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2, const float *u4, float *out6) {
+    if (filter_type > OR_FILTER_GAUSSIAN) return -1;
+    or_pt_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.filter_type = filter_type; cfg.filter_radius = filter_radius;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *u = u4 + 4ull * i;
+        const or_ray r = or_camera_ray(sc, &cfg, pixels2[2ull * i], pixels2[2ull * i + 1], V2(u[0], u[1]), V2(u[2], u[3]));
+        float *o = out6 + 6ull * i;
+        o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
+    }
+    return 0;
+}
+OR_EXPORT uint32_t or_sizeof_punctual_light_desc(void) { return (uint32_t)sizeof(or_punctual_light_desc); }
+OR_EXPORT uint32_t or_sizeof_lens_desc(void) { return (uint32_t)sizeof(or_lens_desc); }
+OR_EXPORT uint32_t or_sizeof_punct_record(void) { return (uint32_t)sizeof(or_punct); }
 /* The environment's size and tables, for comparison with the library's (akr_scene_get_array): returns 0 without one. dims = w, h, filter.
  * Any output pointer may be NULL; entries as {j, t} pairs, row by row for the conditional tables. */
 OR_EXPORT int or_scene_env_tables(const or_scene *sc, uint32_t *dims, float *texels, or_alias_entry *marginal, float *marginal_pdf,

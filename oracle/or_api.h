@@ -91,6 +91,24 @@ typedef struct {
     uint32_t _pad2;
 } or_environment_desc;
 
+/* A point, spot or sun light: layout-identical to akr_punctual_light_desc (60 bytes, the two trailing floats of
+ * version 0.3.8 included). */
+enum { OR_LIGHT_POINT = 0, OR_LIGHT_SPOT = 1, OR_LIGHT_SUN = 2 };
+typedef struct {
+    uint32_t type;
+    float position[3];       /* POINT, SPOT */
+    float direction[3];      /* SPOT, SUN: any length > 0 */
+    float color[3];
+    float strength;
+    float cone_angle;        /* SPOT: the outer half-angle in (0, pi/2] */
+    float blend;             /* SPOT: in [0, 1] */
+    float radius;            /* POINT, SPOT: 0 = a delta light */
+    float angle;             /* SUN: the full angular diameter in [0, pi); 0 = a delta light */
+} or_punctual_light_desc;
+
+/* The camera's thin lens: layout-identical to akr_lens_desc. radius = 0: a pinhole. */
+typedef struct { float radius, focal_distance; } or_lens_desc;
+
 enum { OR_FILTER_BOX = 0, OR_FILTER_GAUSSIAN = 1 };
 enum { OR_SAMPLER_INDEPENDENT = 0 };
 typedef struct {

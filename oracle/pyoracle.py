@@ -120,8 +120,24 @@ def lib() -> C.CDLL:
     L.or_kat_atan2.restype = f32
     L.or_kat_atan2.argtypes = [f32, f32]
     L.or_kat_atan2_many.argtypes = [u32, fp, fp, fp]
-    for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config", "or_sizeof_environment_desc"):
+    L.or_scene_set_punctual_lights.restype = i32
+    L.or_scene_set_punctual_lights.argtypes = [vp, C.POINTER(abi.PunctualLightDesc), u32]
+    L.or_scene_punctual_records.restype = u32
+    L.or_scene_punctual_records.argtypes = [vp, u32, up, C.POINTER(abi.PunctualLightDesc)]
+    L.or_scene_light_table.argtypes = [vp, vp, fp]
+    L.or_punct_sample_many.restype = i32
+    L.or_punct_sample_many.argtypes = [vp, u32, fp, fp, up]
+    L.or_scene_set_lens.restype = i32
+    L.or_scene_set_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
+    L.or_scene_get_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
+    L.or_lens_ray_many.restype = i32
+    L.or_lens_ray_many.argtypes = [vp, u32, f32, u32, up, fp, fp]
+    for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config", "or_sizeof_environment_desc",
+              "or_sizeof_punctual_light_desc", "or_sizeof_lens_desc", "or_sizeof_punct_record"):
         getattr(L, n).restype = u32
+    assert L.or_sizeof_punctual_light_desc() == C.sizeof(abi.PunctualLightDesc) == 60
+    assert L.or_sizeof_lens_desc() == C.sizeof(abi.LensDesc) == 8
+    assert L.or_sizeof_punct_record() == 64
     assert L.or_sizeof_environment_desc() == C.sizeof(abi.EnvironmentDesc)
     assert L.or_sizeof_material() == C.sizeof(abi.MaterialDesc)
     assert L.or_sizeof_config() == C.sizeof(abi.PtConfig)
@@ -136,10 +152,12 @@ def _fp(a):
 
 
 class OracleScene:
-    def __init__(self, scene: abi.SceneData, bvh: bool = False, share_plane_rows: bool = True):
+    def __init__(self, scene: abi.SceneData, bvh: bool = False, share_plane_rows: bool = True, lights: bool = True, lens: bool = True):
         """bvh: build the oracle-side hierarchy (or_accel.h; same hits as the exhaustive loop, checked in
         tests/test_oracle_accel.py) -- for the 1 M / 10 M-triangle configurations. share_plane_rows = False: every triangle
-        keeps the plane row of its own vertices (the records as they were before the coplanar-neighbour rule)."""
+        keeps the plane row of its own vertices (the records as they were before the coplanar-neighbour rule).
+        The scene's environment, punctual lights (scene.lights) and lens (scene.lens) are set as capi.Scene sets them; lights = False /
+        lens = False leaves the punctual lights / the lens out: the oracle of the same scene without them."""
         self.data = scene
         desc, self._keep = scene.to_desc()
         self._desc = desc
@@ -152,6 +170,82 @@ class OracleScene:
         self.n_bvh_nodes = lib().or_scene_build_bvh(self.h) if bvh else 0
         if getattr(scene, "environment", None) is not None:
             self.set_environment(scene.environment)
+        if lights and getattr(scene, "lights", None):
+            self.set_punctual_lights(scene.lights)
+        if lens and getattr(scene, "lens", None) is not None:
+            self.set_lens(scene.lens.radius, scene.lens.focal_distance)
+
+    def set_punctual_lights(self, lights) -> None:
+        """or_scene_set_punctual_lights: replaces the scene's punctual lights by the abi.PunctualLightData given; None or
+        an empty list removes them. A light the library would refuse raises ValueError."""
+        lights = list(lights or ())
+        if not lights:
+            rc = lib().or_scene_set_punctual_lights(self.h, None, 0)
+        else:
+            arr = (abi.PunctualLightDesc * len(lights))(*[l.to_desc() for l in lights])
+            rc = lib().or_scene_set_punctual_lights(self.h, arr, len(lights))
+        if rc != 0:
+            raise ValueError("or_scene_set_punctual_lights refused a light")
+
+    def punctual_lights(self) -> list:
+        """The lights the oracle holds (those that were "no light" are not among them), as abi.PunctualLightData."""
+        n = lib().or_scene_punctual_records(self.h, 0, None, None)
+        arr = (abi.PunctualLightDesc * max(n, 1))()
+        lib().or_scene_punctual_records(self.h, 0, None, arr)
+        return [abi.PunctualLightData.from_desc(arr[i]) for i in range(n)]
+
+    def punctual_records(self, color: int = 0) -> np.ndarray:
+        """The folded records under the ColorPipeline bits `color`: uint32 (n, 16), the words of DESIGN.md 4.14 / 4.15."""
+        n = lib().or_scene_punctual_records(self.h, 0, None, None)
+        out = np.zeros((n, 16), np.uint32)
+        if n:
+            lib().or_scene_punctual_records(self.h, color, out.ctypes.data_as(C.POINTER(C.c_uint32)), None)
+        return out
+
+    def light_table(self):
+        """The light table's alias entries ({j, t} records) and pdfs."""
+        n = self.num_lights()
+        alias = np.dtype([("j", np.uint32), ("t", np.float32)])
+        e, pdf = np.zeros(n, alias), np.zeros(n, np.float32)
+        if n:
+            lib().or_scene_light_table(self.h, e.ctypes.data, _fp(pdf))
+        return e, pdf
+
+    def punct_sample_many(self, rows, color: int = 0):
+        """or_punct_sample_many: rows (n, 9) = p, n, u_select, u_sample (or (n, 7): u_sample = (0.5, 0.5)) -> ((n, 13) = li, wi, pdf, ro, tmax,
+        valid, delta; (n,) the light chosen), the rows of akr_host_light_sample_soft."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim == 2 and r.shape[1] == 7:
+            r = np.ascontiguousarray(np.concatenate([r, np.full((r.shape[0], 2), 0.5, np.float32)], axis=1))
+        r = r.reshape(-1, 9)
+        lib().or_scene_set_color(self.h, color)
+        out, light = np.zeros((r.shape[0], 13), np.float32), np.zeros(r.shape[0], np.uint32)
+        assert lib().or_punct_sample_many(self.h, r.shape[0], _fp(r), _fp(out), light.ctypes.data_as(C.POINTER(C.c_uint32))) == 0, "the scene has no light"
+        return out, light
+
+    def set_lens(self, radius=None, focal_distance: float = 0.0) -> None:
+        """or_scene_set_lens; radius None or 0 removes the lens. Values the library would refuse raise ValueError."""
+        if radius is None:
+            rc = lib().or_scene_set_lens(self.h, None)
+        else:
+            d = abi.LensDesc(float(radius), float(focal_distance))
+            rc = lib().or_scene_set_lens(self.h, C.byref(d))
+        if rc != 0:
+            raise ValueError("or_scene_set_lens refused the lens")
+
+    def lens(self):
+        d = abi.LensDesc()
+        lib().or_scene_get_lens(self.h, C.byref(d))
+        return abi.LensData(float(d.radius), float(d.focal_distance)) if d.radius > 0.0 else None
+
+    def lens_ray_many(self, pixels, u_filter, u_lens, filter_type: int = 0, filter_radius: float = 0.5) -> np.ndarray:
+        """or_lens_ray_many: the camera rays (n, 6) = o, d of (n, 2) pixels for given u_filter, u_lens, the rows of akr_host_lens_ray."""
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1, 2)
+        n = px.shape[0]
+        u = np.ascontiguousarray(np.concatenate([np.asarray(u_filter, np.float32).reshape(n, 2), np.asarray(u_lens, np.float32).reshape(n, 2)], axis=1))
+        out = np.zeros((n, 6), np.float32)
+        assert lib().or_lens_ray_many(self.h, int(filter_type), float(filter_radius), n, px.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(u), _fp(out)) == 0
+        return out
 
     def set_environment(self, env: abi.EnvironmentData | None) -> None:
         """or_scene_set_environment; None removes it. A description the library would refuse raises ValueError."""
@@ -268,7 +362,7 @@ class OracleScene:
         film = np.zeros(7 * n, dtype=np.float32)
         aux = np.zeros(3 * n + 6 * ng, dtype=np.float32)
         rc = lib().or_gpt_render(self.h, C.byref(cfg), _fp(film), _fp(aux), n_threads if n_threads > 0 else (os.cpu_count() or 1))
-        assert rc == 0, "or_gpt_render rejected the configuration"
+        assert rc == 0, f"or_gpt_render rejected the configuration or the scene ({rc}; -5: an environment, a punctual light or a lens)"
         if cfg.reconstruction == 0:
             return film, None
         return film, (aux[:3 * n].reshape(h, w, 3), aux[3 * n:3 * n + 3 * ng].reshape(h + 1, w + 1, 3), aux[3 * n + 3 * ng:].reshape(h + 1, w + 1, 3))

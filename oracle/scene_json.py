@@ -602,7 +602,10 @@ def _fold_material(shader: dict, bufs: "_Buffers" = None, images: list = None, i
     return m
 
 
-def load_scene(path: str, width: int = 0, height: int = 0) -> SceneData:
+def load_scene(path: str, width: int = 0, height: int = 0, lens: bool = False, punctual_lights: bool = True, soft_lights: bool = True) -> SceneData:
+    """lens / punctual_lights / soft_lights mirror the library's options of those names: lens = True turns the
+    camera's focal_distance / fstop into its thin lens; punctual_lights = False drops the file's "lights"; soft_lights = False reads every
+    light with radius 0 and angle 0."""
     with open(path, "r") as fh:
         scene = json.load(fh)
     bufs = _Buffers(scene, os.path.dirname(os.path.abspath(path)))
@@ -657,7 +660,58 @@ def load_scene(path: str, width: int = 0, height: int = 0) -> SceneData:
         height=int(height or cd["sensor_height"]),
     )
     env = _load_environment(scene["environment"], bufs) if scene.get("environment") is not None else None
-    return SceneData(meshes, instances, materials, camera, None, inst_ids, mat_ids, images, environment=env)
+    sd = SceneData(meshes, instances, materials, camera, None, inst_ids, mat_ids, images, environment=env)
+    if punctual_lights and scene.get("lights") is not None:
+        sd.lights = _load_lights(scene["lights"], soft_lights)
+    if lens and "focal_distance" in cd and "fstop" in cd:
+        # lens_radius = focal_distance / (2 fstop), f32 (load.rs:177-189); the option `lens` makes the pair the camera's lens
+        fd, fstop = f32(cd["focal_distance"]), f32(cd["fstop"])
+        radius = fd / (f32(2.0) * fstop)
+        if float(radius) > 0.0:
+            sd.lens = abi.LensData(float(radius), float(fd))
+    return sd
+
+
+def _load_lights(lj: dict, soft: bool) -> list:
+    """The top-level "lights" (DESIGN.md 4.14 "Reader", 4.15): a map name -> {"type": "point" | "spot" | "sun", "data": {...}}, read in the
+    byte-wise order of the names as every collection of the file is. An entry whose data is empty is the reference's own PointLight {} and
+    is ignored; spot_size is the FULL cone angle; radius belongs to point / spot and angle to sun, the other kind's key is not read."""
+    kinds = {"point": abi.LIGHT_POINT, "spot": abi.LIGHT_SPOT, "sun": abi.LIGHT_SUN}
+    out = []
+    for name in sorted(lj.keys(), key=lambda k: k.encode()):
+        entry = lj[name]
+        data = entry.get("data")
+        if not data:
+            continue
+        if entry.get("type") not in kinds:
+            raise ValueError(f"light '{name}': unknown type {entry.get('type')!r}")
+        t = kinds[entry["type"]]
+
+        def v3(key):
+            if key not in data:
+                raise ValueError(f"light '{name}': missing \"{key}\"")
+            return tuple(float(f32(c)) for c in data[key][:3])
+
+        light = abi.PunctualLightData(t)
+        if t != abi.LIGHT_SUN:
+            light.position = v3("position")
+        if t != abi.LIGHT_POINT:
+            light.direction = v3("direction")
+        if "color" in data:
+            light.color = v3("color")
+        light.strength = float(f32(data.get("strength", 1.0)))
+        if t == abi.LIGHT_SPOT:
+            if "spot_size" not in data:
+                raise ValueError(f"light '{name}': missing \"spot_size\"")
+            light.cone_angle = float(f32(data["spot_size"]) * f32(0.5))
+            light.blend = float(f32(data.get("spot_blend", 0.0)))
+        if soft:
+            if t != abi.LIGHT_SUN:
+                light.radius = float(f32(data.get("radius", 0.0)))
+            else:
+                light.angle = float(f32(data.get("angle", 0.0)))
+        out.append(light)
+    return out
 
 
 def _srgb_to_linear(v: np.ndarray) -> np.ndarray:

@@ -1,0 +1,345 @@
+"""The scenes, configurations and expected kernel variants of tests/test_gpu_punct_parity.py (punctual lights, soft lights and the thin lens on
+the GPU against the CPU oracle, bit for bit). They live here, not in that file, so that tests/test_punct_parity_cases.py can check on the CPU,
+with the oracle and the library's host build alone, that every case is what it claims to be: that its lights or its lens do change the film,
+that a spot's cone edge crosses enough pixels, that the session the library plans for it runs the kernel the case is there for."""
+import dataclasses
+import functools
+import math
+
+import numpy as np
+
+from akari_render_amd import abi, capi
+from oracle import pyoracle
+from tests.helpers import instanced_scene, make_config, textured_room
+from tests.test_environment import sample_image
+from tests.test_gpu_env_parity import LIGHTING as ENV_LIGHTING
+from tests.test_gpu_env_parity import MATERIALS as ENV_MATERIALS
+from tests.test_gpu_env_parity import _ggx, _rot, env_scene
+
+PL = abi.PunctualLightData
+EXH = dict(force_bvh=0, instancing=0, wavefront=0, specialise=0)
+BVH = dict(force_bvh=1, instancing=0, wavefront=0, specialise=0)
+SAMPLERS = {"independent": abi.SAMPLER_INDEPENDENT, "pmj02bn": abi.SAMPLER_PMJ02BN, "sobol": abi.SAMPLER_SOBOL}
+PIPELINES = {"srgb_srgb": 0, "rgb_aces": abi.COLOR_RGB_ACESCG, "repr_aces": abi.COLOR_REPR_ACESCG, "acescg": abi.COLOR_RGB_ACESCG | abi.COLOR_REPR_ACESCG}
+# akr_kernel_info.kernel_flags
+F_BVH, F_PMJ, F_STAGE, F_DEFER, F_LENS, F_FEAT, F_PUNCT = 1, 2, 4, 8, 32, 64, 128
+
+MATERIALS = dict(ENV_MATERIALS)
+MATERIALS["coated"] = abi.MaterialData(kind=abi.MAT_PRINCIPLED, base_color=(0.8, 0.3, 0.2), roughness=0.5, coat_weight=0.8, coat_roughness=0.1, coat_ior=1.5,
+                                       coat_tint=(0.9, 0.8, 1.0))
+
+# the lights of the floor-and-box scene (y up; the floor at y = -1, the box around (0, -0.4, 0), the camera at (0, 0.8, 4))
+_SPOT = dict(position=(-1.2, 1.6, 1.4), direction=(1.1, -2.4, -1.2), cone_angle=0.42, color=(2.0, 3.0, 4.0), strength=8.0)
+LIGHTS = {
+    "point": PL(abi.LIGHT_POINT, position=(1.4, 0.9, 1.2), color=(3.0, 2.5, 2.0), strength=3.0),
+    "spot_hard": PL(abi.LIGHT_SPOT, blend=0.0, **_SPOT),
+    "spot_blend": PL(abi.LIGHT_SPOT, blend=0.4, **_SPOT),
+    "sun": PL(abi.LIGHT_SUN, direction=(0.3, -1.0, -0.25), color=(1.0, 0.9, 0.8), strength=1.5),
+    "soft_point": PL(abi.LIGHT_POINT, position=(1.4, 0.9, 1.2), color=(3.0, 2.5, 2.0), strength=3.0, radius=0.3),
+    "soft_spot": PL(abi.LIGHT_SPOT, blend=0.4, radius=0.2, **_SPOT),
+    "soft_sun": PL(abi.LIGHT_SUN, direction=(0.3, -1.0, -0.25), color=(1.0, 0.9, 0.8), strength=1.5, angle=0.25),
+}
+THREE = [LIGHTS["point"], LIGHTS["soft_spot"], LIGHTS["sun"]]
+
+
+def lit_scene(material="diffuse", lights=(), emitters=0, env=None, floor="diffuse", lens=None, w=32, h=32):
+    """tests/test_gpu_env_parity.py's floor and box with `lights`; env: None = no environment, True = that file's sampled image"""
+    sd = env_scene(material if material in ENV_MATERIALS else "diffuse", emitters=emitters, env=None if env in (None, True) else env, floor=floor if floor in ENV_MATERIALS else "diffuse", w=w, h=h)
+    sd.materials[0], sd.materials[1] = MATERIALS[floor], MATERIALS[material]
+    if env is None:
+        sd.environment = None
+    sd.lights = list(lights)
+    sd.lens = lens
+    return lens_ok_scene(sd)
+
+
+def lens_ok_scene(sd, top=1.2):
+    """A wall behind the box, of the floor's material. It is lit by every light, so that most of the frame is surface and not sky; and it raises the
+    scene's box over the camera along y, where the tilted lens plane has a component, so that a scene with a tree takes a lens (DESIGN.md 4.9 "BVH
+    padding"). Its top leaves the upper rows of the frame to the sky."""
+    wall = abi.MeshData(vertices=np.array([[-4, -1, -3.5], [4, -1, -3.5], [4, top, -3.5], [-4, top, -3.5]], np.float32), indices=np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
+    sd.meshes.append(wall)
+    sd.instances.append(abi.InstanceData(len(sd.meshes) - 1, [0], np.eye(4, dtype=np.float32).reshape(16).copy()))
+    return sd
+
+
+LENS = abi.LensData(0.12, 4.2)  # focused on the box, a disk wide enough that the floor in front and the wall behind are blurred
+
+
+def grid_lights(n):
+    """n point lights on a grid over the floor, unequal strengths and colours: the alias table is not flat"""
+    k = max(int(math.ceil(math.sqrt(n))), 2)
+    out = []
+    for i in range(n):
+        x, z = -3.0 + 6.0 * (i % k) / (k - 1), -3.0 + 6.0 * (i // k) / (k - 1)
+        out.append(PL(abi.LIGHT_POINT, position=(x, 0.6 + 0.05 * (i % 5), z), color=(1.0, 0.6 + 0.1 * (i % 4), 0.5), strength=0.3 + 0.25 * (i % 7)))
+    return out
+
+
+def tex_scene(w, h, lights, env=False, lens=None):
+    sd = textured_room(w, h)
+    sd.ggx_table = _ggx()
+    sd.lights = list(lights)
+    if env:  # (a closed room: the environment is in the light table and is sampled, its shadow rays are blocked)
+        sd.environment = abi.EnvironmentData(image=sample_image(W=16, H=8, seed=4), strength=1.0, rotation=_rot(0.2, -0.7), filter=abi.TEX_FILTER_LINEAR)
+    sd.lens = lens
+    return sd
+
+
+ROOM_LIGHTS = [PL(abi.LIGHT_POINT, position=(0.2, 0.3, 0.1), color=(3.0, 2.5, 2.0), strength=1.5), PL(abi.LIGHT_SPOT, position=(-0.4, 0.6, 0.5), direction=(0.3, -1.0, -0.4), cone_angle=0.6, blend=0.3, color=(2.0, 3.0, 4.0), strength=3.0, radius=0.05)]
+
+
+@dataclasses.dataclass
+class Case:
+    name: str
+    scene: object            # () -> abi.SceneData
+    cfg: dict                # make_config's keywords
+    opts: dict = dataclasses.field(default_factory=lambda: dict(EXH))
+    want: dict = dataclasses.field(default_factory=dict)  # entries of the launch plan's variant that the case is there for
+    tags: tuple = ()         # "spot": the cone-edge condition; "interplay": 0 < n_shadow < n_shaded; "clamp"; "lens": differs from the pinhole film; "dark_ok"
+
+    def config(self):
+        return make_config(**self.cfg)
+
+    def flags(self):
+        """the kernel_flags the session must report"""
+        w = self.want
+        return (F_BVH if w.get("bvh") else 0) | (F_PMJ if w.get("pmj") else 0) | (F_STAGE if w.get("stage") else 0) | (F_LENS if w.get("lens") else 0) | (F_PUNCT if w.get("punct") else 0)
+
+
+def _want(opts, cfg, lens=False, punct=True, stage=True, **more):
+    w = dict(bvh=int(bool(opts.get("force_bvh"))), pmj=int(cfg.get("sampler_type", 0) != abi.SAMPLER_INDEPENDENT), stage=int(stage), lens=int(lens), punct=int(punct), inst=0, defer=0)
+    w.update(more)
+    return w
+
+
+CASES = {}
+
+
+def add(name, scene, cfg, opts=EXH, tags=(), **want):
+    assert name not in CASES, name
+    CASES[name] = Case(name, scene, dict(cfg), dict(opts), _want(opts, cfg, **want), tuple(tags))
+    return name
+
+
+BASE = dict(spp=8, spp_per_pass=8, max_depth=5, rr_depth=2)
+
+# ---------------------------------------------------------------------------------------------------------------- materials x light kinds
+# (one small emitter beside the light: a punctual light then also changes every other light's selection probability, so the whole lit frame depends on it,
+# not only the patch a spot reaches, and BSDF rays that hit the emitter weigh it with the changed pdf)
+MATERIAL_CASES = []
+for _m in list(MATERIALS) + ["force_diffuse"]:
+    for _l in LIGHTS:
+        for _r, _o in (("exh", EXH), ("bvh", BVH)):
+            _cfg = dict(BASE, force_diffuse=1) if _m == "force_diffuse" else BASE
+            _size = 64 if _l.endswith(("spot_hard", "spot_blend", "soft_spot")) else 32
+            MATERIAL_CASES.append(add(f"mat-{_m}-{_l}-{_r}", functools.partial(lit_scene, "glass" if _m == "force_diffuse" else _m, [LIGHTS[_l]], emitters=1, w=_size, h=_size), _cfg, _o,
+                                      tags=("spot",) if "spot" in _l else (), fd=int(_m == "force_diffuse")))
+
+# ---------------------------------------------------------------------------------------------------------------- positions that stress the geometry
+POSITION_CASES = [
+    add("pos-inside_glass_box", functools.partial(lit_scene, "glass", [PL(abi.LIGHT_POINT, position=(0.0, -0.4, 0.0), color=(3.0, 2.5, 2.0), strength=2.0)], emitters=1), BASE),
+    add("pos-inside_glass_box-soft-bvh", functools.partial(lit_scene, "glass", [PL(abi.LIGHT_POINT, position=(0.1, -0.5, 0.0), color=(3.0, 2.5, 2.0), strength=2.0, radius=0.25)], emitters=1), BASE, BVH),
+    # below the floor plane: face_forward flips the offset of every shadow ray from the floor's upper side; diffuse gets nothing from it there (the
+    # counters decide), the box's underside and what is reflected do
+    add("pos-below_floor", functools.partial(lit_scene, "rough_metal", [PL(abi.LIGHT_POINT, position=(0.5, -1.5, 1.0), color=(3.0, 2.5, 2.0), strength=4.0), LIGHTS["sun"]]), BASE),
+    add("pos-below_floor-bvh", functools.partial(lit_scene, "glass", [PL(abi.LIGHT_SPOT, position=(0.5, -1.6, 1.0), direction=(0.0, 1.0, 0.0), cone_angle=1.2, blend=0.5, color=(3.0, 2.5, 2.0), strength=4.0), LIGHTS["sun"]]),
+        BASE, BVH),
+    # 1e-3 above the floor: li = I / dist^2 of a million and more; the radiance clamp [0, 1000] of the indirect sum and the finite test
+    add("pos-point_1e-3_above_floor", functools.partial(lit_scene, "rough_metal", [PL(abi.LIGHT_POINT, position=(0.4, -0.999, 1.5), color=(3.0, 2.5, 2.0), strength=3.0e4)], floor="rough_metal"),
+        dict(BASE, max_depth=6), tags=("clamp",)),
+    add("pos-point_1e-3_above_floor-bvh", functools.partial(lit_scene, "diffuse", [PL(abi.LIGHT_POINT, position=(0.4, -0.999, 1.5), color=(3.0, 2.5, 2.0), strength=3.0e4)], floor="rough_metal"),
+        dict(BASE, max_depth=6), BVH, tags=("clamp",)),
+    # 4e-4 below the floor: a shadow ray from a point more than 0.4 above the floor ends, at dist (1 - 1e-3), before it reaches the floor, so the light
+    # shines through it there and is hidden from points lower down: the film depends on the factor of tmax
+    add("pos-just_behind_the_floor", functools.partial(lit_scene, "diffuse", [PL(abi.LIGHT_POINT, position=(0.5, -1.0004, 1.2), color=(3.0, 2.5, 2.0), strength=6.0)], emitters=1), BASE, tags=("tmax",)),
+    add("pos-just_behind_the_floor-soft-bvh", functools.partial(lit_scene, "coated", [PL(abi.LIGHT_SPOT, position=(0.5, -1.0004, 1.2), direction=(0.0, 1.0, 0.0), cone_angle=1.4, blend=0.3, color=(3.0, 2.5, 2.0),
+                                                                                      strength=6.0, radius=2e-4)], emitters=1), BASE, BVH, tags=("tmax",)),
+    add("pos-disk_radius_exceeds_height", functools.partial(lit_scene, "coated", [PL(abi.LIGHT_POINT, position=(0.8, -0.7, 1.4), color=(3.0, 2.5, 2.0), strength=2.0, radius=0.8)]), BASE),
+    add("pos-disk_radius_exceeds_height-spot-bvh", functools.partial(lit_scene, "diffuse", [PL(abi.LIGHT_SPOT, position=(0.8, -0.7, 1.4), direction=(0.0, -1.0, 0.2), cone_angle=1.3, blend=0.2,
+                                                                                            color=(3.0, 2.5, 2.0), strength=2.0, radius=0.8)], emitters=1), BASE, BVH),
+    add("pos-sun_angle_near_pi", functools.partial(lit_scene, "rough_metal", [PL(abi.LIGHT_SUN, direction=(0.1, -1.0, 0.1), color=(1.0, 0.9, 0.8), strength=1.5, angle=math.pi - 1e-3)]), BASE),
+    add("pos-sun_angle_near_pi-bvh", functools.partial(lit_scene, "glass", [PL(abi.LIGHT_SUN, direction=(0.1, -1.0, 0.1), color=(1.0, 0.9, 0.8), strength=1.5, angle=math.pi - 1e-3)]), BASE, BVH),
+    add("pos-spot_cone_half_pi", functools.partial(lit_scene, "rough_metal", [PL(abi.LIGHT_SPOT, position=(-1.0, 0.0, 1.2), direction=(0.6, -1.0, -0.3), cone_angle=float(np.float32(math.pi / 2)), blend=1.0,
+                                                                               color=(2.0, 3.0, 4.0), strength=4.0)], w=64, h=64), BASE, tags=("spot",)),
+    add("pos-spot_cone_half_pi-step-bvh", functools.partial(lit_scene, "diffuse", [PL(abi.LIGHT_SPOT, position=(-1.0, 0.0, 1.2), direction=(0.6, -1.0, -0.3), cone_angle=float(np.float32(math.pi / 2)), blend=0.0,
+                                                                                   color=(2.0, 3.0, 4.0), strength=4.0, radius=0.1)], w=64, h=64), BASE, BVH, tags=("spot",)),
+    add("pos-delta_and_soft_mixed", functools.partial(lit_scene, "glass", [LIGHTS["point"], LIGHTS["soft_spot"], LIGHTS["sun"], LIGHTS["soft_sun"], LIGHTS["spot_hard"], LIGHTS["soft_point"]]), BASE),
+    add("pos-delta_and_soft_mixed-bvh", functools.partial(lit_scene, "coated", [LIGHTS["point"], LIGHTS["soft_spot"], LIGHTS["sun"], LIGHTS["soft_sun"], LIGHTS["spot_hard"], LIGHTS["soft_point"]]), BASE, BVH),
+]
+
+# ---------------------------------------------------------------------------------------------------------------- light-table interplay
+DEEP = dict(spp=8, spp_per_pass=8, max_depth=6, rr_depth=3)
+INTERPLAY_CASES = []
+for _e in (0, 1, 2):
+    for _env in (None, True):
+        _o = BVH if (_e + int(bool(_env))) % 2 else EXH
+        INTERPLAY_CASES.append(add(f"table-{_e}_emitters-{'env' if _env else 'no_env'}", functools.partial(lit_scene, "glass", THREE, emitters=_e, env=_env), DEEP, _o,
+                                   tags=("interplay",), env=int(bool(_env))))
+for _n, _kw in (("indirect_only", dict(indirect_only=1)), ("debug_depth_1", dict(debug_depth=1)), ("debug_depth_2", dict(debug_depth=2)), ("no_nee", dict(use_nee=0))):
+    INTERPLAY_CASES.append(add(f"table-{_n}", functools.partial(lit_scene, "rough_metal", THREE, emitters=2, env=True), dict(DEEP, **_kw), BVH if _n.startswith("debug") else EXH,
+                               tags=("dark_ok",) if _n == "no_nee" else ("interplay",), env=1))
+
+
+# ---------------------------------------------------------------------------------------------------------------- light counts, staged and unstaged
+def _accepts(sd, opts, cfg, stage):
+    """does the library, on the host, accept the scene under `opts` (and, stage = True, still stage its tables in LDS)?"""
+    try:
+        with capi.options(**opts):
+            plan = capi.Scene(None, sd).launch_plan(cfg)
+    except capi.AkariError as e:
+        assert e.code == capi.ERR_UNSUPPORTED
+        return False
+    return (not stage) or plan["variant"]["stage"] == 1
+
+
+def largest_count(make_scene, opts, cfg, stage, lo=1, hi=4096):
+    """the largest number of grid lights for which _accepts holds (it is monotone in the count: the tables only grow), by bisection on the host"""
+    assert _accepts(make_scene(lo), opts, cfg, stage) and not _accepts(make_scene(hi), opts, cfg, stage)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if _accepts(make_scene(mid), opts, cfg, stage):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def count_scene(n, material="rough_metal"):
+    return lit_scene(material, grid_lights(n))
+
+
+@functools.lru_cache(maxsize=None)
+def bvh_stage_limit():
+    """the largest count of punctual lights the BVH kernels still stage (the 12 KB budget)"""
+    return largest_count(count_scene, BVH, make_config(**COUNT_CFG), stage=True)
+
+
+@functools.lru_cache(maxsize=None)
+def exhaustive_limit():
+    """the largest count the exhaustive path accepts (the 32 KB budget); one more is refused"""
+    return largest_count(count_scene, EXH, make_config(**COUNT_CFG), stage=False)
+
+
+COUNT_CFG = dict(spp=8, spp_per_pass=8, max_depth=4, rr_depth=2)
+COUNT_CASES = []
+for _n in (1, 2, 63, 64, 65):
+    for _r, _o in (("exh", EXH), ("bvh", BVH)):
+        COUNT_CASES.append(add(f"count-{_n}-{_r}", functools.partial(count_scene, _n), COUNT_CFG, _o))
+COUNT_CASES += [
+    add("count-bvh_last_staged", lambda: count_scene(bvh_stage_limit()), COUNT_CFG, BVH),
+    add("count-bvh_first_unstaged", lambda: count_scene(bvh_stage_limit() + 1), COUNT_CFG, BVH, stage=False),
+    add("count-bvh_stage_limit-exh", lambda: count_scene(bvh_stage_limit() + 1), COUNT_CFG, EXH),
+    add("count-exhaustive_limit", lambda: count_scene(exhaustive_limit()), COUNT_CFG, EXH),
+    add("count-exhaustive_limit-bvh", lambda: count_scene(exhaustive_limit() + 1), COUNT_CFG, BVH, stage=False),
+]
+
+# ---------------------------------------------------------------------------------------------------------------- all 96 PUNCT kernels
+SWEEP_CFG = dict(spp=4, spp_per_pass=4, max_depth=4, rr_depth=2)
+
+
+@functools.lru_cache(maxsize=None)
+def unstaged_count(tex, env, lens):
+    """a count of punctual lights past which the BVH kernels of this unit's scene no longer stage their tables"""
+    mk = functools.partial(_sweep_scene, tex, env, lens, "bvh_unstaged")
+    return largest_count(lambda n: mk(n_lights=n), BVH, make_config(**SWEEP_CFG), stage=True) + 1
+
+
+def _sweep_scene(tex, env, lens, route, n_lights=None):
+    if n_lights is None:
+        n_lights = unstaged_count(tex, env, lens) if route == "bvh_unstaged" else 0
+    if tex:
+        lights = ROOM_LIGHTS + [dataclasses.replace(l, position=(0.8 * l.position[0] / 3.0, 0.3, 0.8 * l.position[2] / 3.0)) for l in grid_lights(n_lights)]
+        return tex_scene(16, 16, lights, env, abi.LensData(0.05, 1.5) if lens else None)
+    return lit_scene("glass", THREE + grid_lights(n_lights), emitters=1, env=True if env else None, lens=LENS if lens else None, w=16, h=16)
+
+
+SWEEP_CASES = []
+for _u, (_env, _lens) in {"plain": (0, 0), "env": (1, 0), "lens": (0, 1), "lens_env": (1, 1)}.items():
+    for _route in ("exh", "bvh", "bvh_unstaged"):
+        for _fd in (0, 1):
+            for _tex in (0, 1):
+                for _pmj in (0, 1):
+                    _s = 0 if not _pmj else (abi.SAMPLER_SOBOL if (_fd, _tex) == (0, 0) else abi.SAMPLER_PMJ02BN)
+                    SWEEP_CASES.append(add(f"sweep-{_u}-{_route}-fd{_fd}-tex{_tex}-pmj{_pmj}", functools.partial(_sweep_scene, _tex, _env, _lens, _route),
+                                           dict(SWEEP_CFG, force_diffuse=_fd, sampler_type=_s, sampler_seed=7), EXH if _route == "exh" else BVH,
+                                           lens=bool(_lens), stage=_route != "bvh_unstaged", env=_env, fd=_fd, tex=_tex))
+
+# ---------------------------------------------------------------------------------------------------------------- colour pipelines x samplers
+COLOURED = [PL(abi.LIGHT_POINT, position=(1.4, 0.9, 1.2), color=(3.0, 0.5, 1.0), strength=3.0), PL(abi.LIGHT_SUN, direction=(0.3, -1.0, -0.25), color=(0.2, 1.0, 0.6), strength=1.5, angle=0.2),
+            PL(abi.LIGHT_SPOT, blend=0.4, radius=0.1, **dict(_SPOT, color=(4.0, 1.0, 0.3)))]
+COLOURED_AFTER = [PL(abi.LIGHT_POINT, position=(-1.0, 0.5, 1.5), color=(0.3, 1.0, 4.0), strength=2.0), COLOURED[1]]
+PIPELINE_CASES = [add(f"colour-{_s}-{_p}", functools.partial(lit_scene, "coated", COLOURED, emitters=1, floor="alpha"),
+                      dict(BASE, sampler_type=SAMPLERS[_s], sampler_seed=3, color=PIPELINES[_p]), BVH if _s == "pmj02bn" else EXH)
+                  for _s in SAMPLERS for _p in PIPELINES if _s == "independent" or _p in ("srgb_srgb", "acescg")]
+
+# ---------------------------------------------------------------------------------------------------------------- the lens alone
+LENS_CFG = dict(spp=8, spp_per_pass=8, max_depth=5)
+LENS_CASES = []
+for _n in ENV_LIGHTING:
+    for _r, _o in (("exh", EXH), ("bvh", BVH)):
+        LENS_CASES.append(add(f"lens-lighting-{_n}-{_r}", functools.partial(lambda kw: lens_ok_scene(dataclasses.replace(env_scene(material="rough_metal", **kw), lens=LENS)), ENV_LIGHTING[_n]),
+                              LENS_CFG, _o, tags=("lens",), lens=True, punct=False, env=1))
+for _m, (_r, _o) in [(m, r) for m in list(ENV_MATERIALS) + ["force_diffuse"] for r in (("exh", EXH), ("bvh", BVH))]:
+    LENS_CASES.append(add(f"lens-material-{_m}-{_r}", functools.partial(lambda m: lens_ok_scene(dataclasses.replace(env_scene(material="glass" if m == "force_diffuse" else m, emitters=1), lens=LENS)), _m),
+                          dict(LENS_CFG, max_depth=6, force_diffuse=int(_m == "force_diffuse")), _o, tags=("lens",), lens=True, punct=False, env=1, fd=int(_m == "force_diffuse")))
+for _s in SAMPLERS:  # depth >= 7: with a lens the 48 blue-noise columns wrap at the 6th vertex (8 + 7 * 6 = 50)
+    LENS_CASES.append(add(f"lens-deep-{_s}", lambda: lit_scene("glass", [], emitters=2, lens=LENS), dict(spp=8, spp_per_pass=4, max_depth=9, rr_depth=8, sampler_type=SAMPLERS[_s], sampler_seed=9),
+                          BVH if _s == "sobol" else EXH, tags=("lens",), lens=True, punct=False))
+    LENS_CASES.append(add(f"lens-deep-lit-{_s}", lambda: lit_scene("glass", THREE, emitters=1, lens=LENS), dict(spp=8, spp_per_pass=4, max_depth=9, rr_depth=8, sampler_type=SAMPLERS[_s], sampler_seed=9),
+                          EXH if _s == "sobol" else BVH, tags=("lens",), lens=True))
+
+
+def kept_lens_scene():
+    """tests/test_gpu_lens.py's route scene: blobs kept as meshes + instances, the camera inside the box's range, a defocusing lens"""
+    sd = instanced_scene(width=32, height=32, n_inst=4, n=2, emissive_instances=1, textured=True)
+    sd.ggx_table = _ggx()
+    c2w = np.array(sd.camera.c2w, dtype=np.float32)
+    c2w[14] = 5.0
+    sd.camera.c2w = c2w
+    sd.lens = abi.LensData(0.125, 4.0)
+    return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------- scenes of the tests outside the table
+SCHED_SCENE = functools.partial(lit_scene, material="glass", lights=THREE + [LIGHTS["soft_sun"]], emitters=1, env=True)
+WAVEFRONT_LENS_SCENE = functools.partial(lit_scene, "glass", [], emitters=2, env=True, lens=LENS)
+# aov: the albedo of textured surfaces, which a defocused camera ray does change (a flat wall's normal it does not); the lights are there and aov ignores them
+AOV_LENS_SCENE = functools.partial(tex_scene, 32, 32, ROOM_LIGHTS, True, abi.LensData(0.05, 1.5))
+FEAT_LENS_SCENE = functools.partial(lit_scene, "coated", [], emitters=2, env=True, lens=LENS)
+# name -> (scene, make_config's keywords, what must change a quarter of the film's floats)
+EXTRA = {
+    "schedules-independent": (SCHED_SCENE, dict(spp=12, spp_per_pass=5, max_depth=5, rr_depth=2, sampler_seed=4), ("lights",)),
+    "schedules-pmj02bn": (SCHED_SCENE, dict(spp=8, spp_per_pass=4, max_depth=5, rr_depth=2, sampler_type=abi.SAMPLER_PMJ02BN, sampler_seed=6), ("lights",)),
+    "schedules-sobol": (SCHED_SCENE, dict(spp=12, spp_per_pass=4, max_depth=5, rr_depth=2, sampler_type=abi.SAMPLER_SOBOL, sampler_seed=5), ("lights",)),
+    "pipeline-after": (functools.partial(lit_scene, "coated", COLOURED_AFTER, emitters=1, floor="alpha"), dict(BASE, color=PIPELINES["acescg"], sampler_seed=3), ("lights",)),
+    "lens-kept": (kept_lens_scene, dict(spp=8, spp_per_pass=4, max_depth=6, sampler_type=abi.SAMPLER_PMJ02BN, sampler_seed=7), ("lens",)),
+    "lens-wavefront": (WAVEFRONT_LENS_SCENE, dict(spp=8, spp_per_pass=4, max_depth=9, rr_depth=8, sampler_seed=9), ("lens",)),
+    "lens-feat": (FEAT_LENS_SCENE, dict(spp=8, spp_per_pass=4, max_depth=5, sampler_type=abi.SAMPLER_PMJ02BN, sampler_seed=5), ("lens",)),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the oracle's side
+def initial_states(cfg, w, h):
+    """the per-pixel sampler states a session starts from (sampler/mod.rs:702-718): the seeded PCG streams, or {sample_index = u32::MAX, pixel}"""
+    if cfg.sampler_type == abi.SAMPLER_INDEPENDENT:
+        return pyoracle.init_pcg32_states(w * h, cfg.sampler_seed)
+    i = np.arange(w * h, dtype=np.uint64)
+    st = np.zeros(2 * w * h, np.uint64)
+    st[0::2], st[1::2] = 0xFFFFFFFF, (i % np.uint64(w)) | ((i // np.uint64(w)) << np.uint64(32))
+    return st
+
+
+def oracle_render(sd, cfg, film=None, states=None, **kw):
+    """(film, stats, final sampler states) of the oracle; kw: OracleScene's lights = False / lens = False"""
+    w, h = sd.camera.width, sd.camera.height
+    if cfg.sampler_type != abi.SAMPLER_INDEPENDENT:
+        pyoracle.set_pmj_tables(*capi.host_pmj02bn_tables())
+    states = initial_states(cfg, w, h) if states is None else states
+    film, st = pyoracle.OracleScene(sd, **kw).render(cfg, film=film, states=states)
+    return film, st, states
+
+
+def host_plan(sd, cfg, opts):
+    with capi.options(**opts):
+        return capi.Scene(None, sd).launch_plan(cfg, defer_metal=capi.get_option("defer_metal"), simple_kernels=capi.get_option("simple_kernels"), defer_on=capi.get_option("defer_on"))

@@ -61,7 +61,8 @@ def test_nothing_moves_without_a_lens(ctx, cbox_path):
     sd = scene_json.load_scene(cbox_path, w, h)
     cfg = make_config(spp=8, spp_per_pass=4, max_depth=8, sampler_seed=3)
     o_states = pyoracle.init_pcg32_states(w * h, cfg.sampler_seed)
-    o_film, _ = pyoracle.OracleScene(sd).render(cfg, states=o_states)  # (the oracle leaves its final sampler states in o_states)
+    assert sd.lens is None  # the description carries no lens: the oracle's film is the pinhole's (lens=False says so whatever it carried)
+    o_film, _ = pyoracle.OracleScene(sd, lens=False).render(cfg, states=o_states)  # (the oracle leaves its final sampler states in o_states)
     scene = capi.Scene(ctx, sd)
     film, states, info = _session(ctx, scene, cfg)
     assert n_bit_diff(film, o_film) == 0 and np.array_equal(states, o_states)
@@ -184,7 +185,7 @@ def test_in_focus_is_sharp(ctx, sampler):
     sd = _emitter_scene([[-1, -1, -Fd], [1, -1, -Fd], [1, 1, -Fd], [-1, 1, -Fd]], W, H)
     cfg = _focus_cfg(32, sampler)
     # the oracle first: the pinhole film is constant inside the quad
-    o_film, _ = pyoracle.OracleScene(sd).render(cfg)
+    o_film, _ = pyoracle.OracleScene(sd, lens=False).render(cfg)  # the pinhole oracle: the lens is set on the library's scene below, never on sd
     o_img = o_film[: 3 * W * H].reshape(H, W, 3)
     inside = np.zeros((H, W), bool)
     inside[17:47, 17:47] = True
