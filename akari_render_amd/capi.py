@@ -23,9 +23,10 @@ ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_IO, ERR_PARSE, ERR_UNSUPPORTED
  ARRAY_TEX_NODES, ARRAY_TEX_IMAGES, ARRAY_TEX_TEXELS, ARRAY_MAT_INPUTS,
  ARRAY_INST_LEAVES, ARRAY_MESH_TRIS, ARRAY_MESH_POS, ARRAY_MESH_META, ARRAY_MESH_NORMALS,
  ARRAY_ENV_MARGINAL_ENTRIES, ARRAY_ENV_MARGINAL_PDF, ARRAY_ENV_CONDITIONAL_ENTRIES, ARRAY_ENV_CONDITIONAL_PDF, ARRAY_ENV_TEXELS,
- ARRAY_PUNCTUAL_LIGHTS) = range(28)
+ ARRAY_PUNCTUAL_LIGHTS, ARRAY_LIGHT_TREE) = range(29)
 ENV_LIGHT_INSTANCE = 0xFFFFFFFF  # akr_scene_get_light's instance of the environment light
 PUNCTUAL_LIGHT_INSTANCE = 0xFFFFFFFE  # ... of a point, spot or sun light
+LIGHT_TREE_INSTANCE = 0xFFFFFFFD  # ... of the one entry all point and spot lights share in a scene with a light tree (Scene.set_light_tree)
 
 # every symbol include/akari_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
@@ -49,6 +50,7 @@ EXPORTS = [
     "akr_pt_set_active_tiles", "akr_film_tile_error", "akr_adaptive_config_default", "akr_pt_adaptive_render",
     "akr_display_config_default", "akr_film_luminance_histogram", "akr_display_exposure", "akr_display_transform",
     "akr_scene_add_punctual_light", "akr_scene_clear_punctual_lights", "akr_scene_punctual_light_count", "akr_scene_get_punctual_light",
+    "akr_scene_set_light_tree", "akr_scene_get_light_tree",
 ]
 # include/akari_hip_test.h: the test hooks (compiled into the in-tree test build, absent from a build with AKR_SHIP=1)
 TEST_EXPORTS = [
@@ -64,6 +66,7 @@ TEST_EXPORTS = [
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
     "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
     "akr_host_light_sample", "akr_probe_light_sample", "akr_host_light_sample_soft", "akr_probe_light_sample_soft",
+    "akr_host_light_tree_sample", "akr_probe_light_tree_sample",
 ]
 
 
@@ -137,6 +140,10 @@ def lib() -> C.CDLL:
     proto("akr_probe_light_sample", vp, vp, u32, fp, fp, up)
     proto("akr_host_light_sample_soft", vp, u32, fp, fp, up)
     proto("akr_probe_light_sample_soft", vp, vp, u32, fp, fp, up)
+    proto("akr_scene_set_light_tree", vp, u32)
+    proto("akr_scene_get_light_tree", vp, up, up)
+    proto("akr_host_light_tree_sample", vp, u32, fp, fp, up, up)
+    proto("akr_probe_light_tree_sample", vp, vp, u32, fp, fp, up, up)
     proto("akr_host_lens_ray", vp, u32, f32, u32, up, fp, fp)
     proto("akr_probe_camera_rays", vp, vp, u32, f32, u32, up, fp, fp)
     proto("akr_host_pt_launch_plan", vp, C.POINTER(abi.PtConfig), i32, i32, i32, i32, C.POINTER(abi.PtLaunchPlan))
@@ -454,6 +461,33 @@ class Scene:
     def probe_light_sample_soft(self, rows):
         """akr_probe_light_sample_soft (test hook): the same on the device."""
         return self._light_sample(lib().akr_probe_light_sample_soft, (self.ctx.h, self.h), rows, 9)
+
+    def set_light_tree(self, on):
+        """akr_scene_set_light_tree: with `on` and two or more point / spot lights, those lights become one entry of the light list and a light tree
+        chooses among them by power / distance^2."""
+        check(lib().akr_scene_set_light_tree(self.h, 1 if on else 0))
+
+    def light_tree(self):
+        """akr_scene_get_light_tree: (on, n_nodes); n_nodes = 0 when no tree exists."""
+        on, n = C.c_uint32(), C.c_uint32()
+        check(lib().akr_scene_get_light_tree(self.h, C.byref(on), C.byref(n)))
+        return on.value, n.value
+
+    def _light_tree_sample(self, fn, head, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 9)
+        n = rows.shape[0]
+        out, light, record = np.zeros((n, 13), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        check(fn(*head, n, _fp(rows), _fp(out), _up(light), _up(record)))
+        return out, light, record
+
+    def host_light_tree_sample(self, rows):
+        """akr_host_light_tree_sample (test hook, no GPU): rows (n, 9) as host_light_sample_soft -> ((n, 13) with the full pdf in column 6; (n,) the
+        entry of the light list; (n,) the record the tree's walk ended at, 0xFFFFFFFF where the entry was not the tree)."""
+        return self._light_tree_sample(lib().akr_host_light_tree_sample, (self.h,), rows)
+
+    def probe_light_tree_sample(self, rows):
+        """akr_probe_light_tree_sample (test hook): the same on the device."""
+        return self._light_tree_sample(lib().akr_probe_light_tree_sample, (self.ctx.h, self.h), rows)
 
     def set_lens(self, radius: Optional[float] = None, focal_distance: float = 0.0):
         """akr_scene_set_lens: a thin lens of `radius`, focused `focal_distance` along the optical axis. radius None or 0: removes the lens."""

@@ -4,7 +4,7 @@
 // film.rs, sampler/mod.rs, light/{mod,area}.rs of the reference; file:line cited per function.
 #pragma once
 #include "denv.h"
-#include "dpunct.h"
+#include "dlighttree.h"
 #include "dinst_trav.h"
 #include "drng.h"
 #include "../kernels.h"
@@ -290,7 +290,9 @@ struct LightSample {
 // PUNCT: the scene has punctual lights, entries of the light table whose LightRec says kPunctInst (dpunct.h); a choice of
 // one consumes u_select as every choice does; a delta light ignores u_sample, a soft one (a radius, an angle: section 4.15) draws its point from it -- no
 // dimension more.
-template <bool TEX, bool INST = false, bool ENV = false, bool PUNCT = false>
+// LTREE (with PUNCT): the point and spot lights share ONE entry whose LightRec says kPunctTreeInst, and a choice of it walks the scene's light tree
+// with the number the selection left (dlighttree.h) -- no dimension more either.
+template <bool TEX, bool INST = false, bool ENV = false, bool PUNCT = false, bool LTREE = false>
 AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_select, vec2 u_sample, uint32_t color = 0) {
     LightSample s;
     s.li = mk3(0, 0, 0);
@@ -319,8 +321,13 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
         return s;
     }
     const LightRec L = sc.lights[light];
-    if (PUNCT && L.inst == kPunctInst) {
-        const PunctSample ps = punct_sample(sc.punct[L.first_gid], pn_p, pn_n, u_sample, (sc.n_punct & kPunctSoftBit) != 0);
+    if (PUNCT && (L.inst == kPunctInst || (LTREE && L.inst == kPunctTreeInst))) {
+        uint32_t record = L.first_gid;
+        if (LTREE && L.inst == kPunctTreeInst) {  // the point and spot lights' one entry (section 4.16): down the tree with the number the selection left
+            s.delta = true;
+            if (!light_tree_walk((const float4*)(sc.punct + sc.punct_tree), pn_p, u_sel2, light_choice_pdf, record)) return s;
+        }
+        const PunctSample ps = punct_sample(sc.punct[record], pn_p, pn_n, u_sample, (sc.n_punct & kPunctSoftBit) != 0);
         s.li = ps.li;
         s.wi = ps.wi;
         s.ro = ps.ro;
@@ -530,7 +537,7 @@ AKR_D void shifted_pixel(const PtParams& p, uint32_t px, uint32_t py, uint32_t& 
 // for the sample's camera ray -- albedo + emission, shading normal; a miss adds nothing -- goes to the lane's guide accumulators: registers, or
 // with PARK their LDS columns (PK_FEAT_*), where they stay from the first iteration to the lane's last store. No random number is drawn for it.
 // PUNCT: the scene has punctual lights (sample_direct above); nothing changes on a hit or a miss.
-template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false, bool PUNCT = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
+template <int FD = -1, bool TEX = false, bool PMJ = false, int PARK = 0, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false, bool PUNCT = false, bool LTREE = false>  // PARK: 0 no, 1 yes, 2 yes without the DEFER fields; ABSENT: dbsdf.h AB_*; INST: meshes + instances (dinst_trav.h); ENV: the scene has an environment light (denv.h); LENS: the camera has a thin lens (generate_ray)
 AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found, bool occluded, uint32_t pix_in, uint32_t sx_in, uint32_t sy_in,
                      uint32_t* park = nullptr) {
     const bool force_diffuse = FD < 0 ? (p.force_diffuse != 0) : (FD != 0);
@@ -659,7 +666,7 @@ AKR_D void path_step(const PtParams& p, PathRegs& r, const Hit& hit, bool found,
                 LightSample dl;
                 dl.valid = false;
                 if (p.use_nee && (!p.indirect_only || r.depth > 1))
-                    dl = sample_direct<TEX, INST, ENV, PUNCT>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z), p.color);
+                    dl = sample_direct<TEX, INST, ENV, PUNCT, LTREE>(sc, si.p, si.ng, u_direct.x, mk2(u_direct.y, u_direct.z), p.color);
                 vec3 u_bsdf = next_3d<PMJ>(p, r.smp);
                 // sample_surface_and_shade_direct, pt.rs:297-323
                 ShadePoint sp;

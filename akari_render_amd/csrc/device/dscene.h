@@ -76,6 +76,8 @@ struct DEnv {
 // first_gid = the record's index.
 enum : uint32_t { PUNCT_POINT = 0, PUNCT_SPOT = 1, PUNCT_SUN = 2 };
 constexpr uint32_t kPunctInst = 0xfffffffeu;
+// the ONE entry of the light table that stands for all point and spot lights of a scene with a light tree (section 4.16; dlighttree.h): first_gid = 0, no triangles
+constexpr uint32_t kPunctTreeInst = 0xfffffffdu;
 struct DPunct {
     vec3 q;       uint32_t kind;    // position (POINT, SPOT)
     vec3 a;       float cos_o;      // unit axis / direction of travel (SPOT, SUN); cosine of the outer half-angle
@@ -121,7 +123,7 @@ struct DScene {
     DInst in2;                                      // meshes + instances kept as they are (in2.on; else all zero)
     // The punctual lights (DPunct above), or nullptr: a scene with some runs the PUNCT kernels. Last: everything before keeps its offset.
     const DPunct* __restrict__ punct;
-    uint32_t n_punct, _pad_punct;                   // n_punct: count | kPunctSoftBit
+    uint32_t n_punct, punct_tree;                   // n_punct: count | kPunctSoftBit; punct_tree: node 0 of the light tree (section 4.16), in 64-byte records from punct; 0 = no tree
 };
 
 struct SurfacePoint {  // interaction.rs:15-48, minus what this path never reads

@@ -45,9 +45,9 @@ using PairWalkOpt = WalkOpt<!TEX>;
 // ENV: the scene has an environment light (device/denv.h).
 // LENS: the camera has a thin lens (dpath.h generate_ray).
 // FEAT: the session collects the denoiser's albedo and normal guides from its own samples (dpath.h path_step).
-// PUNCT: the scene has punctual lights (device/dpunct.h).
+// PUNCT: the scene has punctual lights (device/dpunct.h). LTREE: ... and a light tree over the point and spot ones (device/dlighttree.h; section 4.16).
 // Which combinations of the flags exist as kernels: kernels.h pt_variant_compiled.
-template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false, bool PUNCT = false>
+template <bool BVH, bool FD, bool TEX, bool PMJ, bool STAGE, bool DEFER, uint32_t ABSENT = 0, bool INST = false, bool ENV = false, bool LENS = false, bool FEAT = false, bool PUNCT = false, bool LTREE = false>
 AKR_D void pt_pass_body(const PtParams& p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];  // BVH: kBvhStackDepth x 256 words; else: staged tables
     TraceCtx tc;
@@ -219,8 +219,8 @@ AKR_D void pt_pass_body(const PtParams& p) {
             }
             if (STRAG > 0 && r.carry) {
                 // still tracing: nothing to resolve or shade yet
-            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV, LENS, FEAT, PUNCT>(q, r, hit, found, occluded, 0, 0, 0, park);
-            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS, FEAT, PUNCT>(q, r, hit, found, occluded, pix, sx, sy);
+            } else if (PARK) path_step<FD ? 1 : 0, TEX, PMJ, DEFER ? 1 : 2, ABSENT, INST, ENV, LENS, FEAT, PUNCT, LTREE>(q, r, hit, found, occluded, 0, 0, 0, park);
+            else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS, FEAT, PUNCT, LTREE>(q, r, hit, found, occluded, pix, sx, sy);
         }
     }
     flush_counters(p, r, tc.cnt, BVH);

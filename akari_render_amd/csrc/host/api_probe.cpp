@@ -282,6 +282,37 @@ AKR_TEST_API int32_t akr_probe_light_sample(akr_context* ctx, akr_scene* scene, 
     if (!ctx || !scene || !rows7 || !out13 || !light) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_sample: NULL argument");
     return akr_probe_light_sample_soft(ctx, scene, n, rows9_of_rows7(n, rows7).data(), out13, light);
 }
+// the same rows over a scene that may have a light tree (device/dlighttree.h)
+AKR_TEST_API int32_t akr_host_light_tree_sample(const akr_scene* scene, uint32_t n, const float* rows9, float* out13, uint32_t* light, uint32_t* record) {
+    if (!scene || !rows9 || !out13 || !light || !record) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_light_tree_sample: NULL argument");
+    return guarded([&] {
+        std::vector<AliasPacked> la, aa;
+        std::vector<LightRec> lr;
+        packed_light_tables(scene->cs, la, aa, lr);
+        const std::vector<DPunct> recs = punctual_device_records(scene->cs.punct, scene->cs.punct_tree);
+        const uint32_t tree = scene->cs.punct_tree.empty() ? 0u : (uint32_t)scene->cs.punct.size();
+        for (uint32_t i = 0; i < n; i++) light_tree_probe_row(la.data(), lr.data(), recs.data(), tree, scene->cs.n_lights, rows9 + 9ull * i, out13 + 13ull * i, light + i, record + i);
+    });
+}
+AKR_TEST_API int32_t akr_probe_light_tree_sample(akr_context* ctx, akr_scene* scene, uint32_t n, const float* rows9, float* out13, uint32_t* light, uint32_t* record) {
+    if (!ctx || !scene || !rows9 || !out13 || !light || !record) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_tree_sample: NULL argument");
+    if (scene->ctx != ctx) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_light_tree_sample: the scene was not created on this context");
+    return guarded([&] {
+        ctx->bind();
+        DevBuf din, dout, dl, dr;
+        din.upload(std::vector<float>(rows9, rows9 + 9ull * n));
+        dout.alloc(13ull * n * 4);
+        dl.alloc(4ull * n);
+        dr.alloc(4ull * n);
+        if (n) HIP_CHECK(launch_probe_light_tree_sample(probe_params(scene), n, din.as<float>(), dout.as<float>(), dl.as<uint32_t>(), dr.as<uint32_t>(), ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (n) {
+            HIP_CHECK(hipMemcpy(out13, dout.p, 13ull * n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(light, dl.p, 4ull * n, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(record, dr.p, 4ull * n, hipMemcpyDeviceToHost));
+        }
+    });
+}
 // the camera's ray generation (device/dpath.h): the parameter block's camera part, filled by the sessions' own function
 static PtParams probe_camera_params(const akr_scene* s, uint32_t filter_type, float filter_radius) {
     PtParams p;

@@ -15,7 +15,7 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
 PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
     const CompiledScene& cs = s->cs;  // (stage, defer, simple: pt_plan)
     return PtVariant{cs.has_tree(), c.force_diffuse != 0, cs.has_textures, c.sampler_type != AKR_SAMPLER_INDEPENDENT, false, false, false,
-                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f, false, !cs.punct.empty()};
+                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f, false, !cs.punct.empty(), !cs.punct_tree.empty()};
 }
 std::string akr_api::pt_punctual_refusal(const akr_scene* s, const TuningOptions& t) {
     if (s->cs.punct.empty()) return "";
@@ -518,7 +518,7 @@ void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, con
     if (cfg->color != 0 && !scene->cs.punct.empty() && !scene->color_sets.at(cfg->color)->punct.p) {  // (dropped when the lights change: api_scene.cpp)
         std::vector<DPunct> recs;
         for (const akr_punctual_light_desc& d : scene->flat.punct) recs.push_back(fold_punctual(d, cfg->color));
-        scene->color_sets.at(cfg->color)->punct.upload(recs);
+        scene->color_sets.at(cfg->color)->punct.upload(punctual_device_records(recs, scene->cs.punct_tree));  // (the tree's nodes are the same in every set)
     }
     if (cfg->color != 0) se->color_set = scene->color_sets.at(cfg->color).get();  // stable: the map owns it through a unique_ptr
     color_lock.unlock();
@@ -816,7 +816,8 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         info->specialised = se->spec_active ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
         const PtVariant& v = se->variant;  // (bit 0: the flattened scene's tree; a kept scene's two-level traversal does not set it)
-        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u) | (v.punct ? 128u : 0u);
+        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u) | (v.punct ? 128u : 0u) |
+                             (v.ltree ? 256u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;

@@ -36,14 +36,24 @@ static void pack_alias(const std::vector<AliasEntry>& e, const std::vector<float
 }
 void akr_api::packed_light_tables(const CompiledScene& cs, std::vector<AliasPacked>& la, std::vector<AliasPacked>& aa, std::vector<LightRec>& lr) {
     pack_alias(cs.light_entries, cs.light_pdf, 0, cs.n_lights, la);
+    // a punctual light's own entry says where its record is: the next one, or with a light tree (only the suns have entries of their own then) the next sun's
     uint32_t n_punct = 0;
+    auto next_record = [&] {
+        if (!cs.punct_tree.empty())
+            while (n_punct < cs.punct.size() && cs.punct[n_punct].kind != PUNCT_SUN) n_punct++;
+        return n_punct++;
+    };
     for (uint32_t l = 0; l < cs.n_lights; l++) {
         if (cs.light_inst[l] == 0xffffffffu) {  // the environment (no triangles)
             lr.push_back(LightRec{cs.light_tri_offset[l], 0u, 0u, 0xffffffffu});
             continue;
         }
         if (cs.light_inst[l] == kPunctInst) {  // a punctual light (no triangles): first_gid = its record in DScene.punct
-            lr.push_back(LightRec{cs.light_tri_offset[l], 0u, n_punct++, kPunctInst});
+            lr.push_back(LightRec{cs.light_tri_offset[l], 0u, next_record(), kPunctInst});
+            continue;
+        }
+        if (cs.light_inst[l] == kPunctTreeInst) {  // all point and spot lights: the walk finds the record
+            lr.push_back(LightRec{cs.light_tri_offset[l], 0u, 0u, kPunctTreeInst});
             continue;
         }
         pack_alias(cs.area_entries, cs.area_pdf, cs.light_tri_offset[l], cs.light_n_tris[l], aa);
@@ -59,7 +69,7 @@ static void upload_lights(akr_scene* s) {
     s->light_inst.upload(cs.light_inst);
     s->light_tri_offset.upload(cs.light_tri_offset);
     s->light_n_tris.upload(cs.light_n_tris);
-    s->punct.upload(cs.punct);
+    s->punct.upload(punctual_device_records(cs.punct, cs.punct_tree));
     {  // the light tables once more, packed so that each level of light sampling is ONE gather (device/dgeom.h, dscene.h)
         auto pack = pack_alias;
         std::vector<AliasPacked> la, aa;
@@ -114,6 +124,7 @@ static void upload_lights(akr_scene* s) {
     d.n_punct = (uint32_t)cs.punct.size();
     for (const DPunct& r : cs.punct)  // (the size is not a matter of the colour pipeline: the colour sets' records have it where these do)
         if (r.radius != 0.0f || r.cos_max != 0.0f) d.n_punct |= kPunctSoftBit;
+    d.punct_tree = cs.punct_tree.empty() ? 0u : (uint32_t)cs.punct.size();
 }
 static void count_device_bytes(akr_scene* s) {
     s->device_bytes = 0;
@@ -266,7 +277,7 @@ static uint64_t compiled_scene_bytes(const CompiledScene& cs) {
                  b(cs.light_inst) + b(cs.light_tri_offset) + b(cs.light_n_tris) + b(cs.area_entries) + b(cs.area_pdf) + b(cs.inst_tri_offset) +
                  16ull * (cs.light_entries.size() + cs.area_entries.size() + cs.n_lights) + b(cs.bvh_nodes) + b(cs.tex_nodes) + b(cs.images) + b(cs.texels) +
                  b(cs.mat_inputs);
-    n += b(cs.punct);
+    n += (uint64_t)punctual_device_records(cs.punct, cs.punct_tree).size() * sizeof(DPunct);
     n += b(cs.env.texels) + 16ull * (cs.env.marginal_entries.size() + cs.env.conditional_entries.size()) + (cs.env.on ? sizeof(DEnv) : 0u);
     const CompiledScene::Instanced& is = cs.instanced;
     return n + b(is.nodes) + b(is.tlas_leaves) + b(is.mesh_tris) + b(is.mesh_pos) + b(is.mesh_meta) + b(is.mesh_normals) + b(is.inst_mats) + (is.on ? std::max<uint64_t>(((uint64_t)cs.n_tris + 31u) / 32u, 1u) * 4u : 0u);
@@ -281,6 +292,7 @@ AKR_API int32_t akr_scene_create(akr_context* ctx, const akr_scene_desc* desc, a
         auto s = std::make_unique<akr_scene>();
         s->ctx = ctx;
         s->flat = FlatScene::from_desc(*desc);
+        s->flat.light_tree = tuning().light_tree;
         scene_finish(s.get());
         *out = s.release();
     });
@@ -292,6 +304,7 @@ AKR_API int32_t akr_scene_load(akr_context* ctx, const char* path, uint32_t widt
         auto s = std::make_unique<akr_scene>();
         s->ctx = ctx;
         s->flat = load_scene_json(path);
+        s->flat.light_tree = tuning().light_tree;
         if (width && height) {
             s->flat.camera.width = width;
             s->flat.camera.height = height;
@@ -402,6 +415,27 @@ AKR_API int32_t akr_scene_clear_punctual_lights(akr_scene* s) {
         s->flat.punct.clear();
         punctual_lights_changed(s, before);
     });
+}
+AKR_API int32_t akr_scene_set_light_tree(akr_scene* s, uint32_t on) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_light_tree: scene is NULL");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_set_light_tree: a session holds the scene (end it first)");
+        const int before_mode = s->flat.light_tree;
+        s->flat.light_tree = on ? 1 : 0;
+        std::vector<akr_punctual_light_desc> before = s->flat.punct;
+        try {
+            punctual_lights_changed(s, before);
+        } catch (...) {
+            s->flat.light_tree = before_mode;
+            throw;
+        }
+    });
+}
+AKR_API int32_t akr_scene_get_light_tree(const akr_scene* s, uint32_t* on, uint32_t* n_nodes) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_light_tree: scene is NULL");
+    if (on) *on = s->flat.light_tree != 0 ? 1u : 0u;
+    if (n_nodes) *n_nodes = (uint32_t)(s->cs.punct_tree.size() / 8);
+    return AKR_OK;
 }
 AKR_API int32_t akr_scene_punctual_light_count(const akr_scene* s, uint32_t* count) {
     if (!s || !count) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_punctual_light_count: NULL argument");
@@ -541,6 +575,7 @@ AKR_API int32_t akr_scene_get_array(const akr_scene* s, int32_t which, const voi
         case AKR_ARRAY_ENV_CONDITIONAL_PDF: set(cs.env.conditional_pdf.data(), cs.env.conditional_pdf.size() * 4); break;
         case AKR_ARRAY_ENV_TEXELS: set(cs.env.texels.data(), cs.env.texels.size() * 4); break;
         case AKR_ARRAY_PUNCTUAL_LIGHTS: set(cs.punct.data(), cs.punct.size() * sizeof(DPunct)); break;
+        case AKR_ARRAY_LIGHT_TREE: set(cs.punct_tree.data(), cs.punct_tree.size() * 4); break;
         default: return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: unknown array id");
     }
     return AKR_OK;

@@ -1,6 +1,6 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
+//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--light-tree] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
 //             [--adaptive [X]] [--adaptive-min-spp N] [--display [linear|reinhard|aces|hable]] [--exposure EV] [--auto-exposure] [--bloom [X]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
@@ -8,6 +8,7 @@
 // through the thin lens of the scene file's focal_distance and fstop (library option "lens"); --lens-radius / --focal-distance override the file's values.
 // --no-punctual-lights (library option "punctual_lights" = 0): the scene file's point, spot and sun lights are dropped, which is how the reference renders it.
 // --no-soft-lights (library option "soft_lights" = 0): the file's lights are loaded with radius 0 and angle 0, so every shadow they cast has a hard edge.
+// --light-tree (library option "light_tree" = 1): the file's point and spot lights are chosen among by a light tree, by power / distance^2.
 // --denoise [N] (library option "denoise"): every pt task also writes {stem}.denoised{ext}, filtered with albedo / normal passes of N spp (16 when N is left out).
 // --denoise-variance (library option "denoise_variance", with --denoise): the filter's colour weights come from the variance between the two halves of the task's passes.
 // --denoise-features (library option "denoise_features"; implies the denoise step): the filter's albedo / normal guides are collected by the pt task's own samples,
@@ -29,7 +30,7 @@
 
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
-              "                 [--resolution <W>x<H>] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
+              "                 [--resolution <W>x<H>] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--light-tree] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
               "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
               "                 [--display [linear|reinhard|aces|hable]] [--exposure <EV>] [--auto-exposure] [--bloom [<X>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
@@ -39,6 +40,7 @@ static void usage() {
               "      --save-intermediate  write {name}-{spp}.exr after every pass\n"
               "      --save-stats <NAME>  write NAME.json (RenderStats) and use NAME for intermediate files\n"
               "      --no-punctual-lights drop the scene file's point, spot and sun lights (default: they light the scene)\n"
+              "      --light-tree         choose among the scene file's point and spot lights with a light tree, by power / distance^2 (default: by power alone)\n"
               "      --no-soft-lights     load the scene file's lights with radius 0 and angle 0: hard shadows (default: soft shadows where the file gives a size)\n"
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
@@ -72,7 +74,7 @@ int main(int argc, char** argv) {
     std::string scene, method, name;
     int device = 0, verbose = 0, save_intermediate = 0, save_stats = 0, indep = 0;
     unsigned w = 0, h = 0;
-    int dof = 0, no_punctual = 0, no_soft = 0;
+    int dof = 0, no_punctual = 0, no_soft = 0, light_tree = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
     int denoise = 0, denoise_variance = 0, denoise_features = 0;
     int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
@@ -90,6 +92,7 @@ int main(int argc, char** argv) {
         else if (a == "--depth-of-field") dof = 1;
         else if (a == "--no-punctual-lights") no_punctual = 1;
         else if (a == "--no-soft-lights") no_soft = 1;
+        else if (a == "--light-tree") light_tree = 1;
         else if (a == "--denoise") {  // the number is optional: taken only if the next argument is one
             denoise = 16;
             if (i + 1 < argc) {
@@ -188,6 +191,7 @@ int main(int argc, char** argv) {
     if (dof && akr_option_set("lens", 1) != AKR_OK) die("option lens");
     if (no_punctual && akr_option_set("punctual_lights", 0) != AKR_OK) die("option punctual_lights");
     if (no_soft && akr_option_set("soft_lights", 0) != AKR_OK) die("option soft_lights");
+    if (light_tree && akr_option_set("light_tree", 1) != AKR_OK) die("option light_tree");
     if (denoise && akr_option_set("denoise", denoise) != AKR_OK) die("option denoise");
     if (denoise_features && akr_option_set("denoise_features", 1) != AKR_OK) die("option denoise_features");
     if (denoise_variance && !denoise && !denoise_features) { std::fputs("akari-cli: --denoise-variance needs --denoise or --denoise-features\n", stderr); return 1; }

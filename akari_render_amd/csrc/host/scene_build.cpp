@@ -830,6 +830,7 @@ void tuning_init_locked() {
     if (const char* e = std::getenv("AKR_LENS")) g_tuning.lens = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_PUNCTUAL_LIGHTS")) g_tuning.punctual_lights = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_SOFT_LIGHTS")) g_tuning.soft_lights = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("AKR_LIGHT_TREE")) g_tuning.light_tree = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("AKR_INSTANCING")) g_tuning.instancing = std::atoi(e);
     if (const char* e = std::getenv("AKR_WF_GROUPS")) g_tuning.wf_groups = std::max(0, std::min(32, std::atoi(e)));
     if (const char* e = std::getenv("AKR_WF_CARRY")) g_tuning.wf_carry = std::max(0, std::min(1 << 30, std::atoi(e)));
@@ -863,6 +864,7 @@ int* tuning_field(const char* name) {
     if (n == "lens") return &g_tuning.lens;
     if (n == "punctual_lights") return &g_tuning.punctual_lights;
     if (n == "soft_lights") return &g_tuning.soft_lights;
+    if (n == "light_tree") return &g_tuning.light_tree;
     if (n == "instancing") return &g_tuning.instancing;
     if (n == "arith") return &g_tuning.arith;
     if (n == "rebraid") return &g_tuning.rebraid;
@@ -902,6 +904,7 @@ bool tuning_set(const char* name, int value) {
     if (f == &g_tuning.lens && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.punctual_lights && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.soft_lights && (value < 0 || value > 1)) return false;
+    if (f == &g_tuning.light_tree && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.instancing && (value < -1 || value > 1)) return false;
     if (f == &g_tuning.arith && (value < 0 || value > 1)) return false;
     if (f == &g_tuning.rebraid && (value < 1 || value > 64)) return false;

@@ -69,6 +69,7 @@ struct FlatScene {
     std::vector<HostGraph> graphs;  // empty, or one per material
     HostEnvironment env;
     std::vector<akr_punctual_light_desc> punct;  // akr_scene_add_punctual_light / scene.json "lights": checked, as given (scene_punct.cpp; not part of akr_scene_desc)
+    int light_tree = 0;  // akr_scene_set_light_tree, initially option `light_tree`: 1 = the point and spot lights are ONE entry of the light table, chosen among by a light tree
     HostLens lens;  // akr_scene_set_lens, or the file's focal_distance / fstop under option `lens` (not part of akr_scene_desc)
     static FlatScene from_desc(const akr_scene_desc& d);
 };
@@ -140,6 +141,9 @@ struct CompiledScene {
     // the punctual lights' records under the default colour pipeline (scene_punct.cpp; device/dscene.h DPunct): their entries in the light table come after
     // the emissive instances' and before the environment's, light_inst = kPunctInst
     std::vector<DPunct> punct;
+    // the light tree over the point and spot lights (device/dlighttree.h): 2 L - 1 nodes of 8 words, `lo.xyz, power | hi.xyz, child`, breadth-first; empty = no
+    // tree. With one, those lights share ONE entry of the light table (light_inst = kPunctTreeInst) behind the suns; `punct` keeps every record in the order given.
+    std::vector<uint32_t> punct_tree;
     bool has_textures = false;
     bool has_alpha = false;
     bool needs_ggx_table = false;
@@ -233,6 +237,8 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 //   lens         AKR_LENS=1               akr_scene_load gives the camera the thin lens of the file's focal_distance and fstop (the reference reads both and renders a pinhole)
 //   punctual_lights AKR_PUNCTUAL_LIGHTS=0 akr_scene_load drops the file's point / spot / sun lights (the reference's lights collection has no implementation)
 //   soft_lights  AKR_SOFT_LIGHTS=0        akr_scene_load loads every light with radius 0 and angle 0: delta lights, hard shadows
+//   light_tree   AKR_LIGHT_TREE=1         the initial mode of scenes from akr_scene_load / akr_scene_create (akr_scene_set_light_tree changes it): 1 = the point and spot lights
+//                                         are one entry of the light table and a light tree chooses among them by power / distance^2; 0 (default) = one entry each
 //   wf_sort      AKR_WF_SORT=1            wavefront schedule: ray queues sorted by origin cell + direction octant before each trace launch
 //   wf_groups    AKR_WF_GROUPS=<g>        wavefront schedule: the slots run as g groups with queues and streams of their own (api_pt.cpp wf_run); 0 = the library decides
 //   wf_carry     AKR_WF_CARRY=0           wavefront schedule: 0 = every trace launch traces its rays to the end (1, default: a wave that finds the queue empty and
@@ -268,6 +274,7 @@ struct TuningOptions {
                            // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
     int punctual_lights = 1;  // akr_scene_load: 1 = the file's point / spot / sun lights light the scene; 0 = dropped, as the reference renders every file
     int soft_lights = 1;  // akr_scene_load: 1 = the file's lights keep their radius / angle; 0 = every light is loaded as a delta light
+    int light_tree = 0;  // akr_scene_load / akr_scene_create: the scene's initial light-tree mode; 0 = selection among all lights by power alone
     int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
     int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
     int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
@@ -303,6 +310,10 @@ bool punctual_from_desc(const akr_punctual_light_desc& d, akr_punctual_light_des
 DPunct fold_punctual(const akr_punctual_light_desc& d, uint32_t color);  // the record under the colour pipeline `color`
 // the punctual lights of `flat` into `out` (records, light-table entries); replaces those `out` has. After compile_scene; the environment's entry stays last.
 void compile_punctual(const FlatScene& flat, CompiledScene& out);
+// the light tree's node words over the point and spot lights among `recs` (weights: every record's f32 selection weight); empty with fewer than two of them
+std::vector<uint32_t> build_light_tree(const std::vector<DPunct>& recs, const std::vector<float>& weights);
+// what DScene.punct points at: the records and, behind them, the tree's nodes padded to whole 64-byte records (DScene.punct_tree = recs.size() with a tree)
+std::vector<DPunct> punctual_device_records(const std::vector<DPunct>& recs, const std::vector<uint32_t>& tree);
 float triangle_emission_power(const CompiledScene& out, const TexScene& host_tex, uint32_t material, uint32_t prim, vec2 uv0, vec2 uv1, vec2 uv2, float area);
 bool instance_may_emit(const CompiledScene& out, const std::vector<akr_material_desc>& descs, const HostInstance& in);
 // scene_inst.cpp: does this scene take the two-level route, and its geometry + light tables if so (materials and the instance table

@@ -1,12 +1,14 @@
 // scene_punct.cpp -- the punctual lights on the host (DESIGN.md sections 4.14 and 4.15): the description checked, the 64-byte record the kernels read
 // (device/dscene.h DPunct; folded in double, each value rounded once) and the lights' entries in the light table, between the emissive instances and
-// the environment.
+// the environment; and the light tree over the point and spot lights (section 4.16; device/dlighttree.h walks it), which gives them one entry in place of theirs.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 
 #include "scene_build.h"
+#include "../device/dlighttree.h"
 
 namespace akr {
 
@@ -92,14 +94,125 @@ static float punctual_power(const DPunct& r, double R) {
     return (float)(((M_PI * R) * R) * m);
 }
 
+// The light tree over the point and spot lights (device/dlighttree.h walks it). items: per local light its record's index in
+// `recs` (the order given) and its f32 selection weight. A range of n >= 2 items splits at the object median of the positions along the axis of their
+// largest f32 extent (ties: the lowest axis), sorted by (q[axis], index); the left child gets (n + 1) / 2. Deterministic, single-threaded.
+namespace {
+struct TreeItem {
+    uint32_t record;
+    float power;
+};
+struct BuildNode {
+    float lo[3], hi[3], power;
+    int left = -1, right = -1;  // BuildNode indices; a leaf has neither
+    uint32_t record = 0;
+};
+float comp(const vec3& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
+int build_range(const std::vector<DPunct>& recs, std::vector<TreeItem>& items, size_t first, size_t n, std::vector<BuildNode>& nodes) {
+    const int me = (int)nodes.size();
+    nodes.emplace_back();
+    if (n == 1) {
+        const DPunct& r = recs[items[first].record];
+        BuildNode& b = nodes[me];
+        for (int a = 0; a < 3; a++) {
+            b.lo[a] = comp(r.q, a) - r.radius;
+            b.hi[a] = comp(r.q, a) + r.radius;
+        }
+        b.power = items[first].power;
+        b.record = items[first].record;
+        return me;
+    }
+    int axis = 0;
+    float best = -1.0f;
+    for (int a = 0; a < 3; a++) {
+        float mn = comp(recs[items[first].record].q, a), mx = mn;
+        for (size_t k = 1; k < n; k++) {
+            const float v = comp(recs[items[first + k].record].q, a);
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+        }
+        const float ext = mx - mn;
+        if (ext > best) {
+            best = ext;
+            axis = a;
+        }
+    }
+    std::sort(items.begin() + first, items.begin() + first + n, [&](const TreeItem& x, const TreeItem& y) {
+        const float qx = comp(recs[x.record].q, axis), qy = comp(recs[y.record].q, axis);
+        return qx < qy || (qx == qy && x.record < y.record);
+    });
+    const size_t nl = (n + 1) / 2;
+    const int l = build_range(recs, items, first, nl, nodes);
+    const int r = build_range(recs, items, first + nl, n - nl, nodes);
+    BuildNode& b = nodes[me];
+    const BuildNode &L = nodes[l], &R = nodes[r];
+    for (int a = 0; a < 3; a++) {
+        b.lo[a] = L.lo[a] < R.lo[a] ? L.lo[a] : R.lo[a];
+        b.hi[a] = L.hi[a] > R.hi[a] ? L.hi[a] : R.hi[a];
+    }
+    b.power = L.power + R.power;
+    b.left = l;
+    b.right = r;
+    return me;
+}
+}  // namespace
+
+std::vector<uint32_t> build_light_tree(const std::vector<DPunct>& recs, const std::vector<float>& weights) {
+    std::vector<TreeItem> items;
+    for (size_t k = 0; k < recs.size(); k++)
+        if (recs[k].kind != PUNCT_SUN) items.push_back(TreeItem{(uint32_t)k, weights[k]});
+    std::vector<uint32_t> words;
+    if (items.size() < 2) return words;
+    std::vector<BuildNode> nodes;
+    nodes.reserve(2 * items.size());
+    build_range(recs, items, 0, items.size(), nodes);
+    // breadth-first from a queue, root = node 0; the children of an inner node taken off the queue get the next two indices
+    std::vector<int> order{0};
+    std::vector<uint32_t> child_of;
+    for (size_t head = 0; head < order.size(); head++) {
+        const BuildNode& b = nodes[order[head]];
+        if (b.left < 0) {
+            child_of.push_back(kLightTreeLeafBit | b.record);
+            continue;
+        }
+        child_of.push_back((uint32_t)order.size());
+        order.push_back(b.left);
+        order.push_back(b.right);
+    }
+    words.resize(8 * order.size());
+    for (size_t k = 0; k < order.size(); k++) {
+        const BuildNode& b = nodes[order[k]];
+        const float f[7] = {b.lo[0], b.lo[1], b.lo[2], b.power, b.hi[0], b.hi[1], b.hi[2]};
+        std::memcpy(&words[8 * k], f, sizeof f);
+        words[8 * k + 7] = child_of[k];
+    }
+    return words;
+}
+
+std::vector<DPunct> punctual_device_records(const std::vector<DPunct>& recs, const std::vector<uint32_t>& tree) {
+    std::vector<DPunct> all = recs;
+    if (!tree.empty()) {
+        all.resize(recs.size() + (tree.size() * 4 + sizeof(DPunct) - 1) / sizeof(DPunct));
+        std::memset((void*)(all.data() + recs.size()), 0, (all.size() - recs.size()) * sizeof(DPunct));
+        std::memcpy((void*)(all.data() + recs.size()), tree.data(), tree.size() * 4);
+    }
+    return all;
+}
+
 void compile_punctual(const FlatScene& flat, CompiledScene& out) {
     if (flat.punct.empty() && out.punct.empty()) return;  // (a scene without one keeps its tables exactly as compile_scene made them)
+    size_t n_local = 0;
+    for (const akr_punctual_light_desc& d : flat.punct) n_local += d.type != AKR_LIGHT_SUN ? 1u : 0u;
+    const bool tree = flat.light_tree != 0 && n_local >= 2;  // (section 4.16: otherwise every table is what the scene without the mode has)
+    size_t had = 0;  // the entries the lights have in the table now: behind the emissive instances', before the environment's
+    for (uint32_t i : out.light_inst) had += (i == kPunctInst || i == kPunctTreeInst) ? 1u : 0u;
     if (!flat.punct.empty()) {
         const std::string who = std::string(punct_kind_name(flat.punct[0].type)) + " light";
         if (out.instanced.on)
             throw std::runtime_error("unsupported: the scene has a " + who + " and is kept as meshes + instances (option instancing); the kernels of kept scenes sample no punctual lights");
         if (out.bvh_nodes.empty()) {  // the exhaustive kernels read the light tables from LDS: scene_build.cpp sized the fit without these entries
-            if (exhaustive_stage_bytes(out, out.light_inst.size() - out.punct.size() + flat.punct.size()) > kStageMaxBytes) throw std::runtime_error("unsupported: the scene's shading tables with its " + who + "s pass the exhaustive kernels' LDS budget");
+            const size_t entries = tree ? flat.punct.size() - n_local + 1 : flat.punct.size();
+            if (exhaustive_stage_bytes(out, out.light_inst.size() - had + entries) > kStageMaxBytes) throw std::runtime_error("unsupported: the scene's shading tables with its " + who + "s pass the exhaustive kernels' LDS budget");
         }
     }
     // the environment's entry is the last: taken off, put back behind the punctual lights
@@ -117,8 +230,9 @@ void compile_punctual(const FlatScene& flat, CompiledScene& out) {
         env_power = out.light_power.back();
         pop();
     }
-    for (size_t k = 0; k < out.punct.size(); k++) pop();
+    for (size_t k = 0; k < had; k++) pop();
     out.punct.clear();
+    out.punct_tree.clear();
     double r2 = 0.0;
     for (int a = 0; a < 3; a++) {
         const double ext = (double)out.scene_hi[a] - (double)out.scene_lo[a];
@@ -126,13 +240,25 @@ void compile_punctual(const FlatScene& flat, CompiledScene& out) {
     }
     double R = 0.5 * std::sqrt(r2);
     if (!(R > 0.0) || !std::isfinite(R)) R = 1.0;
+    auto push = [&](uint32_t inst, float power) {
+        out.light_inst.push_back(inst);
+        out.light_power.push_back(power);
+        out.light_tri_offset.push_back((uint32_t)out.area_entries.size());
+        out.light_n_tris.push_back(0);
+    };
+    std::vector<float> weights;
     for (const akr_punctual_light_desc& d : flat.punct) {
         const DPunct r = fold_punctual(d, 0);
         out.punct.push_back(r);
-        out.light_inst.push_back(kPunctInst);
-        out.light_power.push_back(punctual_power(r, R));
-        out.light_tri_offset.push_back((uint32_t)out.area_entries.size());
-        out.light_n_tris.push_back(0);
+        weights.push_back(punctual_power(r, R));
+        if (!tree || r.kind == PUNCT_SUN) push(kPunctInst, weights.back());
+    }
+    if (tree) {  // one entry for all point and spot lights, behind the suns: the sum of their weights in double, rounded once
+        double sum = 0.0;
+        for (size_t k = 0; k < out.punct.size(); k++)
+            if (out.punct[k].kind != PUNCT_SUN) sum += (double)weights[k];
+        push(kPunctTreeInst, (float)sum);
+        out.punct_tree = build_light_tree(out.punct, weights);
     }
     if (env) {
         out.light_inst.push_back(env_entry[0]);

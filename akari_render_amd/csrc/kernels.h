@@ -15,7 +15,8 @@
 struct PtVariant {
     bool bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens;
     bool feat;  // the session collects the denoiser's guides (device/dpath.h FEAT). After the ten: aggregate initialisers without it mean feat = false
-    bool punct;  // the scene has punctual lights (device/dpunct.h PUNCT). Last, for the same reason
+    bool punct;  // the scene has punctual lights (device/dpunct.h PUNCT). After feat, for the same reason
+    bool ltree;  // ... and a light tree over the point and spot ones (device/dlighttree.h LTREE): the PUNCT kernels that walk it. Last, for the same reason
 };
 // The combinations that exist as precompiled kernels -- the one statement of the exclusion rules: the exhaustive kernels always stage;
 // DEFER only in full-graph kernels, of BVH scenes those with textures; SIMPLE only in full-graph kernels of scenes without textures;
@@ -23,16 +24,16 @@ struct PtVariant {
 // SIMPLE, collects no guides and has no punctual lights; nor does a session that collects guides.
 constexpr bool pt_variant_compiled(const PtVariant& v) {
     return (v.bvh || v.stage) && !(v.defer && (v.fd || (v.bvh && !v.tex))) && !(v.simple && (v.fd || v.tex)) && !((v.env || v.lens || v.feat || v.punct) && (v.defer || v.simple)) &&
-           !(v.inst && !(v.bvh && !v.stage && !v.defer && !v.simple && !v.feat)) && !(v.punct && (v.feat || v.inst));
+           !(v.inst && !(v.bvh && !v.stage && !v.defer && !v.simple && !v.feat)) && !(v.punct && (v.feat || v.inst)) && !(v.ltree && !v.punct);
 }
 // The flags of a per-scene kernel request as one integer: akr_host_spec_compile(_text), the helper process's command line (fd = false,
 // tex = true, no SIMPLE: a per-scene kernel is the full-graph kernel of a scene with textures).
 constexpr uint32_t pt_variant_bits(const PtVariant& v) {
     return (v.bvh ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (v.inst ? 16u : 0u) | (v.env ? 32u : 0u) | (v.lens ? 64u : 0u) |
-           (v.feat ? 128u : 0u) | (v.punct ? 256u : 0u);  // (neither is ever set in a per-scene kernel's request: FEAT sessions and scenes with punctual lights run the interpreter kernels)
+           (v.feat ? 128u : 0u) | (v.punct ? 256u : 0u) | (v.ltree ? 512u : 0u);  // (neither is ever set in a per-scene kernel's request: FEAT sessions and scenes with punctual lights run the interpreter kernels)
 }
 constexpr PtVariant pt_variant_from_bits(uint32_t f) {
-    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0, (f & 128u) != 0, (f & 256u) != 0};
+    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0, (f & 128u) != 0, (f & 256u) != 0, (f & 512u) != 0};
 }
 // pt_lds_layout (below): what it is given ...
 struct PtLdsSizes {
@@ -292,6 +293,7 @@ inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds
 hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_inst_kernels.hip: once per kept scene (DInst::share_bits)
 hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
 hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, hipStream_t stream);  // pt_punct_kernels.hip: test hook
+hipError_t launch_probe_light_tree_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, uint32_t* record, hipStream_t stream);  // ... the same over a light tree
 // pt_lens_kernels.hip, test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
 hipError_t launch_probe_camera_rays(const PtParams& p, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6, hipStream_t stream);
 // One pass launch of a pt session: lays the LDS out (pt_lds_layout) and goes to the translation unit that holds the variant's kernel

@@ -214,6 +214,8 @@ static constexpr PtPassEntry kPtPassEntry[2][2][2] = {{{pt_pass_entry_plain, pt_
 static constexpr PtPassEntry kPtPassEntryFeat[2][2] = {{pt_pass_entry_feat, pt_pass_entry_feat_lens}, {pt_pass_entry_feat_env, pt_pass_entry_feat_lens_env}};
 // ... those of scenes with punctual lights likewise
 static constexpr PtPassEntry kPtPassEntryPunct[2][2] = {{pt_pass_entry_punct, pt_pass_entry_punct_lens}, {pt_pass_entry_punct_env, pt_pass_entry_punct_lens_env}};
+// ... and of those with a light tree
+static constexpr PtPassEntry kPtPassEntryPunctTree[2][2] = {{pt_pass_entry_punct_tree, pt_pass_entry_punct_tree_lens}, {pt_pass_entry_punct_tree_env, pt_pass_entry_punct_tree_lens_env}};
 hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t stream, hipFunction_t spec_fn, bool relaxed) {
     const uint32_t blocks = (p.n_items + 255u) / 256u;
     if (blocks == 0) return hipSuccess;
@@ -225,7 +227,7 @@ hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t str
     }
     if (v.punct) {  // precompiled kernels of flattened scenes on the contract, nothing else (host/api_pt.cpp pt_begin refuses the rest; pt_plan asks for no per-scene kernel)
         if (spec_fn || relaxed || v.inst) return hipErrorInvalidValue;
-        return kPtPassEntryPunct[v.env][v.lens](q, v, blocks, L.total_bytes, stream);
+        return (v.ltree ? kPtPassEntryPunctTree : kPtPassEntryPunct)[v.env][v.lens](q, v, blocks, L.total_bytes, stream);
     }
     if (spec_fn) {  // the scene's own kernel (host/specialise.cpp) wraps the body of whatever the variant is: same parameter block, same LDS layout
         if (L.total_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)spec_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total_bytes);

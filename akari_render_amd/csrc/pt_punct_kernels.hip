@@ -19,4 +19,18 @@ hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float*
     return hipGetLastError();
 }
 
+__global__ void k_probe_light_tree_sample(const AliasPacked* __restrict__ light_alias, const LightRec* __restrict__ lights, const DPunct* __restrict__ punct, uint32_t punct_tree,
+                                          uint32_t n_lights, uint32_t n, const float* __restrict__ rows9, float* __restrict__ out13, uint32_t* __restrict__ light,
+                                          uint32_t* __restrict__ record) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    light_tree_probe_row(light_alias, lights, punct, punct_tree, n_lights, rows9 + 9 * (size_t)i, out13 + 13 * (size_t)i, light + i, record + i);
+}
+hipError_t launch_probe_light_tree_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, uint32_t* record, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_probe_light_tree_sample, dim3((n + 255) / 256), dim3(256), 0, stream, p.sc.light_alias, p.sc.lights, p.sc.punct, p.sc.punct_tree, p.sc.n_lights, n, rows9, out13,
+                       light, record);
+    return hipGetLastError();
+}
+
 }  // namespace akr

@@ -341,6 +341,16 @@ AKR_API int32_t akr_scene_clear_punctual_lights(akr_scene *scene);
 /* The lights the scene holds (those that were "no light" are not among them), as given. */
 AKR_API int32_t akr_scene_punctual_light_count(const akr_scene *scene, uint32_t *count);
 AKR_API int32_t akr_scene_get_punctual_light(const akr_scene *scene, uint32_t index, akr_punctual_light_desc *out);
+/* Light tree: distance-aware selection among many point and spot lights. With the mode on and two or more point / spot lights in the scene,
+ * those lights share ONE entry of the light list (akr_scene_get_light: instance 0xFFFFFFFD, its power the sum of theirs; behind the suns, before the
+ * environment) and a shading point that selects it descends a balanced binary tree over them, weighting the two children of each node by
+ * power / distance^2 from where it stands. It draws no random number more and the estimator's mean is the one of mode 0; its variance among many lights is
+ * far lower. With the mode off (the default; option "light_tree" gives the initial mode), or with fewer than two point / spot lights, every table, film,
+ * counter and sampler state is the one of a scene that never heard of the mode. Runs where the punctual lights run, refused where they are.
+ * akr_scene_set_light_tree is refused while a session holds the scene and rebuilds the light list as akr_scene_add_punctual_light does, which -- like
+ * akr_scene_clear_punctual_lights -- rebuilds the tree when the mode is on. n_nodes: 2 L - 1 for a tree over L lights, 0 when no tree exists. */
+AKR_API int32_t akr_scene_set_light_tree(akr_scene *scene, uint32_t on);
+AKR_API int32_t akr_scene_get_light_tree(const akr_scene *scene, uint32_t *on, uint32_t *n_nodes);
 /* Thin lens of the scene's camera (pt and aov integrators): depth of field. A camera ray starts at a point of a disk of
  * `radius` around the camera position, in the camera's x / y plane, and passes through the point where the pinhole ray of the same film
  * sample meets the plane of focus, `focal_distance` along the optical axis. The sample weight is the filter's: no vignetting. A host that
@@ -405,7 +415,8 @@ typedef enum {
     AKR_ARRAY_ENV_CONDITIONAL_ENTRIES = 24, /* {u32 j, f32 t}[env height * env width], row by row */
     AKR_ARRAY_ENV_CONDITIONAL_PDF = 25,     /* f32[env height * env width] */
     AKR_ARRAY_ENV_TEXELS = 26,              /* f32[4 * env width * env height]: what the kernels look up (strength applied) */
-    AKR_ARRAY_PUNCTUAL_LIGHTS = 27          /* the punctual lights' folded records (default colour pipeline), 64 B each: csrc/device/dscene.h DPunct (words 13 - 15: radius, cos_max, k) */
+    AKR_ARRAY_PUNCTUAL_LIGHTS = 27,         /* the punctual lights' folded records (default colour pipeline), 64 B each: csrc/device/dscene.h DPunct (words 13 - 15: radius, cos_max, k) */
+    AKR_ARRAY_LIGHT_TREE = 28               /* the light tree's nodes (akr_scene_set_light_tree), 32 B each, breadth-first: f32 lo.xyz, f32 power | f32 hi.xyz, u32 child (inner: the left child's index, the right one follows; leaf: 0x80000000 | index of the record in AKR_ARRAY_PUNCTUAL_LIGHTS); empty without a tree */
 } akr_array_id;
 AKR_API int32_t akr_scene_get_array(const akr_scene *scene, int32_t which, const void **ptr, uint64_t *bytes);
 
@@ -517,7 +528,7 @@ typedef struct {
     uint32_t absent_mask;     /* lobes no material of the scene can have: 1 coat, 2 transmission, 4 normal map, 8 glass, 16 conductor */
     uint32_t min_waves;       /* waves per SIMD the kernel was compiled for */
     uint32_t vgprs, scratch_bytes;
-    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features), 7 samples punctual lights (the PUNCT kernels; akr_scene_add_punctual_light) */
+    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features), 7 samples punctual lights (the PUNCT kernels; akr_scene_add_punctual_light), 8 walks a light tree (akr_scene_set_light_tree) */
     uint32_t _pad;
     double compile_ms;        /* hiprtc compile at akr_pt_begin (0 on a cache hit) */
     double load_ms;           /* cache lookup + module load */
@@ -871,6 +882,8 @@ AKR_API uint32_t akr_struct_size(int32_t which);
  *                                           which is how the reference renders every file (its lights collection has no implementation)
  *   "soft_lights"  (AKR_SOFT_LIGHTS=0)      akr_scene_load: 1 (default) = the file's lights keep their "radius" / "angle" (soft shadows);
  *                                           0 = every light is loaded with radius 0 and angle 0: the delta lights and hard shadows of 4.14
+ *   "light_tree"   (AKR_LIGHT_TREE=1)       akr_scene_load / akr_scene_create: the scene's initial light-tree mode (akr_scene_set_light_tree); 0 (default) =
+ *                                           every point and spot light is an entry of the light list of its own, chosen by power alone
  *   "denoise"      (AKR_DENOISE=n)          akr_render_task: n > 0 = after a `pt` task has written film.out, albedo and ns are rendered with the aov
  *                                           integrator at n spp (the task's sampler, seed, filter and colour pipeline), akr_denoise runs with its
  *                                           default configuration and "{stem}.denoised{ext}" is written next to film.out; 0 (default) = off. Other

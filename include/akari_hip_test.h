@@ -110,6 +110,15 @@ AKR_TEST_API int32_t akr_host_light_sample_soft(const akr_scene *scene, uint32_t
 
 AKR_TEST_API int32_t akr_probe_light_sample_soft(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rows9, float *out13, uint32_t *light);
 
+/* The same over a scene that may have a light tree (csrc/device/dlighttree.h light_tree_probe_row): rows9, out13 and light as above. A row
+ * whose entry of the light list is the tree's walks the tree with the number the selection left: out13[6] is then the FULL pdf (the entry's times every
+ * level's) and record[i] the index of the record the walk ended at, whose sample the other columns hold; record[i] = 0xFFFFFFFF where the entry was not
+ * the tree (the row is then akr_*_light_sample_soft's). The four hooks above keep their outputs on a scene without a tree and sample nothing at the
+ * tree's entry of a scene with one. */
+AKR_TEST_API int32_t akr_host_light_tree_sample(const akr_scene *scene, uint32_t n, const float *rows9, float *out13, uint32_t *light, uint32_t *record);
+
+AKR_TEST_API int32_t akr_probe_light_tree_sample(akr_context *ctx, akr_scene *scene, uint32_t n, const float *rows9, float *out13, uint32_t *light, uint32_t *record);
+
 /* The camera ray of the scene's camera and lens (csrc/device/dpath.h generate_ray_from / generate_ray_lens_from) for n items:
  * pixels2 = (x, y) as u32, u4 = u_filter.xy, u_lens.xy (u_lens is ignored without a lens), out6 = o.xyz, d.xyz in world space.
  *   akr_host_lens_ray       the shared text on the host (no GPU; works on a host-only scene)
