@@ -9,13 +9,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libakari_hip.so")
 
+# The precompiled pt kernels: pt_unit_kernels.hip compiled once per unit (kind, ENV, LENS), with -DAKR_PT_UNIT=<index>. The kinds, their order
+# and the index are those of csrc/kernels.h (PtKind, pt_unit_index): the two lists go together. The router (pt_kernels.hip) names kPtUnits
+# entry points, so a unit missing here is an undefined symbol of the library, and one too many does not compile.
+PT_KINDS = ["plain", "inst", "feat", "punct", "punct_tree"]
+PT_UNITS = {"pt_unit_" + kind + ("_env" if env else "") + ("_lens" if lens else ""): 4 * k + 2 * env + lens
+            for k, kind in enumerate(PT_KINDS) for env in (0, 1) for lens in (0, 1)}
+
+# A source is a file under csrc/, or the name of a pt unit (e.g. "pt_unit_punct_tree_env_lens"): what `only` of build_variant and
+# tools/kernel_resources.py take too. Its object is named after it.
 SOURCES = [
-    "pt_kernels.hip", "pt_kernels_relaxed.hip", "pt_inst_kernels.hip",
-    "pt_env_kernels.hip", "pt_inst_env_kernels.hip", "wf_env_kernels.hip",  # the instantiations of scenes with an environment light
-    "pt_lens_kernels.hip", "pt_lens_env_kernels.hip", "pt_inst_lens_kernels.hip", "wf_lens_kernels.hip", "aov_lens_kernels.hip",  # ... of cameras with a thin lens
-    "pt_feat_kernels.hip", "pt_feat_env_kernels.hip", "pt_feat_lens_kernels.hip", "pt_feat_lens_env_kernels.hip",  # ... of sessions that collect the denoiser's guides
-    "pt_punct_kernels.hip", "pt_punct_env_kernels.hip", "pt_punct_lens_kernels.hip", "pt_punct_lens_env_kernels.hip",  # ... of scenes with punctual lights
-    "pt_punct_tree_kernels.hip", "pt_punct_tree_env_kernels.hip", "pt_punct_tree_lens_kernels.hip", "pt_punct_tree_lens_env_kernels.hip",  # ... and a light tree over them
+    "pt_kernels.hip", "pt_kernels_relaxed.hip", *PT_UNITS, "probe_kernels.hip",
+    "wf_env_kernels.hip",  # the instantiations of scenes with an environment light
+    "wf_lens_kernels.hip", "aov_lens_kernels.hip",  # ... of cameras with a thin lens
     "wf_kernels.hip", "wf_sort.hip",
     "aov_kernels.hip", "gpt_kernels.hip", "mcmc_kernels.hip", "denoise_kernels.hip", "adapt_kernels.hip", "display_kernels.hip",
     "host/api_common.cpp", "host/api_scene.cpp", "host/api_pt.cpp", "host/api_aux.cpp", "host/api_task.cpp", "host/api_probe.cpp", "host/api_denoise.cpp", "host/api_adapt.cpp", "host/api_display.cpp",
@@ -56,7 +62,12 @@ FLAGS = [
 # make up the contract (the later flag wins) -- contraction allowed, v_rcp_f32 / v_sqrt_f32 instead of the correctly rounded
 # sequences, denormals flushed (the precondition for the compiler to use them without range scaling).
 RELAXED_FLAGS = ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero"]
-SOURCE_FLAGS = {"pt_kernels_relaxed.hip": RELAXED_FLAGS}
+SOURCE_FLAGS = {"pt_kernels_relaxed.hip": RELAXED_FLAGS, **{u: ["-DAKR_PT_UNIT=%d" % i] for u, i in PT_UNITS.items()}}
+
+
+def source_file(src: str) -> str:
+    """The file under csrc/ that source `src` is compiled from."""
+    return "pt_unit_kernels.hip" if src in PT_UNITS else src
 
 
 # What a per-scene kernel is compiled from at run time (host/specialise.cpp, hiprtc): the device headers and kernels.h, embedded
@@ -113,7 +124,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    for f in SOURCES + _headers() + ["../build.py"]:
+    for f in [source_file(s) for s in SOURCES] + _headers() + ["../build.py"]:
         p = os.path.normpath(os.path.join(CSRC, f))
         if os.path.exists(p) and os.path.getmtime(p) > t:
             return True
@@ -158,7 +169,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     def compile_one(src: str):
         obj = os.path.join(OBJ, src.replace("/", "_") + ".o")
-        path = os.path.join(CSRC, src)
+        path = os.path.join(CSRC, source_file(src))
         if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), newest_header):
             return obj, 0, ""
         cmd = [hipcc] + FLAGS + extra + SOURCE_FLAGS.get(src, []) + ["-c", path, "-I", CSRC, "-I", GEN, "-o", obj]
@@ -186,7 +197,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def build_variant(name: str, extra_flags, verbose: bool = False, only=None) -> str:
     """An A/B build of the library with extra compiler flags (e.g. -DAKR_PT_STRAGGLERS=4) next to the product:
     akari_render_amd/variants/libakari_hip_<name>.so, selected at run time with AKR_HIP_LIB=<path> (measurement only).
-    only = the sources the flags concern (e.g. ["pt_kernels.hip"]): the others are linked from the product's objects."""
+    only = the sources the flags concern (e.g. ["pt_unit_plain"]): the others are linked from the product's objects."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -210,7 +221,7 @@ def build_variant(name: str, extra_flags, verbose: bool = False, only=None) -> s
             return os.path.join(OBJ, src.replace("/", "_") + ".o"), 0, ""
         o = os.path.join(obj, src.replace("/", "_") + ".o")
         # (the variant's flags last: they can take back one of a source's own, e.g. -ffp-contract=off for pt_kernels_relaxed.hip)
-        res = subprocess.run([hipcc] + FLAGS + SOURCE_FLAGS.get(src, []) + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-I", CSRC, "-I", gen, "-o", o],
+        res = subprocess.run([hipcc] + FLAGS + SOURCE_FLAGS.get(src, []) + list(extra_flags) + ["-c", os.path.join(CSRC, source_file(src)), "-I", CSRC, "-I", gen, "-o", o],
                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         return o, res.returncode, res.stdout
 

@@ -14,8 +14,17 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
 }
 PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
     const CompiledScene& cs = s->cs;  // (stage, defer, simple: pt_plan)
-    return PtVariant{cs.has_tree(), c.force_diffuse != 0, cs.has_textures, c.sampler_type != AKR_SAMPLER_INDEPENDENT, false, false, false,
-                     cs.instanced.on, cs.env.on, s->flat.lens.radius > 0.0f, false, !cs.punct.empty(), !cs.punct_tree.empty()};
+    PtVariant v;
+    v.bvh = cs.has_tree();
+    v.fd = c.force_diffuse != 0;
+    v.tex = cs.has_textures;
+    v.pmj = c.sampler_type != AKR_SAMPLER_INDEPENDENT;
+    v.inst = cs.instanced.on;
+    v.env = cs.env.on;
+    v.lens = s->flat.lens.radius > 0.0f;
+    v.punct = !cs.punct.empty();
+    v.ltree = !cs.punct_tree.empty();
+    return v;
 }
 std::string akr_api::pt_punctual_refusal(const akr_scene* s, const TuningOptions& t) {
     if (s->cs.punct.empty()) return "";
@@ -197,7 +206,7 @@ std::vector<uint32_t> akr_api::owned_tiles(uint32_t tiles_x, uint32_t tiles_y, u
     return out;
 }
 
-// Which schedule renders this session: the persistent-lane megakernel (pt_kernels.hip, pt_inst_kernels.hip) or the wavefront schedule --
+// Which schedule renders this session: the persistent-lane megakernel (pt_unit_kernels.hip) or the wavefront schedule --
 // trace / shade kernels with the path state in HBM (wf_kernels.hip; needs a scene with a tree). Option wavefront: 1 = wherever it can run,
 // 0 = never, -1 (default) = the library decides:
 //   * flattened scenes: the megakernel, which measured faster on every one (on the 10 M-triangle hall both schedules

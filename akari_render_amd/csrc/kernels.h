@@ -1,4 +1,4 @@
-// kernels.h -- kernel parameter block and host-callable launchers (implemented in pt_kernels.hip).
+// kernels.h -- kernel parameter block and host-callable launchers (implemented in the .hip file of the kernel; the test hooks: probe_kernels.hip).
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include <hip/hip_runtime.h>
@@ -12,11 +12,12 @@
 // Which instantiation of pt_pass_body (device/pt_pass.h) a pt session runs, decided once per session (host/api_pt.cpp pt_plan) and
 // carried by the session; the launchers, the per-scene kernel's wrapper text and akr_pt_kernel_info all read it. Host side only, and
 // outside the namespace: the relaxed tier's translation unit compiles this header inside another one (pt_kernels_relaxed.hip).
+// Every member is filled by name (pt_scene_facts, pt_variant_from_bits, pt_flat_variant): the order of the members means nothing.
 struct PtVariant {
-    bool bvh, fd, tex, pmj, stage, defer, simple, inst, env, lens;
-    bool feat;  // the session collects the denoiser's guides (device/dpath.h FEAT). After the ten: aggregate initialisers without it mean feat = false
-    bool punct;  // the scene has punctual lights (device/dpunct.h PUNCT). After feat, for the same reason
-    bool ltree;  // ... and a light tree over the point and spot ones (device/dlighttree.h LTREE): the PUNCT kernels that walk it. Last, for the same reason
+    bool bvh = false, fd = false, tex = false, pmj = false, stage = false, defer = false, simple = false, inst = false, env = false, lens = false;
+    bool feat = false;   // the session collects the denoiser's guides (device/dpath.h FEAT)
+    bool punct = false;  // the scene has punctual lights (device/dpunct.h PUNCT)
+    bool ltree = false;  // ... and a light tree over the point and spot ones (device/dlighttree.h LTREE): the PUNCT kernels that walk it
 };
 // The combinations that exist as precompiled kernels -- the one statement of the exclusion rules: the exhaustive kernels always stage;
 // DEFER only in full-graph kernels, of BVH scenes those with textures; SIMPLE only in full-graph kernels of scenes without textures;
@@ -33,8 +34,64 @@ constexpr uint32_t pt_variant_bits(const PtVariant& v) {
            (v.feat ? 128u : 0u) | (v.punct ? 256u : 0u) | (v.ltree ? 512u : 0u);  // (neither is ever set in a per-scene kernel's request: FEAT sessions and scenes with punctual lights run the interpreter kernels)
 }
 constexpr PtVariant pt_variant_from_bits(uint32_t f) {
-    return PtVariant{(f & 1u) != 0, false, true, (f & 2u) != 0, (f & 4u) != 0, (f & 8u) != 0, false, (f & 16u) != 0, (f & 32u) != 0, (f & 64u) != 0, (f & 128u) != 0, (f & 256u) != 0, (f & 512u) != 0};
+    PtVariant v;
+    v.tex = true;
+    v.bvh = (f & 1u) != 0;
+    v.pmj = (f & 2u) != 0;
+    v.stage = (f & 4u) != 0;
+    v.defer = (f & 8u) != 0;
+    v.inst = (f & 16u) != 0;
+    v.env = (f & 32u) != 0;
+    v.lens = (f & 64u) != 0;
+    v.feat = (f & 128u) != 0;
+    v.punct = (f & 256u) != 0;
+    v.ltree = (f & 512u) != 0;
+    return v;
 }
+// The translation units that hold the precompiled pt kernels. A unit fixes (kind, ENV, LENS): pt_unit_kernels.hip is compiled once per
+// unit (build.py PT_KINDS: the same kinds in the same order -- the two lists go together), and launch_pt_pass (pt_kernels.hip) goes
+// through one table of kPtUnits entries to the unit of a session's variant. The ONE statement of which unit holds which variant.
+enum PtKind : uint32_t {
+    PT_KIND_PLAIN,       // flattened scenes: k_pt_pass
+    PT_KIND_INST,        // scenes kept as meshes + instances: k_pt_pass_inst (pt_inst_kernel.h)
+    PT_KIND_FEAT,        // sessions that collect the denoiser's guides: k_pt_pass<.., FEAT>
+    PT_KIND_PUNCT,       // scenes with punctual lights: k_pt_pass<.., PUNCT>
+    PT_KIND_PUNCT_TREE,  // ... and a light tree over them: k_pt_pass<.., PUNCT, LTREE>
+    PT_KIND_COUNT
+};
+constexpr uint32_t kPtUnits = PT_KIND_COUNT * 4u;
+constexpr uint32_t pt_unit_index(const PtVariant& v) {
+    const uint32_t kind = v.inst ? PT_KIND_INST : v.feat ? PT_KIND_FEAT : v.punct ? (v.ltree ? PT_KIND_PUNCT_TREE : PT_KIND_PUNCT) : PT_KIND_PLAIN;
+    return kind * 4u + (v.env ? 2u : 0u) + (v.lens ? 1u : 0u);
+}
+// ... and back: the flags a unit fixes (the others false)
+constexpr PtVariant pt_unit_flags(uint32_t unit) {
+    const uint32_t kind = unit / 4u;
+    PtVariant v;
+    v.inst = kind == PT_KIND_INST;
+    v.feat = kind == PT_KIND_FEAT;
+    v.punct = kind == PT_KIND_PUNCT || kind == PT_KIND_PUNCT_TREE;
+    v.ltree = kind == PT_KIND_PUNCT_TREE;
+    v.env = (unit & 2u) != 0;
+    v.lens = (unit & 1u) != 0;
+    return v;
+}
+// Every variant that exists as a kernel is routed to the unit that was compiled for it, and the two functions are each other's inverse.
+constexpr bool pt_units_hold_every_variant() {
+    for (uint32_t unit = 0; unit < kPtUnits; unit++)
+        if (pt_unit_index(pt_unit_flags(unit)) != unit) return false;
+    for (uint32_t f = 0; f < (1u << 13); f++) {
+        PtVariant v;
+        v.bvh = f & 1u, v.fd = f & 2u, v.tex = f & 4u, v.pmj = f & 8u, v.stage = f & 16u, v.defer = f & 32u, v.simple = f & 64u;
+        v.inst = f & 128u, v.env = f & 256u, v.lens = f & 512u, v.feat = f & 1024u, v.punct = f & 2048u, v.ltree = f & 4096u;
+        if (!pt_variant_compiled(v)) continue;
+        const uint32_t unit = pt_unit_index(v);
+        const PtVariant u = pt_unit_flags(unit);
+        if (unit >= kPtUnits || u.inst != v.inst || u.env != v.env || u.lens != v.lens || u.feat != v.feat || u.punct != v.punct || u.ltree != v.ltree) return false;
+    }
+    return true;
+}
+static_assert(pt_units_hold_every_variant(), "a compiled variant is routed to a unit that fixes other flags");
 // pt_lds_layout (below): what it is given ...
 struct PtLdsSizes {
     uint32_t stack_depth, n_tris, n_nodes;  // DScene.bvh_stack_depth, n_tris, n_nodes
@@ -290,14 +347,14 @@ inline PtParams with_tex_slots(const PtParams& p, size_t base_bytes, size_t& lds
     return q;
 }
 #if !defined(__HIPCC_RTC__)
-hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_inst_kernels.hip: once per kept scene (DInst::share_bits)
-hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // pt_env_kernels.hip: test hook
-hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, hipStream_t stream);  // pt_punct_kernels.hip: test hook
+hipError_t launch_inst_share_bits(const DScene& sc, uint32_t* bits, uint32_t* mesh_tri_words, hipStream_t stream);  // pt_kernels.hip: once per kept scene (DInst::share_bits)
+hipError_t launch_probe_env(const PtParams& p, uint32_t mode, uint32_t n, const float* in, float* out, hipStream_t stream);  // test hook
+hipError_t launch_probe_light_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, hipStream_t stream);  // test hook
 hipError_t launch_probe_light_tree_sample(const PtParams& p, uint32_t n, const float* rows9, float* out13, uint32_t* light, uint32_t* record, hipStream_t stream);  // ... the same over a light tree
-// pt_lens_kernels.hip, test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
+// test hook: the camera ray (o.xyz, d.xyz) of n items, each a pixel (x, y) and the four numbers u_filter.xy, u_lens.xy
 hipError_t launch_probe_camera_rays(const PtParams& p, uint32_t n, const uint32_t* pixels2, const float* u4, float* out6, hipStream_t stream);
 // One pass launch of a pt session: lays the LDS out (pt_lds_layout) and goes to the translation unit that holds the variant's kernel
-// (pt_kernels.hip: the table). spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled one, or nullptr;
+// (pt_unit_index; pt_kernels.hip: the table). spec_fn: the per-scene kernel of the session (host/specialise.cpp) instead of the precompiled one, or nullptr;
 // relaxed: the kernels of the relaxed arithmetic tier (pt_kernels_relaxed.hip), which exist for variants without inst, env and lens
 hipError_t launch_pt_pass(const PtParams& p, const PtVariant& v, hipStream_t stream, hipFunction_t spec_fn = nullptr, bool relaxed = false);
 hipError_t launch_gpt_sample(const PtParams& p, const GptParams& g, hipStream_t stream);

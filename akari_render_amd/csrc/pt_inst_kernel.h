@@ -1,7 +1,6 @@
-// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances, and the entry point of a
-// translation unit that instantiates it. A header so that the instantiations of scenes with an environment light (pt_inst_env_kernels.hip,
-// ENV = true) are compiled in a translation unit of their own: those of pt_inst_kernels.hip (ENV = false), and their code, are the ones of a
-// library without environments. The same for cameras with a thin lens (LENS = true, with and without an environment: pt_inst_lens_kernels.hip).
+// pt_inst_kernel.h -- k_pt_pass_inst, the persistent-lane path tracer over a scene kept as meshes + instances (host/scene_inst.cpp; the two-level
+// traversal of device/dinst_trav.h), and the entry point of a unit that instantiates it: the four units of kind PT_KIND_INST, one per ENV x LENS
+// (kernels.h; pt_unit_kernels.hip).
 #pragma once
 #include "pt_launch.h"
 

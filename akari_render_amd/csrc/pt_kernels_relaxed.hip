@@ -1,6 +1,6 @@
 // pt_kernels_relaxed.hip -- k_pt_pass in the RELAXED arithmetic tier (option `arith` = 1; device/dmath.h AKR_ARITH_RELAXED).
 //
-// The same source as pt_kernels.hip's instantiations -- pt_pass.h, every device header -- compiled a second time with
+// The same source as the plain unit's instantiations (pt_unit_kernels.hip, PT_KIND_PLAIN without ENV and LENS) -- pt_pass.h, every device header -- compiled a second time with
 // -ffp-contract=fast, without correctly rounded division / square root, with denormals flushed (build.py RELAXED_FLAGS) and
 // with AKR_ARITH_RELAXED = 1, inside another namespace so that neither the kernels nor a header's inline function can be
 // mistaken for the contract-bound ones at link time. Films are not the oracle's to the bit, and at fixed seed not within

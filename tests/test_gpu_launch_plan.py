@@ -1,9 +1,11 @@
-"""A pt session runs the kernel variant that the launch plan names, in each translation unit of the pt kernels: flattened, with an
-environment light, through a lens, both, a kept scene, kept with an environment, kept through a lens, and a textured scene with a
-per-scene kernel. Every session renders 32 x 32 at 4 spp; akr_pt_kernel_info's kernel_flags and `specialised` equal what
+"""A pt session runs the kernel variant that the launch plan names, in each of the eight plain and kept units of the pt kernels
+(csrc/pt_unit_kernels.hip; kernels.h PtKind): flattened, with an environment light, through a lens, both, a kept scene, kept with an
+environment, kept through a lens, kept with both, and a textured scene with a per-scene kernel. (The twelve units of sessions that collect
+guides, of punctual lights and of the light tree: tests/test_gpu_pt_features.py, test_gpu_punct_parity.py, test_gpu_light_tree.py.) Every session renders 32 x 32 at 4 spp; akr_pt_kernel_info's kernel_flags and `specialised` equal what
 akr_host_pt_launch_plan predicts for the same scene, config and options on a host-only scene (tests/test_launch_plan.py holds those
-predictions to the recorded decisions), and the film is the CPU oracle's bit for bit. The oracle has no lens: the sessions through a lens
-are held bit for bit to the same scene rendered by the other lens unit (flattened against kept), as tests/test_gpu_lens.py does."""
+predictions to the recorded decisions), and the film is the CPU oracle's bit for bit. The sessions through a lens are held bit for bit to the same scene rendered by the
+other kind's lens unit (flattened against kept), as tests/test_gpu_lens.py does; the oracle's own lens holds them in
+tests/test_gpu_punct_parity.py (test_lens, test_lens_kept_scene_kernels)."""
 import os
 
 import numpy as np
@@ -89,7 +91,7 @@ def test_textured_per_scene_kernel(ctx, root):
 
 @pytest.mark.parametrize("env", [False, True], ids=["lens", "lens_env"])
 def test_lens_flattened_and_kept(ctx, root, env):
-    """pt_lens_kernels.hip / pt_lens_env_kernels.hip against pt_inst_lens_kernels.hip (both of its entry points), and the lens does reach the film"""
+    """the units plain + LENS / plain + ENV + LENS against kept + LENS / kept + ENV + LENS, and the lens does reach the film"""
     sd, cfg = _two_instances(root, env=env, lens=True), make_config(**CFG)
     flat, fst, fv = _session(ctx, sd, cfg, FLAT)
     kept, kst, kv = _session(ctx, sd, cfg, KEPT)

@@ -1,5 +1,5 @@
 """Run with AKR_HIP_LIB=akari_render_amd/variants/libakari_hip_instcheck.so (build.build_variant("instcheck", ["-DAKR_INST_PRETEST_CHECK=1"],
-only=["pt_inst_kernels.hip"])): every candidate of a kept scene takes the exact test and a candidate the conservative reject
+only=["pt_unit_inst"])): every candidate of a kept scene takes the exact test and a candidate the conservative reject
 (dinst.h tri_may_hit) would have dropped although the exact test accepts it fails the render. Scenes chosen to stress the bound:
 instances far from the origin, tiny and huge scales, sliver triangles, mirrored and sheared transforms, grazing views."""
 import os, sys, time
