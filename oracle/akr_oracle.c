@@ -34,6 +34,7 @@
 #include "or_geom.h"
 #include "or_env.h"
 #include "or_punct.h"
+#include "or_lighttree.h"
 #include "or_math.h"
 #include "or_rng.h"
 #include <pthread.h>
@@ -60,7 +61,7 @@ typedef struct {
     or_alias_table area_sampler; /* valid iff light >= 0 */
 } or_instance;
 
-typedef struct {
+typedef struct or_scene_s {
     uint32_t n_meshes, n_instances, n_materials, n_tris, n_lights;
     or_mesh *meshes;
     or_instance *instances;
@@ -91,6 +92,12 @@ typedef struct {
     or_punctual_light_desc *punct_desc; /* as accepted (normalised); those that were "no light" are not among them */
     or_punct *punct[4];                 /* the folded records per colour pipeline (index = the OR_COLOR_* bits) */
     float lens_radius, lens_focal;      /* the thin lens; radius 0 = the pinhole */
+    /* the light tree (or_lighttree.h). The mode; the nodes when a tree exists (mode 1 and >= 2 local lights), else NULL;
+     * and, whatever the mode, per entry of the light list the index of its record in punct[] (OR_INVALID: the entry has none; 0 for the
+     * tree's own entry): with a tree the local lights have left the list and a sun's record index is not its rank. */
+    uint32_t light_tree, n_lt_nodes;
+    or_lt_node *lt_nodes;
+    uint32_t *light_rec;
 } or_scene;
 
 typedef struct { v3 o, d; float t_min, t_max; uint32_t ex0_inst, ex0_prim, ex1_inst, ex1_prim; } or_ray;
@@ -443,8 +450,15 @@ static or_light_sample or_sample_direct(const or_scene *sc, v3 pn_p, v3 pn_n, fl
         s.pdf = pdf * light_choice_pdf;
         return s;
     }
-    if (sc->light_inst[light_idx] == OR_PUNCT_INST) { /* a punctual light (4.14 / 4.15 Sampling): NEE only, pdf = the choice's */
-        const or_punct *L = &sc->punct[sc->color & 3u][light_idx - sc->n_emit];
+    if (sc->light_inst[light_idx] == OR_PUNCT_INST || sc->light_inst[light_idx] == OR_PUNCT_TREE_INST) {
+        /* a punctual light (4.14 / 4.15 Sampling): NEE only, pdf = the choice's. The tree's entry (4.16 Walk) first descends with the
+         * number the choice left to one record, and its pdf is the walked product; the sample is that record's with u_sample unchanged. */
+        uint32_t record = sc->light_rec[light_idx];
+        if (sc->light_inst[light_idx] == OR_PUNCT_TREE_INST && !or_lt_walk(sc->lt_nodes, pn_p, u_sel2, &light_choice_pdf, &record)) {
+            s.pdf = light_choice_pdf; s.delta = 1; /* the bound was reached on an inner node: invalid (no tree the build makes) */
+            return s;
+        }
+        const or_punct *L = &sc->punct[sc->color & 3u][record];
         const or_punct_ls ps = or_punct_sample(L, pn_p, pn_n, u_sample);
         s.li = ps.li; s.wi = ps.wi;
         s.shadow_ray.o = ps.ro; s.shadow_ray.d = ps.wi; s.shadow_ray.t_min = 0.0f; s.shadow_ray.t_max = ps.tmax;
@@ -655,7 +669,7 @@ OR_EXPORT void or_scene_destroy(or_scene *sc) {
     free(sc->images); free(sc->graphs);
     free(sc->meshes); free(sc->instances); free(sc->materials);
     free(sc->woop); free(sc->tri_inst); free(sc->tri_prim);
-    free(sc->light_inst); free(sc->light_power);
+    free(sc->light_inst); free(sc->light_power); free(sc->light_rec); free(sc->lt_nodes);
     or_env_free(sc->env);
     free(sc->punct_desc);
     for (int k = 0; k < 4; k++) free(sc->punct[k]);
@@ -1975,26 +1989,51 @@ static void or_world_bounds(const or_scene *sc, float lo[3], float hi[3]) { /* o
     }
 }
 /* The light list (4.14): the emissive instances as or_scene_create found them, the punctual lights in the order given, the environment
- * last; the alias table rebuilt over all of them. */
+ * last; the alias table rebuilt over all of them. With a tree (4.16 "Light table with a tree": the mode is on and there are >= 2 local
+ * lights): the emissive instances, the suns in the order given, ONE entry for the tree, the environment; the tree's weight is the f64
+ * sum of the local lights' f32 weights in the order given, rounded once; and the tree is built anew (4.16 "Build"). */
 static void or_rebuild_light_list(or_scene *sc) {
     if (sc->n_lights > 0) or_alias_free(&sc->light_dist);
-    const uint32_t cap = sc->n_emit + sc->n_punct + 1;
+    free(sc->lt_nodes);
+    sc->lt_nodes = 0; sc->n_lt_nodes = 0;
+    const uint32_t cap = sc->n_emit + sc->n_punct + 2;
     sc->light_inst = (uint32_t *)realloc(sc->light_inst, 4ull * cap);
     sc->light_power = (float *)realloc(sc->light_power, 4ull * cap);
+    sc->light_rec = (uint32_t *)realloc(sc->light_rec, 4ull * cap);
+    for (uint32_t i = 0; i < sc->n_emit; i++) sc->light_rec[i] = OR_INVALID;
     uint32_t n = sc->n_emit;
     if (sc->n_punct) {
         float lo[3], hi[3];
         or_world_bounds(sc, lo, hi);
         const double R = or_punct_bounds_radius(lo, hi);
+        float *weights = (float *)malloc(4ull * sc->n_punct);
+        uint32_t n_local = 0;
         for (uint32_t k = 0; k < sc->n_punct; k++) {
+            weights[k] = or_punct_power(&sc->punct[0][k], R);
+            n_local += or_lt_is_local(&sc->punct[0][k]) ? 1u : 0u;
+        }
+        const int tree = sc->light_tree && n_local >= 2;
+        double tree_weight = 0.0;
+        for (uint32_t k = 0; k < sc->n_punct; k++) {
+            if (tree && or_lt_is_local(&sc->punct[0][k])) { tree_weight += (double)weights[k]; continue; }
             sc->light_inst[n] = OR_PUNCT_INST;
-            sc->light_power[n] = or_punct_power(&sc->punct[0][k], R);
+            sc->light_power[n] = weights[k];
+            sc->light_rec[n] = k;
             n++;
         }
+        if (tree) {
+            sc->light_inst[n] = OR_PUNCT_TREE_INST;
+            sc->light_power[n] = (float)tree_weight;
+            sc->light_rec[n] = 0;
+            n++;
+            sc->lt_nodes = or_lt_build(sc->punct[0], weights, sc->n_punct, &sc->n_lt_nodes);
+        }
+        free(weights);
     }
     if (sc->env) {
         sc->light_inst[n] = OR_INVALID;
         sc->light_power[n] = sc->env->power;
+        sc->light_rec[n] = OR_INVALID;
         n++;
     }
     sc->n_lights = n;
@@ -2053,6 +2092,11 @@ OR_EXPORT void or_scene_light_table(const or_scene *sc, or_alias_entry *entries,
 /* Known-answer call with the rows of akr_host_light_sample_soft: rows9 = p, n, u_select, u_sample -> out13 = li, wi, pdf, ro, tmax, valid,
  * delta and the light chosen. An emitter or the environment answers the choice's pdf alone. Uses the records of the pipeline set by
  * or_scene_set_color (0 after creation). Returns -1 for a scene without lights. */
+static void or_punct_sample_row(const or_scene *sc, uint32_t record, const float *r, float *o) {
+    const or_punct_ls s = or_punct_sample(&sc->punct[sc->color & 3u][record], V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), V2(r[7], r[8]));
+    o[0] = s.li.x; o[1] = s.li.y; o[2] = s.li.z; o[3] = s.wi.x; o[4] = s.wi.y; o[5] = s.wi.z;
+    o[7] = s.ro.x; o[8] = s.ro.y; o[9] = s.ro.z; o[10] = s.tmax; o[11] = s.valid ? 1.0f : 0.0f; o[12] = 1.0f;
+}
 OR_EXPORT int or_punct_sample_many(const or_scene *sc, uint32_t n, const float *rows9, float *out13, uint32_t *light) {
     if (!sc->n_lights) return -1;
     for (uint32_t i = 0; i < n; i++) {
@@ -2063,13 +2107,47 @@ OR_EXPORT int or_punct_sample_many(const or_scene *sc, uint32_t n, const float *
         memset(o, 0, 13 * sizeof(float));
         o[6] = pdf;
         light[i] = idx;
-        if (sc->light_inst[idx] != OR_PUNCT_INST) continue;
-        const or_punct_ls s = or_punct_sample(&sc->punct[sc->color & 3u][idx - sc->n_emit], V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), V2(r[7], r[8]));
-        o[0] = s.li.x; o[1] = s.li.y; o[2] = s.li.z; o[3] = s.wi.x; o[4] = s.wi.y; o[5] = s.wi.z;
-        o[7] = s.ro.x; o[8] = s.ro.y; o[9] = s.ro.z; o[10] = s.tmax; o[11] = s.valid ? 1.0f : 0.0f; o[12] = 1.0f;
+        if (sc->light_inst[idx] != OR_PUNCT_INST) continue; /* the tree's entry included: nothing is sampled there */
+        or_punct_sample_row(sc, sc->light_rec[idx], r, o);
     }
     return 0;
 }
+/* ---------------------------------- the light tree (or_lighttree.h) ------------------------------------ */
+/* Sets the scene's mode (4.16 "Which lights, and when") and rebuilds the light list; setting the lights while it is on rebuilds the tree. */
+OR_EXPORT void or_scene_set_light_tree(or_scene *sc, uint32_t on) {
+    sc->light_tree = on ? 1u : 0u;
+    or_rebuild_light_list(sc);
+}
+/* The mode, and the number of nodes (0: no tree exists) */
+OR_EXPORT void or_scene_get_light_tree(const or_scene *sc, uint32_t *on, uint32_t *n_nodes) { *on = sc->light_tree; *n_nodes = sc->n_lt_nodes; }
+/* The node words, 8 per node (lo.xyz, power | hi.xyz, child); returns the node count */
+OR_EXPORT uint32_t or_scene_light_tree_nodes(const or_scene *sc, uint32_t *words) {
+    if (words && sc->n_lt_nodes) memcpy(words, sc->lt_nodes, sizeof(or_lt_node) * sc->n_lt_nodes);
+    return sc->n_lt_nodes;
+}
+/* Known-answer call with the rows and columns of akr_host_light_tree_sample: as or_punct_sample_many, but the tree's entry walks (out13[6]
+ * = the walked pdf, delta = 1) and samples the record it reaches; record = that record's index, or 0xffffffff when the entry was not the
+ * tree. */
+OR_EXPORT int or_light_tree_sample_many(const or_scene *sc, uint32_t n, const float *rows9, float *out13, uint32_t *light, uint32_t *record) {
+    if (!sc->n_lights) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *r = rows9 + 9ull * i;
+        float *o = out13 + 13ull * i;
+        float pdf, rest;
+        const uint32_t idx = or_alias_sample_and_remap(&sc->light_dist, r[6], &pdf, &rest);
+        memset(o, 0, 13 * sizeof(float));
+        o[6] = pdf;
+        light[i] = idx;
+        record[i] = OR_LT_NO_RECORD;
+        if (sc->light_inst[idx] == OR_PUNCT_INST) or_punct_sample_row(sc, sc->light_rec[idx], r, o);
+        if (sc->light_inst[idx] != OR_PUNCT_TREE_INST) continue;
+        const int ok = or_lt_walk(sc->lt_nodes, V3(r[0], r[1], r[2]), rest, &pdf, &record[i]);
+        o[6] = pdf; o[12] = 1.0f;
+        if (ok) or_punct_sample_row(sc, record[i], r, o);
+    }
+    return 0;
+}
+OR_EXPORT uint32_t or_sizeof_light_tree_node(void) { return (uint32_t)sizeof(or_lt_node); }
 /* Sets (NULL or radius 0: removes) the camera's lens. Returns -1 for what akr_scene_set_lens refuses on the values alone: a non-finite
  * or negative value, a radius > 0 without a focal distance > 0. (The library's further test against the padding of its acceleration
  * structure is the library's own concern: the oracle has no padded boxes.) */

@@ -132,4 +132,16 @@ typedef struct {
 typedef struct {
     uint64_t n_samples, n_closest, n_shadow, n_shaded, n_tri_tests;
 } or_stats;
+
+/* The light tree (or_lighttree.h), defined in akr_oracle.c. The mode is the scene's: initially 0; setting it, or setting the
+ * punctual lights while it is on, rebuilds the light list and the tree. A tree exists iff the mode is on and the scene has >= 2 point or
+ * spot lights; otherwise nothing of the scene differs from mode 0. or_gpt_render and or_mcmc_render refuse such scenes as they refuse any
+ * punctual light (-5). */
+struct or_scene_s;
+void or_scene_set_light_tree(struct or_scene_s *sc, uint32_t on);
+void or_scene_get_light_tree(const struct or_scene_s *sc, uint32_t *on, uint32_t *n_nodes);
+uint32_t or_scene_light_tree_nodes(const struct or_scene_s *sc, uint32_t *words); /* 8 words a node; returns the count; words may be NULL */
+/* rows9 = p, n, u_select, u_sample -> out13 = li, wi, pdf, ro, tmax, valid, delta; light = the entry chosen; record = the record the walk
+ * reached, or 0xffffffff when the entry was not the tree: the columns of akr_host_light_tree_sample. -1: the scene has no light. */
+int or_light_tree_sample_many(const struct or_scene_s *sc, uint32_t n, const float *rows9, float *out13, uint32_t *light, uint32_t *record);
 #endif

@@ -127,17 +127,24 @@ def lib() -> C.CDLL:
     L.or_scene_light_table.argtypes = [vp, vp, fp]
     L.or_punct_sample_many.restype = i32
     L.or_punct_sample_many.argtypes = [vp, u32, fp, fp, up]
+    L.or_scene_set_light_tree.argtypes = [vp, u32]
+    L.or_scene_get_light_tree.argtypes = [vp, up, up]
+    L.or_scene_light_tree_nodes.restype = u32
+    L.or_scene_light_tree_nodes.argtypes = [vp, up]
+    L.or_light_tree_sample_many.restype = i32
+    L.or_light_tree_sample_many.argtypes = [vp, u32, fp, fp, up, up]
     L.or_scene_set_lens.restype = i32
     L.or_scene_set_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
     L.or_scene_get_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
     L.or_lens_ray_many.restype = i32
     L.or_lens_ray_many.argtypes = [vp, u32, f32, u32, up, fp, fp]
     for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config", "or_sizeof_environment_desc",
-              "or_sizeof_punctual_light_desc", "or_sizeof_lens_desc", "or_sizeof_punct_record"):
+              "or_sizeof_punctual_light_desc", "or_sizeof_lens_desc", "or_sizeof_punct_record", "or_sizeof_light_tree_node"):
         getattr(L, n).restype = u32
     assert L.or_sizeof_punctual_light_desc() == C.sizeof(abi.PunctualLightDesc) == 60
     assert L.or_sizeof_lens_desc() == C.sizeof(abi.LensDesc) == 8
     assert L.or_sizeof_punct_record() == 64
+    assert L.or_sizeof_light_tree_node() == 32
     assert L.or_sizeof_environment_desc() == C.sizeof(abi.EnvironmentDesc)
     assert L.or_sizeof_material() == C.sizeof(abi.MaterialDesc)
     assert L.or_sizeof_config() == C.sizeof(abi.PtConfig)
@@ -152,12 +159,14 @@ def _fp(a):
 
 
 class OracleScene:
-    def __init__(self, scene: abi.SceneData, bvh: bool = False, share_plane_rows: bool = True, lights: bool = True, lens: bool = True):
+    def __init__(self, scene: abi.SceneData, bvh: bool = False, share_plane_rows: bool = True, lights: bool = True, lens: bool = True,
+                 light_tree: bool = False):
         """bvh: build the oracle-side hierarchy (or_accel.h; same hits as the exhaustive loop, checked in
         tests/test_oracle_accel.py) -- for the 1 M / 10 M-triangle configurations. share_plane_rows = False: every triangle
         keeps the plane row of its own vertices (the records as they were before the coplanar-neighbour rule).
         The scene's environment, punctual lights (scene.lights) and lens (scene.lens) are set as capi.Scene sets them; lights = False /
-        lens = False leaves the punctual lights / the lens out: the oracle of the same scene without them."""
+        lens = False leaves the punctual lights / the lens out: the oracle of the same scene without them. light_tree: the scene's mode of
+        DESIGN.md 4.16 (a SceneData carries none: on the library's side it is the option or the setter)."""
         self.data = scene
         desc, self._keep = scene.to_desc()
         self._desc = desc
@@ -168,6 +177,8 @@ class OracleScene:
             lib().or_set_share_plane_rows(1)
         self.width, self.height = scene.camera.width, scene.camera.height
         self.n_bvh_nodes = lib().or_scene_build_bvh(self.h) if bvh else 0
+        if light_tree:
+            self.set_light_tree(True)
         if getattr(scene, "environment", None) is not None:
             self.set_environment(scene.environment)
         if lights and getattr(scene, "lights", None):
@@ -222,6 +233,34 @@ class OracleScene:
         out, light = np.zeros((r.shape[0], 13), np.float32), np.zeros(r.shape[0], np.uint32)
         assert lib().or_punct_sample_many(self.h, r.shape[0], _fp(r), _fp(out), light.ctypes.data_as(C.POINTER(C.c_uint32))) == 0, "the scene has no light"
         return out, light
+
+    def set_light_tree(self, on) -> None:
+        """or_scene_set_light_tree: the mode; the light list and the tree are rebuilt, as they are whenever the lights are set
+        while it is on."""
+        lib().or_scene_set_light_tree(self.h, 1 if on else 0)
+
+    def light_tree(self):
+        """(mode, number of nodes): 0 nodes when no tree exists, as capi.Scene.light_tree answers."""
+        on, n = C.c_uint32(), C.c_uint32()
+        lib().or_scene_get_light_tree(self.h, C.byref(on), C.byref(n))
+        return on.value, n.value
+
+    def light_tree_nodes(self) -> np.ndarray:
+        """The node words, uint32 (n_nodes, 8): lo.xyz, power | hi.xyz, child -- the words of AKR_ARRAY_LIGHT_TREE."""
+        out = np.zeros((lib().or_scene_light_tree_nodes(self.h, None), 8), np.uint32)
+        if out.size:
+            lib().or_scene_light_tree_nodes(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def light_tree_sample_many(self, rows, color: int = 0):
+        """or_light_tree_sample_many: rows (n, 9) = p, n, u_select, u_sample -> ((n, 13), light (n,), record (n,)), the answer of
+        akr_host_light_tree_sample."""
+        r = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 9)
+        lib().or_scene_set_color(self.h, color)
+        out, light, record = np.zeros((r.shape[0], 13), np.float32), np.zeros(r.shape[0], np.uint32), np.zeros(r.shape[0], np.uint32)
+        up = C.POINTER(C.c_uint32)
+        assert lib().or_light_tree_sample_many(self.h, r.shape[0], _fp(r), _fp(out), light.ctypes.data_as(up), record.ctypes.data_as(up)) == 0, "the scene has no light"
+        return out, light, record
 
     def set_lens(self, radius=None, focal_distance: float = 0.0) -> None:
         """or_scene_set_lens; radius None or 0 removes the lens. Values the library would refuse raise ValueError."""
