@@ -66,8 +66,13 @@ TEST_EXPORTS = [
     "akr_host_display_transform", "akr_host_luminance_histogram", "akr_probe_display_times",
     "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
     "akr_host_light_sample", "akr_probe_light_sample", "akr_host_light_sample_soft", "akr_probe_light_sample_soft",
-    "akr_host_light_tree_sample", "akr_probe_light_tree_sample",
+    "akr_host_light_tree_sample", "akr_probe_light_tree_sample", "akr_host_option_info",
 ]
+
+
+class OptionInfo(C.Structure):
+    """akr_option_info (include/akari_hip_test.h)."""
+    _fields_ = [("name", C.c_char_p), ("env", C.c_char_p), ("default_value", C.c_int32), ("ranged", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32)]
 
 
 class RenderSession(C.Structure):
@@ -180,6 +185,7 @@ def lib() -> C.CDLL:
     proto("akr_device_count", C.POINTER(C.c_int32))
     proto("akr_option_set", C.c_char_p, i32)
     proto("akr_option_get", C.c_char_p, C.POINTER(C.c_int32))
+    proto("akr_host_option_info", u32, C.POINTER(OptionInfo))
     proto("akr_comm_unique_id", C.POINTER(C.c_uint8))
     proto("akr_comm_create", vp, C.POINTER(C.c_uint8), i32, i32, vpp)
     proto("akr_comm_wrap", vp, vp, i32, i32, vpp)
@@ -630,6 +636,14 @@ def get_option(name: str) -> int:
     v = C.c_int32()
     check(lib().akr_option_get(name.encode(), C.byref(v)))
     return v.value
+
+
+def option_table() -> list:
+    """akr_host_option_info (test hook, no GPU) over every row: [{"name", "env" ("" = none), "default", "range": (lo, hi) or None = any int}]."""
+    rows, o = [], OptionInfo()
+    while lib().akr_host_option_info(len(rows), C.byref(o)) == 0:
+        rows.append({"name": o.name.decode(), "env": o.env.decode(), "default": o.default_value, "range": (o.lo, o.hi) if o.ranged else None})
+    return rows
 
 
 class options:

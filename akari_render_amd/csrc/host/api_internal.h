@@ -210,11 +210,9 @@ struct RenderBase {
     uint32_t spp_done = 0, n_launches = 0;
     uint32_t pmj_spp = 1;  // the spp the pmj02bn sampler stratifies for (the method's total spp)
     const akr_scene::ColorSet* color_set = nullptr;  // the scene's tables for cfg.color != 0 (looked up under the scene's lock by base_begin)
-    // the process-wide tuning options that shape the parameter block as they were when the session began (base_begin): an
-    // akr_option_set from another thread cannot change the kernel of a running session
-    int defer_metal_option = -1;
-    int simple_kernels_option = 1;
-    int defer_on_option = 0;
+    // the process-wide tuning options as they were when the session began (base_begin; akr_pt_begin_features: before its refusals): the one
+    // state every decision of the session's life is made from -- an akr_option_set on another thread cannot give a session two
+    TuningOptions opt;
     // timed regions on the context's stream: pairs still in flight, and the elapsed time of the completed ones (folded in and
     // destroyed as they complete, so a long progressive session holds a bounded number of events)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -257,7 +255,7 @@ struct WavefrontState {
     uint32_t *sorted_closest = nullptr, *sorted_shadow = nullptr, *sorted_keys = nullptr;
     WfBuffers buf;
     uint32_t slots = 0, trace_blocks = 0;
-    // slot groups (option wf_groups; api_pt.cpp wf_run): each with its own queues, counters and stream
+    // slot groups (option wf_groups; wf_schedule.cpp wf_run): each with its own queues, counters and stream
     std::vector<WfBuffers> group;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> join;
@@ -275,10 +273,10 @@ struct akr_pt_session : RenderBase {
     std::unique_ptr<WavefrontState> wf;  // set = the wavefront schedule renders the session
     int sched_trial = 0;  // flattened scenes, option wavefront = -1: 1 = the first blocking akr_pt_passes call times both schedules and keeps the faster (api_pt.cpp), 2 = done
     uint64_t passes_launched = 0;  // passes of all akr_pt_passes launches so far (kernel_ms / passes_launched = what a pass costs)
-    int max_fused_option = 0;  // option max_fused_passes when the session began
     // per-scene kernel (host/specialise.cpp): set by akr_pt_begin when the options ask for one and the compile succeeded; the
     // precompiled interpreter kernel otherwise. spec_active also shapes session_params (no value slots in LDS, the kernel's own LDS budget).
     bool spec_active = false;
+    bool wf_sort = false;  // opt.wf_sort and the wavefront schedule renders the session from its beginning: PtParams.wf_sort, the queues' keys
     bool arith_relaxed = false;  // option arith = 1 and the session is one the relaxed tier covers: launches go to pt_kernels_relaxed.hip
     int spec_waves = 3;
     std::shared_ptr<SpecKernel> spec;
@@ -290,6 +288,12 @@ struct akr_pt_session : RenderBase {
 };
 
 namespace akr_api {
+// wf_schedule.cpp: the wavefront schedule's host half. Every option it reads is of se->opt.
+bool choose_wavefront(const akr_pt_session* se);  // which schedule renders the session (option wavefront; -1: by scene and frame size)
+std::unique_ptr<WavefrontState> wf_allocate(const akr_pt_session* se, bool sort);  // the buffers: a slot per item of the session's parameter block
+void wf_set_range(WavefrontState& ws, uint32_t n_active);  // the groups' shares of the slots [0, n_active)
+void wf_run(akr_pt_session* se);  // one launch group: the passes set_launch_passes set, for every slot
+bool schedule_trial_eligible(const akr_pt_session* se);  // may the first blocking akr_pt_passes call time both schedules (option sched_trial)
 // One timed region on a session's stream. The event pair is handed to the session by stop(); if the region is left by an
 // exception the pair is destroyed here.
 struct LaunchTimer {
@@ -317,13 +321,14 @@ struct LaunchTimer {
 // api_pt.cpp
 // What all four integrators begin with: the config validated, the film's size checked, the colour set, sampler states, counters, the
 // owned-tile list, the scene reference. Throws; the caller then computes the session's parameter block (session_params).
-void base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film);
+// opt: the snapshot the caller has already taken and decided from (akr_pt_begin_features); null = taken here.
+void base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, const TuningOptions* opt = nullptr);
 // base_begin + the block every integrator but pt renders with, behind the C ABI's error boundary (aov, gpt, mcmc_opt)
 int32_t render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, RenderBase** out);
 int32_t base_end(RenderBase* se, akr_pt_stats* stats);  // the stats read back, the session deleted (the scene released)
 // The session's kernel parameter block, computed once: everything but the two fields of set_launch_passes is constant while the
 // session lives (n_passes = 1 full pass until a launch says otherwise). The arguments are what only pt varies.
-void session_params(RenderBase* se, bool spec_active = false, int spec_waves = 3, bool wf_sort = false);
+void session_params(RenderBase* se, bool spec_active = false, int spec_waves = 3);
 inline void set_launch_passes(RenderBase* se, uint32_t n_passes, uint32_t last_pass_spp) {
     se->params.n_passes = n_passes;
     se->params.last_pass_spp = last_pass_spp;
@@ -336,7 +341,8 @@ struct PtPlan {
     uint32_t stage_bytes[13], stage_total, tex_slots;
 };
 // feat: the session collects the denoiser's guides (akr_pt_begin_features): the FEAT kernels, which exclude DEFER and SIMPLE as ENV and LENS do.
-PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, int defer_metal_option, int simple_kernels_option, int defer_on_option, bool spec_active, int spec_waves, bool feat = false);
+// opt: defer_metal, simple_kernels, defer_on.
+PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat = false);
 // Why a pt session of (scene, options) cannot collect guides -- "" when it can. The ONE statement of akr_pt_begin_features' refusals that need no
 // device: kept scenes, a forced wavefront schedule, the relaxed arithmetic tier (akr_host_pt_features_plan asks it for host-only scenes).
 std::string pt_features_refusal(const akr_scene* s, const TuningOptions& t);
@@ -367,7 +373,7 @@ uint32_t session_samples(const akr_pt_config& c);
 // the tiles (row-major ids) rank `rank` of `count` owns, in Morton order (kernels.h tile_owner)
 std::vector<uint32_t> owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t rank, uint32_t count);
 // api_scene.cpp
-void scene_finish(akr_scene* s);
+void scene_finish(akr_scene* s, const TuningOptions& opt);  // opt: the snapshot akr_scene_create / akr_scene_load took
 // the light tables packed as the kernels read them (dgeom.h AliasPacked, dscene.h LightRec): what upload_lights uploads and akr_host_light_sample samples
 void packed_light_tables(const CompiledScene& cs, std::vector<AliasPacked>& light_alias, std::vector<AliasPacked>& area_alias, std::vector<LightRec>& lights);
 void scene_spec_header(akr_scene* scene, std::string& out);

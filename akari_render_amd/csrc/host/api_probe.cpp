@@ -337,11 +337,11 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_t
 // What akr_pt_begin decides for (scene, config), without a session or a device: the variant and the staged tables (pt_plan), the per-scene
 // kernel's wrapper text, and the LDS layout a launch of the whole frame would get (launch_pt_pass: pt_lds_layout)
 // feat: the plan of akr_pt_begin_features (no per-scene kernel); -> the variant and the layout
-static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves, bool feat,
+static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, const akr_pt_config* cfg, const TuningOptions& opt, int32_t spec_waves, bool feat,
                                                           akr_pt_launch_plan* out) {
         const CompiledScene& cs = scene->cs;
         const bool spec = !feat && spec_waves != 0 && cs.has_textures && !cfg->force_diffuse && cs.punct.empty();  // (where akr_pt_begin asks for a per-scene kernel)
-        const PtPlan pl = pt_plan(scene, *cfg, defer_metal, simple_kernels, defer_on, spec, spec ? spec_waves : 3, feat);
+        const PtPlan pl = pt_plan(scene, *cfg, opt, spec, spec ? spec_waves : 3, feat);
         const PtVariant& v = pl.v;
         const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, pl.stage_total, cfg->sampler_type == AKR_SAMPLER_PMJ02BN};
         const PtLdsLayout L = pt_lds_layout(v, sizes);
@@ -361,10 +361,18 @@ static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, cons
         if (spec) std::snprintf(out->wrapper, sizeof out->wrapper, "%s", spec_wrapper_source(v, spec_waves).c_str());
         return {v, L};
 }
+// the options a plan hook decides from: the defaults, and the three pt_plan reads as the test gives them (not the process's)
+static TuningOptions plan_options(int32_t defer_metal, int32_t simple_kernels, int32_t defer_on) {
+    TuningOptions t;
+    t.defer_metal = defer_metal;
+    t.simple_kernels = simple_kernels;
+    t.defer_on = defer_on;
+    return t;
+}
 AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves,
                                              akr_pt_launch_plan* out) {
     if (!scene || !cfg || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_pt_launch_plan: NULL argument");
-    return guarded([&] { fill_launch_plan(scene, cfg, defer_metal, simple_kernels, defer_on, spec_waves, false, out); });
+    return guarded([&] { fill_launch_plan(scene, cfg, plan_options(defer_metal, simple_kernels, defer_on), spec_waves, false, out); });
 }
 // akr_host_pt_launch_plan for a session that may collect the denoiser's guides: the refusals of akr_pt_begin_features that need no device, decided
 // for the option values given (not the process's), then the plan and what a test needs to know of the layout's sizes
@@ -372,15 +380,15 @@ AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene* scene, const akr_pt_co
                                                int32_t wavefront, int32_t arith, akr_pt_features_plan* out) {
     if (!scene || !cfg || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_pt_features_plan: NULL argument");
     return guarded([&] {
+        TuningOptions t = plan_options(defer_metal, simple_kernels, defer_on);
+        t.wavefront = wavefront;
+        t.arith = arith;
         if (feat) {
-            TuningOptions t;
-            t.wavefront = wavefront;
-            t.arith = arith;
             const std::string why = pt_features_refusal(scene, t);
             if (!why.empty()) throw Unsupported(why);
         }
         std::memset(out, 0, sizeof *out);
-        const auto vl = fill_launch_plan(scene, cfg, defer_metal, simple_kernels, defer_on, spec_waves, feat != 0, &out->plan);
+        const auto vl = fill_launch_plan(scene, cfg, t, spec_waves, feat != 0, &out->plan);
         out->feat = vl.first.feat ? 1u : 0u;
         out->kernel_compiled = pt_variant_compiled(vl.first) ? 1u : 0u;
         out->park_slots = (vl.second.carry_offset - vl.second.park_offset) / 256u;
@@ -388,6 +396,12 @@ AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene* scene, const akr_pt_co
         out->lds_budget = (uint32_t)pt_lds_budget(vl.first.tex);
         out->park_slots_feat = kParkSlotsFeat;
     });
+}
+AKR_TEST_API int32_t akr_host_option_info(uint32_t index, akr_option_info* out) {
+    OptionInfo o;
+    if (!out || !tuning_info(index, &o)) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_option_info: out is NULL or index is past the table's last row");
+    *out = {o.name, o.env, o.def, o.ranged, o.lo, o.hi};
+    return AKR_OK;
 }
 AKR_TEST_API int32_t akr_probe_camera_rays(akr_context* ctx, akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2,
                                       const float* u4, float* out6) {

@@ -180,9 +180,9 @@ static void check_lens_reach(const akr_scene* s, const HostLens& lens) {
     throw std::invalid_argument(msg);
 }
 
-void akr_api::scene_finish(akr_scene* s) {
+void akr_api::scene_finish(akr_scene* s, const TuningOptions& opt) {
     akr_context* ctx = s->ctx;
-    compile_scene(s->flat, s->cs);
+    compile_scene(s->flat, opt, s->cs);
     compile_punctual(s->flat, s->cs);
     compile_environment(s->flat, s->cs);
     check_lens_reach(s, s->flat.lens);  // (a lens from the file, option `lens`)
@@ -291,9 +291,10 @@ AKR_API int32_t akr_scene_create(akr_context* ctx, const akr_scene_desc* desc, a
     return guarded([&] {
         auto s = std::make_unique<akr_scene>();
         s->ctx = ctx;
+        const TuningOptions opt = tuning();  // the one look at the options of this scene's making
         s->flat = FlatScene::from_desc(*desc);
-        s->flat.light_tree = tuning().light_tree;
-        scene_finish(s.get());
+        s->flat.light_tree = opt.light_tree;
+        scene_finish(s.get(), opt);
         *out = s.release();
     });
 }
@@ -303,13 +304,14 @@ AKR_API int32_t akr_scene_load(akr_context* ctx, const char* path, uint32_t widt
     return guarded([&] {
         auto s = std::make_unique<akr_scene>();
         s->ctx = ctx;
-        s->flat = load_scene_json(path);
-        s->flat.light_tree = tuning().light_tree;
+        const TuningOptions opt = tuning();  // the one look at the options of this load
+        s->flat = load_scene_json(path, opt);
+        s->flat.light_tree = opt.light_tree;
         if (width && height) {
             s->flat.camera.width = width;
             s->flat.camera.height = height;
         }
-        scene_finish(s.get());
+        scene_finish(s.get(), opt);
         *out = s.release();
     });
 }

@@ -14,7 +14,6 @@
 
 #include <chrono>
 #include <cstdio>
-#include <mutex>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -542,7 +541,7 @@ struct PhaseTimer {
     }
 };
 }  // namespace
-void compile_scene(const FlatScene& flat, CompiledScene& out) {
+void compile_scene(const FlatScene& flat, const TuningOptions& tune, CompiledScene& out) {
     PhaseTimer phase;
     const size_t n_inst = flat.instances.size();
     out = CompiledScene();
@@ -594,8 +593,8 @@ void compile_scene(const FlatScene& flat, CompiledScene& out) {
     }
     out.inst_tri_offset[n_inst] = n_tris;
     out.n_tris = n_tris;
-    if (want_instancing(flat)) {  // meshes + instances as they are: nothing per instance-triangle (scene_inst.cpp)
-        compile_instanced_geometry(flat, xf, descs, out);
+    if (want_instancing(flat, tune)) {  // meshes + instances as they are: nothing per instance-triangle (scene_inst.cpp)
+        compile_instanced_geometry(flat, tune, xf, descs, out);
         phase.lap("instanced geometry");
         return;
     }
@@ -745,7 +744,6 @@ void compile_scene(const FlatScene& flat, CompiledScene& out) {
     phase.lap("light tables");
     // acceleration structure: tiny scenes are intersected exhaustively (records from LDS or the scalar cache), others get the compressed wide BVH of host/bvh.cpp
     // (AKR_FORCE_BVH=1 builds the BVH for tiny scenes too: lets the tests run both intersectors on scenes/cbox)
-    const TuningOptions tune = tuning();
     const uint32_t kExhaustiveMax = tune.force_bvh ? 0u : 64u;
     // the exhaustive kernels stage the shading tables in LDS (device/pt_pass.h: STAGE): a tiny mesh with a huge material list goes the BVH way
     const size_t stage = exhaustive_stage_bytes(out, out.n_lights);
@@ -809,131 +807,6 @@ size_t exhaustive_stage_bytes(const CompiledScene& out, size_t n_lights) {
                      out.tex_nodes.size() * sizeof(DNode), out.images.size() * sizeof(DImage), out.mat_inputs.size() * sizeof(MatInputs)})
         stage += (b + 15) & ~(size_t)15;
     return stage;
-}
-
-namespace {
-std::mutex g_tuning_mutex;
-bool g_tuning_init = false;
-TuningOptions g_tuning;
-void tuning_init_locked() {
-    if (g_tuning_init) return;
-    g_tuning_init = true;
-    auto flag = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '1' ? 1 : 0; };
-    g_tuning.force_bvh = flag("AKR_FORCE_BVH");
-    g_tuning.bvh_balanced = flag("AKR_BVH_BALANCED");
-    if (const char* e = std::getenv("AKR_PT_DEFER_METAL")) g_tuning.defer_metal = std::atoi(e);
-    if (const char* e = std::getenv("AKR_PT_MODE")) g_tuning.wavefront = std::string(e) == "wavefront" ? 1 : (std::string(e) == "auto" ? -1 : 0);
-    if (const char* e = std::getenv("AKR_PT_SIMPLE")) g_tuning.simple_kernels = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_SPECIALISE")) g_tuning.specialise = std::atoi(e);
-    if (const char* e = std::getenv("AKR_SPECIALISE_WAVES")) g_tuning.specialise_waves = std::atoi(e);
-    if (const char* e = std::getenv("AKR_WF_SORT")) g_tuning.wf_sort = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_LENS")) g_tuning.lens = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_PUNCTUAL_LIGHTS")) g_tuning.punctual_lights = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_SOFT_LIGHTS")) g_tuning.soft_lights = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_LIGHT_TREE")) g_tuning.light_tree = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_INSTANCING")) g_tuning.instancing = std::atoi(e);
-    if (const char* e = std::getenv("AKR_WF_GROUPS")) g_tuning.wf_groups = std::max(0, std::min(32, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_WF_CARRY")) g_tuning.wf_carry = std::max(0, std::min(1 << 30, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_SCHED_TRIAL")) g_tuning.sched_trial = std::max(-1, std::min(1, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_REBRAID")) g_tuning.rebraid = std::max(1, std::min(64, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_ARITH")) g_tuning.arith = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_DENOISE")) g_tuning.denoise = std::max(0, std::min(65536, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_DENOISE_VARIANCE")) g_tuning.denoise_variance = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_DENOISE_FEATURES")) g_tuning.denoise_features = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_DENOISE_KERNEL")) g_tuning.denoise_kernel = std::max(-1, std::min(1, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_ADAPTIVE")) g_tuning.adaptive = std::max(0, std::min(1 << 20, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_DISPLAY")) g_tuning.display = std::max(0, std::min(4, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_DISPLAY_AUTO_EXPOSURE")) g_tuning.display_auto_exposure = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("AKR_DISPLAY_EXPOSURE")) g_tuning.display_exposure = std::max(-65536, std::min(65536, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_DISPLAY_BLOOM")) g_tuning.display_bloom = std::max(0, std::min(65536, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_DISPLAY_KERNEL")) g_tuning.display_kernel = std::max(-1, std::min(1, std::atoi(e)));
-    if (const char* e = std::getenv("AKR_ADAPTIVE_MIN_SPP")) g_tuning.adaptive_min_spp = std::max(0, std::min(65536, std::atoi(e)));
-}
-int* tuning_field(const char* name) {
-    const std::string n = name ? name : "";
-    if (n == "force_bvh") return &g_tuning.force_bvh;
-    if (n == "bvh_balanced") return &g_tuning.bvh_balanced;
-    if (n == "defer_metal") return &g_tuning.defer_metal;
-    if (n == "wavefront") return &g_tuning.wavefront;
-    if (n == "simple_kernels") return &g_tuning.simple_kernels;
-    if (n == "defer_on") return &g_tuning.defer_on;
-    if (n == "specialise") return &g_tuning.specialise;
-    if (n == "specialise_waves") return &g_tuning.specialise_waves;
-    if (n == "max_fused_passes") return &g_tuning.max_fused_passes;
-    if (n == "wf_sort") return &g_tuning.wf_sort;
-    if (n == "lens") return &g_tuning.lens;
-    if (n == "punctual_lights") return &g_tuning.punctual_lights;
-    if (n == "soft_lights") return &g_tuning.soft_lights;
-    if (n == "light_tree") return &g_tuning.light_tree;
-    if (n == "instancing") return &g_tuning.instancing;
-    if (n == "arith") return &g_tuning.arith;
-    if (n == "rebraid") return &g_tuning.rebraid;
-    if (n == "wf_groups") return &g_tuning.wf_groups;
-    if (n == "wf_carry") return &g_tuning.wf_carry;
-    if (n == "sched_trial") return &g_tuning.sched_trial;
-    if (n == "pad_percent") return &g_tuning.pad_percent;
-    if (n == "denoise") return &g_tuning.denoise;
-    if (n == "denoise_variance") return &g_tuning.denoise_variance;
-    if (n == "denoise_features") return &g_tuning.denoise_features;
-    if (n == "denoise_kernel") return &g_tuning.denoise_kernel;
-    if (n == "adaptive") return &g_tuning.adaptive;
-    if (n == "adaptive_min_spp") return &g_tuning.adaptive_min_spp;
-    if (n == "display") return &g_tuning.display;
-    if (n == "display_auto_exposure") return &g_tuning.display_auto_exposure;
-    if (n == "display_exposure") return &g_tuning.display_exposure;
-    if (n == "display_bloom") return &g_tuning.display_bloom;
-    if (n == "display_kernel") return &g_tuning.display_kernel;
-    return nullptr;
-}
-}  // namespace
-TuningOptions tuning() {
-    std::lock_guard<std::mutex> lock(g_tuning_mutex);
-    tuning_init_locked();
-    return g_tuning;
-}
-bool tuning_set(const char* name, int value) {
-    std::lock_guard<std::mutex> lock(g_tuning_mutex);
-    tuning_init_locked();
-    int* f = tuning_field(name);
-    if (!f) return false;
-    if (f == &g_tuning.defer_on && (value < 0 || value > 3)) return false;
-    if (f == &g_tuning.specialise && (value < -1 || value > 1)) return false;
-    if (f == &g_tuning.specialise_waves && value != 0 && (value < 2 || value > 4)) return false;
-    if (f == &g_tuning.max_fused_passes && (value < 0 || value > 64)) return false;
-    if (f == &g_tuning.wf_sort && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.lens && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.punctual_lights && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.soft_lights && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.light_tree && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.instancing && (value < -1 || value > 1)) return false;
-    if (f == &g_tuning.arith && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.rebraid && (value < 1 || value > 64)) return false;
-    if (f == &g_tuning.wf_groups && (value < 0 || value > 32)) return false;
-    if (f == &g_tuning.wf_carry && (value < 0 || value > (1 << 30))) return false;
-    if (f == &g_tuning.sched_trial && (value < -1 || value > 1)) return false;
-    if (f == &g_tuning.wavefront && (value < -1 || value > 1)) return false;
-    if (f == &g_tuning.pad_percent && (value < 1 || value > 10000)) return false;
-    if (f == &g_tuning.denoise && (value < 0 || value > 65536)) return false;
-    if (f == &g_tuning.denoise_variance && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.denoise_features && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.denoise_kernel && (value < -1 || value > 1)) return false;
-    if (f == &g_tuning.adaptive && (value < 0 || value > (1 << 20))) return false;
-    if (f == &g_tuning.adaptive_min_spp && (value < 0 || value > 65536)) return false;
-    if (f == &g_tuning.display && (value < 0 || value > 4)) return false;
-    if (f == &g_tuning.display_auto_exposure && (value < 0 || value > 1)) return false;
-    if (f == &g_tuning.display_exposure && (value < -65536 || value > 65536)) return false;
-    if (f == &g_tuning.display_bloom && (value < 0 || value > 65536)) return false;
-    if (f == &g_tuning.display_kernel && (value < -1 || value > 1)) return false;
-    *f = value;
-    return true;
-}
-bool tuning_get(const char* name, int* value) {
-    std::lock_guard<std::mutex> lock(g_tuning_mutex);
-    tuning_init_locked();
-    int* f = tuning_field(name);
-    if (!f) return false;
-    *value = *f;
-    return true;
 }
 
 }  // namespace akr

@@ -9,6 +9,7 @@
 
 #include "../../../include/akari_hip.h"
 #include "../kernels.h"
+#include "options.h"
 
 namespace akr {
 
@@ -216,83 +217,9 @@ DMaterial fold_material(const akr_material_desc& m, uint32_t color = 0);
 // out.mat_inputs only
 void compile_materials(const FlatScene& flat, uint32_t color, CompiledScene& out, std::vector<akr_material_desc>& descs);
 void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry>& entries, std::vector<float>& pdf);
-// Process-wide tuning switches and test hooks (akr_option_set / akr_option_get of the C ABI). Each starts from its environment
-// variable, read ONCE when the first of them is looked at; after that only akr_option_set changes it. No launch path calls getenv.
-//   force_bvh    AKR_FORCE_BVH=1          scenes of <= 64 triangles get a BVH too (both intersectors on one scene)
-//   bvh_balanced AKR_BVH_BALANCED=1       the median-split fallback builder instead of SAH
-//   defer_metal  AKR_PT_DEFER_METAL=<m>   -1 = the library decides (default); 0 = off; m > 0 = iterations with (i & m) != 0 put conductor hits off
-//   wavefront    AKR_PT_MODE=wavefront|megakernel   the wavefront schedule (wf_kernels.hip) instead of the megakernel: 1 = wherever it can run, 0 = never,
-//                                         -1 = the library decides (default: pt sessions of >= 0.5 M ... 2 M pixels, by mesh size, on scenes kept as meshes + instances)
-//   simple_kernels AKR_PT_SIMPLE=0        0 = never use the SIMPLE instantiations (scenes without coat / transmission / normal map / glass)
-//   defer_on     (no environment hook)   BVH kernels of textured scenes: which hits the deferral puts off (0 / 1 conductor lobe, 2 texture-fed, 3 both)
-//   specialise   AKR_SPECIALISE=<v>       per-scene kernels for scenes with texture-fed materials (host/specialise.cpp): -1 = the library decides (a cached
-//                                         kernel always; a compile for renders of at least kSpecAutoSamples samples), 0 = never (the interpreter), 1 = always
-//   specialise_waves AKR_SPECIALISE_WAVES=<n>  waves per SIMD a per-scene kernel is compiled for: 0 = the library's choice, else 2..4
-//   instancing   AKR_INSTANCING=<v>       meshes + instances kept as they are (BLAS per mesh, TLAS over instances; scene_inst.cpp): -1 auto, 0 never, 1 always
-//   rebraid      AKR_REBRAID=<k>          scenes kept as meshes + instances: the top-level tree is built over k x as many (instance, subtree) pairs as
-//                                         there are instances, the largest instance boxes opened first (scene_inst.cpp); 1 = one pair per instance
-//   arith        AKR_ARITH=1              pt megakernel in the relaxed arithmetic tier (flattened scenes; precompiled kernels): hardware rcp / sqrt /
-//                                         sin / cos / log / exp and contraction instead of the bit-exact contract
-//   pad_percent  (no environment hook)    test hook: box padding in percent of the derived value (100)
-//   lens         AKR_LENS=1               akr_scene_load gives the camera the thin lens of the file's focal_distance and fstop (the reference reads both and renders a pinhole)
-//   punctual_lights AKR_PUNCTUAL_LIGHTS=0 akr_scene_load drops the file's point / spot / sun lights (the reference's lights collection has no implementation)
-//   soft_lights  AKR_SOFT_LIGHTS=0        akr_scene_load loads every light with radius 0 and angle 0: delta lights, hard shadows
-//   light_tree   AKR_LIGHT_TREE=1         the initial mode of scenes from akr_scene_load / akr_scene_create (akr_scene_set_light_tree changes it): 1 = the point and spot lights
-//                                         are one entry of the light table and a light tree chooses among them by power / distance^2; 0 (default) = one entry each
-//   wf_sort      AKR_WF_SORT=1            wavefront schedule: ray queues sorted by origin cell + direction octant before each trace launch
-//   wf_groups    AKR_WF_GROUPS=<g>        wavefront schedule: the slots run as g groups with queues and streams of their own (api_pt.cpp wf_run); 0 = the library decides
-//   wf_carry     AKR_WF_CARRY=0           wavefront schedule: 0 = every trace launch traces its rays to the end (1, default: a wave that finds the queue empty and
-//                                         has few lanes left hands their traversals to the next launch -- wf_kernels.hip; launches of >= 65 536 rays only;
-//                                         a value n > 1 = test hook: launches of >= n rays, and waves hand over after 4 steps with up to 56 lanes left)
-//   sched_trial  AKR_SCHED_TRIAL=<v>      flattened scenes, option wavefront = -1: -1 (default) = a long render of a large frame of a large untextured scene starts with two passes
-//                                         under each schedule and goes on with the faster; 0 = never (the megakernel); 1 = every pt session on a scene with a tree (tests)
-//   denoise      AKR_DENOISE=<n>          akr_render_task: n > 0 = every pt task is followed by albedo + ns aov passes of n spp and akr_denoise, "{stem}.denoised{ext}" written
-//   denoise_variance AKR_DENOISE_VARIANCE=1  akr_render_task with denoise > 0: the step is akr_denoise_variance, its half film the task's film after floor(n_passes / 2) passes
-//   denoise_features AKR_DENOISE_FEATURES=1  akr_render_task: a pt task's denoise step takes its guides from the task's own session (akr_pt_begin_features), not from aov passes
-//   denoise_kernel AKR_DENOISE_KERNEL=<v> akr_denoise's level kernel: 0 = gathering, 1 = LDS-tiled, -1 = the library decides per step (api_denoise.cpp)
-//   adaptive     AKR_ADAPTIVE=<n>         akr_render_task: n > 0 = pt tasks render through akr_pt_adaptive_render with threshold n / 1024 (api_adapt.cpp); 0 = off
-//   adaptive_min_spp AKR_ADAPTIVE_MIN_SPP=<n>  ... with this min_spp; 0 = akr_adaptive_config_default's
-//   display      AKR_DISPLAY=<c>          akr_render_task: c = 1..4 (linear, reinhard, aces, hable) = every pt task also writes "{stem}.display.png" through akr_display_transform; 0 = off
-//   display_auto_exposure, display_exposure (EV x 1024), display_bloom (strength x 1024): AKR_DISPLAY_AUTO_EXPOSURE / _EXPOSURE / _BLOOM, the fields of that transform
-//   display_kernel AKR_DISPLAY_KERNEL=<v> akr_display_transform's blur: 0 = two gathering passes, 1 = through LDS, -1 = the library decides (api_display.cpp)
-//   max_fused_passes (no environment hook)     most passes akr_pt_passes fuses into one launch: 0 = adaptive (16, up to 64 once a pass has been timed), else 1..64
-struct TuningOptions {
-    int force_bvh = 0, bvh_balanced = 0, defer_metal = -1, wavefront = -1, simple_kernels = 1;
-    int defer_on = 0;  // BVH kernels of textured scenes: which hits the deferral puts off -- 0 / 1 = the conductor lobe (default), 2 = texture-fed materials, 3 = both
-    int specialise = -1, specialise_waves = 0;
-    int max_fused_passes = 0;
-    int instancing = -1;  // two-level acceleration structure for scenes whose meshes are instanced: -1 the library decides (flattening is the
-                          // default while its records fit a budget), 0 never, 1 whenever a mesh has more than one instance
-    int rebraid = 1;  // kept scenes: (instance, subtree) pairs of the top-level tree per instance, on average (partial re-braiding); 1 = off
-    int arith = 0;    // arithmetic tier of the pt megakernel: 0 = the AKR-F32 contract (bit-exact with the oracle), 1 = relaxed (pt_kernels_relaxed.hip:
-                      // films not identical to the oracle's; how close at fixed seed: DESIGN.md 4.7)
-    int pad_percent = 100;  // test hook: the padding of the acceleration structures' boxes (flat part and needle part) in percent of what the compiler derives --
-                            // tests/test_bvh_conservative.py shows with it how far the derived padding is from the first lost hit
-    int wf_groups = 0;  // wavefront schedule: slot groups whose init / trace / shade chains run side by side on streams of their own (1 = one chain, 0 = the library decides)
-    int wf_carry = 1;  // wavefront schedule: 1 = the last rays of a trace launch are carried into the next one (wf_kernels.hip), 0 = every launch traces to the end
-    int sched_trial = -1;  // flattened scenes under option wavefront = -1: a timed trial of both schedules at the start of a long render (api_pt.cpp schedule_trial):
-                           // -1 = for the sessions it can pay for (large frame, large scene, many passes), 0 = never, 1 = every pt session on a scene with a tree (tests)
-    int punctual_lights = 1;  // akr_scene_load: 1 = the file's point / spot / sun lights light the scene; 0 = dropped, as the reference renders every file
-    int soft_lights = 1;  // akr_scene_load: 1 = the file's lights keep their radius / angle; 0 = every light is loaded as a delta light
-    int light_tree = 0;  // akr_scene_load / akr_scene_create: the scene's initial light-tree mode; 0 = selection among all lights by power alone
-    int lens = 0;  // akr_scene_load: 1 = the file's focal_distance / fstop become the camera's thin lens (radius = focal_distance / (2 fstop), load.rs:177-179); 0 = a pinhole, as the reference renders
-    int denoise = 0;  // akr_render_task: spp of the feature passes of the denoise step after a pt task; 0 = no such step
-    int denoise_variance = 0;  // akr_render_task, denoise > 0: 1 = akr_denoise_variance with the film after the first half of the passes as the half film; 0 = akr_denoise
-    int denoise_features = 0;  // akr_render_task: 1 = the denoise step's guides come from the pt task's own session (akr_pt_begin_features), not from aov passes
-    int denoise_kernel = -1;  // akr_denoise: which level kernel (0 gathering, 1 LDS-tiled, -1 the library's choice per step); same bits either way
-    int adaptive = 0;  // akr_render_task: > 0 = pt tasks render adaptively, threshold = adaptive / 1024.0f; 0 = uniformly
-    int adaptive_min_spp = 0;  // ... min_spp of those renders; 0 = the default configuration's
-    int display = 0;  // akr_render_task: 1..4 = the curve of the display transform that follows every pt task; 0 = no such step
-    int display_auto_exposure = 0, display_exposure = 0, display_bloom = 0;  // ... its auto_exposure, exposure_ev x 1024, bloom_strength x 1024
-    int display_kernel = -1;  // akr_display_transform: which blur (0 gathering passes, 1 through LDS, -1 the library's choice); same bits either way
-    int wf_sort = 0;  // wavefront schedule: 1 = the ray queues are sorted by (Morton code of the origin, octant) before every trace launch (wf_sort.hip)
-};
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it
-TuningOptions tuning();                          // a snapshot (thread-safe)
-bool tuning_set(const char* name, int value);    // false: unknown name
-bool tuning_get(const char* name, int* value);
 
-void compile_scene(const FlatScene& flat, CompiledScene& out);
+void compile_scene(const FlatScene& flat, const TuningOptions& opt, CompiledScene& out);  // opt: the caller's one snapshot of the options
 // What the exhaustive kernels stage in LDS (device/pt_pass.h: STAGE) of a compiled scene whose light list has n_lights entries, in bytes, each table padded to 16:
 // the ONE sum that compile_scene (exhaustive or BVH?), compile_environment and compile_punctual (does the scene still fit with the entry added?) compare
 // with kStageMaxBytes. A table staged in future is added here.
@@ -318,15 +245,15 @@ float triangle_emission_power(const CompiledScene& out, const TexScene& host_tex
 bool instance_may_emit(const CompiledScene& out, const std::vector<akr_material_desc>& descs, const HostInstance& in);
 // scene_inst.cpp: does this scene take the two-level route, and its geometry + light tables if so (materials and the instance table
 // of `out` must be filled: compile_scene calls it)
-bool want_instancing(const FlatScene& flat);
+bool want_instancing(const FlatScene& flat, const TuningOptions& opt);
 struct InstXf;
-void compile_instanced_geometry(const FlatScene& flat, const std::vector<InstXf>& xf, const std::vector<akr_material_desc>& descs, CompiledScene& out);
+void compile_instanced_geometry(const FlatScene& flat, const TuningOptions& opt, const std::vector<InstXf>& xf, const std::vector<akr_material_desc>& descs, CompiledScene& out);
 // PerspectiveCameraData::new (camera/mod.rs:119-153)
 void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], uint32_t* c2w_identity);
 PcgStartConsts pcg_start_constants();
 
 // scene.json / method.json readers (host/scene_json.cpp); throw std::runtime_error on failure
-FlatScene load_scene_json(const std::string& path);
+FlatScene load_scene_json(const std::string& path, const TuningOptions& opt);  // opt: punctual_lights, soft_lights, lens
 void parse_method_json(const std::string& text, akr_pt_config* cfg, std::string* film_out);
 // all tasks of a RenderTask file (Single | Multi), lib.rs:103-109; allow_sampler_override: pmj02bn -> independent
 // most LDS a workgroup of the exhaustive path tracer kernels spends on staged scene tables (4 workgroups per CU, 160 KB of LDS)

@@ -134,8 +134,7 @@ float world_half_area(const InstXf& x, const float* lo, const float* hi) {
 }
 }  // namespace
 
-bool want_instancing(const FlatScene& flat) {
-    const TuningOptions t = tuning();
+bool want_instancing(const FlatScene& flat, const TuningOptions& t) {
     if (t.instancing == 0) return false;
     std::vector<uint32_t> uses(flat.meshes.size(), 0);
     uint64_t flat_tris = 0;
@@ -155,7 +154,7 @@ bool want_instancing(const FlatScene& flat) {
     return flat_tris * kFlatBytesPerTriangle > kFlatBudgetBytes || flat_tris > kFlatMaxTriangles;
 }
 
-void compile_instanced_geometry(const FlatScene& flat, const std::vector<InstXf>& xf, const std::vector<akr_material_desc>& descs, CompiledScene& out) {
+void compile_instanced_geometry(const FlatScene& flat, const TuningOptions& tune, const std::vector<InstXf>& xf, const std::vector<akr_material_desc>& descs, CompiledScene& out) {
     CompiledScene::Instanced& is = out.instanced;
     is = CompiledScene::Instanced();
     is.on = true;
@@ -187,7 +186,7 @@ void compile_instanced_geometry(const FlatScene& flat, const std::vector<InstXf>
             out.scene_hi[a] = max_f(out.scene_hi[a], inst_bounds[6 * i + 3 + a]);
         }
     }
-    const float pad_scale = 0.01f * (float)tuning().pad_percent;  // (test hook: 100)
+    const float pad_scale = 0.01f * (float)tune.pad_percent;  // (test hook: 100)
     const float pad_world = pad_scale * bvh_box_padding(out.scene_lo, out.scene_hi, flat.camera.c2w);  // the flattened tree's padding
     float scene_mag;  // 2-norm of the largest coordinates a ray origin or a hit point can have
     {
@@ -309,7 +308,6 @@ void compile_instanced_geometry(const FlatScene& flat, const std::vector<InstXf>
     std::vector<uint32_t> blas_depth(n_mesh, 0);
     std::vector<float> mesh_size(n_mesh, 0.0f);
     std::vector<float> mesh_k2max(n_mesh, 0.0f);  // worst conditioning (isotropic: 2 |e1||e2| / |n|) of a mesh's triangles, scene_build.h
-    const TuningOptions tune = tuning();
     const bool rebraid = tune.rebraid > 1;
     std::vector<std::vector<uint32_t>> mesh_order(n_mesh);   // (re-braiding only) tree order -> prim, and the decoded tree
     std::vector<std::vector<TreeNode>> mesh_tree(n_mesh);

@@ -427,7 +427,7 @@ void load_shader(const JsonValue& shader, BufferStore& bufs, FlatScene& flat, st
 
 }  // namespace
 
-FlatScene load_scene_json(const std::string& path) {
+FlatScene load_scene_json(const std::string& path, const TuningOptions& opt) {
     JsonPtr root = JsonParser::parse(read_file(path, false));
     const JsonValue& scene = *root;
     BufferStore bufs{scene, dirname_of(path), {}};
@@ -538,7 +538,7 @@ FlatScene load_scene_json(const std::string& path) {
         }
         flat.env = environment_from_desc(d);
     }
-    if (scene.has("lights") && tuning().punctual_lights != 0) {
+    if (scene.has("lights") && opt.punctual_lights != 0) {
         // optional punctual lights: {name: {"type": "point" | "spot" | "sun", "data": {position, direction, color, strength, spot_size, spot_blend, radius (point, spot), angle (sun)}}}. An entry
         // whose data is empty is the reference's own `Light::Point(PointLight {})` (akari_scenegraph/src/scene.rs), which lights nothing: ignored.
         for (const auto& kv : scene.at("lights").obj) {
@@ -563,7 +563,7 @@ FlatScene load_scene_json(const std::string& path) {
                     d.cone_angle = dj.at("spot_size").as_f32() * 0.5f;  // spot_size is the full cone angle
                     d.blend = dj.has("spot_blend") ? dj.at("spot_blend").as_f32() : 0.0f;
                 }
-                if (tuning().soft_lights != 0) {  // the soft size; option soft_lights = 0: every light a delta light
+                if (opt.soft_lights != 0) {  // the soft size; option soft_lights = 0: every light a delta light
                     if (d.type != AKR_LIGHT_SUN && dj.has("radius")) d.radius = dj.at("radius").as_f32();
                     if (d.type == AKR_LIGHT_SUN && dj.has("angle")) d.angle = dj.at("angle").as_f32();
                 }
@@ -586,7 +586,7 @@ FlatScene load_scene_json(const std::string& path) {
     flat.camera.height = (uint32_t)cd.at("sensor_height").as_number();
     // focal_distance / fstop: the reference turns them into lens_radius and focal_length of PerspectiveCameraData (load.rs:177-189) and its
     // generate_ray never reads them; the exporter writes the pair whether or not depth of field is on. Option `lens` = 1 makes them the camera's lens.
-    if (tuning().lens != 0 && cd.has("focal_distance") && cd.has("fstop")) {
+    if (opt.lens != 0 && cd.has("focal_distance") && cd.has("fstop")) {
         const float focal_distance = cd.at("focal_distance").as_f32(), fstop = cd.at("fstop").as_f32();
         flat.lens = lens_from_values(focal_distance / (2.0f * fstop), focal_distance);
     }

@@ -163,6 +163,15 @@ typedef struct akr_pt_features_plan {
 AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
                                                int32_t spec_waves, int32_t feat, int32_t wavefront, int32_t arith, akr_pt_features_plan *out);
 
+/* Row `index` of the table of options behind akr_option_set / akr_option_get (host/options.cpp), in the table's order; AKR_ERR_INVALID_ARGUMENT
+ * past its last row. name, env: static strings (env = "" for an option without an environment variable); default_value: what the option is when
+ * the environment says nothing; ranged = 1: akr_option_set refuses values outside [lo, hi]; 0: it takes any int32 (lo, hi = INT32_MIN, INT32_MAX). */
+typedef struct akr_option_info {
+    const char *name, *env;
+    int32_t default_value, ranged, lo, hi;
+} akr_option_info;
+AKR_TEST_API int32_t akr_host_option_info(uint32_t index, akr_option_info *out);
+
 /* akr_denoise on the host (no GPU): the text of csrc/device/ddenoise.h compiled for the host, over host arrays. Each film is an accumulator
  * in the reference layout [rgb 3N | splat 3N | weight N] with its splat scale; albedo_film / normal_film may be NULL. out_rgb = 3 N floats,
  * what akr_film_resolve returns for akr_denoise's output film. Same refusals as akr_denoise. */

@@ -289,6 +289,45 @@ def test_a_session_that_times_both_schedules_renders_the_same_film(ctx, cbox_pat
     assert_parity(film.read(), o, w, h, gst, ost)
 
 
+def test_a_session_keeps_the_options_it_began_with(ctx):
+    """A session takes one snapshot of the options when it begins and reads nothing else afterwards: session A begins under sched_trial = 1 and runs
+    its passes after the options are back at their defaults, session B runs wholly under them -- both time the two schedules (the box is closed, 0.999
+    shaded vertices per closest-hit ray: a session that looked at the option again in akr_pt_passes would say "no trial of the other schedule" for
+    A), and both render the oracle's film."""
+    sd, cfg = box_scene(albedo=0.5, emission=1.0, width=32, height=32), make_config(spp=8, spp_per_pass=1, max_depth=8)
+    n = 32 * 32
+
+    def begin():
+        scene = capi.Scene(ctx, sd)
+        film = capi.Film(ctx, 32, 32)
+        return scene, film, capi.PtSession(ctx, scene, cfg, film)
+
+    def finish(scene, film, se):
+        se.passes(8, blocking=True)
+        status = se.kernel_info()["status"]
+        states = se.sampler_states(n)
+        return film.read(), se.end(), states, status
+
+    opts = dict(force_bvh=1, sched_trial=1, max_fused_passes=1)
+    before = {k: capi.get_option(k) for k in opts}
+    assert before["sched_trial"] != 1
+    with capi.options(**opts):
+        a = begin()
+    assert {k: capi.get_option(k) for k in opts} == before
+    ga, sta, sa, status_a = finish(*a)
+    with capi.options(**opts):
+        gb, stb, sb, status_b = finish(*begin())
+    print(status_a, "|", status_b)
+    for status in (status_a, status_b):
+        assert "timed trial" in status and status.split()[0] in ("megakernel", "wavefront"), (status_a, status_b)
+    os_ = pyoracle.init_pcg32_states(n, cfg.sampler_seed)
+    o, ost = pyoracle.OracleScene(sd).render(cfg, states=os_)
+    for g, st, s in ((ga, sta, sa), (gb, stb, sb)):
+        assert_parity(g, o, 32, 32, st, ost)
+        assert np.array_equal(s, os_)
+    assert n_bit_diff(ga, gb) == 0 and sta["n_launches"] == stb["n_launches"] == 6  # the trial: two launches of two passes; then max_fused_passes = 1, for A as well
+
+
 @pytest.mark.parametrize("case", ["cbox_full", "hall"])
 def test_wavefront_with_sorted_ray_queues_changes_no_bit(ctx, cbox_path, wavefront_mode, case):
     """option wf_sort (wf_sort.hip): the trace kernel reads its ray queues sorted by origin cell + direction octant. A ray's result is

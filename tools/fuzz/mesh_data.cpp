@@ -34,7 +34,7 @@ int main(int argc, char** argv) {
         }
         { std::ofstream o(dir + "/Scene.bin", std::ios::binary); o.write(d.data(), (std::streamsize)d.size()); }
         tuning_set("force_bvh", it & 1);
-        try { FlatScene fs = load_scene_json(dir + "/scene.json"); CompiledScene cs; compile_scene(fs, cs); ok++; }
+        try { FlatScene fs = load_scene_json(dir + "/scene.json", tuning()); CompiledScene cs; compile_scene(fs, tuning(), cs); ok++; }
         catch (const std::exception&) { err++; }
     }
     printf("mesh data: %zu compiled, %zu refused\n", ok, err);

@@ -38,7 +38,7 @@ int main(int argc, char** argv) {
             else d.resize(o);
         }
         { std::ofstream o(dir + "/fuzz.json", std::ios::binary); o << d; }
-        try { FlatScene fs = load_scene_json(dir + "/fuzz.json"); CompiledScene cs; compile_scene(fs, cs); ok++; }
+        try { FlatScene fs = load_scene_json(dir + "/fuzz.json", tuning()); CompiledScene cs; compile_scene(fs, tuning(), cs); ok++; }
         catch (const std::exception&) { err++; }
         std::string m = mbase;
         for (int i = 0; i < n; i++) {
