@@ -67,6 +67,7 @@ TEST_EXPORTS = [
     "akr_host_pt_features_plan", "akr_host_pcg_end_pass", "akr_probe_pcg_end_pass",
     "akr_host_light_sample", "akr_probe_light_sample", "akr_host_light_sample_soft", "akr_probe_light_sample_soft",
     "akr_host_light_tree_sample", "akr_probe_light_tree_sample", "akr_host_option_info",
+    "akr_probe_pt_cost_order", "akr_probe_pt_cost_order_mode",
 ]
 
 
@@ -186,6 +187,8 @@ def lib() -> C.CDLL:
     proto("akr_option_set", C.c_char_p, i32)
     proto("akr_option_get", C.c_char_p, C.POINTER(C.c_int32))
     proto("akr_host_option_info", u32, C.POINTER(OptionInfo))
+    proto("akr_probe_pt_cost_order", vp, up, up, up, u32, up, fp)
+    proto("akr_probe_pt_cost_order_mode", i32, C.POINTER(C.c_int32))
     proto("akr_comm_unique_id", C.POINTER(C.c_uint8))
     proto("akr_comm_create", vp, C.POINTER(C.c_uint8), i32, i32, vpp)
     proto("akr_comm_wrap", vp, vp, i32, i32, vpp)
@@ -646,6 +649,22 @@ def option_table() -> list:
     return rows
 
 
+class cost_order_mode:
+    """with capi.cost_order_mode(0): ...   -- akr_probe_pt_cost_order_mode (test hook): sessions begun inside deal their work items by position (0),
+    by measured cost where the library's rule says so (1, its behaviour) or always (2); the previous mode is restored on exit."""
+
+    def __init__(self, mode: int):
+        self.mode, self.old = int(mode), C.c_int32(1)
+
+    def __enter__(self):
+        check(lib().akr_probe_pt_cost_order_mode(self.mode, C.byref(self.old)))
+        return self
+
+    def __exit__(self, *exc):
+        check(lib().akr_probe_pt_cost_order_mode(self.old.value, None))
+        return False
+
+
 class options:
     """with capi.options(force_bvh=1, wavefront=1): ...   -- sets the options, restores the previous values on exit."""
 
@@ -799,6 +818,17 @@ class PtSession:
             return
         t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
         check(lib().akr_pt_set_active_tiles(self.h, _up(t) if t.size else C.cast(C.pointer(C.c_uint32(0)), C.POINTER(C.c_uint32)), t.size))
+
+    def cost_order(self, n_pixels: int) -> dict:
+        """akr_probe_pt_cost_order (test hook): {"state": 0 off / 1 recording / 2 in use, "cost": u32[n_pixels] or None for a session that
+        never recorded, "table": the item -> pixel table (empty before it exists), "sort_ms"}."""
+        state, n_table, ms = C.c_uint32(), C.c_uint32(), C.c_float()
+        check(lib().akr_probe_pt_cost_order(self.h, C.byref(state), None, None, 0, C.byref(n_table), None))
+        cost = np.zeros(n_pixels, dtype=np.uint32) if state.value or n_table.value else None
+        table = np.zeros(n_table.value, dtype=np.uint32)
+        check(lib().akr_probe_pt_cost_order(self.h, C.byref(state), _up(cost) if cost is not None else None, _up(table) if table.size else None, table.size,
+                                            C.byref(n_table), C.byref(ms)))
+        return {"state": state.value, "cost": cost, "table": table, "sort_ms": ms.value}
 
     def sampler_states(self, n_pixels: int) -> np.ndarray:
         st = np.zeros(2 * n_pixels, dtype=np.uint64)

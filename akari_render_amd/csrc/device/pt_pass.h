@@ -78,7 +78,14 @@ AKR_D void pt_pass_body(const PtParams& p) {
     // (an XCD-aware assignment of work items to workgroups was measured and not adopted: HISTORY.md, profiles/r4_ab_walk.txt)
     const uint32_t item = blockIdx.x * 256u + threadIdx.x;
     uint32_t px = 0, py = 0;
-    const bool in_frame = item < p.n_items && item_to_pixel(p, item, px, py);
+    bool in_frame;
+    if (p.item_pixels != nullptr) {  // cost order (kernels.h): the table covers every item of the grid, padding included
+        const uint32_t t = p.item_pixels[item];
+        in_frame = t != kInvalid;
+        if (in_frame) { py = t / p.width; px = t - py * p.width; }
+    } else {
+        in_frame = item < p.n_items && item_to_pixel(p, item, px, py);
+    }
     const uint32_t pix = px + py * p.width;
     uint32_t sx, sy;
     shifted_pixel(p, px, py, sx, sy);
@@ -223,6 +230,9 @@ AKR_D void pt_pass_body(const PtParams& p) {
             else path_step<FD ? 1 : 0, TEX, PMJ, 0, ABSENT, INST, ENV, LENS, FEAT, PUNCT, LTREE>(q, r, hit, found, occluded, pix, sx, sy);
         }
     }
+    // Cost order (kernels.h): what the lane's pixel cost this launch, by ITEM -- the index costs no register (the pixel's would have to stay
+    // live to this point: two more spilled VGPRs in the force_diffuse kernel), and the host maps items to pixels when it sorts.
+    if (p.item_cost != nullptr) p.item_cost[item] = r.c_closest;
     flush_counters(p, r, tc.cnt, BVH);
 }
 

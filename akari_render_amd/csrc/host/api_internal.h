@@ -218,6 +218,8 @@ struct RenderBase {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double kernel_ms = 0.0;
     PtVariant variant{};  // which instantiation of the pt kernel the session runs (session_params; kernels.h)
+    int cost_order_mode = 1;  // the process-wide cost-order mode as it was when the session began (base_begin; cost_order_mode() below)
+    bool plan_cost_order = false;  // pt_plan's answer for the session (session_params): its items may be ordered by measured pixel cost
     PtParams params;  // the session's constant block (session_params); a launch sets n_passes / last_pass_spp (set_launch_passes)
     bool holds_scene = false;  // counted in scene->sessions (base_begin)
     // a pt session begun by akr_pt_begin_features: the two guide films its FEAT kernels accumulate into; else null
@@ -285,6 +287,19 @@ struct akr_pt_session : RenderBase {
     // is at least 2 so that item_to_pixel reads it, params.n_items counts its pixels); room for every tile of the grid, allocated at the first call
     DevBuf active_tiles;
     bool active_set = false;
+    // Work items ordered by measured pixel cost (decided by pt_plan from the session's cost_order_mode). 1: a megakernel launch stores every item's
+    // closest-hit rays in item_cost (params.item_cost); the first launch after one that recorded sorts the session's items by it into
+    // item_pixels (params.item_pixels), on the stream, and the state becomes 2: recording stops, every later launch deals its items from the
+    // table. 0: off -- not planned, another schedule or tier renders the session, or it got an active-tile list.
+    int cost_order = 0;
+    bool cost_recorded = false;  // a launch has written item_cost
+    DevBuf item_cost, item_pixels, cost_keys, cost_keys_sorted, cost_sort_tmp;  // (the last three: the sort's scratch, released once it has run)
+    float cost_sort_ms = 0.0f;  // test hook: the one-time cost of building the table, by HIP events (0 until it has completed)
+    hipEvent_t cost_ev0 = nullptr, cost_ev1 = nullptr;
+    ~akr_pt_session() override {
+        if (cost_ev0) (void)hipEventDestroy(cost_ev0);
+        if (cost_ev1) (void)hipEventDestroy(cost_ev1);
+    }
 };
 
 namespace akr_api {
@@ -339,10 +354,16 @@ struct PtPlan {
     PtVariant v;
     uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
     uint32_t stage_bytes[13], stage_total, tex_slots;
+    bool cost_order;  // the session's megakernel launches may deal their items by measured pixel cost (akr_pt_session::cost_order)
 };
 // feat: the session collects the denoiser's guides (akr_pt_begin_features): the FEAT kernels, which exclude DEFER and SIMPLE as ENV and LENS do.
-// opt: defer_metal, simple_kernels, defer_on.
-PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat = false);
+// opt: defer_metal, simple_kernels, defer_on. cost_order: the mode below.
+PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat = false, int cost_order = 1);
+// Whether pt sessions order their work items by measured pixel cost: 0 never, 1 where pt_plan's rule says it pays (the library's behaviour),
+// 2 every megakernel session. Process-wide, read once per session by base_begin. It is not a row of the option table (host/options.cpp): results do
+// not depend on it, and only the test hook akr_probe_pt_cost_order_mode sets it, for tests and measurements.
+int cost_order_mode();
+int cost_order_mode_set(int mode);  // returns the previous mode; values outside 0..2 are ignored
 // Why a pt session of (scene, options) cannot collect guides -- "" when it can. The ONE statement of akr_pt_begin_features' refusals that need no
 // device: kept scenes, a forced wavefront schedule, the relaxed arithmetic tier (akr_host_pt_features_plan asks it for host-only scenes).
 std::string pt_features_refusal(const akr_scene* s, const TuningOptions& t);

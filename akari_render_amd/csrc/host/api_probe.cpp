@@ -403,6 +403,38 @@ AKR_TEST_API int32_t akr_host_option_info(uint32_t index, akr_option_info* out) 
     *out = {o.name, o.env, o.def, o.ranged, o.lo, o.hi};
     return AKR_OK;
 }
+AKR_TEST_API int32_t akr_probe_pt_cost_order_mode(int32_t mode, int32_t* previous) {
+    if (mode < 0 || mode > 2) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_pt_cost_order_mode: mode must be 0, 1 or 2");
+    const int before = cost_order_mode_set(mode);
+    if (previous) *previous = before;
+    return AKR_OK;
+}
+AKR_TEST_API int32_t akr_probe_pt_cost_order(akr_pt_session* se, uint32_t* state, uint32_t* cost, uint32_t* table, uint32_t capacity, uint32_t* n_table, float* sort_ms) {
+    if (!se || !state || !n_table) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_pt_cost_order: NULL argument");
+    return guarded([&] {
+        se->ctx->bind();
+        HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
+        *state = (uint32_t)se->cost_order;
+        *n_table = (uint32_t)(se->item_pixels.bytes / sizeof(uint32_t));
+        if (cost) {
+            if (!se->item_cost.p || se->active_set) throw std::invalid_argument("akr_probe_pt_cost_order: the session has no cost map, or renders an active-tile list");
+            DevBuf map;  // the items' costs, pixel by pixel (the session's own items: dealt by position, whatever the table says)
+            map.alloc(se->film->n_floats() / 7 * sizeof(uint32_t));
+            HIP_CHECK(hipMemsetAsync(map.p, 0, map.bytes, se->ctx->stream));
+            HIP_CHECK(launch_cost_to_pixels(se->params, se->item_cost.as<uint32_t>(), map.as<uint32_t>(), se->ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
+            HIP_CHECK(hipMemcpy(cost, map.p, map.bytes, hipMemcpyDeviceToHost));
+        }
+        if (table && *n_table) {
+            if (capacity < *n_table) throw std::invalid_argument("akr_probe_pt_cost_order: the table has " + std::to_string(*n_table) + " entries");
+            HIP_CHECK(hipMemcpy(table, se->item_pixels.p, se->item_pixels.bytes, hipMemcpyDeviceToHost));
+        }
+        if (sort_ms) {
+            *sort_ms = 0.0f;
+            if (se->cost_ev1) HIP_CHECK(hipEventElapsedTime(sort_ms, se->cost_ev0, se->cost_ev1));
+        }
+    });
+}
 AKR_TEST_API int32_t akr_probe_camera_rays(akr_context* ctx, akr_scene* scene, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t* pixels2,
                                       const float* u4, float* out6) {
     if (!ctx || !scene || !pixels2 || !u4 || !out6) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_probe_camera_rays: NULL argument");

@@ -43,7 +43,10 @@ std::string akr_api::pt_features_refusal(const akr_scene* s, const TuningOptions
         return "unsupported: akr_pt_begin_features: the scene has a " + punctual_light_name(s->cs) + "; the kernels that sample punctual lights collect no guides -- render them with akr_aov_render";
     return "";
 }
-PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat) {
+static std::atomic<int> g_cost_order_mode{1};
+int akr_api::cost_order_mode() { return g_cost_order_mode.load(); }
+int akr_api::cost_order_mode_set(int mode) { return mode >= 0 && mode <= 2 ? g_cost_order_mode.exchange(mode) : g_cost_order_mode.load(); }
+PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat, int cost_order) {
     const CompiledScene& cs = s->cs;
     PtPlan pl{};
     PtVariant& v = pl.v = pt_scene_facts(s, c);
@@ -120,6 +123,10 @@ PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const Tuning
             pl.stage_total = (uint32_t)std::max<size_t>(total, 16);
         }
     }
+    // Work items ordered by measured pixel cost: on where a wave's spatial coherence buys nothing -- the exhaustive walk reads
+    // every record for every lane, and a scene without textures gathers from tables in LDS. Off for the BVH kernels and kept scenes (a wave's
+    // rays share nodes), textured scenes (its lanes share texels) and sessions that collect guides (not measured). 2: all of them, to measure.
+    pl.cost_order = cost_order == 2 || (cost_order == 1 && !v.bvh && !v.tex && !v.inst && !v.feat);
     if (!pt_variant_compiled(v)) throw RenderError("pt_plan: no kernel for the variant decided");  // (cannot happen: the rules above are pt_variant_compiled's)
     return pl;
 }
@@ -169,8 +176,9 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves) {
         }
     }
     {   // which kernel, which tables staged in LDS: decided from the scene and the config (pt_plan), kept with the session
-        const PtPlan plan = pt_plan(s, c, se->opt, spec_active, spec_waves, se->feat_albedo != nullptr);
+        const PtPlan plan = pt_plan(s, c, se->opt, spec_active, spec_waves, se->feat_albedo != nullptr, se->cost_order_mode);
         se->variant = plan.v;
+        se->plan_cost_order = plan.cost_order;
         std::memcpy(p.stage_bytes, plan.stage_bytes, sizeof p.stage_bytes);
         p.stage_total = plan.stage_total;
         p.tex_slots = plan.tex_slots;
@@ -207,6 +215,32 @@ std::vector<uint32_t> akr_api::owned_tiles(uint32_t tiles_x, uint32_t tiles_y, u
 }
 
 static void read_stats(RenderBase* se, akr_pt_stats* stats);
+
+// A session's items dealt by position from now on: another schedule took it over, or it renders an active-tile list.
+static void cost_order_drop(akr_pt_session* se) {
+    se->cost_order = 0;
+    se->params.item_cost = nullptr;
+    se->params.item_pixels = nullptr;
+}
+// Before a megakernel launch of a session in state 1 whose earlier launch recorded: the table from the costs so far, on the stream (no
+// host synchronisation: the launch before wrote item_cost, the launches after read item_pixels, all in stream order).
+static void cost_order_build(akr_pt_session* se) {
+    PtParams& p = se->params;
+    const uint32_t n_padded = (p.n_items + 255u) & ~255u;
+    se->item_pixels.alloc((size_t)n_padded * sizeof(uint32_t));
+    se->cost_keys.alloc((size_t)n_padded * sizeof(uint64_t));
+    se->cost_keys_sorted.alloc((size_t)n_padded * sizeof(uint64_t));
+    se->cost_sort_tmp.alloc(std::max<size_t>(16, cost_order_temp_bytes(n_padded)));
+    HIP_CHECK(hipEventCreate(&se->cost_ev0));
+    HIP_CHECK(hipEventCreate(&se->cost_ev1));
+    HIP_CHECK(hipEventRecord(se->cost_ev0, se->ctx->stream));
+    HIP_CHECK(launch_cost_order(p, n_padded, se->cost_keys.as<uint64_t>(), se->cost_keys_sorted.as<uint64_t>(), se->cost_sort_tmp.p, se->cost_sort_tmp.bytes,
+                                se->item_pixels.as<uint32_t>(), se->ctx->stream));
+    HIP_CHECK(hipEventRecord(se->cost_ev1, se->ctx->stream));
+    p.item_pixels = se->item_pixels.as<uint32_t>();
+    p.item_cost = nullptr;  // one sort per session: nothing reads later costs
+    se->cost_order = 2;
+}
 
 static void validate_config(const akr_pt_config& c, const TileGrid& grid) {
     if (c.spp_per_pass == 0) throw std::invalid_argument("akr_pt_config: spp_per_pass must be > 0");
@@ -313,6 +347,7 @@ void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, con
     HIP_CHECK(hipMemsetAsync(se->counters.p, 0, se->counters.bytes, ctx->stream));
     if (cfg->shard_count > 1) se->owned_tiles.upload(owned_tiles(se->grid.tiles_x, se->grid.tiles_y, cfg->shard_rank, cfg->shard_count));
     se->opt = opt ? *opt : tuning();  // the session's one look at the options
+    se->cost_order_mode = cost_order_mode();
     scene->sessions++;
     se->holds_scene = true;
 }
@@ -388,6 +423,12 @@ static int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config*
             se->params.wf_sort = se->wf_sort ? 1u : 0u;
         }
         if (wavefront) se->wf = wf_allocate(se.get(), se->wf_sort);
+        if (se->plan_cost_order && !wavefront && !se->arith_relaxed) {  // (the relaxed tier and the other schedule deal by position)
+            se->item_cost.alloc((size_t)((se->grid.n_items + 255u) & ~255u) * sizeof(uint32_t));  // (a launch's whole grid writes)
+            if (se->item_cost.p) HIP_CHECK(hipMemsetAsync(se->item_cost.p, 0, se->item_cost.bytes, ctx->stream));
+            se->params.item_cost = se->item_cost.as<uint32_t>();
+            se->cost_order = 1;
+        }
         se->sched_trial = schedule_trial_eligible(se.get()) ? 1 : 0;
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         *out = se.release();
@@ -429,6 +470,11 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
         // profiles/r4_ab_walk.txt). The bound keeps a launch on a heavy scene from running for minutes.
         uint32_t kMaxFusedPasses = 16;
         se->fold_events(false);
+        if (se->cost_order == 2 && se->cost_keys.p && se->pending.empty()) {  // the sort has run: its scratch goes
+            se->cost_keys.release();
+            se->cost_keys_sorted.release();
+            se->cost_sort_tmp.release();
+        }
         if (se->opt.max_fused_passes > 0) {
             kMaxFusedPasses = (uint32_t)se->opt.max_fused_passes;  // option max_fused_passes: a fixed bound (deterministic launch counts)
         } else if (blocking && se->pending.empty() && se->passes_launched > 0 && se->kernel_ms > 0.0) {
@@ -449,8 +495,14 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             set_launch_passes(se, fused, last);
             LaunchTimer timer(se);
             if (se->active_set && se->params.n_items == 0) {}  // an empty active-tile list: the passes are counted, nothing runs
-            else if (se->wf) wf_run(se);
-            else HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr, se->arith_relaxed));
+            else if (se->wf) {
+                if (se->cost_order) cost_order_drop(se);  // (a timed trial handed the session to the other schedule)
+                wf_run(se);
+            } else {
+                if (se->cost_order == 1 && se->cost_recorded && se->params.n_items > 0) cost_order_build(se);
+                se->cost_recorded = se->cost_recorded || se->cost_order == 1;
+                HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr, se->arith_relaxed));
+            }
             timer.stop();
             se->spp_done = done;
             se->n_launches++;
@@ -513,6 +565,7 @@ AKR_API int32_t akr_pt_set_active_tiles(akr_pt_session* se, const uint32_t* tile
         }
         HIP_CHECK(hipStreamSynchronize(se->ctx->stream));  // launches in flight read the list
         se->sched_trial = se->sched_trial == 1 ? 0 : se->sched_trial;  // no timed schedule trial for a session that ever set a list
+        if (se->cost_order) cost_order_drop(se);  // ... and no cost order: its table is of the session's own tiles, and a list's tiles are few and alike
         if (!tiles) {
             se->active_set = false;
             p.shard_count = count;
@@ -590,7 +643,9 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
             info->compile_ms = se->spec->compile_ms;
             info->load_ms = se->spec->load_ms;
         }
-        std::snprintf(info->status, sizeof info->status, "%s", se->spec_status.c_str());
+        // (a session whose items are dealt by position says nothing: callers compare the status of such sessions with fixed strings)
+        const char* order = se->cost_order == 2 ? "; cost order: in use" : (se->cost_order == 1 ? "; cost order: recording" : "");
+        std::snprintf(info->status, sizeof info->status, "%s%s", se->spec_status.c_str(), order);
         if (se->wf && se->wf->buf.carry != nullptr && se->counters.p) {  // what the launches so far carried over (wf_kernels.hip; counter 7)
             const uint64_t carried = read_counters(se)[7];
             std::snprintf(info->status, sizeof info->status, "%s; %llu rays carried into a later trace launch", se->spec_status.c_str(), (unsigned long long)carried);

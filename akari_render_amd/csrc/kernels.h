@@ -232,6 +232,12 @@ struct PtParams {
     uint32_t shard_rank, shard_count;
     uint32_t tile_w, tile_h, tiles_x, tiles_y;
     const uint32_t* owned_tiles;  // shard_count > 1: the tiles (row-major ids) this rank owns, in Morton order (tile_owner below); else null
+    // cost order (host/api_pt.cpp pt_plan decides): a pt session's first launch stores every lane's closest-hit rays in item_cost[item]
+    // (pt_pass.h, after the loop; room for n_items rounded up to 256); later launches take item -> pixel from item_pixels, the session's
+    // pixels sorted by that cost, dearest first (kInvalid = no pixel: padding up to a multiple of 256). Either may be null: nothing
+    // recorded / items dealt by position (dpath.h item_to_pixel).
+    uint32_t* item_cost;
+    const uint32_t* item_pixels;
     // thin lens (dpath.h generate_ray_lens_from): radius > 0 = the session runs the LENS kernels, which alone read these
     float lens_radius, lens_focal;
     // FEAT kernels alone read these: the accumulators (7 N floats, the film's layout) of the albedo and the shading-normal guide
@@ -369,6 +375,11 @@ hipError_t launch_wf_trace(const PtParams& p, const WfBuffers& wf, uint32_t q_in
 // wf_sort.hip: key-value radix sort of a ray queue (24-bit keys)
 size_t wf_sort_temp_bytes(uint32_t n);
 hipError_t wf_sort_pairs(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n, hipStream_t stream);
+// cost_order_kernels.hip: PtParams.item_pixels from PtParams.item_cost -- the items of p (dealt by position, p.item_pixels ignored) sorted by descending cost,
+// ties by ascending pixel, kInvalid behind them. n_padded = p.n_items rounded up to 256 = entries of `table` and of each of the two key buffers.
+size_t cost_order_temp_bytes(uint32_t n_padded);
+hipError_t launch_cost_order(const PtParams& p, uint32_t n_padded, uint64_t* keys, uint64_t* keys_sorted, void* temp, size_t temp_bytes, uint32_t* table, hipStream_t stream);
+hipError_t launch_cost_to_pixels(const PtParams& p, const uint32_t* item_cost, uint32_t* pixel_cost, hipStream_t stream);  // test hook: item costs as a map over the pixels
 hipError_t launch_probe_material(const PtParams& p, uint32_t material, uint32_t n, const float* uv, uint32_t* out, hipStream_t stream);
 hipError_t launch_init_pcg32(const uint64_t* seeds, void* states, uint64_t n, hipStream_t stream);
 hipError_t launch_film_resolve(const float* film, uint64_t n, float splat_scale, float* rgb, hipStream_t stream);

@@ -163,6 +163,18 @@ typedef struct akr_pt_features_plan {
 AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene *scene, const akr_pt_config *cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on,
                                                int32_t spec_waves, int32_t feat, int32_t wavefront, int32_t arith, akr_pt_features_plan *out);
 
+/* Whether pt sessions begun from now on order their work items by measured pixel cost: 0 = never, 1 = where the library's rule says it
+ * pays (its behaviour without this hook: the exhaustive intersector without textures and without collected guides), 2 = every megakernel session.
+ * Process-wide; *previous (may be NULL) = the mode before the call. Films, sampler states and counters are the same bit for bit in every mode. */
+AKR_TEST_API int32_t akr_probe_pt_cost_order_mode(int32_t mode, int32_t *previous);
+/* A pt session's work items ordered by measured pixel cost, once everything on its stream has run:
+ *   state    0 = the items are dealt by position, 1 = the launches record the cost, 2 = the table is in use
+ *   cost     W * H words, or NULL: closest-hit rays of every pixel in the launch that recorded, 0 for pixels the session does not render (the kernel
+ *            records by work item; the hook maps items to pixels). Refused for a session that never recorded or renders an active-tile list
+ *   table    `capacity` words, or NULL: the item -> pixel table; *n_table = its entries (0 before it exists), a multiple of 256, 0xFFFFFFFF = no pixel
+ *   sort_ms  or NULL: what building the table took on the device, by HIP events (0 before it exists) */
+AKR_TEST_API int32_t akr_probe_pt_cost_order(akr_pt_session *se, uint32_t *state, uint32_t *cost, uint32_t *table, uint32_t capacity, uint32_t *n_table, float *sort_ms);
+
 /* Row `index` of the table of options behind akr_option_set / akr_option_get (host/options.cpp), in the table's order; AKR_ERR_INVALID_ARGUMENT
  * past its last row. name, env: static strings (env = "" for an option without an environment variable); default_value: what the option is when
  * the environment says nothing; ranged = 1: akr_option_set refuses values outside [lo, hi]; 0: it takes any int32 (lo, hi = INT32_MIN, INT32_MAX). */
