@@ -25,7 +25,7 @@ SOURCES = [
     "wf_kernels.hip", "wf_sort.hip",
     "cost_order_kernels.hip",  # a pt session's item -> pixel table, sorted by measured pixel cost
     "aov_kernels.hip", "gpt_kernels.hip", "mcmc_kernels.hip", "denoise_kernels.hip", "adapt_kernels.hip", "display_kernels.hip",
-    "host/options.cpp", "host/api_common.cpp", "host/api_scene.cpp", "host/api_pt.cpp", "host/wf_schedule.cpp", "host/api_aux.cpp", "host/api_task.cpp", "host/api_probe.cpp", "host/api_denoise.cpp", "host/api_adapt.cpp", "host/api_display.cpp",
+    "host/options.cpp", "host/api_common.cpp", "host/api_scene.cpp", "host/api_pt.cpp", "host/pt_plan.cpp", "host/wf_schedule.cpp", "host/api_aux.cpp", "host/api_task.cpp", "host/api_probe.cpp", "host/api_denoise.cpp", "host/api_adapt.cpp", "host/api_display.cpp",
     "host/scene_build.cpp", "host/scene_inst.cpp", "host/scene_env.cpp", "host/scene_punct.cpp",
     "host/scene_json.cpp",
     "host/bvh.cpp",

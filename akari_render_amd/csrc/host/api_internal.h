@@ -218,8 +218,6 @@ struct RenderBase {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double kernel_ms = 0.0;
     PtVariant variant{};  // which instantiation of the pt kernel the session runs (session_params; kernels.h)
-    int cost_order_mode = 1;  // the process-wide cost-order mode as it was when the session began (base_begin; cost_order_mode() below)
-    bool plan_cost_order = false;  // pt_plan's answer for the session (session_params): its items may be ordered by measured pixel cost
     PtParams params;  // the session's constant block (session_params); a launch sets n_passes / last_pass_spp (set_launch_passes)
     bool holds_scene = false;  // counted in scene->sessions (base_begin)
     // a pt session begun by akr_pt_begin_features: the two guide films its FEAT kernels accumulate into; else null
@@ -248,6 +246,29 @@ struct RenderBase {
     }
 };
 
+// Which kernel a pt session of (scene, config) runs and which tables it stages in LDS: the ONE place that decides it (pt_plan.cpp pt_plan), from the
+// compiled scene, the config and the options a session snapshots -- never from device pointers, so it answers for a host-only scene too.
+struct PtPlan {
+    PtVariant v;
+    uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
+    uint32_t stage_bytes[13], stage_total, tex_slots;
+    bool cost_order;  // the session's megakernel launches may deal their items by measured pixel cost (PtRoute::record_costs)
+};
+// What kind of session akr_pt_begin / akr_pt_begin_features make of (scene, config, options): the ONE place that decides it (pt_plan.cpp pt_route).
+struct PtRoute {
+    std::string refusal;  // not empty: no session; this message with AKR_ERR_UNSUPPORTED, and nothing below is filled in
+    bool wavefront = false;  // the wavefront schedule renders the session from its beginning ...
+    bool wf_sort = false;    // ... with sorted queues (option wf_sort): PtParams.wf_sort, the queues' keys
+    bool relaxed = false;    // option arith = 1 and the session is one the relaxed tier covers: launches go to pt_kernels_relaxed.hip
+    // per-scene kernel (host/specialise.cpp): asked for -- which also shapes the plan --, for spec_waves waves per SIMD, compiled on a cache miss only if may_compile
+    bool spec = false, may_compile = false;
+    int spec_waves = 3;
+    std::string status;  // akr_pt_kernel_info's text, until a per-scene kernel's own status or a timed trial's result takes its place
+    bool sched_trial = false;   // the first blocking akr_pt_passes call may time both schedules and keep the faster (option sched_trial)
+    bool record_costs = false;  // its megakernel launches record item costs and then deal items by them (CostOrder)
+    PtPlan plan{};  // for those choices
+};
+
 // wavefront schedule (wf_kernels.hip): path state SoA + ray queues. A pt session holds one only while that schedule renders it.
 struct WavefrontState {
     DevBuf state, queues, ctrl, pend, carry;
@@ -269,46 +290,42 @@ struct WavefrontState {
     }
 };
 
+// Work items ordered by measured pixel cost, where the route records costs. State 1: a megakernel launch stores every item's closest-hit
+// rays in item_cost (params.item_cost); the first launch after one that recorded sorts the items by it into item_pixels (params.item_pixels), on the stream;
+// then 2: recording stops, later launches deal from the table. 0: off -- not routed so, another schedule took the session over, or an active-tile list.
+struct CostOrder {
+    int state = 0;
+    bool recorded = false;  // a launch has written item_cost
+    DevBuf item_cost, item_pixels, keys, keys_sorted, sort_tmp;  // (the last three: the sort's scratch, released once it has run)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the sort (test hook: its one-time cost)
+    float sort_ms = 0.0f;
+    ~CostOrder() {  // (not copyable: its DevBufs are not)
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
 // The pt integrator's session: the base plus what only k_pt_pass and the wavefront schedule need. The other integrators hold a plain
 // RenderBase, so a per-scene kernel's parameter block (no graph value slots in LDS) cannot reach their kernels.
 struct akr_pt_session : RenderBase {
+    PtRoute route;  // what akr_pt_begin decided (pt_route); route.spec: the per-scene kernel compiled and `spec` launches
     std::unique_ptr<WavefrontState> wf;  // set = the wavefront schedule renders the session
-    int sched_trial = 0;  // flattened scenes, option wavefront = -1: 1 = the first blocking akr_pt_passes call times both schedules and keeps the faster (api_pt.cpp), 2 = done
+    int sched_trial = 0;  // 1 = route.sched_trial and still to run: the first blocking akr_pt_passes call times both schedules and keeps the faster (api_pt.cpp), 2 = done
     uint64_t passes_launched = 0;  // passes of all akr_pt_passes launches so far (kernel_ms / passes_launched = what a pass costs)
-    // per-scene kernel (host/specialise.cpp): set by akr_pt_begin when the options ask for one and the compile succeeded; the
-    // precompiled interpreter kernel otherwise. spec_active also shapes session_params (no value slots in LDS, the kernel's own LDS budget).
-    bool spec_active = false;
-    bool wf_sort = false;  // opt.wf_sort and the wavefront schedule renders the session from its beginning: PtParams.wf_sort, the queues' keys
-    bool arith_relaxed = false;  // option arith = 1 and the session is one the relaxed tier covers: launches go to pt_kernels_relaxed.hip
-    int spec_waves = 3;
     std::shared_ptr<SpecKernel> spec;
     std::string spec_status = "not requested";
     // akr_pt_set_active_tiles: the list the passes render instead of the session's own tiles (params.owned_tiles points at it, params.shard_count
     // is at least 2 so that item_to_pixel reads it, params.n_items counts its pixels); room for every tile of the grid, allocated at the first call
     DevBuf active_tiles;
     bool active_set = false;
-    // Work items ordered by measured pixel cost (decided by pt_plan from the session's cost_order_mode). 1: a megakernel launch stores every item's
-    // closest-hit rays in item_cost (params.item_cost); the first launch after one that recorded sorts the session's items by it into
-    // item_pixels (params.item_pixels), on the stream, and the state becomes 2: recording stops, every later launch deals its items from the
-    // table. 0: off -- not planned, another schedule or tier renders the session, or it got an active-tile list.
-    int cost_order = 0;
-    bool cost_recorded = false;  // a launch has written item_cost
-    DevBuf item_cost, item_pixels, cost_keys, cost_keys_sorted, cost_sort_tmp;  // (the last three: the sort's scratch, released once it has run)
-    float cost_sort_ms = 0.0f;  // test hook: the one-time cost of building the table, by HIP events (0 until it has completed)
-    hipEvent_t cost_ev0 = nullptr, cost_ev1 = nullptr;
-    ~akr_pt_session() override {
-        if (cost_ev0) (void)hipEventDestroy(cost_ev0);
-        if (cost_ev1) (void)hipEventDestroy(cost_ev1);
-    }
+    CostOrder cost;
 };
 
 namespace akr_api {
 // wf_schedule.cpp: the wavefront schedule's host half. Every option it reads is of se->opt.
-bool choose_wavefront(const akr_pt_session* se);  // which schedule renders the session (option wavefront; -1: by scene and frame size)
 std::unique_ptr<WavefrontState> wf_allocate(const akr_pt_session* se, bool sort);  // the buffers: a slot per item of the session's parameter block
 void wf_set_range(WavefrontState& ws, uint32_t n_active);  // the groups' shares of the slots [0, n_active)
 void wf_run(akr_pt_session* se);  // one launch group: the passes set_launch_passes set, for every slot
-bool schedule_trial_eligible(const akr_pt_session* se);  // may the first blocking akr_pt_passes call time both schedules (option sched_trial)
 // One timed region on a session's stream. The event pair is handed to the session by stop(); if the region is left by an
 // exception the pair is destroyed here.
 struct LaunchTimer {
@@ -342,36 +359,30 @@ void base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt
 int32_t render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, RenderBase** out);
 int32_t base_end(RenderBase* se, akr_pt_stats* stats);  // the stats read back, the session deleted (the scene released)
 // The session's kernel parameter block, computed once: everything but the two fields of set_launch_passes is constant while the
-// session lives (n_passes = 1 full pass until a launch says otherwise). The arguments are what only pt varies.
-void session_params(RenderBase* se, bool spec_active = false, int spec_waves = 3);
+// session lives (n_passes = 1 full pass until a launch says otherwise). plan: a pt session's (its route's); null = the plan of a session without
+// per-scene kernel, guides and cost order, which is every other integrator's.
+void session_params(RenderBase* se, const PtPlan* plan = nullptr);
 inline void set_launch_passes(RenderBase* se, uint32_t n_passes, uint32_t last_pass_spp) {
     se->params.n_passes = n_passes;
     se->params.last_pass_spp = last_pass_spp;
 }
-// Which kernel a pt session of (scene, config) runs and which tables it stages in LDS: the ONE place that decides it, from the compiled scene,
-// the config and the options a session snapshots -- never from device pointers, so it answers for a host-only scene too (akr_host_pt_launch_plan).
-struct PtPlan {
-    PtVariant v;
-    uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
-    uint32_t stage_bytes[13], stage_total, tex_slots;
-    bool cost_order;  // the session's megakernel launches may deal their items by measured pixel cost (akr_pt_session::cost_order)
-};
+// pt_plan.cpp
 // feat: the session collects the denoiser's guides (akr_pt_begin_features): the FEAT kernels, which exclude DEFER and SIMPLE as ENV and LENS do.
 // opt: defer_metal, simple_kernels, defer_on. cost_order: the mode below.
 PtPlan pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat = false, int cost_order = 1);
 // Whether pt sessions order their work items by measured pixel cost: 0 never, 1 where pt_plan's rule says it pays (the library's behaviour),
-// 2 every megakernel session. Process-wide, read once per session by base_begin. It is not a row of the option table (host/options.cpp): results do
+// 2 every megakernel session. Process-wide, read once per session by akr_pt_begin. It is not a row of the option table (host/options.cpp): results do
 // not depend on it, and only the test hook akr_probe_pt_cost_order_mode sets it, for tests and measurements.
 int cost_order_mode();
 int cost_order_mode_set(int mode);  // returns the previous mode; values outside 0..2 are ignored
-// Why a pt session of (scene, options) cannot collect guides -- "" when it can. The ONE statement of akr_pt_begin_features' refusals that need no
-// device: kept scenes, a forced wavefront schedule, the relaxed arithmetic tier (akr_host_pt_features_plan asks it for host-only scenes).
-std::string pt_features_refusal(const akr_scene* s, const TuningOptions& t);
 // the part of the variant that is a fact of the scene and the config: bvh, fd, tex, pmj, inst, env, lens, punct
 PtVariant pt_scene_facts(const akr_scene* s, const akr_pt_config& c);
-// Why a pt session of (scene, options) cannot render the scene's punctual lights -- "" when it can, or has none. The ONE statement of akr_pt_begin's
-// refusals for such a scene: a forced wavefront schedule, the relaxed arithmetic tier (kept scenes are refused when the scene is compiled).
-std::string pt_punctual_refusal(const akr_scene* s, const TuningOptions& t);
+// The route of a pt session: t = its snapshot of the options, grid = its tiles, feat = it collects guides, cost_order = the mode above, spec_possible =
+// false once the per-scene kernel asked for has failed to compile. Reads no device pointer; an unvalidated config does no harm (the test hooks).
+PtRoute pt_route(const akr_scene* s, const akr_pt_config& c, const TuningOptions& t, const TileGrid& grid, bool feat, int cost_order, bool spec_possible = true);
+// pt_route's refusals that are facts of scene and options alone ("" = none): punctual lights, guides. akr_pt_begin reports them before it has looked at its
+// other arguments, so it asks ahead of the route (whose refusal they also are); the relaxed tier's two come with the route, after those checks.
+std::string pt_route_refusal(const akr_scene* s, const TuningOptions& t, bool feat);
 // DScene.bvh_stack_depth / n_nodes of a compiled scene (scene_finish fills them in; a host-only scene has no DScene)
 inline uint32_t scene_stack_depth(const CompiledScene& cs) {
     // one pending group per tree level at most (disect.h); a kept scene: two levels + the three words that remember the TLAS position
@@ -397,7 +408,6 @@ std::vector<uint32_t> owned_tiles(uint32_t tiles_x, uint32_t tiles_y, uint32_t r
 void scene_finish(akr_scene* s, const TuningOptions& opt);  // opt: the snapshot akr_scene_create / akr_scene_load took
 // the light tables packed as the kernels read them (dgeom.h AliasPacked, dscene.h LightRec): what upload_lights uploads and akr_host_light_sample samples
 void packed_light_tables(const CompiledScene& cs, std::vector<AliasPacked>& light_alias, std::vector<AliasPacked>& area_alias, std::vector<LightRec>& lights);
-void scene_spec_header(akr_scene* scene, std::string& out);
 // api_aux.cpp: shard_count > 1 = this rank's share (akr_mcmc_render_shard); on_pass: akr_render_task's progress hook
 int32_t mcmc_render_impl(akr_context* ctx, akr_scene* scene, const akr_mcmc_config* cfg, akr_film* film, akr_mcmc_result* result, uint32_t* chain_states,
                          akr_pt_stats* stats, const std::function<void(uint32_t, double)>& on_pass, uint32_t shard_rank = 0, uint32_t shard_count = 1,

@@ -334,18 +334,18 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_t
     }
     return AKR_OK;
 }
-// What akr_pt_begin decides for (scene, config), without a session or a device: the variant and the staged tables (pt_plan), the per-scene
-// kernel's wrapper text, and the LDS layout a launch of the whole frame would get (launch_pt_pass: pt_lds_layout)
-// feat: the plan of akr_pt_begin_features (no per-scene kernel); -> the variant and the layout
-static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, const akr_pt_config* cfg, const TuningOptions& opt, int32_t spec_waves, bool feat,
-                                                          akr_pt_launch_plan* out) {
+// What akr_pt_begin decides for (scene, config) under the options `opt`, without a session or a device: the session's route (pt_route; its refusal is
+// thrown), of it the variant and the staged tables, the per-scene kernel's wrapper text, and the LDS layout a launch of the whole frame would
+// get (launch_pt_pass: pt_lds_layout). feat: the route of akr_pt_begin_features; -> the variant and the layout
+static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, const akr_pt_config* cfg, const TuningOptions& opt, bool feat, akr_pt_launch_plan* out) {
         const CompiledScene& cs = scene->cs;
-        const bool spec = !feat && spec_waves != 0 && cs.has_textures && !cfg->force_diffuse && cs.punct.empty();  // (where akr_pt_begin asks for a per-scene kernel)
-        const PtPlan pl = pt_plan(scene, *cfg, opt, spec, spec ? spec_waves : 3, feat);
+        const TileGrid grid = tile_grid(cfg->tile_w, cfg->tile_h, scene->flat.camera.width, scene->flat.camera.height, cfg->shard_rank, cfg->shard_count);
+        const PtRoute route = pt_route(scene, *cfg, opt, grid, feat, /*cost_order=*/1);
+        if (!route.refusal.empty()) throw Unsupported(route.refusal);
+        const PtPlan& pl = route.plan;
         const PtVariant& v = pl.v;
         const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, pl.stage_total, cfg->sampler_type == AKR_SAMPLER_PMJ02BN};
         const PtLdsLayout L = pt_lds_layout(v, sizes);
-        const TileGrid grid = tile_grid(cfg->tile_w, cfg->tile_h, scene->flat.camera.width, scene->flat.camera.height, cfg->shard_rank, cfg->shard_count);
         std::memset(out, 0, sizeof *out);
         const bool flags[10] = {v.bvh, v.fd, v.tex, v.pmj, v.stage, v.defer, v.simple, v.inst, v.env, v.lens};
         for (int i = 0; i < 10; i++) out->variant[i] = flags[i] ? 1u : 0u;
@@ -356,39 +356,37 @@ static std::pair<PtVariant, PtLdsLayout> fill_launch_plan(akr_scene* scene, cons
         out->bn_offset = L.bn_offset; out->val_offset_words = L.val_offset_words;
         out->lds_bytes = (uint32_t)L.total_bytes;
         out->blocks = (grid.n_items + 255u) / 256u;
-        out->specialised = spec ? 1u : 0u;
+        out->specialised = route.spec ? 1u : 0u;
         out->punct = v.punct ? 1u : 0u;
-        if (spec) std::snprintf(out->wrapper, sizeof out->wrapper, "%s", spec_wrapper_source(v, spec_waves).c_str());
+        if (route.spec) std::snprintf(out->wrapper, sizeof out->wrapper, "%s", spec_wrapper_source(v, route.spec_waves).c_str());
         return {v, L};
 }
-// the options a plan hook decides from: the defaults, and the three pt_plan reads as the test gives them (not the process's)
-static TuningOptions plan_options(int32_t defer_metal, int32_t simple_kernels, int32_t defer_on) {
+// the options a plan hook decides from: the defaults, and those the test gives (not the process's). spec_waves != 0: a per-scene kernel of that many waves
+static TuningOptions plan_options(int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves) {
     TuningOptions t;
     t.defer_metal = defer_metal;
     t.simple_kernels = simple_kernels;
     t.defer_on = defer_on;
+    t.specialise = spec_waves != 0 ? 1 : 0;
+    t.specialise_waves = spec_waves;
     return t;
 }
 AKR_TEST_API int32_t akr_host_pt_launch_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves,
                                              akr_pt_launch_plan* out) {
     if (!scene || !cfg || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_pt_launch_plan: NULL argument");
-    return guarded([&] { fill_launch_plan(scene, cfg, plan_options(defer_metal, simple_kernels, defer_on), spec_waves, false, out); });
+    return guarded([&] { fill_launch_plan(scene, cfg, plan_options(defer_metal, simple_kernels, defer_on, spec_waves), false, out); });
 }
-// akr_host_pt_launch_plan for a session that may collect the denoiser's guides: the refusals of akr_pt_begin_features that need no device, decided
-// for the option values given (not the process's), then the plan and what a test needs to know of the layout's sizes
+// akr_host_pt_launch_plan for a session that may collect the denoiser's guides, under options wavefront and arith as given: the route's refusals, those
+// of akr_pt_begin_features that need no device among them, then the plan and what a test needs to know of the layout's sizes
 AKR_TEST_API int32_t akr_host_pt_features_plan(akr_scene* scene, const akr_pt_config* cfg, int32_t defer_metal, int32_t simple_kernels, int32_t defer_on, int32_t spec_waves, int32_t feat,
                                                int32_t wavefront, int32_t arith, akr_pt_features_plan* out) {
     if (!scene || !cfg || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_pt_features_plan: NULL argument");
     return guarded([&] {
-        TuningOptions t = plan_options(defer_metal, simple_kernels, defer_on);
+        TuningOptions t = plan_options(defer_metal, simple_kernels, defer_on, spec_waves);
         t.wavefront = wavefront;
         t.arith = arith;
-        if (feat) {
-            const std::string why = pt_features_refusal(scene, t);
-            if (!why.empty()) throw Unsupported(why);
-        }
         std::memset(out, 0, sizeof *out);
-        const auto vl = fill_launch_plan(scene, cfg, t, spec_waves, feat != 0, &out->plan);
+        const auto vl = fill_launch_plan(scene, cfg, t, feat != 0, &out->plan);
         out->feat = vl.first.feat ? 1u : 0u;
         out->kernel_compiled = pt_variant_compiled(vl.first) ? 1u : 0u;
         out->park_slots = (vl.second.carry_offset - vl.second.park_offset) / 256u;
@@ -414,24 +412,24 @@ AKR_TEST_API int32_t akr_probe_pt_cost_order(akr_pt_session* se, uint32_t* state
     return guarded([&] {
         se->ctx->bind();
         HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
-        *state = (uint32_t)se->cost_order;
-        *n_table = (uint32_t)(se->item_pixels.bytes / sizeof(uint32_t));
+        *state = (uint32_t)se->cost.state;
+        *n_table = (uint32_t)(se->cost.item_pixels.bytes / sizeof(uint32_t));
         if (cost) {
-            if (!se->item_cost.p || se->active_set) throw std::invalid_argument("akr_probe_pt_cost_order: the session has no cost map, or renders an active-tile list");
+            if (!se->cost.item_cost.p || se->active_set) throw std::invalid_argument("akr_probe_pt_cost_order: the session has no cost map, or renders an active-tile list");
             DevBuf map;  // the items' costs, pixel by pixel (the session's own items: dealt by position, whatever the table says)
             map.alloc(se->film->n_floats() / 7 * sizeof(uint32_t));
             HIP_CHECK(hipMemsetAsync(map.p, 0, map.bytes, se->ctx->stream));
-            HIP_CHECK(launch_cost_to_pixels(se->params, se->item_cost.as<uint32_t>(), map.as<uint32_t>(), se->ctx->stream));
+            HIP_CHECK(launch_cost_to_pixels(se->params, se->cost.item_cost.as<uint32_t>(), map.as<uint32_t>(), se->ctx->stream));
             HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
             HIP_CHECK(hipMemcpy(cost, map.p, map.bytes, hipMemcpyDeviceToHost));
         }
         if (table && *n_table) {
             if (capacity < *n_table) throw std::invalid_argument("akr_probe_pt_cost_order: the table has " + std::to_string(*n_table) + " entries");
-            HIP_CHECK(hipMemcpy(table, se->item_pixels.p, se->item_pixels.bytes, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(table, se->cost.item_pixels.p, se->cost.item_pixels.bytes, hipMemcpyDeviceToHost));
         }
         if (sort_ms) {
             *sort_ms = 0.0f;
-            if (se->cost_ev1) HIP_CHECK(hipEventElapsedTime(sort_ms, se->cost_ev0, se->cost_ev1));
+            if (se->cost.ev1) HIP_CHECK(hipEventElapsedTime(sort_ms, se->cost.ev0, se->cost.ev1));
         }
     });
 }

@@ -1,5 +1,6 @@
-// api_pt.cpp -- the `pt` integrator: the plan, kernel parameters, the base session, the pt sessions and their per-scene kernels (C ABI of libakari_hip.so,
-// include/akari_hip.h; shared internals: api_internal.h; the wavefront schedule's host half: wf_schedule.cpp)
+// api_pt.cpp -- the `pt` integrator: kernel parameters, the base session, the pt sessions and their per-scene kernels (C ABI of libakari_hip.so,
+// include/akari_hip.h; shared internals: api_internal.h; what a session is routed to and what its launches run: pt_plan.cpp; the wavefront
+// schedule's host half: wf_schedule.cpp)
 #include "api_internal.h"
 
 void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_type, float filter_radius) {
@@ -13,124 +14,7 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
     p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
     p.lens_focal = s->flat.lens.focal_distance;
 }
-PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
-    const CompiledScene& cs = s->cs;  // (stage, defer, simple: pt_plan)
-    PtVariant v;
-    v.bvh = cs.has_tree();
-    v.fd = c.force_diffuse != 0;
-    v.tex = cs.has_textures;
-    v.pmj = c.sampler_type != AKR_SAMPLER_INDEPENDENT;
-    v.inst = cs.instanced.on;
-    v.env = cs.env.on;
-    v.lens = s->flat.lens.radius > 0.0f;
-    v.punct = !cs.punct.empty();
-    v.ltree = !cs.punct_tree.empty();
-    return v;
-}
-std::string akr_api::pt_punctual_refusal(const akr_scene* s, const TuningOptions& t) {
-    if (s->cs.punct.empty()) return "";
-    const std::string who = "a " + punctual_light_name(s->cs);
-    if (t.wavefront == 1) return "unsupported: the scene has " + who + " and the wavefront schedule is forced (option wavefront = 1); only the megakernel samples punctual lights";
-    if (t.arith == 1) return "unsupported: the scene has " + who + "; the relaxed arithmetic tier (option arith = 1) has no kernels that sample punctual lights";
-    return "";
-}
-std::string akr_api::pt_features_refusal(const akr_scene* s, const TuningOptions& t) {
-    if (s->cs.instanced.on)
-        return "unsupported: akr_pt_begin_features: the scene is kept as meshes + instances (option instancing); its kernels collect no guides -- render them with akr_aov_render";
-    if (t.wavefront == 1) return "unsupported: akr_pt_begin_features: the wavefront schedule is forced (option wavefront = 1); only the megakernel collects guides";
-    if (t.arith == 1) return "unsupported: akr_pt_begin_features: the relaxed arithmetic tier (option arith = 1) has no kernels that collect guides";
-    if (!s->cs.punct.empty())
-        return "unsupported: akr_pt_begin_features: the scene has a " + punctual_light_name(s->cs) + "; the kernels that sample punctual lights collect no guides -- render them with akr_aov_render";
-    return "";
-}
-static std::atomic<int> g_cost_order_mode{1};
-int akr_api::cost_order_mode() { return g_cost_order_mode.load(); }
-int akr_api::cost_order_mode_set(int mode) { return mode >= 0 && mode <= 2 ? g_cost_order_mode.exchange(mode) : g_cost_order_mode.load(); }
-PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const TuningOptions& opt, bool spec_active, int spec_waves, bool feat, int cost_order) {
-    const CompiledScene& cs = s->cs;
-    PtPlan pl{};
-    PtVariant& v = pl.v = pt_scene_facts(s, c);
-    v.feat = feat;
-    // The exclusion rules, applied here and nowhere else (kernels.h pt_variant_compiled states them): no DEFER and no SIMPLE kernels with an
-    // environment light, a lens, collected guides or punctual lights; a kept scene has neither, and its kernels stage no tables.
-    const bool plain = !v.env && !v.lens && !v.feat && !v.punct;
-    {   // SIMPLE instantiations (dbsdf.h principled_eval): the reference traces its kernel from the scene's shader graphs, so a scene
-        // without coat / transmission / normal map / glass runs a kernel without that code there too. The conditions are on the
-        // folded VALUES (coat_weight and transmission exactly 0), which is what makes dropping the branches exact.
-        bool simple = !cs.has_textures;
-        for (const DMaterial& m : cs.materials) {
-            if (m.kind == MAT_GLASS) simple = false;
-            if (m.kind == MAT_PRINCIPLED && ((m.flags & (MF_COAT | MF_EVAL_DIEL | MF_NORMAL_MAP)) != 0 || m.transmission != 0.0f || m.coat_weight != 0.0f)) simple = false;
-        }
-        pl.simple_scene = (simple && opt.simple_kernels && plain) ? 1u : 0u;
-        v.simple = pl.simple_scene != 0 && !v.fd && !v.tex && !v.inst;  // (full-graph kernels of scenes without textures)
-    }
-    {   // hits on "expensive" materials on even iterations only (device/pt_pass.h: DEFER): pays when SOME materials are expensive and
-        // most hits are not. Expensive = the conductor lobe; in the BVH kernels of scenes with textures (option defer_on) also /
-        // instead a shader graph to evaluate at the hit.
-        uint32_t flags = MF_EVAL_METAL;
-        // (measured on the textured room, BVH kernel: conductor hits deferred 591 Msamples/s, textured hits 573, both 573, none 544)
-        if (v.bvh && v.tex) flags = opt.defer_on == 2 ? MF_TEXTURED : (opt.defer_on == 3 ? (MF_EVAL_METAL | MF_TEXTURED) : MF_EVAL_METAL);
-        size_t n_dear = 0, n_surface = 0;
-        for (const DMaterial& m : cs.materials) {
-            if (m.kind == MAT_EMISSION) continue;
-            n_surface++;
-            if (m.flags & flags) n_dear++;  // the kernel's own test (pt_pass.h: DEFER), whatever the material's kind
-        }
-        bool want = n_dear > 0 && 2 * n_dear <= n_surface;
-        uint32_t mask = 1u;  // iterations with (iteration & mask) != 0 put those hits off
-        if (opt.defer_metal >= 0) { mask = (uint32_t)opt.defer_metal; want = mask != 0; }  // akr_option_set("defer_metal"): measurements / tests
-        // (full-graph kernels, of BVH scenes those with textures)
-        pl.defer_metal = (want && (!v.bvh || v.tex) && !v.fd && !v.inst && plain) ? mask : 0u;
-        pl.defer_flags = flags;
-        v.defer = pl.defer_metal != 0;
-    }
-    {   // LDS staging of the tables the shading phase gathers from (device/pt_pass.h: STAGE)
-        // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
-        // BVH path: the per-scene tables only, if the launch still fits its share of the CU's LDS with them (kernels.h pt_lds_layout)
-        const bool bvh = v.bvh;
-        size_t bytes[13] = {bvh ? 0 : cs.shade.size() * 4, bvh ? 0 : cs.normals.size() * 4, cs.inst.size() * 4, cs.materials.size() * sizeof(DMaterial),
-                            (size_t)cs.n_lights * sizeof(AliasPacked), cs.area_entries.size() * sizeof(AliasPacked), (size_t)cs.n_lights * sizeof(LightRec),
-                            cs.light_pdf.size() * 4, cs.area_pdf.size() * 4, 0, 0, 0, 0};
-        if (cs.has_textures) {  // the node lists have the same size in every colour pipeline
-            bytes[9] = cs.tex_nodes.size() * sizeof(DNode);
-            bytes[10] = cs.images.size() * sizeof(DImage);
-            bytes[11] = cs.mat_inputs.size() * sizeof(MatInputs);
-        }
-        size_t total = 0;
-        for (int i = 0; i < 12; i++) total += (bytes[i] + 15) & ~(size_t)15;
-        pl.tex_slots = (cs.has_textures && !spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
-        // the workgroup's share: a per-scene kernel built for four waves per SIMD has a quarter of the CU's LDS whatever the scene
-        const size_t budget = pt_lds_budget(v.tex && !(spec_active && spec_waves >= 4));
-        auto fits = [&](size_t staged) {  // (the blue-noise columns and the node tile only take what is left: not part of the question)
-            const PtLdsSizes sizes{scene_stack_depth(cs), cs.n_tris, scene_n_nodes(cs), pl.tex_slots, (uint32_t)staged, false};
-            return pt_lds_layout(v, sizes, /*plan_larger_park=*/true).required_bytes <= budget;
-        };
-        // all of it or nothing (a TEX kernel reads its tables through LDS addresses); the kept-scene kernels do not stage
-        const bool may = !v.inst && total <= (bvh ? kStageMaxBytesBvh : kStageMaxBytes);
-        // the albedo table as well for the full-graph exhaustive kernel of a textured scene (stage_scene_tables: GGX), if three
-        // workgroups per CU still fit (AKR_PT_MIN_WAVES_TEX = 3: 160 KB / 3)
-        const size_t ggx_bytes = 4096 * sizeof(float);
-        if (may && !bvh && v.tex && !v.fd && fits(total + ggx_bytes)) {
-            bytes[12] = ggx_bytes;
-            total += ggx_bytes;
-            v.stage = true;
-        } else {
-            v.stage = may && (!bvh || fits(total));
-        }
-        if (v.stage) {
-            for (int i = 0; i < 13; i++) pl.stage_bytes[i] = (uint32_t)bytes[i];
-            pl.stage_total = (uint32_t)std::max<size_t>(total, 16);
-        }
-    }
-    // Work items ordered by measured pixel cost: on where a wave's spatial coherence buys nothing -- the exhaustive walk reads
-    // every record for every lane, and a scene without textures gathers from tables in LDS. Off for the BVH kernels and kept scenes (a wave's
-    // rays share nodes), textured scenes (its lanes share texels) and sessions that collect guides (not measured). 2: all of them, to measure.
-    pl.cost_order = cost_order == 2 || (cost_order == 1 && !v.bvh && !v.tex && !v.inst && !v.feat);
-    if (!pt_variant_compiled(v)) throw RenderError("pt_plan: no kernel for the variant decided");  // (cannot happen: the rules above are pt_variant_compiled's)
-    return pl;
-}
-void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves) {
+void akr_api::session_params(RenderBase* se, const PtPlan* pt) {
     PtParams& p = se->params;
     const akr_scene* s = se->scene;
     const akr_pt_config& c = se->cfg;
@@ -176,9 +60,8 @@ void akr_api::session_params(RenderBase* se, bool spec_active, int spec_waves) {
         }
     }
     {   // which kernel, which tables staged in LDS: decided from the scene and the config (pt_plan), kept with the session
-        const PtPlan plan = pt_plan(s, c, se->opt, spec_active, spec_waves, se->feat_albedo != nullptr, se->cost_order_mode);
+        const PtPlan plan = pt ? *pt : pt_plan(s, c, se->opt, false, 3, false, /*cost_order=*/0);
         se->variant = plan.v;
-        se->plan_cost_order = plan.cost_order;
         std::memcpy(p.stage_bytes, plan.stage_bytes, sizeof p.stage_bytes);
         p.stage_total = plan.stage_total;
         p.tex_slots = plan.tex_slots;
@@ -218,7 +101,7 @@ static void read_stats(RenderBase* se, akr_pt_stats* stats);
 
 // A session's items dealt by position from now on: another schedule took it over, or it renders an active-tile list.
 static void cost_order_drop(akr_pt_session* se) {
-    se->cost_order = 0;
+    se->cost.state = 0;
     se->params.item_cost = nullptr;
     se->params.item_pixels = nullptr;
 }
@@ -226,20 +109,20 @@ static void cost_order_drop(akr_pt_session* se) {
 // host synchronisation: the launch before wrote item_cost, the launches after read item_pixels, all in stream order).
 static void cost_order_build(akr_pt_session* se) {
     PtParams& p = se->params;
+    CostOrder& co = se->cost;
     const uint32_t n_padded = (p.n_items + 255u) & ~255u;
-    se->item_pixels.alloc((size_t)n_padded * sizeof(uint32_t));
-    se->cost_keys.alloc((size_t)n_padded * sizeof(uint64_t));
-    se->cost_keys_sorted.alloc((size_t)n_padded * sizeof(uint64_t));
-    se->cost_sort_tmp.alloc(std::max<size_t>(16, cost_order_temp_bytes(n_padded)));
-    HIP_CHECK(hipEventCreate(&se->cost_ev0));
-    HIP_CHECK(hipEventCreate(&se->cost_ev1));
-    HIP_CHECK(hipEventRecord(se->cost_ev0, se->ctx->stream));
-    HIP_CHECK(launch_cost_order(p, n_padded, se->cost_keys.as<uint64_t>(), se->cost_keys_sorted.as<uint64_t>(), se->cost_sort_tmp.p, se->cost_sort_tmp.bytes,
-                                se->item_pixels.as<uint32_t>(), se->ctx->stream));
-    HIP_CHECK(hipEventRecord(se->cost_ev1, se->ctx->stream));
-    p.item_pixels = se->item_pixels.as<uint32_t>();
+    co.item_pixels.alloc((size_t)n_padded * sizeof(uint32_t));
+    co.keys.alloc((size_t)n_padded * sizeof(uint64_t));
+    co.keys_sorted.alloc((size_t)n_padded * sizeof(uint64_t));
+    co.sort_tmp.alloc(std::max<size_t>(16, cost_order_temp_bytes(n_padded)));
+    HIP_CHECK(hipEventCreate(&co.ev0));
+    HIP_CHECK(hipEventCreate(&co.ev1));
+    HIP_CHECK(hipEventRecord(co.ev0, se->ctx->stream));
+    HIP_CHECK(launch_cost_order(p, n_padded, co.keys.as<uint64_t>(), co.keys_sorted.as<uint64_t>(), co.sort_tmp.p, co.sort_tmp.bytes, co.item_pixels.as<uint32_t>(), se->ctx->stream));
+    HIP_CHECK(hipEventRecord(co.ev1, se->ctx->stream));
+    p.item_pixels = co.item_pixels.as<uint32_t>();
     p.item_cost = nullptr;  // one sort per session: nothing reads later costs
-    se->cost_order = 2;
+    co.state = 2;
 }
 
 static void validate_config(const akr_pt_config& c, const TileGrid& grid) {
@@ -347,7 +230,6 @@ void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, con
     HIP_CHECK(hipMemsetAsync(se->counters.p, 0, se->counters.bytes, ctx->stream));
     if (cfg->shard_count > 1) se->owned_tiles.upload(owned_tiles(se->grid.tiles_x, se->grid.tiles_y, cfg->shard_rank, cfg->shard_count));
     se->opt = opt ? *opt : tuning();  // the session's one look at the options
-    se->cost_order_mode = cost_order_mode();
     scene->sessions++;
     se->holds_scene = true;
 }
@@ -361,75 +243,41 @@ int32_t akr_api::render_begin(akr_context* ctx, akr_scene* scene, const akr_pt_c
         *out = se.release();
     });
 }
-// akr_pt_begin, and with the two guide films akr_pt_begin_features (whose refusals the caller has already made, from the same snapshot `t`)
+// akr_pt_begin, and with the two guide films akr_pt_begin_features: the session is routed (pt_route), refused if the route refuses, and the route carried out
 static int32_t pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, const TuningOptions& t, akr_pt_session** out) {
     *out = nullptr;
     return guarded([&] {
         auto se = std::make_unique<akr_pt_session>();
-        if (scene) {  // what a scene with punctual lights cannot do, before a byte is allocated
-            const std::string why = pt_punctual_refusal(scene, t);
+        const bool features = albedo != nullptr;
+        if (scene) {  // what the scene or the guides cannot do under these options, before a byte is allocated ...
+            const std::string why = pt_route_refusal(scene, t, features);
             if (!why.empty()) throw Unsupported(why);
         }
         base_begin(se.get(), ctx, scene, cfg, film, &t);
         se->feat_albedo = albedo;
         se->feat_normal = normal;
-        const bool features = albedo != nullptr;
-        const bool wavefront = !features && choose_wavefront(se.get());
-        se->wf_sort = wavefront && t.wf_sort != 0;
-        {
-            // A per-scene kernel (host/specialise.cpp) for the megakernel of a scene with texture-fed materials: always / never by
-            // option, else when the render is long enough for a first-use compile to pay.
-            const uint64_t samples = (uint64_t)film->width * film->height * (uint64_t)session_samples(*cfg);
-            // (automatic: a kernel that is already cached is used whatever the render's size; a compile -- about a second -- only
-            // when the render is long enough to win it back)
-            const bool may_compile = t.specialise == 1 || samples >= kSpecAutoSamples;
-            // The relaxed arithmetic tier (pt_kernels_relaxed.hip): the precompiled megakernels of flattened scenes. Everything else --
-            // kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
-            // Which sessions it takes is decided here and nowhere else: its translation unit holds the variants without inst, env and lens.
-            const PtVariant facts = pt_scene_facts(scene, *cfg);
-            se->arith_relaxed = t.arith == 1 && !facts.inst && !wavefront && !features;
-            if (se->arith_relaxed && facts.env)
-                throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light");
-            if (se->arith_relaxed && facts.lens)
-                throw Unsupported("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)");
-            if (se->arith_relaxed) se->spec_status = "relaxed arithmetic tier: precompiled kernels";
-            else if (wavefront) se->spec_status = "wavefront schedule";
-            else if (features) se->spec_status = scene->cs.has_textures && t.specialise == 1 ? "guides are collected by the interpreter kernels: no per-scene kernel (option specialise ignored)"
-                                                                                            : "guides are collected by the precompiled kernels";
-            else if (!scene->cs.has_textures) se->spec_status = "the scene has no texture-fed material";
-            else if (facts.punct) se->spec_status = "punctual lights are sampled by the interpreter kernels: no per-scene kernel (option specialise ignored)";
-            else if (t.specialise == 0) se->spec_status = "option specialise = 0";
-            else if (cfg->force_diffuse) se->spec_status = "force_diffuse kernels evaluate no surface graphs";
-            else {
-                {
-                    std::lock_guard<std::mutex> lock(scene->spec_mutex);
-                    if (!scene->spec_header_made) {
-                        scene->spec_header = generate_scene_spec(scene->cs);
-                        scene->spec_header_made = true;
-                    }
-                }
-                se->spec_waves = t.specialise_waves ? t.specialise_waves : 3;
-                se->spec_active = true;
-            }
-            session_params(se.get(), se->spec_active, se->spec_waves);
-            if (se->spec_active) {  // the session's variant, compiled with the scene's graphs
-                se->spec = ctx->spec_cache.get(scene->spec_header, se->variant, se->spec_waves, ctx->props.gcnArchName, may_compile);
-                se->spec_status = se->spec->status;
-                if (!se->spec->fn) {  // the interpreter kernel renders the same film: with graph value slots in LDS and its own LDS budget
-                    se->spec_active = false;
-                    session_params(se.get(), false, se->spec_waves);
-                }
-            }
-            se->params.wf_sort = se->wf_sort ? 1u : 0u;
+        const int cost_mode = cost_order_mode();
+        PtRoute& r = se->route = pt_route(scene, *cfg, t, se->grid, features, cost_mode);
+        if (!r.refusal.empty()) throw Unsupported(r.refusal);  // ... and what the relaxed tier cannot, once the arguments have been checked
+        if (r.spec) {  // the route's variant, compiled with the scene's graphs
+            std::unique_lock<std::mutex> lock(scene->spec_mutex);
+            if (!scene->spec_header_made) scene->spec_header = generate_scene_spec(scene->cs);
+            scene->spec_header_made = true;
+            lock.unlock();
+            se->spec = ctx->spec_cache.get(scene->spec_header, r.plan.v, r.spec_waves, ctx->props.gcnArchName, r.may_compile);
+            if (!se->spec->fn) r = pt_route(scene, *cfg, t, se->grid, features, cost_mode, /*spec_possible=*/false);  // the interpreter kernel renders the same film: value slots in LDS, its own LDS budget
         }
-        if (wavefront) se->wf = wf_allocate(se.get(), se->wf_sort);
-        if (se->plan_cost_order && !wavefront && !se->arith_relaxed) {  // (the relaxed tier and the other schedule deal by position)
-            se->item_cost.alloc((size_t)((se->grid.n_items + 255u) & ~255u) * sizeof(uint32_t));  // (a launch's whole grid writes)
-            if (se->item_cost.p) HIP_CHECK(hipMemsetAsync(se->item_cost.p, 0, se->item_cost.bytes, ctx->stream));
-            se->params.item_cost = se->item_cost.as<uint32_t>();
-            se->cost_order = 1;
+        se->spec_status = se->spec ? se->spec->status : r.status;
+        session_params(se.get(), &r.plan);
+        se->params.wf_sort = r.wf_sort ? 1u : 0u;
+        if (r.wavefront) se->wf = wf_allocate(se.get(), r.wf_sort);
+        if (r.record_costs) {
+            se->cost.item_cost.alloc((size_t)((se->grid.n_items + 255u) & ~255u) * sizeof(uint32_t));  // (a launch's whole grid writes)
+            if (se->cost.item_cost.p) HIP_CHECK(hipMemsetAsync(se->cost.item_cost.p, 0, se->cost.item_cost.bytes, ctx->stream));
+            se->params.item_cost = se->cost.item_cost.as<uint32_t>();
+            se->cost.state = 1;
         }
-        se->sched_trial = schedule_trial_eligible(se.get()) ? 1 : 0;
+        se->sched_trial = r.sched_trial ? 1 : 0;
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         *out = se.release();
     });
@@ -440,7 +288,7 @@ AKR_API int32_t akr_pt_begin(akr_context* ctx, akr_scene* scene, const akr_pt_co
     return pt_begin(ctx, scene, cfg, film, nullptr, nullptr, tuning(), out);
 }
 // A pt session whose kernels also accumulate the denoiser's guides (include/akari_hip.h). Everything it cannot do is refused
-// here, before a byte is allocated or written.
+// here or at the head of pt_begin, before a byte is allocated or written.
 AKR_API int32_t akr_pt_begin_features(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, akr_pt_session** out) {
     if (!out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: NULL argument");
     *out = nullptr;
@@ -454,10 +302,7 @@ AKR_API int32_t akr_pt_begin_features(akr_context* ctx, akr_scene* scene, const 
         if (g->width != scene->flat.camera.width || g->height != scene->flat.camera.height)
             return fail(AKR_ERR_INVALID_ARGUMENT, "akr_pt_begin_features: a guide film's resolution does not match the scene camera");
     }
-    const TuningOptions t = tuning();  // the refusal and the session see the same options
-    const std::string why = pt_features_refusal(scene, t);
-    if (!why.empty()) return fail(AKR_ERR_UNSUPPORTED, why);
-    return pt_begin(ctx, scene, cfg, film, albedo, normal, t, out);
+    return pt_begin(ctx, scene, cfg, film, albedo, normal, tuning(), out);
 }
 AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blocking, uint32_t* spp_done) {
     if (!se) return fail(AKR_ERR_INVALID_ARGUMENT, "session is NULL");
@@ -470,10 +315,10 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
         // profiles/r4_ab_walk.txt). The bound keeps a launch on a heavy scene from running for minutes.
         uint32_t kMaxFusedPasses = 16;
         se->fold_events(false);
-        if (se->cost_order == 2 && se->cost_keys.p && se->pending.empty()) {  // the sort has run: its scratch goes
-            se->cost_keys.release();
-            se->cost_keys_sorted.release();
-            se->cost_sort_tmp.release();
+        if (se->cost.state == 2 && se->cost.keys.p && se->pending.empty()) {  // the sort has run: its scratch goes
+            se->cost.keys.release();
+            se->cost.keys_sorted.release();
+            se->cost.sort_tmp.release();
         }
         if (se->opt.max_fused_passes > 0) {
             kMaxFusedPasses = (uint32_t)se->opt.max_fused_passes;  // option max_fused_passes: a fixed bound (deterministic launch counts)
@@ -496,12 +341,12 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             LaunchTimer timer(se);
             if (se->active_set && se->params.n_items == 0) {}  // an empty active-tile list: the passes are counted, nothing runs
             else if (se->wf) {
-                if (se->cost_order) cost_order_drop(se);  // (a timed trial handed the session to the other schedule)
+                if (se->cost.state) cost_order_drop(se);  // (a timed trial handed the session to the other schedule)
                 wf_run(se);
             } else {
-                if (se->cost_order == 1 && se->cost_recorded && se->params.n_items > 0) cost_order_build(se);
-                se->cost_recorded = se->cost_recorded || se->cost_order == 1;
-                HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->spec_active ? se->spec->fn : nullptr, se->arith_relaxed));
+                if (se->cost.state == 1 && se->cost.recorded && se->params.n_items > 0) cost_order_build(se);
+                se->cost.recorded = se->cost.recorded || se->cost.state == 1;
+                HIP_CHECK(launch_pt_pass(se->params, se->variant, se->ctx->stream, se->route.spec ? se->spec->fn : nullptr, se->route.relaxed));
             }
             timer.stop();
             se->spp_done = done;
@@ -509,7 +354,7 @@ AKR_API int32_t akr_pt_passes(akr_pt_session* se, uint32_t n_passes, int32_t blo
             se->passes_launched += fused;
             left -= fused;
         };
-        if (se->sched_trial == 1 && blocking && left >= 4 && total - se->spp_done >= 4 * se->cfg.spp_per_pass) {  // (schedule_trial_eligible)
+        if (se->sched_trial == 1 && blocking && left >= 4 && total - se->spp_done >= 4 * se->cfg.spp_per_pass) {  // (pt_route)
             se->sched_trial = 2;
             auto timed = [&](double& ms_per_sample, double& shaded_per_closest) {  // two passes under the current schedule
                 HIP_CHECK(hipStreamSynchronize(se->ctx->stream));
@@ -565,7 +410,7 @@ AKR_API int32_t akr_pt_set_active_tiles(akr_pt_session* se, const uint32_t* tile
         }
         HIP_CHECK(hipStreamSynchronize(se->ctx->stream));  // launches in flight read the list
         se->sched_trial = se->sched_trial == 1 ? 0 : se->sched_trial;  // no timed schedule trial for a session that ever set a list
-        if (se->cost_order) cost_order_drop(se);  // ... and no cost order: its table is of the session's own tiles, and a list's tiles are few and alike
+        if (se->cost.state) cost_order_drop(se);  // ... and no cost order: its table is of the session's own tiles, and a list's tiles are few and alike
         if (!tiles) {
             se->active_set = false;
             p.shard_count = count;
@@ -629,22 +474,22 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
         const uint32_t size = info->struct_size;
         std::memset(info, 0, sizeof *info);
         info->struct_size = size;
-        info->specialised = se->spec_active ? 1u : 0u;
+        info->specialised = se->route.spec ? 1u : 0u;
         info->n_shader_kinds = (uint32_t)se->scene->cs.shader_kinds.size();
         const PtVariant& v = se->variant;  // (bit 0: the flattened scene's tree; a kept scene's two-level traversal does not set it)
-        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->arith_relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u) | (v.punct ? 128u : 0u) |
+        info->kernel_flags = (v.bvh && !v.inst ? 1u : 0u) | (v.pmj ? 2u : 0u) | (v.stage ? 4u : 0u) | (v.defer ? 8u : 0u) | (se->route.relaxed ? 16u : 0u) | (v.lens ? 32u : 0u) | (v.feat ? 64u : 0u) | (v.punct ? 128u : 0u) |
                              (v.ltree ? 256u : 0u);
         info->absent_mask = se->scene->cs.absent;
         if (se->spec) {
             info->cache_hit = se->spec->cache_hit ? 1u : 0u;
-            info->min_waves = (uint32_t)se->spec_waves;
+            info->min_waves = (uint32_t)se->route.spec_waves;
             info->vgprs = (uint32_t)se->spec->vgprs;
             info->scratch_bytes = (uint32_t)se->spec->scratch_bytes;
             info->compile_ms = se->spec->compile_ms;
             info->load_ms = se->spec->load_ms;
         }
         // (a session whose items are dealt by position says nothing: callers compare the status of such sessions with fixed strings)
-        const char* order = se->cost_order == 2 ? "; cost order: in use" : (se->cost_order == 1 ? "; cost order: recording" : "");
+        const char* order = se->cost.state == 2 ? "; cost order: in use" : (se->cost.state == 1 ? "; cost order: recording" : "");
         std::snprintf(info->status, sizeof info->status, "%s%s", se->spec_status.c_str(), order);
         if (se->wf && se->wf->buf.carry != nullptr && se->counters.p) {  // what the launches so far carried over (wf_kernels.hip; counter 7)
             const uint64_t carried = read_counters(se)[7];
@@ -653,21 +498,20 @@ AKR_API int32_t akr_pt_kernel_info(akr_pt_session* se, akr_kernel_info* info) {
     });
 }
 AKR_API int32_t akr_pt_end(akr_pt_session* se, akr_pt_stats* stats) { return base_end(se, stats); }
+// every pass of the session begun with status rc_begin, then its end: what akr_pt_render and akr_pt_render_features do with their session
+static int32_t render_and_end(int32_t rc_begin, akr_pt_session* se, const akr_pt_config* cfg, akr_pt_stats* stats) {
+    if (rc_begin != AKR_OK) return rc_begin;
+    const uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
+    const int32_t rc = akr_pt_passes(se, n_passes, 1, nullptr);
+    return end_keeping_first_error(rc, [&] { return akr_pt_end(se, stats); });
+}
 AKR_API int32_t akr_pt_render(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_pt_stats* stats) {
     akr_pt_session* se = nullptr;
-    int32_t rc = akr_pt_begin(ctx, scene, cfg, film, &se);
-    if (rc != AKR_OK) return rc;
-    uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
-    rc = akr_pt_passes(se, n_passes, 1, nullptr);
-    return end_keeping_first_error(rc, [&] { return akr_pt_end(se, stats); });
+    return render_and_end(akr_pt_begin(ctx, scene, cfg, film, &se), se, cfg, stats);
 }
 AKR_API int32_t akr_pt_render_features(akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, akr_film* albedo, akr_film* normal, akr_pt_stats* stats) {
     akr_pt_session* se = nullptr;
-    int32_t rc = akr_pt_begin_features(ctx, scene, cfg, film, albedo, normal, &se);
-    if (rc != AKR_OK) return rc;
-    uint32_t n_passes = (session_samples(*cfg) + cfg->spp_per_pass - 1) / cfg->spp_per_pass;
-    rc = akr_pt_passes(se, n_passes, 1, nullptr);
-    return end_keeping_first_error(rc, [&] { return akr_pt_end(se, stats); });
+    return render_and_end(akr_pt_begin_features(ctx, scene, cfg, film, albedo, normal, &se), se, cfg, stats);
 }
 
 }  // extern "C"

@@ -1,39 +1,7 @@
-// wf_schedule.cpp -- the host half of the wavefront schedule (wf_kernels.hip): which sessions it renders, its buffers and slot groups, one launch
-// group, and which sessions may time it against the megakernel (declarations: api_internal.h, next to WavefrontState). Every option read is of
-// the session's snapshot (RenderBase::opt).
+// wf_schedule.cpp -- the host half of the wavefront schedule (wf_kernels.hip): its buffers and slot groups and one launch group (declarations:
+// api_internal.h, next to WavefrontState; which sessions it renders, and which may time it against the megakernel: pt_plan.cpp pt_route). Every
+// option read is of the session's snapshot (RenderBase::opt).
 #include "api_internal.h"
-
-// Which schedule renders this session: the persistent-lane megakernel (pt_unit_kernels.hip) or the wavefront schedule --
-// trace / shade kernels with the path state in HBM (wf_kernels.hip; needs a scene with a tree). Option wavefront: 1 = wherever it can run,
-// 0 = never, -1 (default) = the library decides:
-//   * flattened scenes: the megakernel, which measured faster on every one (on the 10 M-triangle hall both schedules
-//     are bound by the memory system's rate for random 64-byte records, and the wavefront schedule pays for streaming the path state on top);
-//   * scenes kept as meshes + instances: the WAVEFRONT schedule for pt sessions of at least wf_auto_items() pixels (round 6). The two-level
-//     traversal with its exact test spills 172 registers inside the megakernel (one lane = one whole path) and none in k_wf_trace, and the
-//     trace kernel refills a wave's idle lanes where the megakernel's wait: 1080p forest 1000 x 10 k triangles 163 -> 228 Msamples/s, 4K
-//     177 -> 282 (x 100 k: 113 -> 136 with two slot groups, 4K 125 -> 179). Below that size the persistent trace kernel's 262 k lanes
-//     are not filled and the megakernel wins (1024 x 1024, x 100 k: 124 against 85) -- profiles/r6_kept_schedules.txt. Kept scenes with
-//     texture-fed materials as well: k_wf_shade interprets the shader graphs where the megakernel has its per-scene kernels, and still
-//     the same forest with image-textured leaves and bark renders at 193 against 157 Msamples/s (x 100 k: 123 against 100).
-// The option is process-wide and aov / gpt / mcmc_opt sessions come through here too: they render with their own kernels; a scene without a
-// tree (64 triangles or fewer, no force_bvh) has no wavefront kernels and renders with the megakernel whatever the option says.
-// How large: the persistent trace kernel wants its 262 k lanes refilled many times over, and the larger the meshes the longer a launch's last
-// rays take. Measured crossovers (tools/kept_schedules.py at seven frame sizes, profiles/r6_kept_schedules.txt), with a launch's last rays carried
-// into the next one (option wf_carry, the default): 0.5 M pixels for the forest of 10 k-triangle meshes (1.7 MB of per-mesh data; 800 x 600: 145 vs
-// 147, 1024 x 768: 167 -> 189), 0.8 M for 100 k-triangle ones (17 MB; 1024 x 768: 118 vs 122, 1024 x 1024: 138 -> 150). Without carried rays: 0.7 M
-// and 1.45 M. 2 M, the constant of the first version, beyond what was measured.
-static uint32_t wf_auto_items(const akr_scene* scene, const TuningOptions& opt) {
-    const uint64_t mesh_bytes = ((uint64_t)scene->cs.instanced.nodes.size() + scene->cs.instanced.mesh_tris.size()) * 4u;
-    const bool carry = opt.wf_carry != 0 && opt.wf_sort == 0;
-    return (uint32_t)std::min<uint64_t>(2000000u, carry ? 500000u + mesh_bytes / 55u : 700000u + mesh_bytes / 18u);
-}
-bool akr_api::choose_wavefront(const akr_pt_session* se) {
-    const akr_scene* scene = se->scene;
-    const int opt = se->opt.wavefront;
-    if (opt == 0 || !scene->cs.has_tree()) return false;
-    if (opt > 0) return true;
-    return scene->cs.instanced.on && se->grid.n_items >= wf_auto_items(scene, se->opt);
-}
 
 // The groups' shares of the slots [0, n_active): the session's slots, or the shorter range of an active-tile list (akr_pt_set_active_tiles;
 // the buffers stay as they were allocated, for the session's own n_items)
@@ -224,25 +192,4 @@ void akr_api::wf_run(akr_pt_session* se) {
         }
         if (iter > (1ull << 26)) throw RenderError("wavefront schedule did not terminate");
     }
-}
-
-// Flattened scenes under option wavefront = -1. Which schedule is faster there depends on the scene -- 1080p, 10 M triangles: the closed hall 308
-// (megakernel) against 252 Msamples/s (wavefront), the open forest 309 against 369 -- through how much the lengths of a wave's traversals differ, which
-// no number the compiler has predicts. So a render that can pay for it MEASURES: the first blocking akr_pt_passes call runs two passes under the
-// megakernel, two under the wavefront schedule (HIP-event time per sample of each), and the session goes on with the faster one. Films are the same
-// bit for bit under either schedule and under any sequence of them (both start a launch from, and leave behind, the session's sampler states and
-// film). "Can pay": a pt session without textures / relaxed tier / ray sort on a scene with a tree of >= 256 MB (small scenes: the megakernel wins
-// by up to 2 x), >= 1 M pixels (the persistent trace kernel wants its lanes refilled), >= 16 passes to render; a scene whose paths practically
-// never end at a light or in the open (shaded vertices per closest-hit ray >= 0.97 in the megakernel's two passes: the hall 0.999) skips the
-// wavefront half -- it has measured slower on every such scene. Option sched_trial: 0 = never, 1 = every session on a scene with a tree (tests).
-bool akr_api::schedule_trial_eligible(const akr_pt_session* se) {
-    const TuningOptions& t = se->opt;
-    const akr_scene* sc = se->scene;
-    if (t.wavefront != -1 || t.sched_trial == 0 || se->wf || se->arith_relaxed || se->spec_active) return false;
-    if (se->feat_albedo) return false;  // a session that collects guides stays on the megakernel
-    if (!sc->cs.punct.empty()) return false;  // ... and so does a scene with punctual lights
-    if (sc->cs.instanced.on || !sc->cs.has_tree() || t.wf_sort != 0) return false;
-    if (t.sched_trial == 1) return true;
-    const uint64_t passes = (session_samples(se->cfg) + se->cfg.spp_per_pass - 1) / se->cfg.spp_per_pass;
-    return !sc->cs.has_textures && sc->device_bytes >= (256ull << 20) && passes >= 16 && se->grid.n_items >= 1000000u;
 }

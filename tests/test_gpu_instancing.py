@@ -335,7 +335,7 @@ def test_rays_carried_from_one_trace_launch_into_the_next_change_no_bit(ctx, roo
 
 
 def test_the_library_picks_the_wavefront_schedule_for_large_kept_frames(ctx, root):
-    """Option wavefront = -1 (default): pt sessions of large frames on a kept scene run the wavefront schedule (api_pt.cpp choose_wavefront:
+    """Option wavefront = -1 (default): pt sessions of large frames on a kept scene run the wavefront schedule (pt_plan.cpp choose_wavefront:
     1080p forest 163 -> 239 Msamples/s; "large" = from 0.7 M pixels for meshes that fit the L2s to 2 M, wf_auto_items), smaller ones and aov
     sessions the megakernel; same film either way."""
     assert capi.get_option("wavefront") == -1

@@ -1,4 +1,4 @@
-"""The timed schedule trial of a long render on a large flattened scene (api_pt.cpp schedule_trial_eligible): which schedule the session kept and what the
+"""The timed schedule trial of a long render on a large flattened scene (pt_plan.cpp pt_route): which schedule the session kept and what the
 render then runs at, against the same render with the trial switched off.  python tools/sched_trial_check.py   (needs a GPU)"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
