@@ -1,8 +1,9 @@
-// ddenoise.h -- the edge-avoiding a-trous filter of akr_denoise, written once for the device (denoise_kernels.hip)
-// and the host (host/api_denoise.cpp akr_host_denoise). Under the AKR-F32 contract: no contraction, IEEE division, exp_f of dmath.h.
+// ddenoise.h -- the edge-avoiding a-trous filter of akr_denoise and akr_denoise_variance, written once for the device
+// (denoise_kernels.hip) and the host (host/api_denoise.cpp host_denoise). Under the AKR-F32 contract: no contraction, IEEE division, exp_f of dmath.h.
 //
-// A pixel is three 16-byte records: {x.rgb, valid}, {n.xyz, -}, {a.rgb, -} -- x the (demodulated) colour, n and a the guides as resolved.
+// A pixel is three 16-byte records: {x.rgb, x.w}, {n.xyz, n.w}, {a.rgb, -} -- x the (demodulated) colour, n and a the guides as resolved.
 // One level at step s reads the 5 x 5 taps q = p + s (dx, dy) of the previous level's x and writes the next x; n and a never change.
+// What the fourth components hold is the guide policy's (below): the one thing akr_denoise and akr_denoise_variance differ in.
 #pragma once
 #include "dmath.h"
 
@@ -14,6 +15,20 @@ struct DenoiseLevel {
     float kc, kn, ka;
 };
 
+// The guide policies. akr_denoise: x.w = 1 for a valid pixel, 0 for an invalid one; n.w is not read; lv.kc = 1 / (sigma_color 2^-i)^2.
+struct DnPlain {
+    static constexpr bool kVariance = false;
+    static constexpr float kValidW = 1.0f, kInvalidW = 0.0f;  // x.w as prepare writes it; kInvalidW is an out-of-image record's too
+    static AKR_HD bool valid(const float4& x) { return x.w != 0.0f; }
+};
+// akr_denoise_variance ("Variance guide"): x.w = v, the variance of the pixel's colour, and -1 for an invalid pixel; n.w = r, the pixel's own
+// two-half estimate, and -1 where there is none. A level reads lv.kc as kv = 1 / sigma_variance^2.
+struct DnVariance {
+    static constexpr bool kVariance = true;
+    static constexpr float kValidW = 0.0f, kInvalidW = -1.0f;
+    static AKR_HD bool valid(const float4& x) { return !(x.w < 0.0f); }
+};
+
 // dot(v, v) = (vx vx + vy vy) + vz vz of v = p - q
 AKR_HD float dn_dist2(const float4& p, const float4& q) {
     const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
@@ -23,6 +38,9 @@ AKR_HD float dn_dist2(const float4& p, const float4& q) {
 // B = {1/16, 1/4, 3/8, 1/4, 1/16}: the B3 spline, every product of two entries exact
 AKR_HD float dn_b3(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 
+// G = {1/4, 1/2, 1/4}
+AKR_HD float dn_g3(int d) { return d == 0 ? 0.5f : 0.25f; }
+
 // w = h exp(-e), e = (|x_p - x_q|^2 kc + |n_p - n_q|^2 kn) + |a_p - a_q|^2 ka
 AKR_HD float dn_tap_weight(float h, const float4& xp, const float4& np_, const float4& ap, const float4& xq, const float4& nq, const float4& aq,
                            const DenoiseLevel& lv) {
@@ -30,14 +48,33 @@ AKR_HD float dn_tap_weight(float h, const float4& xp, const float4& np_, const f
     return h * exp_f(-e);
 }
 
-// The record x of pixel (px, py) after one level. fetch(dx, dy, xq, nq, aq) -> bool reads the records of the in-image pixel
-// (px, py) + step (dx, dy) and says whether it is valid: the two level kernels and the host differ in nothing but where the records lie.
-template <class Fetch>
+// The record x of pixel (px, py) after one level under guide G. fetch(dx, dy, xq, nq, aq) -> bool reads the records of the in-image pixel
+// (px, py) + step (dx, dy) and says whether it is valid (G::valid(xq)): the two level kernels and the host differ in nothing but where the
+// records lie. DnVariance: kc is divided by g, the variance smoothed over the 3 x 3 taps of the level's own lattice, and x.w becomes v'.
+template <class G, class Fetch>
 AKR_HD float4 dn_level_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& fetch) {
     float4 xp, np_, ap;
     if (!fetch(0, 0, xp, np_, ap)) return xp;  // an invalid centre passes through unchanged
-    float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, wsum = 0.0f;
     const int s = (int)lv.step;
+    DenoiseLevel lp = lv;
+    if constexpr (G::kVariance) {
+        float gn = 0.0f, gd = 0.0f;
+        for (int dy = -1; dy <= 1; dy++) {
+            const int qy = py + s * dy;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = px + s * dx;
+                if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
+                float4 xq, nq, aq;
+                if (!fetch(dx, dy, xq, nq, aq)) continue;
+                const float gw = dn_g3(dx) * dn_g3(dy);
+                gn = gn + gw * xq.w;
+                gd = gd + gw;
+            }
+        }
+        const float g = gn / gd;
+        lp.kc = lv.kc / (g + 1e-10f);
+    }
+    [[maybe_unused]] float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, vacc = 0.0f, wsum = 0.0f;  // (vacc: DnVariance alone)
     for (int dy = -2; dy <= 2; dy++) {
         const int qy = py + s * dy;
         for (int dx = -2; dx <= 2; dx++) {
@@ -45,10 +82,11 @@ AKR_HD float4 dn_level_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& fet
             if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;  // no clamping, no mirroring
             float4 xq, nq, aq;
             if (!fetch(dx, dy, xq, nq, aq)) continue;
-            const float w = dn_tap_weight(dn_b3(dx) * dn_b3(dy), xp, np_, ap, xq, nq, aq, lv);
+            const float w = dn_tap_weight(dn_b3(dx) * dn_b3(dy), xp, np_, ap, xq, nq, aq, lp);
             acc0 = acc0 + w * xq.x;
             acc1 = acc1 + w * xq.y;
             acc2 = acc2 + w * xq.z;
+            if constexpr (G::kVariance) vacc = vacc + (w * w) * xq.w;
             wsum = wsum + w;
         }
     }
@@ -56,7 +94,8 @@ AKR_HD float4 dn_level_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& fet
     y.x = acc0 / wsum;
     y.y = acc1 / wsum;
     y.z = acc2 / wsum;
-    y.w = xp.w;
+    if constexpr (G::kVariance) y.w = vacc / (wsum * wsum);
+    else y.w = xp.w;
     return y;
 }
 
@@ -85,9 +124,11 @@ AKR_HD float4 dn_divisor(const float4& a, bool demodulate, float albedo_floor) {
     return d;
 }
 
-// resolve, demodulate, validity: the three records of pixel i
-AKR_HD void dn_prepare_pixel(const float* color, float color_scale, const float* albedo, float albedo_scale, const float* normal, float normal_scale,
-                             uint64_t n, uint64_t i, bool demodulate, float albedo_floor, float4& x, float4& nn, float4& a) {
+// resolve, demodulate, validity: the three records of pixel i. DnVariance: plus the two-half estimate r = |xA - xB|^2 (wA wB) / (C.w C.w) of
+// `half`, the colour film as it stood after a subset of the samples (its splat plane is not read). DnPlain does not read `half`.
+template <class G>
+AKR_HD void dn_prepare_pixel(const float* color, float color_scale, const float* half, const float* albedo, float albedo_scale, const float* normal,
+                             float normal_scale, uint64_t n, uint64_t i, bool demodulate, float albedo_floor, float4& x, float4& nn, float4& a) {
     const float4 c = dn_resolve(color, n, i, color_scale);
     a = dn_resolve(albedo, n, i, albedo_scale);
     nn = dn_resolve(normal, n, i, normal_scale);
@@ -97,41 +138,27 @@ AKR_HD void dn_prepare_pixel(const float* color, float color_scale, const float*
     x.z = c.z / d.z;
     const bool valid = dn_finite(x.x) && dn_finite(x.y) && dn_finite(x.z) && dn_finite(nn.x) && dn_finite(nn.y) && dn_finite(nn.z) && dn_finite(a.x) &&
                        dn_finite(a.y) && dn_finite(a.z);
-    x.w = valid ? 1.0f : 0.0f;
+    x.w = valid ? G::kValidW : G::kInvalidW;
+    if constexpr (G::kVariance) {
+        const float wc = color[6 * n + i];
+        const float wa = half[6 * n + i], wb = wc - wa;
+        float4 xa, xb;
+        xa.x = (half[3 * i + 0] / wa) / d.x;
+        xa.y = (half[3 * i + 1] / wa) / d.y;
+        xa.z = (half[3 * i + 2] / wa) / d.z;
+        xb.x = ((color[3 * i + 0] - half[3 * i + 0]) / wb) / d.x;
+        xb.y = ((color[3 * i + 1] - half[3 * i + 1]) / wb) / d.y;
+        xb.z = ((color[3 * i + 2] - half[3 * i + 2]) / wb) / d.z;
+        xa.w = xb.w = 0.0f;
+        const float f = (wa * wb) / (wc * wc);
+        const float r = dn_dist2(xa, xb) * f;
+        const bool est = valid && wa > 0.0f && wb > 0.0f && dn_finite(r);
+        nn.w = est ? r : -1.0f;
+    }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// The variance guide of akr_denoise_variance (DESIGN.md 4.10 "Variance guide"). The records differ from the ones above in their fourth
-// components: x = {x.rgb, v} with v the variance of the pixel's colour, and -1 for an invalid pixel (valid <=> !(x.w < 0));
-// n = {n.xyz, r} with r the pixel's own two-half estimate, and -1 where there is none. A level reads lv.kc as kv = 1 / sigma_variance^2.
-AKR_HD bool dn_var_valid(const float4& x) { return !(x.w < 0.0f); }
-
-// dn_prepare_pixel plus the two-half estimate r = |xA - xB|^2 (wA wB) / (C.w C.w) of `half`, the colour film as it stood after a subset
-// of the samples (its splat plane is not read)
-AKR_HD void dn_prepare_pixel_var(const float* color, float color_scale, const float* half, const float* albedo, float albedo_scale, const float* normal,
-                                 float normal_scale, uint64_t n, uint64_t i, bool demodulate, float albedo_floor, float4& x, float4& nn, float4& a) {
-    dn_prepare_pixel(color, color_scale, albedo, albedo_scale, normal, normal_scale, n, i, demodulate, albedo_floor, x, nn, a);
-    const bool valid = x.w != 0.0f;
-    const float4 d = dn_divisor(a, demodulate, albedo_floor);
-    const float wc = color[6 * n + i];
-    const float wa = half[6 * n + i], wb = wc - wa;
-    float4 xa, xb;
-    xa.x = (half[3 * i + 0] / wa) / d.x;
-    xa.y = (half[3 * i + 1] / wa) / d.y;
-    xa.z = (half[3 * i + 2] / wa) / d.z;
-    xb.x = ((color[3 * i + 0] - half[3 * i + 0]) / wb) / d.x;
-    xb.y = ((color[3 * i + 1] - half[3 * i + 1]) / wb) / d.y;
-    xb.z = ((color[3 * i + 2] - half[3 * i + 2]) / wb) / d.z;
-    xa.w = xb.w = 0.0f;
-    const float f = (wa * wb) / (wc * wc);
-    const float r = dn_dist2(xa, xb) * f;
-    const bool est = valid && wa > 0.0f && wb > 0.0f && dn_finite(r);
-    x.w = valid ? 0.0f : -1.0f;
-    nn.w = est ? r : -1.0f;
-}
-
-// v0 of the valid pixel (px, py): the 7 x 7 guide-weighted mean of the estimates r. fetch(dx, dy, nq, aq) -> bool reads the n and a records
-// of the in-image pixel (px, py) + (dx, dy) and says whether it carries an estimate (nq.w, then)
+// v0 of the valid pixel (px, py) of akr_denoise_variance: the 7 x 7 guide-weighted mean of the estimates r. fetch(dx, dy, nq, aq) -> bool reads
+// the n and a records of the in-image pixel (px, py) + (dx, dy) and says whether it carries an estimate (nq.w, then)
 template <class Fetch>
 AKR_HD float dn_prefilter_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& fetch) {
     float4 np_, ap;
@@ -150,56 +177,6 @@ AKR_HD float dn_prefilter_pixel(int px, int py, const DenoiseLevel& lv, Fetch&& 
         }
     }
     return den > 0.0f ? num / den : 0.0f;
-}
-
-// G = {1/4, 1/2, 1/4}
-AKR_HD float dn_g3(int d) { return d == 0 ? 0.5f : 0.25f; }
-
-// The record x = {y.rgb, v'} of pixel (px, py) after one variance-guided level; fetch as for dn_level_pixel, valid <=> dn_var_valid(xq)
-template <class Fetch>
-AKR_HD float4 dn_level_pixel_var(int px, int py, const DenoiseLevel& lv, Fetch&& fetch) {
-    float4 xp, np_, ap;
-    if (!fetch(0, 0, xp, np_, ap)) return xp;  // an invalid centre passes through unchanged
-    const int s = (int)lv.step;
-    // g: the variance smoothed over the 3 x 3 taps of the level's own lattice
-    float gn = 0.0f, gd = 0.0f;
-    for (int dy = -1; dy <= 1; dy++) {
-        const int qy = py + s * dy;
-        for (int dx = -1; dx <= 1; dx++) {
-            const int qx = px + s * dx;
-            if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
-            float4 xq, nq, aq;
-            if (!fetch(dx, dy, xq, nq, aq)) continue;
-            const float gw = dn_g3(dx) * dn_g3(dy);
-            gn = gn + gw * xq.w;
-            gd = gd + gw;
-        }
-    }
-    const float g = gn / gd;
-    DenoiseLevel lp = lv;
-    lp.kc = lv.kc / (g + 1e-10f);
-    float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, vacc = 0.0f, wsum = 0.0f;
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = py + s * dy;
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = px + s * dx;
-            if (qx < 0 || qy < 0 || qx >= (int)lv.width || qy >= (int)lv.height) continue;
-            float4 xq, nq, aq;
-            if (!fetch(dx, dy, xq, nq, aq)) continue;
-            const float w = dn_tap_weight(dn_b3(dx) * dn_b3(dy), xp, np_, ap, xq, nq, aq, lp);
-            acc0 = acc0 + w * xq.x;
-            acc1 = acc1 + w * xq.y;
-            acc2 = acc2 + w * xq.z;
-            vacc = vacc + (w * w) * xq.w;
-            wsum = wsum + w;
-        }
-    }
-    float4 y;
-    y.x = acc0 / wsum;
-    y.y = acc1 / wsum;
-    y.z = acc2 / wsum;
-    y.w = vacc / (wsum * wsum);
-    return y;
 }
 
 // out = y d

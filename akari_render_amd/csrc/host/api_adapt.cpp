@@ -229,21 +229,16 @@ AKR_TEST_API int32_t akr_probe_adapt_times(akr_context* ctx, akr_film* film, akr
         DevBuf d_tiles, d_err;
         d_tiles.upload(std::vector<uint32_t>(tiles, tiles + n));
         d_err.alloc((size_t)n * sizeof(float));
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        struct Guard {
-            hipEvent_t* e;
-            ~Guard() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); }
-        } guard{ev};
-        for (int k = 0; k < 4; k++) HIP_CHECK(hipEventCreate(&ev[k]));
-        HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
+        StreamMarks marks(ctx->stream, true);
+        marks.mark();
         HIP_CHECK(launch_tile_error(fr, film->data, half->data, d_tiles.as<uint32_t>(), n, d_err.as<float>(), ctx->stream));
-        HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
+        marks.mark();
         HIP_CHECK(launch_half_bracket(fr, film->data, half->data, d_tiles.as<uint32_t>(), n, false, ctx->stream));
-        HIP_CHECK(hipEventRecord(ev[2], ctx->stream));
+        marks.mark();
         HIP_CHECK(launch_half_bracket(fr, film->data, half->data, d_tiles.as<uint32_t>(), n, true, ctx->stream));
-        HIP_CHECK(hipEventRecord(ev[3], ctx->stream));
+        marks.mark();
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < 3; k++) HIP_CHECK(hipEventElapsedTime(&times3[k], ev[k], ev[k + 1]));
+        for (int k = 0; k < 3; k++) times3[k] = marks.ms(k, k + 1);
     });
 }
 #endif

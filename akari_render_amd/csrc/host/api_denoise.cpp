@@ -1,6 +1,6 @@
 // api_denoise.cpp -- akr_denoise: the edge-avoiding a-trous filter over a colour film and its albedo / normal guides
 // (C ABI of libakari_hip.so, include/akari_hip.h; shared internals: api_internal.h). The arithmetic is csrc/device/ddenoise.h: the kernels
-// of denoise_kernels.hip run it on the device, akr_host_denoise (a test hook) runs the same text here.
+// of denoise_kernels.hip run it on the device, host_denoise (behind two test hooks) runs the same text here.
 #include "api_internal.h"
 #include "../denoise_kernels.h"
 #if defined(AKR_TEST_HOOKS) && AKR_TEST_HOOKS
@@ -10,7 +10,8 @@
 namespace {
 constexpr uint32_t kMaxIterations = 8;
 
-void check_config(const akr_denoise_config& c) {
+// variance: akr_denoise's refusals, then those of sigma_variance. kv / (g + 1e-10f) has to stay finite for g = 0
+void check_config(const akr_denoise_config& c, bool variance) {
     auto sigma_ok = [](float s) { return s >= 0.0f && s <= 3.4028235e38f; };  // (false for NaN and inf)
     if (c.iterations > kMaxIterations) throw std::invalid_argument("akr_denoise: iterations = " + std::to_string(c.iterations) + " (at most 8)");
     if (!sigma_ok(c.sigma_color) || !sigma_ok(c.sigma_normal) || !sigma_ok(c.sigma_albedo))
@@ -21,11 +22,7 @@ void check_config(const akr_denoise_config& c) {
     auto k_ok = [](float s) { return s == 0.0f || 1.0f / (s * s) <= 3.4028235e38f; };
     if (!k_ok(c.sigma_color * (1.0f / (float)(1u << last))) || !k_ok(c.sigma_normal) || !k_ok(c.sigma_albedo))
         throw std::invalid_argument("akr_denoise: a sigma is too small: 1 / sigma^2 (sigma_color at the last level: sigma_color 2^-(iterations - 1)) is not finite in f32");
-}
-
-// akr_denoise_variance: akr_denoise's refusals and those of sigma_variance. kv / (g + 1e-10f) has to stay finite for g = 0
-void check_config_variance(const akr_denoise_config& c) {
-    check_config(c);
+    if (!variance) return;
     if (!(c.sigma_variance > 0.0f && c.sigma_variance <= 3.4028235e38f)) throw std::invalid_argument("akr_denoise_variance: sigma_variance must be finite and > 0");
     const float kv = 1.0f / (c.sigma_variance * c.sigma_variance);
     if (!(kv / 1e-10f <= 3.4028235e38f))
@@ -35,21 +32,15 @@ void check_config_variance(const akr_denoise_config& c) {
 // k = 1 / sigma^2 in f32; a sigma of exactly 0 switches the term off
 float inv_sigma2(float sigma) { return sigma == 0.0f ? 0.0f : 1.0f / (sigma * sigma); }
 
-DenoiseLevel level_params(const akr_denoise_config& c, uint32_t w, uint32_t h, uint32_t i, bool have_albedo, bool have_normal) {
+// variance: kc = kv = 1 / sigma_variance^2 at every level (the variance shrinks by itself)
+DenoiseLevel level_params(const akr_denoise_config& c, uint32_t w, uint32_t h, uint32_t i, bool have_albedo, bool have_normal, bool variance) {
     DenoiseLevel lv;
     lv.width = w;
     lv.height = h;
     lv.step = 1u << i;
-    lv.kc = inv_sigma2(c.sigma_color * (1.0f / (float)(1u << i)));  // sigma_color 2^-i: an exact scaling
+    lv.kc = variance ? 1.0f / (c.sigma_variance * c.sigma_variance) : inv_sigma2(c.sigma_color * (1.0f / (float)(1u << i)));  // sigma_color 2^-i: an exact scaling
     lv.kn = have_normal ? inv_sigma2(c.sigma_normal) : 0.0f;
     lv.ka = have_albedo ? inv_sigma2(c.sigma_albedo) : 0.0f;
-    return lv;
-}
-
-// The same for a variance-guided level: kc = kv = 1 / sigma_variance^2 at every level (the variance shrinks by itself)
-DenoiseLevel level_params_variance(const akr_denoise_config& c, uint32_t w, uint32_t h, uint32_t i, bool have_albedo, bool have_normal) {
-    DenoiseLevel lv = level_params(c, w, h, i, have_albedo, have_normal);
-    lv.kc = 1.0f / (c.sigma_variance * c.sigma_variance);
     return lv;
 }
 
@@ -63,8 +54,8 @@ bool tiled_by_default(uint32_t step) { return step <= 4; }
 // variance-guided ones.
 void denoise_run(akr_context* ctx, const akr_denoise_config& cfg, akr_film* color, akr_film* half, akr_film* albedo, akr_film* normal, akr_film* out, int kernel,
                  float* times) {
-    if (half) check_config_variance(cfg);
-    else check_config(cfg);
+    const bool variance = half != nullptr;
+    check_config(cfg, variance);
     if (half && half == out) throw std::invalid_argument("akr_denoise_variance: the half film cannot be the output film");
     for (akr_film* f : {half, albedo, normal, out}) {
         if (!f) continue;
@@ -75,55 +66,83 @@ void denoise_run(akr_context* ctx, const akr_denoise_config& cfg, akr_film* colo
     const uint32_t w = color->width, h = color->height;
     const uint64_t n = (uint64_t)w * h;
     const uint32_t demodulate = cfg.demodulate && albedo ? 1u : 0u;
+    auto level = [&](uint32_t i) { return level_params(cfg, w, h, i, albedo != nullptr, normal != nullptr, variance); };
     DevBuf bx0, bx1, bn, ba;  // the call's work buffers: x ping, x pong, n, a
     bx0.alloc(n * sizeof(float4));
     bx1.alloc(n * sizeof(float4));
     bn.alloc(n * sizeof(float4));
     ba.alloc(n * sizeof(float4));
-    std::vector<hipEvent_t> ev;
-    struct EventGuard {
-        std::vector<hipEvent_t>& v;
-        ~EventGuard() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
-    } guard{ev};
-    auto mark = [&] {
-        if (!times) return;
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_CHECK(hipEventRecord(e, ctx->stream));
-    };
+    StreamMarks marks(ctx->stream, times != nullptr);
     DenoiseRecords rec{bx0.as<float4>(), bn.as<float4>(), ba.as<float4>()};
     float4* other = bx1.as<float4>();
-    mark();
-    if (half) {
-        HIP_CHECK(launch_denoise_prepare_var(color->data, color->splat_scale, half->data, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
-                                             normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
-        HIP_CHECK(launch_denoise_variance(level_params_variance(cfg, w, h, 0, albedo != nullptr, normal != nullptr), rec, ctx->stream));
-    } else {
-        HIP_CHECK(launch_denoise_prepare(color->data, color->splat_scale, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
-                                         normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
-    }
-    mark();
+    marks.mark();
+    HIP_CHECK(launch_denoise_prepare(color->data, color->splat_scale, half ? half->data : nullptr, albedo ? albedo->data : nullptr, albedo ? albedo->splat_scale : 0.0f,
+                                     normal ? normal->data : nullptr, normal ? normal->splat_scale : 0.0f, n, demodulate, cfg.albedo_floor, rec, ctx->stream));
+    if (variance) HIP_CHECK(launch_denoise_variance(level(0), rec, ctx->stream));
+    marks.mark();
     for (uint32_t i = 0; i < cfg.iterations; i++) {
-        const DenoiseLevel lv = half ? level_params_variance(cfg, w, h, i, albedo != nullptr, normal != nullptr) : level_params(cfg, w, h, i, albedo != nullptr, normal != nullptr);
+        const DenoiseLevel lv = level(i);
         const bool tiled = kernel < 0 ? tiled_by_default(lv.step) : kernel != 0;
-        HIP_CHECK(half ? launch_denoise_level_var(lv, rec, other, tiled, ctx->stream) : launch_denoise_level(lv, rec, other, tiled, ctx->stream));
+        HIP_CHECK(launch_denoise_level(lv, rec, other, tiled, variance, ctx->stream));
         std::swap(rec.x, other);
-        mark();
+        marks.mark();
     }
     HIP_CHECK(launch_denoise_finish(rec.x, rec.a, n, demodulate, cfg.albedo_floor, out->data, ctx->stream));
-    mark();
+    marks.mark();
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     out->splat_scale = 1.0f;
     if (times) {
         for (int k = 0; k < 11; k++) times[k] = 0.0f;
-        auto ms = [&](size_t a, size_t b) { float t = 0.0f; HIP_CHECK(hipEventElapsedTime(&t, ev[a], ev[b])); return t; };
-        times[0] = ms(0, 1);
-        for (uint32_t i = 0; i < cfg.iterations; i++) times[1 + i] = ms(1 + i, 2 + i);
-        times[9] = ms(1 + cfg.iterations, 2 + cfg.iterations);
-        times[10] = ms(0, 2 + cfg.iterations);
+        times[0] = marks.ms(0, 1);
+        for (uint32_t i = 0; i < cfg.iterations; i++) times[1 + i] = marks.ms(1 + i, 2 + i);
+        times[9] = marks.ms(1 + cfg.iterations, 2 + cfg.iterations);
+        times[10] = marks.ms(0, 2 + cfg.iterations);
     }
 }
+
+#if defined(AKR_TEST_HOOKS) && AKR_TEST_HOOKS
+// What denoise_run computes, on the host from the same text, under guide G (ddenoise.h; half is read by DnVariance alone) -> out_rgb[3 N]
+template <class G>
+void host_denoise(const akr_denoise_config& cfg, uint32_t width, uint32_t height, const float* color, float color_scale, const float* half, const float* albedo,
+                  float albedo_scale, const float* normal, float normal_scale, float* out_rgb) {
+    check_config(cfg, G::kVariance);
+    const uint64_t n = (uint64_t)width * height;
+    const bool demodulate = cfg.demodulate && albedo;
+    auto level = [&](uint32_t i) { return level_params(cfg, width, height, i, albedo != nullptr, normal != nullptr, G::kVariance); };
+    std::vector<float4> x(n), y(n), nn(n), a(n);
+    for (uint64_t i = 0; i < n; i++)
+        dn_prepare_pixel<G>(color, color_scale, half, albedo, albedo_scale, normal, normal_scale, n, i, demodulate, cfg.albedo_floor, x[i], nn[i], a[i]);
+    if constexpr (G::kVariance) {
+        const DenoiseLevel lv0 = level(0);
+        for (int py = 0; py < (int)height; py++)
+            for (int px = 0; px < (int)width; px++) {
+                const size_t p = (size_t)py * width + px;
+                if (!G::valid(x[p])) continue;
+                x[p].w = dn_prefilter_pixel(px, py, lv0, [&](int dx, int dy, float4& nq, float4& aq) {
+                    const size_t q = (size_t)(py + dy) * width + (px + dx);
+                    nq = nn[q];
+                    aq = a[q];
+                    return !(nq.w < 0.0f);
+                });
+            }
+    }
+    for (uint32_t it = 0; it < cfg.iterations; it++) {
+        const DenoiseLevel lv = level(it);
+        const int s = (int)lv.step;
+        for (int py = 0; py < (int)height; py++)
+            for (int px = 0; px < (int)width; px++)
+                y[(size_t)py * width + px] = dn_level_pixel<G>(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
+                    const size_t q = (size_t)(py + s * dy) * width + (px + s * dx);
+                    xq = x[q];
+                    nq = nn[q];
+                    aq = a[q];
+                    return G::valid(xq);
+                });
+        x.swap(y);
+    }
+    for (uint64_t i = 0; i < n; i++) dn_finish_pixel(x[i], a[i], demodulate, cfg.albedo_floor, out_rgb + 3 * i);
+}
+#endif
 }  // namespace
 
 extern "C" {
@@ -172,28 +191,7 @@ AKR_TEST_API int32_t akr_host_denoise(const akr_denoise_config* cfg, uint32_t wi
                                       const float* albedo_film, float albedo_splat_scale, const float* normal_film, float normal_splat_scale, float* out_rgb) {
     if (!cfg || !color_film || !out_rgb || !width || !height) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_denoise: bad argument");
     return guarded([&] {
-        check_config(*cfg);
-        const uint64_t n = (uint64_t)width * height;
-        const bool demodulate = cfg->demodulate && albedo_film;
-        std::vector<float4> x(n), y(n), nn(n), a(n);
-        for (uint64_t i = 0; i < n; i++)
-            dn_prepare_pixel(color_film, color_splat_scale, albedo_film, albedo_splat_scale, normal_film, normal_splat_scale, n, i, demodulate, cfg->albedo_floor,
-                             x[i], nn[i], a[i]);
-        for (uint32_t it = 0; it < cfg->iterations; it++) {
-            const DenoiseLevel lv = level_params(*cfg, width, height, it, albedo_film != nullptr, normal_film != nullptr);
-            const int s = (int)lv.step;
-            for (int py = 0; py < (int)height; py++)
-                for (int px = 0; px < (int)width; px++)
-                    y[(size_t)py * width + px] = dn_level_pixel(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
-                        const size_t q = (size_t)(py + s * dy) * width + (px + s * dx);
-                        xq = x[q];
-                        nq = nn[q];
-                        aq = a[q];
-                        return xq.w != 0.0f;
-                    });
-            x.swap(y);
-        }
-        for (uint64_t i = 0; i < n; i++) dn_finish_pixel(x[i], a[i], demodulate, cfg->albedo_floor, out_rgb + 3 * i);
+        host_denoise<DnPlain>(*cfg, width, height, color_film, color_splat_scale, nullptr, albedo_film, albedo_splat_scale, normal_film, normal_splat_scale, out_rgb);
     });
 }
 
@@ -202,40 +200,7 @@ AKR_TEST_API int32_t akr_host_denoise_variance(const akr_denoise_config* cfg, ui
                                                float normal_splat_scale, float* out_rgb) {
     if (!cfg || !color_film || !half_film || !out_rgb || !width || !height) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_host_denoise_variance: bad argument");
     return guarded([&] {
-        check_config_variance(*cfg);
-        const uint64_t n = (uint64_t)width * height;
-        const bool demodulate = cfg->demodulate && albedo_film;
-        std::vector<float4> x(n), y(n), nn(n), a(n);
-        for (uint64_t i = 0; i < n; i++)
-            dn_prepare_pixel_var(color_film, color_splat_scale, half_film, albedo_film, albedo_splat_scale, normal_film, normal_splat_scale, n, i, demodulate,
-                                 cfg->albedo_floor, x[i], nn[i], a[i]);
-        const DenoiseLevel lv0 = level_params_variance(*cfg, width, height, 0, albedo_film != nullptr, normal_film != nullptr);
-        for (int py = 0; py < (int)height; py++)
-            for (int px = 0; px < (int)width; px++) {
-                const size_t p = (size_t)py * width + px;
-                if (!dn_var_valid(x[p])) continue;
-                x[p].w = dn_prefilter_pixel(px, py, lv0, [&](int dx, int dy, float4& nq, float4& aq) {
-                    const size_t q = (size_t)(py + dy) * width + (px + dx);
-                    nq = nn[q];
-                    aq = a[q];
-                    return !(nq.w < 0.0f);
-                });
-            }
-        for (uint32_t it = 0; it < cfg->iterations; it++) {
-            const DenoiseLevel lv = level_params_variance(*cfg, width, height, it, albedo_film != nullptr, normal_film != nullptr);
-            const int s = (int)lv.step;
-            for (int py = 0; py < (int)height; py++)
-                for (int px = 0; px < (int)width; px++)
-                    y[(size_t)py * width + px] = dn_level_pixel_var(px, py, lv, [&](int dx, int dy, float4& xq, float4& nq, float4& aq) {
-                        const size_t q = (size_t)(py + s * dy) * width + (px + s * dx);
-                        xq = x[q];
-                        nq = nn[q];
-                        aq = a[q];
-                        return dn_var_valid(xq);
-                    });
-            x.swap(y);
-        }
-        for (uint64_t i = 0; i < n; i++) dn_finish_pixel(x[i], a[i], demodulate, cfg->albedo_floor, out_rgb + 3 * i);
+        host_denoise<DnVariance>(*cfg, width, height, color_film, color_splat_scale, half_film, albedo_film, albedo_splat_scale, normal_film, normal_splat_scale, out_rgb);
     });
 }
 #endif

@@ -123,18 +123,7 @@ void display_run(akr_context* ctx, const akr_display_config& cfg, akr_film* film
     const uint32_t w = film->width, h = film->height;
     const bool bloom = cfg.bloom_strength != 0.0f;
     const bool tiled = kernel < 0 ? tiled_by_default() : kernel != 0;
-    std::vector<hipEvent_t> ev;
-    struct EventGuard {
-        std::vector<hipEvent_t>& v;
-        ~EventGuard() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
-    } guard{ev};
-    auto mark = [&] {
-        if (!times) return;
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_CHECK(hipEventRecord(e, ctx->stream));
-    };
+    StreamMarks marks(ctx->stream, times != nullptr);
     // the bloom's work buffers in one allocation: the unblurred levels D, the blurred levels G (U after the recombination), one pass's temporary
     const Pyramid pyr(w, h, bloom ? cfg.bloom_levels : 0);
     DevBuf work;
@@ -154,44 +143,43 @@ void display_run(akr_context* ctx, const akr_display_config& cfg, akr_film* film
         }
         tmp = at;
     }
-    mark();  // 0
+    marks.mark();  // 0
     float k = manual_exposure(cfg);
     if (cfg.auto_exposure) {
         uint32_t counts[kDpBins + 1];
-        histogram_run(ctx, film, counts, mark);  // 1, 2
+        histogram_run(ctx, film, counts, [&] { marks.mark(); });  // 1, 2
         k = dp_exposure(cfg, counts);
     } else {
-        mark();
-        mark();
+        marks.mark();
+        marks.mark();
     }
     check_exposure(k);
     const DisplayParams p = dp_params(cfg, k);
-    mark();  // 3
+    marks.mark();  // 3
     if (bloom) HIP_CHECK(launch_bloom_source(film->data, film->splat_scale, w, h, k, cfg.bloom_threshold, D[1], ctx->stream));
-    mark();  // 4
+    marks.mark();  // 4
     for (uint32_t l = 1; l < L; l++) HIP_CHECK(launch_bloom_down(D[l], pyr.w[l], pyr.h[l], D[l + 1], ctx->stream));
-    mark();  // 5
+    marks.mark();  // 5
     if (bloom) HIP_CHECK(launch_bloom_blur(D[1], tmp, G[1], pyr.w[1], pyr.h[1], tiled, ctx->stream));
-    mark();  // 6
+    marks.mark();  // 6
     for (uint32_t l = 2; l <= L; l++) HIP_CHECK(launch_bloom_blur(D[l], tmp, G[l], pyr.w[l], pyr.h[l], tiled, ctx->stream));
-    mark();  // 7
+    marks.mark();  // 7
     for (uint32_t l = L; l-- > 1;) HIP_CHECK(launch_bloom_up(G[l], pyr.w[l], pyr.h[l], G[l + 1], pyr.w[l + 1], pyr.h[l + 1], ctx->stream));
-    mark();  // 8
+    marks.mark();  // 8
     HIP_CHECK(launch_display_apply(film->data, film->splat_scale, w, h, p, bloom ? G[1] : nullptr, bloom ? pyr.w[1] : 1, bloom ? pyr.h[1] : 1, out->data, ctx->stream));
-    mark();  // 9
+    marks.mark();  // 9
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     out->splat_scale = 1.0f;
     if (exposure_used) *exposure_used = k;
     if (times) {
-        auto ms = [&](size_t a, size_t b) { float t = 0.0f; HIP_CHECK(hipEventElapsedTime(&t, ev[a], ev[b])); return t; };
-        times[0] = ms(1, 2);
-        times[1] = ms(3, 4);
-        times[2] = ms(4, 5);
-        times[3] = ms(5, 7);
-        times[4] = ms(7, 8);
-        times[5] = ms(8, 9);
-        times[6] = ms(0, 9);
-        times[7] = ms(5, 6);
+        times[0] = marks.ms(1, 2);
+        times[1] = marks.ms(3, 4);
+        times[2] = marks.ms(4, 5);
+        times[3] = marks.ms(5, 7);
+        times[4] = marks.ms(7, 8);
+        times[5] = marks.ms(8, 9);
+        times[6] = marks.ms(0, 9);
+        times[7] = marks.ms(5, 6);
     }
 }
 }  // namespace

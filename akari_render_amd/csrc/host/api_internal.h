@@ -112,6 +112,32 @@ struct DevBuf {
     T* as() const { return (T*)p; }
 };
 
+// The timing events of a call's stages on one stream (the *_times test hooks): mark() records the next one, ms(a, b) is the time from
+// mark a to mark b once the stream is synchronised. Not enabled (the entry points that time nothing): mark() does nothing, no event is made.
+struct StreamMarks {
+    hipStream_t stream;
+    bool enabled;
+    std::vector<hipEvent_t> ev;
+    StreamMarks(hipStream_t stream, bool enabled) : stream(stream), enabled(enabled) {}
+    StreamMarks(const StreamMarks&) = delete;
+    StreamMarks& operator=(const StreamMarks&) = delete;
+    ~StreamMarks() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    void mark() {
+        if (!enabled) return;
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        ev.push_back(e);
+        HIP_CHECK(hipEventRecord(e, stream));
+    }
+    float ms(size_t a, size_t b) const {
+        float t = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&t, ev[a], ev[b]));
+        return t;
+    }
+};
+
 // A frame cut into tiles (0 = the default size, 32) and the pixels of the tiles rank `rank` of `count` owns, whole tiles counted
 struct TileGrid {
     uint32_t tile_w = 32, tile_h = 32, tiles_x = 0, tiles_y = 0, n_items = 0;
