@@ -1881,6 +1881,9 @@ OR_EXPORT void or_kat_sincos(float x, float *s, float *c) { or_sincosf(x, s, c);
 OR_EXPORT float or_kat_log(float x) { return or_logf(x); }
 OR_EXPORT float or_kat_exp(float x) { return or_expf(x); }
 OR_EXPORT float or_kat_pow(float x, float y) { return or_powf(x, y); }
+/* or_kat_exp / or_kat_log of every element: what a restatement over a whole frame calls (one call, not one per pixel and tap) */
+OR_EXPORT void or_kat_exp_many(uint64_t n, const float *x, float *out) { for (uint64_t i = 0; i < n; i++) out[i] = or_expf(x[i]); }
+OR_EXPORT void or_kat_log_many(uint64_t n, const float *x, float *out) { for (uint64_t i = 0; i < n; i++) out[i] = or_logf(x[i]); }
 /* the ColorPipeline (OR_COLOR_* bits) the probes below evaluate materials under; renders set it from their config */
 OR_EXPORT void or_scene_set_color(or_scene *sc, uint32_t color) { sc->color = color; }
 /* dimension pair (dim, dim + 1) of sample `index` of pixel (px, py) of the sobol sampler, as fixed-point-free floats */

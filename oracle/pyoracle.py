@@ -90,6 +90,8 @@ def lib() -> C.CDLL:
     L.or_kat_exp.argtypes = [f32]
     L.or_kat_pow.restype = f32
     L.or_kat_pow.argtypes = [f32, f32]
+    L.or_kat_exp_many.argtypes = [u64, fp, fp]
+    L.or_kat_log_many.argtypes = [u64, fp, fp]
     L.or_material_inputs.argtypes = [vp, u32, u32, fp, fp]
     L.or_tex_sample_many.argtypes = [C.POINTER(abi.ImageDesc), u32, fp, fp]
     L.or_kat_alias_build.argtypes = [fp, u32, up, fp, fp]
@@ -457,6 +459,22 @@ def atan2_many(y, x) -> np.ndarray:
     x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
     out = np.zeros(y.shape[0], np.float32)
     lib().or_kat_atan2_many(y.shape[0], _fp(y), _fp(x), _fp(out))
+    return out
+
+
+def exp_many(x) -> np.ndarray:
+    """or_kat_exp elementwise, in one call."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    out = np.zeros(x.shape[0], np.float32)
+    lib().or_kat_exp_many(x.shape[0], _fp(x), _fp(out))
+    return out
+
+
+def log_many(x) -> np.ndarray:
+    """or_kat_log elementwise, in one call."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    out = np.zeros(x.shape[0], np.float32)
+    lib().or_kat_log_many(x.shape[0], _fp(x), _fp(out))
     return out
 
 

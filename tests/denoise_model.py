@@ -14,6 +14,10 @@ B3 = [f32(1 / 16), f32(1 / 4), f32(3 / 8), f32(1 / 4), f32(1 / 16)]
 # (W, H). At 33 x 17 and step 16 the rows 1 .. 15 have no tap row but their own inside the image (y - 16 < 0, y + 16 >= 17); at 70 x 45 the taps
 # of step 16 reach 32 pixels, two 16-wide tiles, to both sides of the columns 32 .. 37.
 SHAPES = [(1, 1), (1, 7), (7, 1), (5, 5), (33, 17), (70, 45)]
+# One frame on which the residue classes of steps 8 and 16 span several 16-wide tiles in both axes and differ in size (261 = 16 * 16 + 5,
+# 259 = 16 * 16 + 3: tests/test_gpu_frame_thresholds.py derives it). It runs LARGE_CASES of cases(), not the whole matrix.
+LARGE_SHAPE = (261, 259)
+LARGE_CASES = ["random-all-demod-5", "edge-all-demod-5"]
 
 
 def config(iterations=5, demodulate=1, sigma_color=2.0, sigma_normal=0.125, sigma_albedo=0.0625, albedo_floor=1e-3) -> abi.DenoiseConfig:

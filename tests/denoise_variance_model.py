@@ -12,6 +12,7 @@ from tests.denoise_model import _dist2, _exp, _k, f32
 G3 = [f32(1 / 4), f32(1 / 2), f32(1 / 4)]
 SIGMA_VARIANCE = 8.0  # akr_denoise_config_default's (the sigma_variance table)
 SHAPES = dm.SHAPES
+LARGE_SHAPE, LARGE_CASES = dm.LARGE_SHAPE, dm.LARGE_CASES  # (the names are cases of this file's cases() as well)
 
 
 def config(sigma_variance=SIGMA_VARIANCE, **kw):

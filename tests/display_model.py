@@ -14,6 +14,10 @@ LN2, INV_LN2 = f32(0.6931471805599453), f32(1.4426950408889634)
 # (W, H): a pyramid that is 1 x 1 from the start; one that reaches 1 x 1 at level 3; odd sizes at every level (41 -> 21 -> 11 -> 6 -> 3 -> 2 -> 1);
 # a frame wider than 64 and one wider than 128 and taller than 64, whose levels 1 and 2 cross the 16-pixel tiles of the LDS blur unevenly
 SHAPES = [(1, 1), (7, 5), (41, 23), (70, 45), (130, 67)]
+# One frame past the histogram kernel's grid cap of 2048 workgroups x 256 threads (tests/test_gpu_frame_thresholds.py derives it): 790 777
+# pixels, odd, no multiple of 16, 64 or 256 per side. It runs the histogram and ONE configuration of cases(), not the whole matrix.
+LARGE_SHAPE = (1031, 767)
+LARGE_CASE = "hable-auto-bloom5"
 CURVES = [abi.DISPLAY_LINEAR, abi.DISPLAY_REINHARD, abi.DISPLAY_ACES, abi.DISPLAY_HABLE]
 KINDS = ["random", "special"]
 SPLAT_SCALE = {"random": 0.375, "special": 1.0}

@@ -31,6 +31,21 @@ def test_host_equals_the_restatement(hip_lib, oracle_lib, case, shape):
     assert np.isfinite(ref).all()  # (no case above feeds a non-finite value: the NaN route has a test of its own)
 
 
+@pytest.mark.parametrize("name", dm.LARGE_CASES)
+def test_host_equals_the_restatement_on_the_large_frame(hip_lib, oracle_lib, name):
+    """dm.LARGE_SHAPE, all guides, demodulation, five iterations: the reference tests/test_gpu_frame_thresholds.py holds the device to, held to
+    the host build first."""
+    _, kind, use_a, use_n, cfg, scales = next(c for c in CASES if c[0] == name)
+    assert use_a and use_n and cfg.demodulate == 1 and cfg.iterations == 5
+    w, h = dm.LARGE_SHAPE
+    color, albedo, normal = dm.case_inputs(w, h, kind)
+    got = host(w, h, color, albedo, normal, cfg, scales)
+    ref = dm.case_reference(w, h, name)
+    same = same_bits_or_both_nan(got, ref)
+    assert same.all(), f"{name} {w}x{h}: {np.count_nonzero(~same)} of {same.size} floats differ"
+    assert np.isfinite(ref).all()
+
+
 @pytest.mark.parametrize("demodulate", [0, 1])
 @pytest.mark.parametrize("shape", [(5, 5), (33, 17), (70, 45)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_a_constant_image_stays_itself(hip_lib, shape, demodulate):

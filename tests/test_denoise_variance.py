@@ -34,6 +34,21 @@ def test_host_equals_the_restatement(hip_lib, oracle_lib, case, shape):
     assert np.isfinite(ref).all()  # (no case feeds a non-finite colour: the NaN route has a test of its own)
 
 
+@pytest.mark.parametrize("name", dvm.LARGE_CASES)
+def test_host_equals_the_restatement_on_the_large_frame(hip_lib, oracle_lib, name):
+    """dvm.LARGE_SHAPE, all guides, demodulation, five iterations: the reference tests/test_gpu_frame_thresholds.py holds the device to, held
+    to the host build first."""
+    _, kind, halves, use_a, use_n, cfg = next(c for c in CASES if c[0] == name)
+    assert use_a and use_n and cfg.demodulate == 1 and cfg.iterations == 5
+    w, h = dvm.LARGE_SHAPE
+    color, half, albedo, normal = dvm.case_inputs(w, h, kind, halves)
+    got = host(w, h, color, half, albedo, normal, cfg)
+    ref = dvm.case_reference(w, h, name)
+    same = same_bits_or_both_nan(got, ref)
+    assert same.all(), f"{name} {w}x{h}: {np.count_nonzero(~same)} of {same.size} floats differ"
+    assert np.isfinite(ref).all()
+
+
 def test_the_unequal_halves_case_has_pixels_without_an_estimate():
     """(what the case is for: wA = 0 at some pixels, wA != wB at the others)"""
     color, half, _, _ = dvm.case_inputs(33, 17, "intweights", "unequal")

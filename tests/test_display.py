@@ -39,6 +39,29 @@ def test_host_histogram_is_the_bincount_of_the_restated_bins(hip_lib, oracle_lib
     assert int(counts.sum()) + skipped == w * h
 
 
+def test_host_equals_the_restatement_on_the_large_frame(hip_lib, oracle_lib):
+    """dm.LARGE_SHAPE under dm.LARGE_CASE (Hable, auto-exposure, bloom of five levels): the reference tests/test_gpu_frame_thresholds.py holds
+    the device to, held to the host build first."""
+    w, h = dm.LARGE_SHAPE
+    cfg = next(c for n, c in CASES if n == dm.LARGE_CASE)
+    assert (cfg.curve, cfg.auto_exposure, cfg.bloom_levels) == (abi.DISPLAY_HABLE, 1, 5) and cfg.bloom_strength > 0
+    got, k = capi.host_display_transform(w, h, dm.case_film(w, h, "random"), cfg, dm.SPLAT_SCALE["random"])
+    ref, k_ref = dm.case_reference(w, h, "random", dm.LARGE_CASE)
+    assert f32(k).view(np.uint32) == f32(k_ref).view(np.uint32), f"exposure {k} against {k_ref}"
+    same = same_bits_or_both_nan(got, ref)
+    assert same.all(), f"{np.count_nonzero(~same)} of {same.size} floats differ"
+    assert np.isfinite(ref).all() and ref.min() >= 0 and ref.max() <= 1
+
+
+@pytest.mark.parametrize("kind", dm.KINDS)
+def test_host_histogram_on_the_large_frame(hip_lib, oracle_lib, kind):
+    w, h = dm.LARGE_SHAPE
+    counts, skipped = capi.host_luminance_histogram(w, h, dm.case_film(w, h, kind), dm.SPLAT_SCALE[kind])
+    ref_counts, ref_skipped = dm.case_histogram(w, h, kind)
+    assert np.array_equal(counts, ref_counts) and skipped == ref_skipped
+    assert int(counts.sum()) + skipped == w * h
+
+
 def test_exposure_on_hand_made_counts(hip_lib, oracle_lib):
     def both(cfg, counts):
         k, ref = capi.display_exposure(cfg, counts), dm.exposure(cfg, counts)

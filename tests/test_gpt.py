@@ -223,6 +223,13 @@ def test_gpt_sharded_across_ranks_is_the_single_gpu_render(ctx, cbox_path, root,
     w, h = 56, 40   # ragged: 3.5 x 5 tiles
     sd = make_scene(name, cbox_path, root, w, h)
     cfg = gpt_config(spp=4, max_depth=6, rr_depth=2, reconstruction=recon, reconstruction_iter=5, stride=stride)
+    sharded_is_unsharded(ctx, sd, cfg)
+
+
+def sharded_is_unsharded(ctx, sd, cfg):
+    """Three ranks with 16 x 8 tiles against one session over the whole frame of `sd`, as the test above says."""
+    w, h = sd.camera.width, sd.camera.height
+    recon = cfg.reconstruction
     scene = capi.Scene(ctx, sd)
     full = capi.Film(ctx, w, h)
     se = capi.GptSession(ctx, scene, cfg, full)

@@ -32,19 +32,21 @@ def base_config(**kw):
     return make_config(spp=CALLS * PASSES * PASS_SPP, spp_per_pass=PASS_SPP, **kw)
 
 
-def run(ctx, sd, cfg, order, force_bvh=0, between=None):
-    """The session's state after each of the three calls: (film as uint32, sampler states, counters, cost-order hook, status).
-    between(i, se): called after call i (active-tile lists)."""
+def run(ctx, sd, cfg, order, force_bvh=0, between=None, passes=PASSES):
+    """The session's state after each of the three calls of `passes` passes, on the scene's own frame: (film as uint32, sampler states, counters,
+    cost-order hook, status). between(i, se): called after call i (active-tile lists)."""
+    w, h = sd.camera.width, sd.camera.height
+    n = w * h
     with capi.cost_order_mode(order), capi.options(force_bvh=force_bvh):
         scene = capi.Scene(ctx, sd)
-        film = capi.Film(ctx, W, H)
+        film = capi.Film(ctx, w, h)
         film.clear()
         se = capi.PtSession(ctx, scene, cfg, film)
     snaps = []
     for i in range(CALLS):
-        se.passes(PASSES, blocking=True)
+        se.passes(passes, blocking=True)
         st = se.stats()
-        snaps.append((film.read().view(np.uint32).copy(), se.sampler_states(N).copy(), {k: st[k] for k in COUNTERS}, se.cost_order(N), se.kernel_info()["status"]))
+        snaps.append((film.read().view(np.uint32).copy(), se.sampler_states(n).copy(), {k: st[k] for k in COUNTERS}, se.cost_order(n), se.kernel_info()["status"]))
         if between:
             between(i, se)
     se.end()

@@ -198,6 +198,19 @@ def test_elementary_function_error_against_f64(oracle_lib):
     assert np.isnan(pm.oracle_log(t[t < 0])).all()
 
 
+def test_exp_and_log_over_an_array_are_the_scalar_functions(oracle_lib):
+    """or_kat_exp_many / or_kat_log_many, which the frame-sized restatements call, return or_kat_exp / or_kat_log of every element bit for bit."""
+    from tests import probe_matrix as pm
+
+    x = pm.exp_inputs()
+    one = np.array([oracle_lib.or_kat_exp(float(v)) for v in x], dtype=np.float32)
+    assert pm.same_bits_or_both_nan(pyoracle.exp_many(x), one).all()
+    t = np.concatenate([np.abs(x), pm.sqrt_rcp_inputs()]).astype(np.float32)  # denormals, both signs, zeros, inf and NaN included
+    one = np.array([oracle_lib.or_kat_log(float(v)) for v in t], dtype=np.float32)
+    assert pm.same_bits_or_both_nan(pyoracle.log_many(t), one).all()
+    assert pyoracle.exp_many(np.zeros(0, np.float32)).size == 0
+
+
 def test_sampling_warps(oracle_lib):
     rng = np.random.default_rng(2)
     fp = C.POINTER(C.c_float)
