@@ -56,7 +56,8 @@ AKR_HD uint32_t uniform_discrete_choice_and_remap(uint32_t n, float u, float& re
 // sampling.rs:61-71; true = the first alternative (weight_a) was taken
 AKR_HD bool weighted_choice2_and_remap(float weight_a, float u, float& remapped) {
     bool first = u < weight_a;
-    remapped = first ? u / weight_a : (u - weight_a) / (1.0f - weight_a);
+    // one division of the selected operands: the same IEEE operation on the same numbers as a division per alternative
+    remapped = (first ? u : u - weight_a) / (first ? weight_a : 1.0f - weight_a);
     return first;
 }
 
@@ -88,6 +89,25 @@ AKR_HD uint32_t alias_sample_and_remap(const AliasPacked* __restrict__ entries, 
     float u1;
     uint32_t idx = uniform_discrete_choice_and_remap(n, u, u1);
     AliasPacked e = entries[idx];
+    float u2;
+    bool first = weighted_choice2_and_remap(e.t, u1, u2);
+    pdf = first ? e.pdf_i : e.pdf_j;
+    remapped = u2;
+    return first ? idx : e.j;
+}
+// The same lookup for a wave: where every active lane's entry has t == 1 and u1 < 1, each lane takes its own entry and u1 / 1.0f is u1, so
+// the wave skips the division (a compare and a ballot). build_alias_table writes t = 1 for the entry of a one-entry table and for entries
+// whose weight is exactly the mean: one area light, or a light of two triangles of equal area. Any other lane sends the wave down
+// the lookup above.
+AKR_D uint32_t alias_sample_and_remap_wave(const AliasPacked* __restrict__ entries, uint32_t n, float u, float& pdf, float& remapped) {
+    float u1;
+    uint32_t idx = uniform_discrete_choice_and_remap(n, u, u1);
+    AliasPacked e = entries[idx];
+    if (__builtin_amdgcn_ballot_w64(!((e.t == 1.0f) & (u1 < 1.0f))) == 0) {
+        pdf = e.pdf_i;
+        remapped = u1;
+        return idx;
+    }
     float u2;
     bool first = weighted_choice2_and_remap(e.t, u1, u2);
     pdf = first ? e.pdf_i : e.pdf_j;

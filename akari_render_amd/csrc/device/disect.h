@@ -160,8 +160,10 @@ AKR_D bool trace_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmin, float 
 // scalar cache come 16 such instructions in a row. The bookkeeping per record is cut down too (a v_cmp costs 4.4 cycles and a v_cndmask
 // on its result 3.7): the alpha test is unswitched out of the loop, min / max come without the compiler's canonicalising v_max x, x, the
 // shadow ray's margin is folded with one v_max, and only (t, id) of the best hit are selected per record -- its (u, v) are recomputed
-// once after the walk. Two records per trip on alternating register sets: a one-record software prefetch without the moves that
-// rotating a single set costs.
+// once after the walk. Operations whose result nothing reads are left out (profiles/walk_unread_ops.md): the closest-hit ray's margin has
+// no tmax - t where no alpha test reads the margin (t < best_t says it), the shadow ray's range term min(t, stmax - t) is computed with
+// its plane solve, not per record, and the best hit is chosen by one test and two selects. Two records per trip on alternating register
+// sets: a one-record software prefetch without the moves that rotating a single set costs.
 // Five other forms were measured and retired (records through the scalar cache, both rays packed into v_pk_fma_f32 with and
 // without op_sel broadcast, lockstep pairs of coplanar records); this one was +4.2 % on C2 and +3.3 % on C3 over the next best:
 // HISTORY.md, profiles/r4_ab_walk.txt. The arithmetic (operation order, fma placement) is tri_plane / tri_uv / hit_margin's.
@@ -210,7 +212,8 @@ AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
 // set S of operands it is the contract's quotient). Whether a solve's operands are in S is not tested per solve -- a compare and a branch
 // would cost what the shortcut saves -- but once per walk, and a wave with a lane that fails repeats the walk with the compiler's division
 // (walk_ieee below: rolled, one record per trip; it runs in a vanishing share of the walks) and takes that result. What is checked, per
-// ray that exists (tmax >= 0; a ray that does not exist is never accepted whatever its t, because min(t, tmax - t) < 0 or NaN for tmax < 0):
+// ray that exists (tmax >= 0; a ray that does not exist is never accepted whatever its t: the shadow ray because min(t, stmax - t) < 0 or NaN
+// for stmax < 0, the closest-hit ray because its margin >= 0 needs t >= 0 and t < best_t needs t <= tmax < 0):
 //   before the walk   |o| <= B and |d| <= 2 per component, tmax <= 1e20. The host chose B (dscene.h walk_bound_word) so that under these
 //                     bounds every plane row of the scene gives |oz| < 2^46 and |dz| < 2^46 (api_scene.cpp; a negative bound = no such
 //                     bound exists, the scene always takes walk_ieee). A NaN component passes the test (maxNum ignores it), harmlessly:
@@ -220,11 +223,18 @@ AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
 // Why that suffices. For a solve of a checked lane, a = -oz and b = dz have 2^-47 <= |a| < 2^47 and |b| < 2^47. Of the conditions of S,
 // "a's biased exponent >= 24" holds (it is >= 80), "|b| <= 2^125" holds, and exp(a) - exp(b) >= -47 - 46 > -125. So (a, b) can leave S
 // only through b zero or denormal, or through exp(a) - exp(b) >= 96. In both cases the exact quotient has |t| > 2^79 (|a| >= 2^-47 over
-// |b| < 2^-126; or 2^(96 - 1)), which is > 1e20 >= tmax: IEEE's quotient (+-inf for b = 0) fails min(t, tmax - t) >= 0, the record is
+// |b| < 2^-126; or 2^(96 - 1)), which is > 1e20 >= tmax: IEEE's quotient (+-inf for b = 0) fails the range test, the record is
 // rejected. The unscaled sequence returns for such a pair a value of magnitude > 1e20, +-inf or NaN (checked on the device for both kinds
-// of exit, tests/test_gpu_div_unscaled.py), which fails the same test -- for t = NaN every operand of the margin is NaN. The record is
+// of exit, tests/test_gpu_div_unscaled.py), which fails the same test. The range test is, for the shadow ray and for the closest-hit ray
+// of a walk with an alpha test, min(t, tmax - t) >= 0: false for |t| > tmax and for NaN. For the closest-hit ray of a walk without one it
+// is (t >= 0) & (t < best_t), the margin's last operand being t alone (tmax - t is left out: best_t starts at next_up(tmax) and only
+// decreases, so t < best_t implies t <= tmax and fl(tmax - t) >= 0 -- the term could only have lowered a margin whose record fails
+// t < best_t anyway): a positive |t| > 1e20 fails t < best_t (best_t <= next_up(1e20)), a negative one fails t >= 0, and for t = NaN
+// every operand of the margin is NaN and every comparison false. The record is
 // rejected on both paths, and no bit of its t reaches the result: best_t, the recomputed (u, v) and the sign of occ_margin come from
 // accepted records only, whose pairs are in S.
+// (The alpha walks keep tmax - t in the margin because they read it once more: alpha_test is guarded by m >= 0 and must not be evaluated at
+// the (u, v) of a record beyond tmax.)
 // (tmax and stmax are taken to be numbers: a NaN would read as "the ray does not exist" and skip the checks while min(t, NaN) = t could still
 // accept a record. The callers pass 1e20, -1 or a light sample's distance, which is finite by construction: dpath.h sample_direct.)
 // (Measured with it and retired: the excluded ids as bit masks, v_bfe_i32 + v_or on the margin's bits per ray and record in place of the
@@ -251,8 +261,11 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     const uint32_t n = sc.n_tris;
     const v4f* lrec = (const v4f*)lds_recs;
     const bool has_alpha = __builtin_amdgcn_readfirstlane((int)sc.has_alpha) != 0;  // (a scalar branch per walk, nothing per lane)
-    // the two rays' plane solves of the current plane, as pairs {closest-hit ray, shadow ray}: t and the hit point
-    v2f T2 = {0.0f, 0.0f}, hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};
+    // the two rays' plane solves of the current plane: the hit points as pairs {closest-hit ray, shadow ray}; of the distances, the
+    // closest-hit ray's t and the shadow ray's range term min(t, stmax - t) -- all a record reads of the shadow ray's t, so it is computed
+    // once per solve and a record that takes its neighbour's plane spends nothing on it
+    float T = 0.0f, srange = 0.0f;
+    v2f hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};
     float lo = __builtin_inff(), slo = __builtin_inff();  // UNSCALED: the smallest |oz| of the walk, per ray
     // alpha_tag: 0 = no alpha test, 1 = alpha test, 2 = has_alpha decides at run time; div_tag: the plane solves use div_f_unscaled
     auto record = [&](auto alpha_tag, auto div_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
@@ -261,18 +274,19 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
         if (!((sc.plane_share_mask >> k) & 1ull)) {  // wave-uniform: one plane solve per ray per coplanar pair of records
             const float4 r2 = make_float4(q2.x, q2.y, q2.z, q2.w);
             const PlaneHit a = FAST ? tri_plane_unscaled(o, d, r2, lo) : tri_plane(o, d, r2), b = FAST ? tri_plane_unscaled(so, sd, r2, slo) : tri_plane(so, sd, r2);
-            T2 = (v2f){a.t, b.t};
+            T = a.t;
+            srange = min_raw(b.t, stmax - b.t);
             hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
         }
         float u, v, su, sv;
-        tri_uv(PlaneHit{T2.x, hx2.x, hy2.x, hz2.x}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), u, v);
-        tri_uv(PlaneHit{T2.y, hx2.y, hy2.y, hz2.y}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), su, sv);
+        tri_uv(PlaneHit{T, hx2.x, hy2.x, hz2.x}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), u, v);
+        tri_uv(PlaneHit{0.0f, hx2.y, hy2.y, hz2.y}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), su, sv);
         const v2f u2 = {u, su}, v2 = {v, sv};
-        // hit_margin: min(min(min(u, v), 1 - (u + v)), min(t, tmax - t)) per ray
+        // hit_margin per ray: min(min(min(u, v), 1 - (u + v)), range), with the range terms described above the WalkOpt struct
         const v2f s2 = {1.0f - (u2.x + v2.x), 1.0f - (u2.y + v2.y)};
-        const v2f w2 = {tmax - T2.x, stmax - T2.y};
-        float m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), min_raw(T2.x, w2.x));
-        float sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), min_raw(T2.y, w2.y));
+        const float range = ALPHA == 0 ? T : min_raw(T, tmax - T);
+        float m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), range);
+        float sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), srange);
         m = (k == ex0) ? -1.0f : m;
         sm = (k == sex0) ? -1.0f : sm;
         sm = (k == sex1) ? -1.0f : sm;
@@ -284,9 +298,10 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
             if (sm >= 0.0f && !alpha_test<TEX>(sc, ka, u2.y, v2.y)) sm = -1.0f;
         }
         // only the distance and the id of the best hit are tracked here; its (u, v) are recomputed after the walk (below)
-        const float tc = (m >= 0.0f) ? T2.x : __builtin_inff();
-        const bool better = tc < best_t;
-        best_t = better ? tc : best_t;
+        // (one test, two selects: "m >= 0 ? t : inf" in front of the comparison would be a third select per record for the same truth
+        // value -- inf < best_t is false, a NaN t has a NaN margin)
+        const bool better = (m >= 0.0f) & (T < best_t);
+        best_t = better ? T : best_t;
         best = better ? k : best;
         // max over the records of the shadow ray's margin (a NaN margin leaves it as it is, like the comparison it replaces; only
         // the sign of the result is read)

@@ -305,7 +305,7 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
     s.delta = false;
     if (sc.n_lights == 0) return s;
     float light_choice_pdf, u_sel2, pdf_prim, u_unused;
-    uint32_t light = alias_sample_and_remap(sc.light_alias, sc.n_lights, u_select, light_choice_pdf, u_sel2);
+    uint32_t light = alias_sample_and_remap_wave(sc.light_alias, sc.n_lights, u_select, light_choice_pdf, u_sel2);
     if (ENV && light == sc.env->light) {
         const DEnv& env = *sc.env;
         vec3 wi;
@@ -338,7 +338,7 @@ AKR_D LightSample sample_direct(const DScene& sc, vec3 pn_p, vec3 pn_n, float u_
         s.delta = true;
         return s;
     }
-    uint32_t prim = alias_sample_and_remap(sc.area_alias + L.tri_offset, L.n_tris, u_sel2, pdf_prim, u_unused);
+    uint32_t prim = alias_sample_and_remap_wave(sc.area_alias + L.tri_offset, L.n_tris, u_sel2, pdf_prim, u_unused);
     uint32_t gid = L.first_gid + prim;
     vec2 bary = uniform_sample_triangle(u_sample);
     SurfacePoint y = surface_interaction_any<INST>(sc, gid, bary);
