@@ -121,6 +121,15 @@ class LensDesc(C.Structure):
     _fields_ = [("radius", C.c_float), ("focal_distance", C.c_float)]
 
 
+PROJECTION_PERSPECTIVE, PROJECTION_ORTHOGRAPHIC, PROJECTION_PANORAMA = 0, 1, 2  # akr_projection_type
+
+
+class ProjectionDesc(C.Structure):
+    """akr_projection_desc: the camera's projection."""
+    _fields_ = [("type", C.c_uint32), ("ortho_scale", C.c_float), ("longitude_min", C.c_float), ("longitude_max", C.c_float),
+                ("latitude_min", C.c_float), ("latitude_max", C.c_float)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("c2w", C.c_float * 16), ("fov", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -636,6 +645,29 @@ class LensData:
     focal_distance: float
 
 
+_PI_F32, _HALF_PI_F32 = float(np.float32(np.pi)), float(np.float32(np.pi / 2))
+
+
+@dataclass
+class ProjectionData:
+    """The projection of a scene's camera (akr_projection_desc): `type` PROJECTION_PERSPECTIVE (the default: the camera of CameraData),
+    PROJECTION_ORTHOGRAPHIC (`ortho_scale` = the world-space length the larger image side spans) or PROJECTION_PANORAMA (equirectangular over the
+    longitude / latitude window in radians; the defaults are the full sphere)."""
+    type: int = PROJECTION_PERSPECTIVE
+    ortho_scale: float = 1.0
+    longitude_min: float = -_PI_F32
+    longitude_max: float = _PI_F32
+    latitude_min: float = -_HALF_PI_F32
+    latitude_max: float = _HALF_PI_F32
+
+    def to_desc(self) -> ProjectionDesc:
+        return ProjectionDesc(int(self.type), float(self.ortho_scale), float(self.longitude_min), float(self.longitude_max), float(self.latitude_min), float(self.latitude_max))
+
+    @staticmethod
+    def from_desc(d: ProjectionDesc) -> "ProjectionData":
+        return ProjectionData(int(d.type), float(d.ortho_scale), float(d.longitude_min), float(d.longitude_max), float(d.latitude_min), float(d.latitude_max))
+
+
 @dataclass
 class CameraData:
     c2w: np.ndarray  # (16,) f32 column-major
@@ -657,6 +689,7 @@ class SceneData:
     environment: Optional[EnvironmentData] = None  # set by capi.Scene through akr_scene_set_environment (not part of akr_scene_desc)
     lens: Optional[LensData] = None  # set by capi.Scene through akr_scene_set_lens (not part of akr_scene_desc / akr_camera_desc)
     lights: List["PunctualLightData"] = field(default_factory=list)  # added by capi.Scene through akr_scene_add_punctual_light (not part of akr_scene_desc)
+    projection: Optional[ProjectionData] = None  # set by capi.Scene through akr_scene_set_projection (not part of akr_scene_desc / akr_camera_desc); None = perspective
 
     def n_triangles(self) -> int:
         return sum(self.meshes[i.mesh].indices.shape[0] for i in self.instances)

@@ -46,6 +46,7 @@ EXPORTS = [
     "akr_pt_kernel_info", "akr_scene_spec_source", "akr_host_spec_compile", "akr_host_spec_compile_text",
     "akr_film_reduce_planes", "akr_mcmc_render_shard", "akr_mcmc_combine_host", "akr_mcmc_combine",
     "akr_scene_set_environment", "akr_scene_get_environment", "akr_scene_set_lens", "akr_scene_get_lens",
+    "akr_projection_desc_default", "akr_scene_set_projection", "akr_scene_get_projection",
     "akr_denoise_config_default", "akr_denoise", "akr_denoise_variance",
     "akr_pt_set_active_tiles", "akr_film_tile_error", "akr_adaptive_config_default", "akr_pt_adaptive_render",
     "akr_display_config_default", "akr_film_luminance_histogram", "akr_display_exposure", "akr_display_transform",
@@ -113,7 +114,7 @@ def lib() -> C.CDLL:
                                abi.EnvironmentDesc, abi.LensDesc, abi.DenoiseConfig), start=1):
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
-    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats), (22, abi.DisplayConfig), (24, abi.PunctualLightDesc)):  # (ids 18, 21 and 23 are not assigned)
+    for sid, cls in ((19, abi.AdaptiveConfig), (20, abi.AdaptiveStats), (22, abi.DisplayConfig), (24, abi.PunctualLightDesc), (26, abi.ProjectionDesc)):  # (ids 18, 21, 23 and 25 are not assigned)
         if L.akr_struct_size(sid) != C.sizeof(cls):
             raise ImportError("libakari_hip.so and akari_render_amd/abi.py disagree on sizeof(%s): %d vs %d" % (cls.__name__, L.akr_struct_size(sid), C.sizeof(cls)))
 
@@ -138,6 +139,9 @@ def lib() -> C.CDLL:
     proto("akr_scene_get_environment", vp, C.POINTER(abi.EnvironmentDesc))
     proto("akr_scene_set_lens", vp, C.POINTER(abi.LensDesc))
     proto("akr_scene_get_lens", vp, C.POINTER(abi.LensDesc))
+    proto("akr_projection_desc_default", C.POINTER(abi.ProjectionDesc))
+    proto("akr_scene_set_projection", vp, C.POINTER(abi.ProjectionDesc))
+    proto("akr_scene_get_projection", vp, C.POINTER(abi.ProjectionDesc))
     proto("akr_scene_add_punctual_light", vp, C.POINTER(abi.PunctualLightDesc))
     proto("akr_scene_clear_punctual_lights", vp)
     proto("akr_scene_punctual_light_count", vp, up)
@@ -332,6 +336,9 @@ class Scene:
             env = getattr(source, "environment", None)
             if env is not None:
                 self._set_environment_data(env)
+            projection = getattr(source, "projection", None)
+            if projection is not None:  # (before the lens: an orthographic film is checked with it, a panorama refuses one)
+                self.set_projection(projection)
             lens = getattr(source, "lens", None)
             if lens is not None:
                 self.set_lens(lens.radius, lens.focal_distance)
@@ -512,6 +519,24 @@ class Scene:
         check(lib().akr_scene_get_lens(self.h, C.byref(d)))
         return abi.LensData(float(d.radius), float(d.focal_distance)) if d.radius > 0.0 else None
 
+    def set_projection(self, projection=None, **fields):
+        """akr_scene_set_projection: an abi.ProjectionData, or a type -- abi.PROJECTION_* or "perspective" / "orthographic" / "panorama" -- with the
+        fields to change from their defaults (ortho_scale=, longitude_min=, ...). None: the perspective camera."""
+        if projection is None and not fields:
+            check(lib().akr_scene_set_projection(self.h, None))
+            return
+        if not isinstance(projection, abi.ProjectionData):
+            names = {"perspective": abi.PROJECTION_PERSPECTIVE, "orthographic": abi.PROJECTION_ORTHOGRAPHIC, "panorama": abi.PROJECTION_PANORAMA}
+            projection = abi.ProjectionData(type=names.get(projection, projection) if projection is not None else abi.PROJECTION_PERSPECTIVE, **fields)
+        d = projection.to_desc()
+        check(lib().akr_scene_set_projection(self.h, C.byref(d)))
+
+    def projection(self) -> abi.ProjectionData:
+        """akr_scene_get_projection: the projection as the scene holds it (abi.ProjectionData() = the perspective default)."""
+        d = abi.ProjectionDesc()
+        check(lib().akr_scene_get_projection(self.h, C.byref(d)))
+        return abi.ProjectionData.from_desc(d)
+
     def _camera_rays(self, fn, head, pixels, u_filter, u_lens, filter_type, filter_radius):
         px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1, 2)
         n = px.shape[0]
@@ -627,7 +652,7 @@ class Scene:
         c = abi.CameraDesc()
         check(lib().akr_scene_get_camera(self.h, C.byref(c)))
         cam = abi.CameraData(np.array(list(c.c2w), dtype=np.float32), float(c.fov), c.width, c.height)
-        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment(), lens=self.lens(), lights=self.punctual_lights())
+        return abi.SceneData(meshes, instances, materials, cam, images=images, environment=self.environment(), lens=self.lens(), lights=self.punctual_lights(), projection=self.projection())
 
 
 def set_option(name: str, value: int) -> None:

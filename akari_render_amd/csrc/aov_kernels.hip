@@ -5,7 +5,7 @@ namespace akr {
 
 hipError_t launch_aov(const PtParams& p, uint32_t spp, uint32_t aov, uint32_t remap, hipStream_t stream) {
     static constexpr hipError_t (*kEntry[2])(const PtParams&, uint32_t, uint32_t, uint32_t, hipStream_t) = {launch_aov_t<false>, aov_entry_lens};  // by [lens]
-    return kEntry[p.lens_radius > 0.0f](p, spp, aov, remap, stream);
+    return kEntry[camera_runs_lens_kernels(p.lens_radius, p.projection)](p, spp, aov, remap, stream);
 }
 
 }  // namespace akr

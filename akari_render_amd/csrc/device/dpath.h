@@ -194,17 +194,25 @@ AKR_D void sampler_end_pass(const PtParams& p, Sampler& s) {
     }  // pmj02bn: the state is stored as it is; dim is reset by the next start()
 }
 
-// the pinhole direction in camera space of film sample (pixel, u_filter): camera/mod.rs:70-96. Shared by the pinhole and the lens.
-AKR_HD vec3 camera_space_dir(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter) {
+// the film point of sample (pixel, u_filter), and raster -> camera of it before the perspective division: camera/mod.rs:70-96
+AKR_HD vec2 film_point(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter) {
     vec2 fpixel = mk2((float)px + 0.5f, (float)py + 0.5f);
     vec2 offset = filter_sample(p, u_filter);
-    vec2 pf = mk2(fpixel.x + offset.x, fpixel.y + offset.y);
+    return mk2(fpixel.x + offset.x, fpixel.y + offset.y);
+}
+AKR_HD vec3 camera_space_q(const PtParams& p, vec2 pf, float& qw) {
     const float* m = p.r2c;
     float qx = ((m[0] * pf.x + m[4] * pf.y) + m[8] * 0.0f) + m[12] * 1.0f;
     float qy = ((m[1] * pf.x + m[5] * pf.y) + m[9] * 0.0f) + m[13] * 1.0f;
     float qz = ((m[2] * pf.x + m[6] * pf.y) + m[10] * 0.0f) + m[14] * 1.0f;
-    float qw = ((m[3] * pf.x + m[7] * pf.y) + m[11] * 0.0f) + m[15] * 1.0f;
-    return normalize(div_s(mk3(qx, qy, qz), qw));
+    qw = ((m[3] * pf.x + m[7] * pf.y) + m[11] * 0.0f) + m[15] * 1.0f;
+    return mk3(qx, qy, qz);
+}
+// the pinhole direction in camera space of film sample (pixel, u_filter). Shared by the pinhole and the lens.
+AKR_HD vec3 camera_space_dir(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter) {
+    float qw;
+    const vec3 q = camera_space_q(p, film_point(p, px, py, u_filter), qw);
+    return normalize(div_s(q, qw));
 }
 // camera/mod.rs:70-103 (AKR_HD: the test hook akr_host_lens_ray runs this text on the host)
 AKR_HD void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec3& o, vec3& d) {
@@ -219,15 +227,51 @@ AKR_HD void generate_ray_from(const PtParams& p, uint32_t px, uint32_t py, vec2 
 }
 // The thin lens (the reference stores lens_radius and focal_length in PerspectiveCameraData, camera/mod.rs:105-118,
 // and leaves them unused). The lens point comes from dgeom.h concentric_disk.
-// generate_ray_from with a lens of radius p.lens_radius > 0 focused at distance p.lens_focal along the optical axis: the pinhole
-// direction dc in camera space meets the plane of focus at dc * ft; the ray leaves the lens point l towards that point.
-AKR_HD void generate_ray_lens_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& o, vec3& d) {
+// The perspective camera with a lens of radius p.lens_radius > 0 focused at distance p.lens_focal along the optical axis: the pinhole
+// direction dc in camera space meets the plane of focus at dc * ft; the ray leaves the lens point l towards that point. -> camera space
+AKR_HD void lens_ray_camera(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& l, vec3& d) {
     const vec3 dc = camera_space_dir(p, px, py, u_filter);
     const vec2 ab = concentric_disk(u_lens);
-    const vec3 l = mk3(p.lens_radius * ab.x, p.lens_radius * ab.y, 0.0f);
+    l = mk3(p.lens_radius * ab.x, p.lens_radius * ab.y, 0.0f);
     const float ft = p.lens_focal / (-dc.z);
     const vec3 p_focus = dc * ft;
     d = normalize(p_focus - l);
+}
+// The other projections (no reference counterpart: its camera is the perspective one), in camera space.
+// Orthographic: r2c is camera_matrices' chain with half the ortho scale for tan(fov / 2), so q / w is the film point on the plane z = -1; every ray
+// leaves its (x, y) on the plane z = 0 along -z. With a lens the origin moves by the lens point and the ray is bent so that the plane z = -F is sharp.
+AKR_HD void ortho_ray_camera(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& o, vec3& d) {
+    float qw;
+    const vec3 q = camera_space_q(p, film_point(p, px, py, u_filter), qw);
+    const vec3 s = div_s(q, qw);
+    o = mk3(s.x, s.y, 0.0f);
+    d = mk3(0.0f, 0.0f, -1.0f);
+    if (p.lens_radius > 0.0f) {
+        const vec2 ab = concentric_disk(u_lens);
+        const vec3 l = mk3(p.lens_radius * ab.x, p.lens_radius * ab.y, 0.0f);
+        o = mk3(s.x + l.x, s.y + l.y, 0.0f);
+        d = normalize(mk3(-l.x, -l.y, -p.lens_focal));
+    }
+}
+// Equirectangular panorama: the film's columns are longitudes (growing to the right, 0 = the camera's -z), its rows latitudes (row 0 up), over the
+// window the host folded into pano_*; the origin is the pinhole's. A film point outside the film continues the mapping.
+AKR_HD void panorama_ray_camera(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec3& o, vec3& d) {
+    const vec2 pf = film_point(p, px, py, u_filter);
+    const float lon = p.pano_lon0 + (pf.x * p.pano_inv_w) * p.pano_dlon;
+    const float lat = p.pano_lat1 - (pf.y * p.pano_inv_h) * p.pano_dlat;
+    float sl, cl, sp, cp;
+    sincos_f(lon, sl, cl);
+    sincos_f(lat, sp, cp);
+    o = mk3(0.0f, 0.0f, 0.0f);
+    d = normalize(mk3(cp * sl, sp, -(cp * cl)));
+}
+// The camera ray of the LENS kernels: by projection (a kernel argument: the branch is uniform), then camera -> world. (AKR_HD: the test hook
+// akr_host_lens_ray runs this text on the host.)
+AKR_HD void generate_ray_lens_from(const PtParams& p, uint32_t px, uint32_t py, vec2 u_filter, vec2 u_lens, vec3& o, vec3& d) {
+    vec3 l;
+    if (p.projection == PROJ_PERSPECTIVE) lens_ray_camera(p, px, py, u_filter, u_lens, l, d);
+    else if (p.projection == PROJ_ORTHOGRAPHIC) ortho_ray_camera(p, px, py, u_filter, u_lens, l, d);
+    else panorama_ray_camera(p, px, py, u_filter, l, d);
     o = l;
     if (!p.c2w_identity) {  // c2w . point(l) and c2w . vector(d)
         const float* c = p.c2w;
@@ -240,7 +284,7 @@ AKR_HD void generate_ray_lens_from(const PtParams& p, uint32_t px, uint32_t py, 
                 (c[2] * d.x + c[6] * d.y) + c[10] * d.z);
     }
 }
-// LENS: u_lens is the next_2d right after the filter's; the pinhole camera does not draw it
+// LENS: u_lens is the next_2d right after the filter's (drawn by every camera that runs the LENS kernels, read only with a lens); the pinhole camera does not draw it
 template <bool PMJ, bool LENS = false>
 AKR_D void generate_ray(const PtParams& p, uint32_t px, uint32_t py, Sampler& smp, vec3& o, vec3& d) {
     const vec2 u_filter = next_2d<PMJ>(p, smp);

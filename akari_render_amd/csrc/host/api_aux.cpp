@@ -92,6 +92,8 @@ AKR_API int32_t akr_gpt_begin(akr_context* ctx, akr_scene* scene, const akr_gpt_
     if (shard && shard->shard_count > 1 && shard->shard_rank >= shard->shard_count) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_gpt_begin: shard_rank >= shard_count");
     if (scene->cs.env.on) return fail(AKR_ERR_UNSUPPORTED, "akr_gpt_begin: gpt does not render scenes with an environment light (its path code has none)");
     if (!scene->cs.punct.empty()) return fail(AKR_ERR_UNSUPPORTED, "akr_gpt_begin: the scene has a " + punctual_light_name(scene->cs) + "; gpt does not render punctual lights (its path code has none)");
+    if (scene->flat.projection.type != AKR_PROJECTION_PERSPECTIVE)
+        return fail(AKR_ERR_UNSUPPORTED, std::string("akr_gpt_begin: gpt does not render through ") + projection_name(scene->flat.projection.type) + " projection (its shift mapping assumes a pinhole camera)");
     if (scene->flat.lens.radius > 0.0f) return fail(AKR_ERR_UNSUPPORTED, "akr_gpt_begin: gpt does not render through a lens (its shift mapping assumes a pinhole camera)");
     akr_pt_config pc;
     akr_pt_config_default(&pc);
@@ -295,6 +297,8 @@ int32_t akr_api::mcmc_render_impl(akr_context* ctx, akr_scene* scene, const akr_
     if (cfg->spp_per_pass == 0) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_mcmc_render: spp_per_pass must be positive");
     if (scene->cs.env.on) return fail(AKR_ERR_UNSUPPORTED, "akr_mcmc_render: mcmc_opt does not render scenes with an environment light (its path code has none)");
     if (!scene->cs.punct.empty()) return fail(AKR_ERR_UNSUPPORTED, "akr_mcmc_render: the scene has a " + punctual_light_name(scene->cs) + "; mcmc_opt does not render punctual lights (its path code has none)");
+    if (scene->flat.projection.type != AKR_PROJECTION_PERSPECTIVE)
+        return fail(AKR_ERR_UNSUPPORTED, std::string("akr_mcmc_render: mcmc_opt does not render through ") + projection_name(scene->flat.projection.type) + " projection (its own ray generation is a pinhole's)");
     if (scene->flat.lens.radius > 0.0f) return fail(AKR_ERR_UNSUPPORTED, "akr_mcmc_render: mcmc_opt does not render through a lens (its own ray generation is a pinhole's)");
     const uint32_t W = scene->flat.camera.width, H = scene->flat.camera.height;
     if (cfg->direct_spp > 0) {  // direct illumination by the path tracer, mcmc_opt.rs:704-729

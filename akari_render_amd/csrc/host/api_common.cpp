@@ -42,10 +42,11 @@ AKR_API uint32_t akr_struct_size(int32_t which) {
         case AKR_STRUCT_ADAPTIVE_STATS: return sizeof(akr_adaptive_stats);
         case AKR_STRUCT_DISPLAY_CONFIG: return sizeof(akr_display_config);
         case AKR_STRUCT_PUNCTUAL_LIGHT_DESC: return sizeof(akr_punctual_light_desc);
+        case AKR_STRUCT_PROJECTION_DESC: return sizeof(akr_projection_desc);
         default: return 0;
     }
 }
-AKR_API const char* akr_version(void) { return "akari_hip 0.3.8 gfx950"; }  // 0.3.8: soft shadows (akr_punctual_light_desc gains radius and angle, option soft_lights); 0.3.7: punctual lights (akr_punctual_light_desc, akr_scene_add_punctual_light / clear / count / get, option punctual_lights); 0.3.6: guides collected inside the pt pass (akr_pt_begin_features, akr_pt_render_features, option denoise_features); 0.3.5: display transform (akr_display_config, akr_film_luminance_histogram, akr_display_exposure, akr_display_transform, options display / display_*); 0.3.4: adaptive sampling (akr_pt_set_active_tiles, akr_film_tile_error, akr_pt_adaptive_render, options adaptive / adaptive_min_spp); 0.3.3: akr_denoise (akr_denoise_config, options denoise / denoise_kernel); 0.3.2: thin lens (akr_lens_desc, akr_scene_set_lens / get, option lens); 0.3.1: environment lights (akr_environment_desc, akr_scene_set_environment / get); 0.3.0: akr_struct_size, scenes kept as meshes + instances; 0.2.0: akr_pt_config gained sample_begin / sample_count (88 bytes); akr_kernel_info carries its own size
+AKR_API const char* akr_version(void) { return "akari_hip 0.3.9 gfx950"; }  // 0.3.9: camera projections (akr_projection_desc, akr_scene_set_projection / get: orthographic and panorama); 0.3.8: soft shadows (akr_punctual_light_desc gains radius and angle, option soft_lights); 0.3.7: punctual lights (akr_punctual_light_desc, akr_scene_add_punctual_light / clear / count / get, option punctual_lights); 0.3.6: guides collected inside the pt pass (akr_pt_begin_features, akr_pt_render_features, option denoise_features); 0.3.5: display transform (akr_display_config, akr_film_luminance_histogram, akr_display_exposure, akr_display_transform, options display / display_*); 0.3.4: adaptive sampling (akr_pt_set_active_tiles, akr_film_tile_error, akr_pt_adaptive_render, options adaptive / adaptive_min_spp); 0.3.3: akr_denoise (akr_denoise_config, options denoise / denoise_kernel); 0.3.2: thin lens (akr_lens_desc, akr_scene_set_lens / get, option lens); 0.3.1: environment lights (akr_environment_desc, akr_scene_set_environment / get); 0.3.0: akr_struct_size, scenes kept as meshes + instances; 0.2.0: akr_pt_config gained sample_begin / sample_count (88 bytes); akr_kernel_info carries its own size
 AKR_API int32_t akr_option_set(const char* name, int32_t value) {
     if (!tuning_set(name, value)) return fail(AKR_ERR_INVALID_ARGUMENT, std::string("akr_option_set: unknown option '") + (name ? name : "(null)") + "' or value out of range");
     return AKR_OK;

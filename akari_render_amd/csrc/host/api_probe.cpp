@@ -327,7 +327,7 @@ AKR_TEST_API int32_t akr_host_lens_ray(const akr_scene* scene, uint32_t filter_t
     for (uint32_t i = 0; i < n; i++) {
         const float* u = u4 + 4ull * i;
         vec3 o, d;
-        if (p.lens_radius > 0.0f) generate_ray_lens_from(p, pixels2[2ull * i], pixels2[2ull * i + 1], mk2(u[0], u[1]), mk2(u[2], u[3]), o, d);
+        if (camera_runs_lens_kernels(p.lens_radius, p.projection)) generate_ray_lens_from(p, pixels2[2ull * i], pixels2[2ull * i + 1], mk2(u[0], u[1]), mk2(u[2], u[3]), o, d);
         else generate_ray_from(p, pixels2[2ull * i], pixels2[2ull * i + 1], mk2(u[0], u[1]), o, d);
         float* r = out6 + 6ull * i;
         r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;

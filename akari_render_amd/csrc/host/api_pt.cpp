@@ -13,6 +13,15 @@ void akr_api::camera_params(PtParams& p, const akr_scene* s, uint32_t filter_typ
     p.filter_radius = filter_radius;
     p.lens_radius = s->flat.lens.radius;  // > 0: the LENS kernels (device/dpath.h generate_ray_lens_from)
     p.lens_focal = s->flat.lens.focal_distance;
+    // the projection: anything but perspective runs the LENS kernels too; the panorama's window folded, each value rounded once
+    const HostProjection& pr = s->flat.projection;
+    p.projection = pr.type;
+    p.pano_lon0 = pr.lon_min;
+    p.pano_dlon = pr.lon_max - pr.lon_min;
+    p.pano_lat1 = pr.lat_max;
+    p.pano_dlat = pr.lat_max - pr.lat_min;
+    p.pano_inv_w = 1.0f / (float)s->flat.camera.width;
+    p.pano_inv_h = 1.0f / (float)s->flat.camera.height;
 }
 void akr_api::session_params(RenderBase* se, const PtPlan* pt) {
     PtParams& p = se->params;

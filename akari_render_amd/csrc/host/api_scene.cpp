@@ -156,15 +156,19 @@ static float walk_origin_bound(const std::vector<float>& woop, uint32_t n) {
     return b >= 0x1p-40 ? (float)b : -1.0f;
 }
 
-// A lens moves the ray origins off the camera's position, and the padding of the scene's boxes was sized from the largest coordinate magnitude an
+// A lens moves the ray origins off the camera's position, and so does an orthographic projection, whose origins cover the film rectangle in the camera's
+// x / y plane. The padding of the scene's boxes was sized from the largest coordinate magnitude an
 // origin can have (scene_build.cpp, scene_inst.cpp: the camera's translation against the scene's box). The trees of a scene
-// are the ones of its lens-less compile, so the lens is accepted only where every origin on its disk stays inside that magnitude.
-static void check_lens_reach(const akr_scene* s, const HostLens& lens) {
+// are the ones of its lens-less perspective compile, so a lens and a film are accepted only where every origin on them stays inside that magnitude.
+// A panorama's origins are the pinhole's.
+static void check_lens_reach(const akr_scene* s, const HostLens& lens, const HostProjection& proj, uint32_t width, uint32_t height) {
     const CompiledScene& cs = s->cs;
-    if (lens.radius == 0.0f || (cs.bvh_nodes.empty() && !cs.instanced.on)) return;  // (the exhaustive walk has no boxes)
+    const bool ortho = proj.type == AKR_PROJECTION_ORTHOGRAPHIC;
+    if ((lens.radius == 0.0f && !ortho) || (cs.bvh_nodes.empty() && !cs.instanced.on)) return;  // (the exhaustive walk has no boxes)
     const float* c2w = s->flat.camera.c2w;
-    float bound[3], moved[16];
-    lens_origin_bound(c2w, lens.radius, bound);
+    float bound[3], moved[16], half_x = 0.0f, half_y = 0.0f;
+    if (ortho) ortho_film_half_extents(proj.ortho_scale, width, height, &half_x, &half_y);
+    lens_origin_bound(c2w, lens.radius, half_x, half_y, bound);
     std::memcpy(moved, c2w, sizeof moved);
     bool inside = true;
     for (int a = 0; a < 3; a++) {
@@ -174,10 +178,20 @@ static void check_lens_reach(const akr_scene* s, const HostLens& lens) {
     }
     // flattened scenes: the padding looks at max(diagonal, reach) only -- unchanged is enough; kept scenes also use the per-axis magnitudes
     if (inside || (!cs.instanced.on && bvh_box_padding(cs.scene_lo, cs.scene_hi, moved) == bvh_box_padding(cs.scene_lo, cs.scene_hi, c2w))) return;
-    char msg[320];
-    std::snprintf(msg, sizeof msg, "lens: a lens of radius %g puts ray origins at coordinates up to (%g, %g, %g), beyond the magnitude the scene's acceleration "
-                  "structure was padded for (its box and the camera position); use a smaller radius", lens.radius, bound[0], bound[1], bound[2]);
+    char msg[400];
+    if (ortho)
+        std::snprintf(msg, sizeof msg, "projection: an orthographic film of scale %g%s puts ray origins at coordinates up to (%g, %g, %g), beyond the magnitude the scene's "
+                      "acceleration structure was padded for (its box and the camera position); use a smaller ortho_scale", proj.ortho_scale,
+                      lens.radius > 0.0f ? " with its lens" : "", bound[0], bound[1], bound[2]);
+    else
+        std::snprintf(msg, sizeof msg, "lens: a lens of radius %g puts ray origins at coordinates up to (%g, %g, %g), beyond the magnitude the scene's acceleration "
+                      "structure was padded for (its box and the camera position); use a smaller radius", lens.radius, bound[0], bound[1], bound[2]);
     throw std::invalid_argument(msg);
+}
+static void check_lens_reach(const akr_scene* s, const HostLens& lens, const HostProjection& proj) { check_lens_reach(s, lens, proj, s->flat.camera.width, s->flat.camera.height); }
+static void refuse_lens_on_panorama(const HostLens& lens, const HostProjection& proj, const char* who) {
+    if (lens.radius > 0.0f && proj.type == AKR_PROJECTION_PANORAMA)
+        throw std::invalid_argument(std::string(who) + ": a panorama camera has no lens (remove the lens, or choose another projection)");
 }
 
 void akr_api::scene_finish(akr_scene* s, const TuningOptions& opt) {
@@ -185,9 +199,10 @@ void akr_api::scene_finish(akr_scene* s, const TuningOptions& opt) {
     compile_scene(s->flat, opt, s->cs);
     compile_punctual(s->flat, s->cs);
     compile_environment(s->flat, s->cs);
-    check_lens_reach(s, s->flat.lens);  // (a lens from the file, option `lens`)
+    refuse_lens_on_panorama(s->flat.lens, s->flat.projection, "scene");
+    check_lens_reach(s, s->flat.lens, s->flat.projection);  // (a lens from the file, option `lens`; an orthographic camera of the file)
     CompiledScene& cs = s->cs;
-    camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity);
+    camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity, &s->flat.projection);
     if (!ctx) {  // host-only scene: inspectable, not renderable
         s->ggx_host = s->flat.ggx_table.empty() ? std::vector<float>(4096, 0.0f) : s->flat.ggx_table;
         std::memset(&s->dscene, 0, sizeof s->dscene);
@@ -326,9 +341,13 @@ AKR_API int32_t akr_scene_set_resolution(akr_scene* s, uint32_t width, uint32_t 
     if (!s || !width || !height) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_resolution: bad argument");
     // (a session's film, sampler states and parameter block are sized for the resolution it began with)
     if (s->sessions.load() != 0) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_resolution: a session holds the scene (end it first)");
+    if (s->flat.projection.type == AKR_PROJECTION_ORTHOGRAPHIC) {  // (the film's smaller side changes with the aspect: the reach check of akr_scene_set_projection)
+        const int32_t rc = guarded([&] { check_lens_reach(s, s->flat.lens, s->flat.projection, width, height); });
+        if (rc != AKR_OK) return rc;
+    }
     s->flat.camera.width = width;
     s->flat.camera.height = height;
-    camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity);
+    camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity, &s->flat.projection);
     return AKR_OK;
 }
 AKR_API int32_t akr_scene_get_info(const akr_scene* s, akr_scene_info* info) {
@@ -455,9 +474,40 @@ AKR_API int32_t akr_scene_set_lens(akr_scene* s, const akr_lens_desc* desc) {
         if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_set_lens: a session holds the scene (end it first)");
         HostLens lens;
         if (desc) lens = lens_from_values(desc->radius, desc->focal_distance);
-        check_lens_reach(s, lens);
+        refuse_lens_on_panorama(lens, s->flat.projection, "akr_scene_set_lens");
+        check_lens_reach(s, lens, s->flat.projection);
         s->flat.lens = lens;
     });
+}
+AKR_API int32_t akr_projection_desc_default(akr_projection_desc* desc) {
+    if (!desc) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_projection_desc_default: desc is NULL");
+    const HostProjection p;
+    desc->type = p.type;
+    desc->ortho_scale = p.ortho_scale;
+    desc->longitude_min = p.lon_min; desc->longitude_max = p.lon_max;
+    desc->latitude_min = p.lat_min; desc->latitude_max = p.lat_max;
+    return AKR_OK;
+}
+AKR_API int32_t akr_scene_set_projection(akr_scene* s, const akr_projection_desc* desc) {
+    if (!s) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_set_projection: scene is NULL");
+    return guarded([&] {
+        if (s->sessions.load() != 0) throw std::invalid_argument("akr_scene_set_projection: a session holds the scene (end it first)");
+        HostProjection proj;
+        if (desc) proj = projection_from_values(desc->type, desc->ortho_scale, desc->longitude_min, desc->longitude_max, desc->latitude_min, desc->latitude_max);
+        refuse_lens_on_panorama(s->flat.lens, proj, "akr_scene_set_projection");
+        check_lens_reach(s, s->flat.lens, proj);
+        s->flat.projection = proj;
+        camera_matrices(s->flat.camera, s->r2c, s->c2w, &s->c2w_identity, &s->flat.projection);
+    });
+}
+AKR_API int32_t akr_scene_get_projection(const akr_scene* s, akr_projection_desc* out) {
+    if (!s || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_projection: NULL argument");
+    const HostProjection& p = s->flat.projection;
+    out->type = p.type;
+    out->ortho_scale = p.ortho_scale;
+    out->longitude_min = p.lon_min; out->longitude_max = p.lon_max;
+    out->latitude_min = p.lat_min; out->latitude_max = p.lat_max;
+    return AKR_OK;
 }
 AKR_API int32_t akr_scene_get_lens(const akr_scene* s, akr_lens_desc* out) {
     if (!s || !out) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_lens: NULL argument");

@@ -1,6 +1,6 @@
 // akari-cli -- the reference's command line (crates/akari_api/src/bin/akari_cli.rs:8-95) over libakari_hip.so:
 //   akari-cli -s scene.json -m method.json [-d <hip device ordinal>] [-v] [--save-intermediate] [--save-stats NAME]
-//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--light-tree] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--denoise [N]] [--denoise-variance] [--denoise-features]
+//             [--resolution WxH] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--light-tree] [--depth-of-field] [--lens-radius X] [--focal-distance Y] [--projection P] [--ortho-scale X] [--denoise [N]] [--denoise-variance] [--denoise-features]
 //             [--adaptive [X]] [--adaptive-min-spp N] [--display [linear|reinhard|aces|hable]] [--exposure EV] [--auto-exposure] [--bloom [X]]
 // -d accepts a HIP device ordinal (the reference's "cpu|cuda|dx|metal" back ends do not exist here; "hip" = 0).
 // --gui is not supported. --independent-sampler renders method files that ask for pmj02bn (scenes/cbox/pt.json)
@@ -31,6 +31,7 @@
 static void usage() {
     std::puts("Usage: akari-cli -s <SCENE> -m <METHOD> [-d <DEVICE>] [-v] [--save-intermediate] [--save-stats <NAME>]\n"
               "                 [--resolution <W>x<H>] [--independent-sampler] [--no-punctual-lights] [--no-soft-lights] [--light-tree] [--depth-of-field] [--lens-radius <X>] [--focal-distance <Y>] [--denoise [<N>]] [--denoise-variance] [--denoise-features]\n"
+              "                 [--projection perspective|orthographic|panorama] [--ortho-scale <X>]\n"
               "                 [--adaptive [<X>]] [--adaptive-min-spp <N>]\n"
               "                 [--display [linear|reinhard|aces|hable]] [--exposure <EV>] [--auto-exposure] [--bloom [<X>]]\n"
               "  -s, --scene <SCENE>      Scene file to render (akari scene-graph JSON)\n"
@@ -44,6 +45,8 @@ static void usage() {
               "      --no-soft-lights     load the scene file's lights with radius 0 and angle 0: hard shadows (default: soft shadows where the file gives a size)\n"
               "      --depth-of-field     render through the thin lens of the scene file's focal_distance and fstop (default: a pinhole)\n"
               "      --lens-radius <X>, --focal-distance <Y>  the lens's radius / distance of the plane of focus, instead of the file's\n"
+              "      --projection <P>     the camera's projection instead of the scene file's: perspective, orthographic or panorama (equirectangular, the file's window or the full sphere)\n"
+              "      --ortho-scale <X>    the world-space length the larger image side of an orthographic camera spans, instead of the file's\n"
               "      --denoise [<N>]      pt tasks also write {stem}.denoised{ext}: an edge-avoiding filter guided by albedo / normal passes of N spp (default 16)\n"
               "      --denoise-variance   with --denoise: per-pixel colour weights from the variance between the two halves of the passes (needs spp > spp_per_pass)\n"
               "      --denoise-features   the denoise step (implied) takes its albedo / normal guides from the pt task's own samples instead of from passes of their own\n"
@@ -76,6 +79,8 @@ int main(int argc, char** argv) {
     unsigned w = 0, h = 0;
     int dof = 0, no_punctual = 0, no_soft = 0, light_tree = 0;
     float lens_radius = -1.0f, focal_distance = -1.0f;  // < 0: not given
+    int projection = -1;  // akr_projection_type; < 0: not given
+    float ortho_scale = -1.0f;
     int denoise = 0, denoise_variance = 0, denoise_features = 0;
     int adaptive = 0, adaptive_min_spp = 0;  // adaptive: the option's value, threshold x 1024
     int display = 0, display_exposure = 0, display_auto = 0, display_bloom = 0, display_fields = 0;  // the options' values; display_fields: one of the three others was given
@@ -169,6 +174,20 @@ int main(int argc, char** argv) {
             if (end == text || *end != 0 || !(v >= 0.0f)) { std::fprintf(stderr, "akari-cli: %s wants a number >= 0, got '%s'\n", a.c_str(), text); return 1; }
             (a == "--lens-radius" ? lens_radius : focal_distance) = v;
         }
+        else if (a == "--projection") {
+            const char* text = next();
+            static const char* const names[] = {"perspective", "orthographic", "panorama"};
+            for (int c = 0; c < 3; c++)
+                if (std::strcmp(text, names[c]) == 0) projection = c;
+            if (projection < 0) { std::fprintf(stderr, "akari-cli: --projection wants perspective, orthographic or panorama, got '%s'\n", text); return 1; }
+        }
+        else if (a == "--ortho-scale") {
+            const char* text = next();
+            char* end = nullptr;
+            const float v = std::strtof(text, &end);
+            if (end == text || *end != 0 || !(v > 0.0f)) { std::fprintf(stderr, "akari-cli: --ortho-scale wants a number > 0, got '%s'\n", text); return 1; }
+            ortho_scale = v;
+        }
         else if (a == "--resolution") { if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { usage(); return 1; } }
         else if (a == "--gui") { std::fputs("akari-cli: --gui is not supported by the HIP integrator\n", stderr); return 1; }
         else { usage(); return 1; }
@@ -204,6 +223,13 @@ int main(int argc, char** argv) {
                     akr_option_set("display_exposure", display_exposure) != AKR_OK || akr_option_set("display_bloom", display_bloom) != AKR_OK))
         die("option display");
     if (akr_scene_load(ctx, scene.c_str(), w, h, &sc) != AKR_OK) die("scene");
+    if (projection >= 0 || ortho_scale > 0.0f) {  // (before the lens: a panorama refuses one, an orthographic film is checked with it)
+        akr_projection_desc pd;
+        if (akr_scene_get_projection(sc, &pd) != AKR_OK) die("projection");
+        if (projection >= 0) pd.type = (uint32_t)projection;
+        if (ortho_scale > 0.0f) pd.ortho_scale = ortho_scale;
+        if (akr_scene_set_projection(sc, &pd) != AKR_OK) die("projection");
+    }
     if (lens_radius >= 0.0f || focal_distance >= 0.0f) {
         akr_lens_desc lens;
         if (akr_scene_get_lens(sc, &lens) != AKR_OK) die("lens");

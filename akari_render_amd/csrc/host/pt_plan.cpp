@@ -12,7 +12,7 @@ PtVariant akr_api::pt_scene_facts(const akr_scene* s, const akr_pt_config& c) {
     v.pmj = c.sampler_type != AKR_SAMPLER_INDEPENDENT;
     v.inst = cs.instanced.on;
     v.env = cs.env.on;
-    v.lens = s->flat.lens.radius > 0.0f;
+    v.lens = camera_runs_lens_kernels(s->flat.lens.radius, s->flat.projection.type);  // (a lens, or a projection other than the perspective one: DESIGN.md 4.17)
     v.punct = !cs.punct.empty();
     v.ltree = !cs.punct_tree.empty();
     return v;
@@ -171,6 +171,8 @@ PtRoute akr_api::pt_route(const akr_scene* s, const akr_pt_config& c, const Tuni
     // else -- kept scenes, the wavefront schedule, aov / gpt / mcmc_opt -- stays on the contract whatever the option says.
     r.relaxed = t.arith == 1 && !facts.inst && !r.wavefront && !feat;
     if (r.relaxed && facts.env) r.refusal = "unsupported: the relaxed arithmetic tier (option arith = 1) does not render scenes with an environment light";
+    else if (r.relaxed && s->flat.projection.type != AKR_PROJECTION_PERSPECTIVE)
+        r.refusal = std::string("unsupported: the relaxed arithmetic tier (option arith = 1) does not render through ") + projection_name(s->flat.projection.type) + " projection (akr_scene_set_projection)";
     else if (r.relaxed && facts.lens) r.refusal = "unsupported: the relaxed arithmetic tier (option arith = 1) does not render through a lens (akr_scene_set_lens)";
     if (!r.refusal.empty()) return r;
     // A per-scene kernel (host/specialise.cpp) for the megakernel of a scene with texture-fed materials: always / never by option, else a cached

@@ -380,7 +380,7 @@ static void m4_translate(float x, float y, float z, float* m) {
     m4_scale(1, 1, 1, m);
     m[12] = x; m[13] = y; m[14] = z;
 }
-void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], uint32_t* c2w_identity) {
+void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], uint32_t* c2w_identity, const HostProjection* proj) {
     float m[16], s[16];
     float fw = (float)cam.width, fh = (float)cam.height;
     m4_scale(1, 1, 1, m);
@@ -388,7 +388,7 @@ void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], u
     m4_scale(2.0f, 2.0f, 1.0f, s); m4_mul(s, m, m);
     m4_translate(-1.0f, -1.0f, 0.0f, s); m4_mul(s, m, m);
     m4_scale(1.0f, -1.0f, 1.0f, s); m4_mul(s, m, m);
-    float t = tanf(cam.fov / 2.0f);
+    float t = (proj && proj->type == 1u) ? 0.5f * proj->ortho_scale : tanf(cam.fov / 2.0f);  // (1: orthographic)
     if (cam.width > cam.height) m4_scale(t, t * fh / fw, 1.0f, s); else m4_scale(t * fw / fh, t, 1.0f, s);
     m4_mul(s, m, m);
     m4_translate(0.0f, 0.0f, -1.0f, s); m4_mul(s, m, m);

@@ -59,6 +59,33 @@ inline HostLens lens_from_values(float radius, float focal_distance) {
     if (radius > 0.0f) { l.radius = radius; l.focal_distance = focal_distance; }
     return l;
 }
+// The camera's projection (akr_projection_desc). type 0: the perspective camera, and the other fields at their defaults.
+struct HostProjection {
+    uint32_t type = 0;  // akr_projection_type
+    float ortho_scale = 1.0f;
+    float lon_min = -3.14159274f, lon_max = 3.14159274f, lat_min = -1.57079637f, lat_max = 1.57079637f;  // (the f32 nearest to pi, pi / 2)
+};
+// an akr_projection_desc checked (throws std::invalid_argument); the fields the type does not read come back at their defaults
+inline HostProjection projection_from_values(uint32_t type, float ortho_scale, float lon_min, float lon_max, float lat_min, float lat_max) {
+    HostProjection p;
+    if (type > 2u) throw std::invalid_argument("projection: unknown type (0 perspective, 1 orthographic, 2 panorama)");
+    p.type = type;
+    if (type == 1u) {
+        if (!std::isfinite(ortho_scale) || !(ortho_scale > 0.0f)) throw std::invalid_argument("projection: an orthographic camera needs a finite ortho_scale > 0");
+        p.ortho_scale = ortho_scale;
+    } else if (type == 2u) {
+        const HostProjection full;
+        if (!std::isfinite(lon_min) || !std::isfinite(lon_max) || !std::isfinite(lat_min) || !std::isfinite(lat_max))
+            throw std::invalid_argument("projection: a panorama's longitude and latitude bounds must be finite");
+        if (lon_min < full.lon_min || lon_max > full.lon_max || !(lon_min < lon_max))
+            throw std::invalid_argument("projection: a panorama needs -pi <= longitude_min < longitude_max <= pi");
+        if (lat_min < full.lat_min || lat_max > full.lat_max || !(lat_min < lat_max))
+            throw std::invalid_argument("projection: a panorama needs -pi/2 <= latitude_min < latitude_max <= pi/2");
+        p.lon_min = lon_min; p.lon_max = lon_max; p.lat_min = lat_min; p.lat_max = lat_max;
+    }
+    return p;
+}
+inline const char* projection_name(uint32_t type) { return type == 1u ? "an orthographic" : (type == 2u ? "a panorama" : "a perspective"); }
 // Owning copy of an akr_scene_desc.
 struct FlatScene {
     std::vector<HostMesh> meshes;
@@ -72,6 +99,7 @@ struct FlatScene {
     std::vector<akr_punctual_light_desc> punct;  // akr_scene_add_punctual_light / scene.json "lights": checked, as given (scene_punct.cpp; not part of akr_scene_desc)
     int light_tree = 0;  // akr_scene_set_light_tree, initially option `light_tree`: 1 = the point and spot lights are ONE entry of the light table, chosen among by a light tree
     HostLens lens;  // akr_scene_set_lens, or the file's focal_distance / fstop under option `lens` (not part of akr_scene_desc)
+    HostProjection projection;  // akr_scene_set_projection, or the file's camera type (not part of akr_scene_desc / akr_camera_desc)
     static FlatScene from_desc(const akr_scene_desc& d);
 };
 
@@ -168,12 +196,20 @@ inline float bvh_box_padding(const float lo[3], const float hi[3], const float* 
     const float diag = __builtin_sqrtf(diag2);
     return 4e-6f * (diag > reach ? diag : reach);
 }
-// Per axis, the largest |coordinate| of a ray origin on the lens disk: o = T + radius (a c2w[0..2] + b c2w[4..6]) with a^2 + b^2 <= 1
-// (device/dpath.h generate_ray_lens_from), over the camera's w.
-inline void lens_origin_bound(const float* c2w /* column-major 4x4 */, float radius, float out[3]) {
+// Per axis, the largest |coordinate| of a ray origin of the camera: o = T + (a c2w[0..2] + b c2w[4..6]) with (a, b) on the lens disk, a^2 + b^2 <=
+// radius^2 (device/dpath.h lens_ray_camera), plus -- an orthographic camera -- a point of the film rectangle |a| <= half_x, |b| <= half_y
+// (ortho_ray_camera; 0, 0 for the cameras whose origins are the camera position or the lens), over the camera's w.
+inline void lens_origin_bound(const float* c2w /* column-major 4x4 */, float radius, float half_x, float half_y, float out[3]) {
     const double w = std::fabs((double)c2w[15]) > 0.0 ? std::fabs((double)c2w[15]) : 1.0;
     for (int a = 0; a < 3; a++)
-        out[a] = (float)(((double)std::fabs(c2w[12 + a]) + (double)radius * std::sqrt((double)c2w[a] * c2w[a] + (double)c2w[4 + a] * c2w[4 + a])) / w * 1.000001);
+        out[a] = (float)(((double)std::fabs(c2w[12 + a]) + (double)radius * std::sqrt((double)c2w[a] * c2w[a] + (double)c2w[4 + a] * c2w[4 + a]) +
+                          (double)half_x * std::fabs((double)c2w[a]) + (double)half_y * std::fabs((double)c2w[4 + a])) / w * 1.000001);
+}
+// the half-extents of an orthographic camera's film in camera space: the larger image side spans ortho_scale (camera_matrices)
+inline void ortho_film_half_extents(float ortho_scale, uint32_t width, uint32_t height, float* half_x, float* half_y) {
+    const float t = 0.5f * ortho_scale, fw = (float)width, fh = (float)height;
+    *half_x = width > height ? t : t * fw / fh;
+    *half_y = width > height ? t * fh / fw : t;
 }
 
 // Conditioning of a triangle's (u, v) parametrisation. The inside test computes u = r0 . p + c0 with |r0| = |e2| / |n| (v likewise with
@@ -249,7 +285,8 @@ bool want_instancing(const FlatScene& flat, const TuningOptions& opt);
 struct InstXf;
 void compile_instanced_geometry(const FlatScene& flat, const TuningOptions& opt, const std::vector<InstXf>& xf, const std::vector<akr_material_desc>& descs, CompiledScene& out);
 // PerspectiveCameraData::new (camera/mod.rs:119-153)
-void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], uint32_t* c2w_identity);
+// proj: an orthographic camera's r2c has half its ortho_scale in the place of tan(fov / 2); nullptr or any other type = the perspective matrix
+void camera_matrices(const akr_camera_desc& cam, float r2c[16], float c2w[16], uint32_t* c2w_identity, const HostProjection* proj = nullptr);
 PcgStartConsts pcg_start_constants();
 
 // scene.json / method.json readers (host/scene_json.cpp); throw std::runtime_error on failure

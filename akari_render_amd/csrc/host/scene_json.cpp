@@ -576,12 +576,32 @@ FlatScene load_scene_json(const std::string& path, const TuningOptions& opt) {
     }
     if (!scene.has("camera")) throw std::runtime_error("scene has no camera");
     const JsonValue& cam = scene.at("camera");
-    if (cam.at("type").as_string() != "perspective") throw std::runtime_error("unsupported camera type");
+    const std::string cam_type = cam.at("type").as_string();
+    if (cam_type != "perspective" && cam_type != "orthographic" && cam_type != "panorama") throw std::runtime_error("unsupported camera type");
     const JsonValue& cd = cam.at("data");
     M4 c2w = load_transform(cd.at("transform"), true);
     std::memcpy(flat.camera.c2w, c2w.m, sizeof flat.camera.c2w);
     const float kPiF = 3.14159265358979323846f;
-    flat.camera.fov = cd.at("fov").as_f32() * (kPiF / 180.0f);  // f32::to_radians
+    if (cam_type == "perspective") {
+        flat.camera.fov = cd.at("fov").as_f32() * (kPiF / 180.0f);  // f32::to_radians
+    } else {
+        // The other projections (no reference counterpart). fov is optional and unread while the projection stays: what a later
+        // akr_scene_set_projection(perspective) renders with (Blender's default field of view when the file has none).
+        flat.camera.fov = (cd.has("fov") ? cd.at("fov").as_f32() : 39.6f) * (kPiF / 180.0f);
+        try {
+            const HostProjection full;
+            if (cam_type == "orthographic") {
+                if (!cd.has("ortho_scale")) throw std::runtime_error("an orthographic camera needs \"ortho_scale\"");
+                flat.projection = projection_from_values(1u, cd.at("ortho_scale").as_f32(), 0, 0, 0, 0);
+            } else {
+                auto opt_f = [&](const char* key, float dflt) { return cd.has(key) ? cd.at(key).as_f32() : dflt; };
+                flat.projection = projection_from_values(2u, 0, opt_f("longitude_min", full.lon_min), opt_f("longitude_max", full.lon_max), opt_f("latitude_min", full.lat_min),
+                                                         opt_f("latitude_max", full.lat_max));
+            }
+        } catch (const std::invalid_argument& e) {
+            throw std::runtime_error(std::string("camera: ") + e.what());
+        }
+    }
     flat.camera.width = (uint32_t)cd.at("sensor_width").as_number();
     flat.camera.height = (uint32_t)cd.at("sensor_height").as_number();
     // focal_distance / fstop: the reference turns them into lens_radius and focal_length of PerspectiveCameraData (load.rs:177-189) and its

@@ -242,7 +242,14 @@ struct PtParams {
     float lens_radius, lens_focal;
     // FEAT kernels alone read these: the accumulators (7 N floats, the film's layout) of the albedo and the shading-normal guide
     float *feat_albedo, *feat_normal;
+    // the camera's projection (dpath.h generate_ray_lens_from): PROJ_*; anything but PROJ_PERSPECTIVE = the session runs the LENS
+    // kernels, which alone read these. Orthographic needs its r2c only; the panorama's window folded by the host (camera_params).
+    uint32_t projection;
+    float pano_lon0, pano_dlon, pano_lat1, pano_dlat, pano_inv_w, pano_inv_h;
 };
+enum : uint32_t { PROJ_PERSPECTIVE = 0, PROJ_ORTHOGRAPHIC = 1, PROJ_PANORAMA = 2 };  // akr_projection_type
+// "this camera needs the LENS kernels": the one statement of it, for the router (pt_plan.cpp), the launchers with a [lens] table and the test hooks
+AKR_HD bool camera_runs_lens_kernels(float lens_radius, uint32_t projection) { return lens_radius > 0.0f || projection != PROJ_PERSPECTIVE; }
 
 // Which rank owns tile (tx, ty) of a frame shared by `count` ranks: its position on the Z-order (Morton) curve, modulo the ranks
 // ("tile t owned by GPU t mod G in Morton order"): 8 ranks each get one tile of every aligned 4 x 2 block of tiles, so every

@@ -225,7 +225,7 @@ __global__ void k_probe_camera_rays(const PtParams p, uint32_t n, const uint32_t
     if (i >= n) return;
     const float* ui = u + 4 * (size_t)i;
     vec3 o, d;
-    if (p.lens_radius > 0.0f) generate_ray_lens_from(p, pixels[2 * (size_t)i], pixels[2 * (size_t)i + 1], mk2(ui[0], ui[1]), mk2(ui[2], ui[3]), o, d);
+    if (camera_runs_lens_kernels(p.lens_radius, p.projection)) generate_ray_lens_from(p, pixels[2 * (size_t)i], pixels[2 * (size_t)i + 1], mk2(ui[0], ui[1]), mk2(ui[2], ui[3]), o, d);
     else generate_ray_from(p, pixels[2 * (size_t)i], pixels[2 * (size_t)i + 1], mk2(ui[0], ui[1]), o, d);
     float* r = out + 6 * (size_t)i;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;

@@ -191,12 +191,12 @@ __global__ __launch_bounds__(256, INST ? AKR_WF_TRACE_INST_WAVES : 1) void k_wf_
 // the translation unit that holds a session's kernels: k_wf_init by [lens], k_wf_shade by [env][lens]
 hipError_t launch_wf_init(const PtParams& p, const WfBuffers& wf, hipStream_t stream) {
     static constexpr hipError_t (*kEntry[2])(const PtParams&, const WfBuffers&, hipStream_t) = {launch_wf_init_t<false>, wf_init_entry_lens};
-    return kEntry[p.lens_radius > 0.0f](p, wf, stream);
+    return kEntry[camera_runs_lens_kernels(p.lens_radius, p.projection)](p, wf, stream);
 }
 hipError_t launch_wf_shade(const PtParams& p, const WfBuffers& wf, uint32_t q_out, hipStream_t stream) {
     static constexpr hipError_t (*kEntry[2][2])(const PtParams&, const WfBuffers&, uint32_t, hipStream_t) = {{launch_wf_shade_t<false, false>, wf_shade_entry_lens},
                                                                                                          {wf_shade_entry_env, wf_shade_entry_lens_env}};
-    return kEntry[p.sc.env != nullptr][p.lens_radius > 0.0f](p, wf, q_out, stream);
+    return kEntry[p.sc.env != nullptr][camera_runs_lens_kernels(p.lens_radius, p.projection)](p, wf, q_out, stream);
 }
 // The trace launch of a scene: its kernel (textures x kept or flattened), its parameter block and its dynamic LDS -- the traversal stacks, then
 // the graph-value slots of a scene with textures. One place, so that the occupancy query and the launch cannot name different kernels.

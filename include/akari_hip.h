@@ -367,6 +367,35 @@ typedef struct {
 AKR_API int32_t akr_scene_set_lens(akr_scene *scene, const akr_lens_desc *desc);
 /* The lens as the scene holds it; radius = focal_distance = 0 without one. */
 AKR_API int32_t akr_scene_get_lens(const akr_scene *scene, akr_lens_desc *out);
+/* Projection of the scene's camera (pt and aov integrators). The default is the perspective camera of akr_camera_desc, and a scene
+ * that never asks for another renders through the kernels, and to the bits, it did before projections existed.
+ *   ORTHOGRAPHIC  parallel rays along the camera's -z from the film rectangle in the camera's x / y plane; `ortho_scale` is the world-space
+ *                 length the LARGER image side spans (Blender's meaning). akr_camera_desc.fov is not read. A lens (akr_scene_set_lens) makes
+ *                 the plane `focal_distance` in front of the camera the sharp one.
+ *   PANORAMA      equirectangular: the film's columns are longitudes in [longitude_min, longitude_max], growing to the right, 0 = the
+ *                 camera's -z; its rows latitudes from latitude_max (row 0) down to latitude_min. The defaults are the full sphere -- the
+ *                 image akr_scene_set_environment consumes. A lens is refused with a panorama, whichever is set second.
+ * A projected session runs the kernels of the thin lens (akr_kernel_info.kernel_flags bit 5) and draws the lens's two sampler dimensions
+ * whether or not it has a lens. gpt, mcmc_opt and the relaxed arithmetic tier refuse a projected scene (AKR_ERR_UNSUPPORTED). Not part of
+ * akr_camera_desc / akr_scene_desc. */
+typedef enum { AKR_PROJECTION_PERSPECTIVE = 0, AKR_PROJECTION_ORTHOGRAPHIC = 1, AKR_PROJECTION_PANORAMA = 2 } akr_projection_type;
+typedef struct {
+    uint32_t type;          /* akr_projection_type */
+    float ortho_scale;      /* ORTHOGRAPHIC: > 0, world units */
+    float longitude_min;    /* PANORAMA: -pi <= longitude_min < longitude_max <= pi (the f32 nearest to pi, inclusive), radians */
+    float longitude_max;
+    float latitude_min;     /* PANORAMA: -pi/2 <= latitude_min < latitude_max <= pi/2, radians */
+    float latitude_max;
+} akr_projection_desc;
+/* type PERSPECTIVE, ortho_scale 1, the full sphere. */
+AKR_API int32_t akr_projection_desc_default(akr_projection_desc *desc);
+/* Sets the camera's projection (desc = NULL: perspective); the fields the type does not read are kept at their defaults. Refused while a session
+ * holds the scene; refused with AKR_ERR_INVALID_ARGUMENT for an unknown type, non-finite values, values outside the ranges above, a panorama on
+ * a camera with a lens, and an orthographic film so large that ray origins on it would leave the coordinate magnitude the scene's
+ * acceleration structure was padded for (akr_scene_set_resolution refuses a resolution for the same reason). A refused call changes nothing. */
+AKR_API int32_t akr_scene_set_projection(akr_scene *scene, const akr_projection_desc *desc);
+/* The projection as the scene holds it. */
+AKR_API int32_t akr_scene_get_projection(const akr_scene *scene, akr_projection_desc *out);
 /* The folded ggx_dielectric_s table in use (4096 floats), for comparison with a golden copy. */
 AKR_API int32_t akr_scene_get_ggx_table(const akr_scene *scene, float *dst4096);
 /* Host-side copy of the flattened description akr_scene_load produced (for loader tests):
@@ -528,7 +557,7 @@ typedef struct {
     uint32_t absent_mask;     /* lobes no material of the scene can have: 1 coat, 2 transmission, 4 normal map, 8 glass, 16 conductor */
     uint32_t min_waves;       /* waves per SIMD the kernel was compiled for */
     uint32_t vgprs, scratch_bytes;
-    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features), 7 samples punctual lights (the PUNCT kernels; akr_scene_add_punctual_light), 8 walks a light tree (akr_scene_set_light_tree) */
+    uint32_t kernel_flags;    /* the instantiation: bit 0 BVH intersector, 1 index-based sampler, 2 tables staged in LDS, 3 deferral, 4 relaxed arithmetic tier (option arith), 5 thin lens (the LENS kernels; akr_scene_set_lens, and every projection but the perspective one: akr_scene_set_projection), 6 collects the denoiser's guides (the FEAT kernels; akr_pt_begin_features), 7 samples punctual lights (the PUNCT kernels; akr_scene_add_punctual_light), 8 walks a light tree (akr_scene_set_light_tree) */
     uint32_t _pad;
     double compile_ms;        /* hiprtc compile at akr_pt_begin (0 on a cache hit) */
     double load_ms;           /* cache lookup + module load */
@@ -835,7 +864,9 @@ typedef enum {
     /* (21 stays unknown for the same reason) */
     AKR_STRUCT_DISPLAY_CONFIG = 22,
     /* (23 stays unknown for the same reason) */
-    AKR_STRUCT_PUNCTUAL_LIGHT_DESC = 24
+    AKR_STRUCT_PUNCTUAL_LIGHT_DESC = 24,
+    /* (25 stays unknown for the same reason) */
+    AKR_STRUCT_PROJECTION_DESC = 26
 } akr_struct_id;
 AKR_API uint32_t akr_struct_size(int32_t which);
 /* Process-wide tuning switches and test hooks (no reference counterpart). Each starts from its environment variable, read once;
