@@ -92,6 +92,11 @@ typedef struct or_scene_s {
     or_punctual_light_desc *punct_desc; /* as accepted (normalised); those that were "no light" are not among them */
     or_punct *punct[4];                 /* the folded records per colour pipeline (index = the OR_COLOR_* bits) */
     float lens_radius, lens_focal;      /* the thin lens; radius 0 = the pinhole */
+    /* the projection: as accepted, the fields its type does not read at their defaults; fov as the scene was made with;
+     * the panorama's six folded constants. An orthographic scene holds ITS raster -> camera matrix in r2c (or_projection_fold). */
+    or_projection_desc proj;
+    float fov;
+    float pano_lon0, pano_dlon, pano_lat1, pano_dlat, pano_inv_w, pano_inv_h;
     /* the light tree (or_lighttree.h). The mode; the nodes when a tree exists (mode 1 and >= 2 local lights), else NULL;
      * and, whatever the mode, per entry of the light list the index of its record in punct[] (OR_INVALID: the entry has none; 0 for the
      * tree's own entry): with a tree the local lights have left the list and a sun's record index is not its rank. */
@@ -528,19 +533,34 @@ static float or_estimate_power(const or_scene *sc, uint32_t inst_id, uint32_t tr
 }
 
 /* ---------------------------------- scene construction ------------------------------------------ */
-static void or_camera_setup(or_scene *sc, const or_camera_desc *c) { /* camera/mod.rs:119-153 */
+/* raster -> camera, camera/mod.rs:119-153, with t = tan(fov / 2); an orthographic camera hands in half its scale */
+static void or_raster_to_camera(uint32_t width, uint32_t height, float t, float *r2c) {
     float m[16], s[16];
-    float fw = (float)c->width, fh = (float)c->height;
+    float fw = (float)width, fh = (float)height;
     m4_scale(1, 1, 1, m);
     m4_scale(1.0f / fw, 1.0f / fh, 1.0f, s); m4_mul(s, m, m);
     m4_scale(2.0f, 2.0f, 1.0f, s); m4_mul(s, m, m);
     m4_translate(-1.0f, -1.0f, 0.0f, s); m4_mul(s, m, m);
     m4_scale(1.0f, -1.0f, 1.0f, s); m4_mul(s, m, m);
-    float t = tanf(c->fov / 2.0f);
-    if (c->width > c->height) m4_scale(t, t * fh / fw, 1.0f, s); else m4_scale(t * fw / fh, t, 1.0f, s);
+    if (width > height) m4_scale(t, t * fh / fw, 1.0f, s); else m4_scale(t * fw / fh, t, 1.0f, s);
     m4_mul(s, m, m);
     m4_translate(0.0f, 0.0f, -1.0f, s); m4_mul(s, m, m);
-    memcpy(sc->r2c, m, 64);
+    memcpy(r2c, m, 64);
+}
+/* The host's part of a projection (4.17 "Definition"), for the scene's present resolution: the matrix of the camera in use and a
+ * panorama's six constants, each rounded once. Runs whenever the projection or the resolution is set. */
+static void or_projection_fold(or_scene *sc) {
+    const or_projection_desc *p = &sc->proj;
+    or_raster_to_camera(sc->width, sc->height, p->type == OR_PROJECTION_ORTHOGRAPHIC ? 0.5f * p->ortho_scale : tanf(sc->fov / 2.0f), sc->r2c);
+    sc->pano_lon0 = p->longitude_min;
+    sc->pano_dlon = p->longitude_max - p->longitude_min;
+    sc->pano_lat1 = p->latitude_max;
+    sc->pano_dlat = p->latitude_max - p->latitude_min;
+    sc->pano_inv_w = 1.0f / (float)sc->width;
+    sc->pano_inv_h = 1.0f / (float)sc->height;
+}
+static const or_projection_desc OR_PROJECTION_DEFAULT = {OR_PROJECTION_PERSPECTIVE, 1.0f, -3.14159274f, 3.14159274f, -1.57079637f, 1.57079637f};
+static void or_camera_setup(or_scene *sc, const or_camera_desc *c) { /* camera/mod.rs:119-153 */
     memcpy(sc->c2w, c->c2w, 64);
     sc->c2w_identity = 1; /* glam abs_diff_eq(IDENTITY, 1e-4), geometry.rs:212-218 */
     for (int i = 0; i < 16; i++) {
@@ -548,6 +568,9 @@ static void or_camera_setup(or_scene *sc, const or_camera_desc *c) { /* camera/m
         if (!(fabsf(c->c2w[i] - id) <= 1e-4f)) sc->c2w_identity = 0;
     }
     sc->width = c->width; sc->height = c->height;
+    sc->fov = c->fov;
+    sc->proj = OR_PROJECTION_DEFAULT;
+    or_projection_fold(sc);
 }
 
 OR_EXPORT void or_scene_destroy(or_scene *sc);
@@ -790,18 +813,60 @@ static v2 or_filter_sample(const or_pt_config *cfg, v2 u) { /* film.rs:32-49 */
     v2 off = V2((r * cs) * sigma, (r * sn) * sigma);
     return V2(or_clamp(off.x, -width, width), or_clamp(off.y, -width, width));
 }
+/* Camera -> world of DESIGN.md 4.9 step 4 for a camera-space origin and direction: nothing under the c2w_identity shortcut, else the
+ * point formula for the origin (rotation columns and translation, over w) and the rotation for the direction, summed left to right. */
+static void or_camera_to_world(const or_scene *sc, v3 *o, v3 *d) {
+    if (sc->c2w_identity) return;
+    const float *c = sc->c2w;
+    const v3 p = *o, v = *d;
+    const float r0 = ((c[0] * p.x + c[4] * p.y) + c[8] * p.z) + c[12] * 1.0f;
+    const float r1 = ((c[1] * p.x + c[5] * p.y) + c[9] * p.z) + c[13] * 1.0f;
+    const float r2 = ((c[2] * p.x + c[6] * p.y) + c[10] * p.z) + c[14] * 1.0f;
+    const float r3 = ((c[3] * p.x + c[7] * p.y) + c[11] * p.z) + c[15] * 1.0f;
+    *o = v3divs(V3(r0, r1, r2), r3);
+    *d = V3((c[0] * v.x + c[4] * v.y) + c[8] * v.z, (c[1] * v.x + c[5] * v.y) + c[9] * v.z, (c[2] * v.x + c[6] * v.y) + c[10] * v.z);
+}
 /* The camera ray of a film sample for given numbers (camera/mod.rs:70-103; with a lens DESIGN.md 4.9 steps 2 - 5: u_lens -> the point l of
- * the lens disk, the pinhole direction's point on the plane of focus, the ray from l through it; the weight stays the filter's) */
+ * the lens disk, the pinhole direction's point on the plane of focus, the ray from l through it; the weight stays the filter's). The
+ * orthographic and the panorama camera restate DESIGN.md 4.17 "Definition"; the perspective arm is the text it was. */
 static or_ray or_camera_ray(const or_scene *sc, const or_pt_config *cfg, uint32_t px, uint32_t py, v2 u_filter, v2 u_lens) {
     v2 fpixel = V2((float)px + 0.5f, (float)py + 0.5f);
     v2 offset = or_filter_sample(cfg, u_filter);
     v2 pf = V2(fpixel.x + offset.x, fpixel.y + offset.y);
+    if (sc->proj.type == OR_PROJECTION_PANORAMA) {
+        /* longitude grows to the right from lon0, latitude falls from lat1 with the rows; a film point outside the film continues both */
+        const float lambda = sc->pano_lon0 + (pf.x * sc->pano_inv_w) * sc->pano_dlon;
+        const float phi = sc->pano_lat1 - (pf.y * sc->pano_inv_h) * sc->pano_dlat;
+        float sl, cl, sp, cp;
+        or_sincosf(lambda, &sl, &cl);
+        or_sincosf(phi, &sp, &cp);
+        v3 pd = v3normalize(V3(cp * sl, sp, -(cp * cl)));
+        v3 po = V3(0.0f, 0.0f, 0.0f);
+        or_camera_to_world(sc, &po, &pd);
+        or_ray pr = {po, pd, 0.0f, 1e20f, OR_INVALID, OR_INVALID, OR_INVALID, OR_INVALID};
+        return pr;
+    }
     const float *m = sc->r2c;
     /* r2c.transform_point((x,y,0)): M * (x,y,0,1), then / w */
     float qx = ((m[0] * pf.x + m[4] * pf.y) + m[8] * 0.0f) + m[12] * 1.0f;
     float qy = ((m[1] * pf.x + m[5] * pf.y) + m[9] * 0.0f) + m[13] * 1.0f;
     float qz = ((m[2] * pf.x + m[6] * pf.y) + m[10] * 0.0f) + m[14] * 1.0f;
     float qw = ((m[3] * pf.x + m[7] * pf.y) + m[11] * 0.0f) + m[15] * 1.0f;
+    if (sc->proj.type == OR_PROJECTION_ORTHOGRAPHIC) {
+        /* the film point itself is the origin, on the plane z = 0 of camera space; every ray looks along -z. A lens moves the origin over
+         * its disk and aims at the point the lens-less ray has on the plane z = -F, which therefore stays sharp */
+        const v3 s = v3divs(V3(qx, qy, qz), qw);
+        v3 oo = V3(s.x, s.y, 0.0f), od = V3(0.0f, 0.0f, -1.0f);
+        if (sc->lens_radius > 0.0f) {
+            const v2 ab = or_concentric_disk(u_lens);
+            const float lx = sc->lens_radius * ab.x, ly = sc->lens_radius * ab.y;
+            oo = V3(s.x + lx, s.y + ly, 0.0f);
+            od = v3normalize(V3(-lx, -ly, -sc->lens_focal));
+        }
+        or_camera_to_world(sc, &oo, &od);
+        or_ray rr = {oo, od, 0.0f, 1e20f, OR_INVALID, OR_INVALID, OR_INVALID, OR_INVALID};
+        return rr;
+    }
     v3 d = v3normalize(v3divs(V3(qx, qy, qz), qw));
     v3 o = V3(0, 0, 0);
     const float *c = sc->c2w;
@@ -828,10 +893,12 @@ static or_ray or_camera_ray(const or_scene *sc, const or_pt_config *cfg, uint32_
     or_ray r = {o, d, 0.0f, 1e20f, OR_INVALID, OR_INVALID, OR_INVALID, OR_INVALID};
     return r;
 }
-/* 4.9 step 1: the lens draws u_lens = next_2d right after the filter's next_2d; the pinhole draws nothing */
+/* 4.9 step 1: the lens draws u_lens = next_2d right after the filter's next_2d; the pinhole draws nothing. 4.17 "Sampler dimensions": a
+ * camera that is not the perspective one draws the pair whether or not it has a lens, and leaves it unused without one */
 static or_ray or_generate_ray(const or_scene *sc, const or_pt_config *cfg, uint32_t px, uint32_t py, or_sampler *smp) {
     const v2 u_filter = smp_2d(smp);
-    const v2 u_lens = sc->lens_radius > 0.0f ? smp_2d(smp) : V2(0.0f, 0.0f);
+    const int draws_lens = sc->lens_radius > 0.0f || sc->proj.type != OR_PROJECTION_PERSPECTIVE;
+    const v2 u_lens = draws_lens ? smp_2d(smp) : V2(0.0f, 0.0f);
     return or_camera_ray(sc, cfg, px, py, u_filter, u_lens);
 }
 
@@ -1452,6 +1519,7 @@ static int or_gpt_sources(int32_t cp, int32_t o, uint32_t r, uint32_t out[3]) {
 OR_EXPORT int or_gpt_render(const or_scene *sc, const or_gpt_config *g, float *film, float *aux, uint32_t n_threads) {
     if (sc->env) return -5; /* no environment in gpt (refused) */
     if (sc->n_punct || sc->lens_radius > 0.0f) return -5; /* nor a punctual light (4.14) or a lens (4.9) */
+    if (sc->proj.type != OR_PROJECTION_PERSPECTIVE) return -5; /* nor a projection (4.17): this integrator's rays are the pinhole's */
     ((or_scene *)sc)->color = g->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H, NG = (uint64_t)(W + 1) * (H + 1);
@@ -1686,6 +1754,7 @@ static or_mcmc_eval or_mcmc_evaluate(const or_scene *sc, const or_mcmc_config *c
 OR_EXPORT int or_mcmc_render(const or_scene *sc, const or_mcmc_config *c, float *film, double *result, uint32_t *chain_states, uint32_t n_threads) {
     if (sc->env) return -5; /* no environment in mcmc_opt (refused) */
     if (sc->n_punct || sc->lens_radius > 0.0f) return -5; /* nor a punctual light (4.14) or a lens (4.9) */
+    if (sc->proj.type != OR_PROJECTION_PERSPECTIVE) return -5; /* nor a projection (4.17): this integrator's rays are the pinhole's */
     ((or_scene *)sc)->color = c->color; /* the pipeline every material evaluation of this render sees */
     const uint32_t W = sc->width, H = sc->height;
     const uint64_t N = (uint64_t)W * H;
@@ -2158,12 +2227,48 @@ OR_EXPORT int or_scene_set_lens(or_scene *sc, const or_lens_desc *d) {
     if (d) {
         if (!or_isfinite(d->radius) || !or_isfinite(d->focal_distance) || d->radius < 0.0f || d->focal_distance < 0.0f) return -1;
         if (d->radius > 0.0f && !(d->focal_distance > 0.0f)) return -1;
+        if (d->radius > 0.0f && sc->proj.type == OR_PROJECTION_PANORAMA) return -1; /* 4.17: a panorama has no lens */
     }
     sc->lens_radius = (d && d->radius > 0.0f) ? d->radius : 0.0f;
     sc->lens_focal = (d && d->radius > 0.0f) ? d->focal_distance : 0.0f;
     return 0;
 }
 OR_EXPORT void or_scene_get_lens(const or_scene *sc, or_lens_desc *out) { out->radius = sc->lens_radius; out->focal_distance = sc->lens_focal; }
+/* Sets (NULL: back to the perspective camera) the camera's projection. Returns -1, and leaves the scene as it was, for what
+ * akr_scene_set_projection refuses on the values alone: an unknown type; an orthographic scale that is not finite and > 0; a panorama
+ * window with a non-finite bound, a bound outside [-pi, pi] x [-pi/2, pi/2] (the f32 nearest to them, inclusive) or min >= max; a panorama
+ * on a scene that has a lens. The fields a type does not read are kept at their defaults. (The library's further test of an orthographic
+ * film against the padding of its acceleration structure is the library's own concern, as for the lens.) */
+OR_EXPORT int or_scene_set_projection(or_scene *sc, const or_projection_desc *d) {
+    or_projection_desc p = OR_PROJECTION_DEFAULT;
+    if (d) {
+        if (d->type > OR_PROJECTION_PANORAMA) return -1;
+        p.type = d->type;
+        if (d->type == OR_PROJECTION_ORTHOGRAPHIC) {
+            if (!or_isfinite(d->ortho_scale) || !(d->ortho_scale > 0.0f)) return -1;
+            p.ortho_scale = d->ortho_scale;
+        } else if (d->type == OR_PROJECTION_PANORAMA) {
+            const float b[4] = {d->longitude_min, d->longitude_max, d->latitude_min, d->latitude_max};
+            for (int i = 0; i < 4; i++) if (!or_isfinite(b[i])) return -1;
+            if (b[0] < p.longitude_min || b[1] > p.longitude_max || !(b[0] < b[1])) return -1;
+            if (b[2] < p.latitude_min || b[3] > p.latitude_max || !(b[2] < b[3])) return -1;
+            if (sc->lens_radius > 0.0f) return -1;
+            p.longitude_min = b[0]; p.longitude_max = b[1]; p.latitude_min = b[2]; p.latitude_max = b[3];
+        }
+    }
+    sc->proj = p;
+    or_projection_fold(sc);
+    return 0;
+}
+OR_EXPORT void or_scene_get_projection(const or_scene *sc, or_projection_desc *out) { *out = sc->proj; }
+/* The film's size; the camera's matrix and a panorama's constants follow it (4.17: the fold is per resolution). -1 for an empty film. */
+OR_EXPORT int or_scene_set_resolution(or_scene *sc, uint32_t width, uint32_t height) {
+    if (!width || !height) return -1;
+    sc->width = width; sc->height = height;
+    or_projection_fold(sc);
+    return 0;
+}
+OR_EXPORT uint32_t or_sizeof_projection_desc(void) { return (uint32_t)sizeof(or_projection_desc); }
 /* Known-answer call with the rows of akr_host_lens_ray: pixels2 = x, y; u4 = u_filter, u_lens -> out6 = o, d */
 OR_EXPORT int or_lens_ray_many(const or_scene *sc, uint32_t filter_type, float filter_radius, uint32_t n, const uint32_t *pixels2, const float *u4, float *out6) {
     if (filter_type > OR_FILTER_GAUSSIAN) return -1;

@@ -109,6 +109,11 @@ typedef struct {
 /* The camera's thin lens: layout-identical to akr_lens_desc. radius = 0: a pinhole. */
 typedef struct { float radius, focal_distance; } or_lens_desc;
 
+/* The camera's projection: layout-identical to akr_projection_desc (24 bytes). PERSPECTIVE reads none of the fields,
+ * ORTHOGRAPHIC ortho_scale (the world-space length the larger image side spans), PANORAMA the window in radians (default: the sphere). */
+enum { OR_PROJECTION_PERSPECTIVE = 0, OR_PROJECTION_ORTHOGRAPHIC = 1, OR_PROJECTION_PANORAMA = 2 };
+typedef struct { uint32_t type; float ortho_scale, longitude_min, longitude_max, latitude_min, latitude_max; } or_projection_desc;
+
 enum { OR_FILTER_BOX = 0, OR_FILTER_GAUSSIAN = 1 };
 enum { OR_SAMPLER_INDEPENDENT = 0 };
 typedef struct {

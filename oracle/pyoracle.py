@@ -138,13 +138,20 @@ def lib() -> C.CDLL:
     L.or_scene_set_lens.restype = i32
     L.or_scene_set_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
     L.or_scene_get_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
+    L.or_scene_set_projection.restype = i32
+    L.or_scene_set_projection.argtypes = [vp, C.POINTER(abi.ProjectionDesc)]
+    L.or_scene_get_projection.argtypes = [vp, C.POINTER(abi.ProjectionDesc)]
+    L.or_scene_set_resolution.restype = i32
+    L.or_scene_set_resolution.argtypes = [vp, u32, u32]
     L.or_lens_ray_many.restype = i32
     L.or_lens_ray_many.argtypes = [vp, u32, f32, u32, up, fp, fp]
     for n in ("or_sizeof_material", "or_sizeof_config", "or_sizeof_scene_desc", "or_sizeof_aov_config", "or_sizeof_environment_desc",
-              "or_sizeof_punctual_light_desc", "or_sizeof_lens_desc", "or_sizeof_punct_record", "or_sizeof_light_tree_node"):
+              "or_sizeof_punctual_light_desc", "or_sizeof_lens_desc", "or_sizeof_punct_record", "or_sizeof_light_tree_node",
+              "or_sizeof_projection_desc"):
         getattr(L, n).restype = u32
     assert L.or_sizeof_punctual_light_desc() == C.sizeof(abi.PunctualLightDesc) == 60
     assert L.or_sizeof_lens_desc() == C.sizeof(abi.LensDesc) == 8
+    assert L.or_sizeof_projection_desc() == C.sizeof(abi.ProjectionDesc) == 24
     assert L.or_sizeof_punct_record() == 64
     assert L.or_sizeof_light_tree_node() == 32
     assert L.or_sizeof_environment_desc() == C.sizeof(abi.EnvironmentDesc)
@@ -162,13 +169,15 @@ def _fp(a):
 
 class OracleScene:
     def __init__(self, scene: abi.SceneData, bvh: bool = False, share_plane_rows: bool = True, lights: bool = True, lens: bool = True,
-                 light_tree: bool = False):
+                 light_tree: bool = False, projection: bool = True):
         """bvh: build the oracle-side hierarchy (or_accel.h; same hits as the exhaustive loop, checked in
         tests/test_oracle_accel.py) -- for the 1 M / 10 M-triangle configurations. share_plane_rows = False: every triangle
         keeps the plane row of its own vertices (the records as they were before the coplanar-neighbour rule).
         The scene's environment, punctual lights (scene.lights) and lens (scene.lens) are set as capi.Scene sets them; lights = False /
         lens = False leaves the punctual lights / the lens out: the oracle of the same scene without them. light_tree: the scene's mode of
-        DESIGN.md 4.16 (a SceneData carries none: on the library's side it is the option or the setter)."""
+        DESIGN.md 4.16 (a SceneData carries none: on the library's side it is the option or the setter). projection: the scene's projection
+        (scene.projection) is set, before the lens as capi.Scene does; projection = False is the same scene through the
+        perspective camera."""
         self.data = scene
         desc, self._keep = scene.to_desc()
         self._desc = desc
@@ -185,6 +194,8 @@ class OracleScene:
             self.set_environment(scene.environment)
         if lights and getattr(scene, "lights", None):
             self.set_punctual_lights(scene.lights)
+        if projection and getattr(scene, "projection", None) is not None:
+            self.set_projection(scene.projection)
         if lens and getattr(scene, "lens", None) is not None:
             self.set_lens(scene.lens.radius, scene.lens.focal_distance)
 
@@ -278,6 +289,31 @@ class OracleScene:
         d = abi.LensDesc()
         lib().or_scene_get_lens(self.h, C.byref(d))
         return abi.LensData(float(d.radius), float(d.focal_distance)) if d.radius > 0.0 else None
+
+    def set_projection(self, projection=None, **kw) -> None:
+        """or_scene_set_projection, with capi.Scene.set_projection's arguments: None = perspective; an abi.ProjectionData; or a
+        type by number or name with the fields as keywords. What the library would refuse raises ValueError and changes nothing."""
+        if projection is None:
+            rc = lib().or_scene_set_projection(self.h, None)
+        else:
+            if not isinstance(projection, abi.ProjectionData):
+                names = {"perspective": abi.PROJECTION_PERSPECTIVE, "orthographic": abi.PROJECTION_ORTHOGRAPHIC, "panorama": abi.PROJECTION_PANORAMA}
+                projection = abi.ProjectionData(type=names.get(projection, projection), **kw)
+            d = projection.to_desc()
+            rc = lib().or_scene_set_projection(self.h, C.byref(d))
+        if rc != 0:
+            raise ValueError("or_scene_set_projection refused the projection")
+
+    def projection(self) -> abi.ProjectionData:
+        d = abi.ProjectionDesc()
+        lib().or_scene_get_projection(self.h, C.byref(d))
+        return abi.ProjectionData.from_desc(d)
+
+    def set_resolution(self, width: int, height: int) -> None:
+        """The film's size; the projection's host fold is redone for it."""
+        if lib().or_scene_set_resolution(self.h, int(width), int(height)) != 0:
+            raise ValueError("or_scene_set_resolution refused the size")
+        self.width, self.height = int(width), int(height)
 
     def lens_ray_many(self, pixels, u_filter, u_lens, filter_type: int = 0, filter_radius: float = 0.5) -> np.ndarray:
         """or_lens_ray_many: the camera rays (n, 6) = o, d of (n, 2) pixels for given u_filter, u_lens, the rows of akr_host_lens_ray."""
@@ -403,7 +439,7 @@ class OracleScene:
         film = np.zeros(7 * n, dtype=np.float32)
         aux = np.zeros(3 * n + 6 * ng, dtype=np.float32)
         rc = lib().or_gpt_render(self.h, C.byref(cfg), _fp(film), _fp(aux), n_threads if n_threads > 0 else (os.cpu_count() or 1))
-        assert rc == 0, f"or_gpt_render rejected the configuration or the scene ({rc}; -5: an environment, a punctual light or a lens)"
+        assert rc == 0, f"or_gpt_render rejected the configuration or the scene ({rc}; -5: an environment, a punctual light, a lens or a projection)"
         if cfg.reconstruction == 0:
             return film, None
         return film, (aux[:3 * n].reshape(h, w, 3), aux[3 * n:3 * n + 3 * ng].reshape(h + 1, w + 1, 3), aux[3 * n + 3 * ng:].reshape(h + 1, w + 1, 3))

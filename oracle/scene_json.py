@@ -649,10 +649,22 @@ def load_scene(path: str, width: int = 0, height: int = 0, lens: bool = False, p
             )
         )
     cam = scene["camera"]
-    assert cam["type"] == "perspective"
+    if cam["type"] not in ("perspective", "orthographic", "panorama"):
+        raise ValueError("unsupported camera type")
     cd = cam["data"]
     c2w = load_transform(cd["transform"], True)
-    fov = f32(cd["fov"]) * (f32(math.pi) / f32(180.0))  # f32::to_radians = x * (PI / 180.0f32)
+    # the other projections (DESIGN.md 4.17 "Interface"): fov is optional for them, 39.6 degrees when absent
+    fov_deg = cd["fov"] if cam["type"] == "perspective" else cd.get("fov", 39.6)
+    fov = f32(fov_deg) * (f32(math.pi) / f32(180.0))  # f32::to_radians = x * (PI / 180.0f32)
+    projection = None
+    if cam["type"] == "orthographic":
+        if "ortho_scale" not in cd:
+            raise ValueError("an orthographic camera needs \"ortho_scale\"")
+        projection = abi.ProjectionData(type=abi.PROJECTION_ORTHOGRAPHIC, ortho_scale=float(f32(cd["ortho_scale"])))
+    elif cam["type"] == "panorama":
+        projection = abi.ProjectionData(type=abi.PROJECTION_PANORAMA, **{k: float(f32(cd[k])) for k in ("longitude_min", "longitude_max", "latitude_min", "latitude_max") if k in cd})
+    if projection is not None:
+        _check_projection(projection)
     camera = CameraData(
         c2w=_col_major(c2w),
         fov=float(fov),
@@ -661,6 +673,7 @@ def load_scene(path: str, width: int = 0, height: int = 0, lens: bool = False, p
     )
     env = _load_environment(scene["environment"], bufs) if scene.get("environment") is not None else None
     sd = SceneData(meshes, instances, materials, camera, None, inst_ids, mat_ids, images, environment=env)
+    sd.projection = projection
     if punctual_lights and scene.get("lights") is not None:
         sd.lights = _load_lights(scene["lights"], soft_lights)
     if lens and "focal_distance" in cd and "fstop" in cd:
@@ -670,6 +683,23 @@ def load_scene(path: str, width: int = 0, height: int = 0, lens: bool = False, p
         if float(radius) > 0.0:
             sd.lens = abi.LensData(float(radius), float(fd))
     return sd
+
+
+def _check_projection(p) -> None:
+    """What the C reader refuses as a parse error: an orthographic scale that is not finite and > 0; a panorama window with a
+    non-finite bound, a bound outside [-pi, pi] x [-pi/2, pi/2] (the f32 nearest to them, inclusive) or min >= max."""
+    full = abi.ProjectionData()
+    if p.type == abi.PROJECTION_ORTHOGRAPHIC:
+        if not (math.isfinite(p.ortho_scale) and p.ortho_scale > 0.0):
+            raise ValueError("an orthographic camera needs a finite ortho_scale > 0")
+        return
+    b = (p.longitude_min, p.longitude_max, p.latitude_min, p.latitude_max)
+    if not all(math.isfinite(x) for x in b):
+        raise ValueError("a panorama's longitude and latitude bounds must be finite")
+    if b[0] < full.longitude_min or b[1] > full.longitude_max or not b[0] < b[1]:
+        raise ValueError("a panorama needs -pi <= longitude_min < longitude_max <= pi")
+    if b[2] < full.latitude_min or b[3] > full.latitude_max or not b[2] < b[3]:
+        raise ValueError("a panorama needs -pi/2 <= latitude_min < latitude_max <= pi/2")
 
 
 def _load_lights(lj: dict, soft: bool) -> list:

@@ -1,7 +1,8 @@
 """Camera projections on the GPU (through the LENS kernels): the device's camera rays against the host's, a panorama of an
 environment is that environment texel for texel, a panorama sees behind the camera, the orthographic closed form with and without a lens, one
-film under every route, aov and the collected guides, the refusals, and akari-cli --projection. The oracle has no projections: bit-identities,
-the restated definition (tests/camera_model.py, tests/test_projection.py) and closed forms are what pins them."""
+film under every route, aov and the collected guides, the refusals, and akari-cli --projection. These are bit-identities, the restated definition
+(tests/camera_model.py, tests/test_projection.py) and closed forms; the comparison with the CPU oracle's own projections, film for film, is
+tests/test_gpu_projection_parity.py."""
 import json
 import subprocess
 
