@@ -51,10 +51,10 @@ def one_metal() -> abi.SceneData:
     return sd
 
 
-def textured_many_graphs(n_extra=120) -> abi.SceneData:
-    """the textured room with a tree, plus `n_extra` copies of its normal-mapped wall material on copies of that wall: more node lists
-    than the BVH kernels stage"""
-    sd = textured_room(32, 32, n_floor=8)
+def textured_many_graphs(n_extra=120, sd=None) -> abi.SceneData:
+    """the textured room with a tree (or `sd`, a textured room of another size), plus `n_extra` copies of its normal-mapped wall material on
+    copies of that wall: more node lists than the BVH kernels stage"""
+    sd = sd if sd is not None else textured_room(32, 32, n_floor=8)
     wall = sd.instances[2]
     for k in range(n_extra):
         sd.materials.append(copy.deepcopy(sd.materials[wall.materials[0]]))

@@ -193,12 +193,14 @@ def _accepts(sd, opts, cfg, stage):
     return (not stage) or plan["variant"]["stage"] == 1
 
 
-def largest_count(make_scene, opts, cfg, stage, lo=1, hi=4096):
-    """the largest number of grid lights for which _accepts holds (it is monotone in the count: the tables only grow), by bisection on the host"""
-    assert _accepts(make_scene(lo), opts, cfg, stage) and not _accepts(make_scene(hi), opts, cfg, stage)
+def largest_count(make_scene, opts, cfg, stage, lo=1, hi=4096, accepts=None):
+    """the largest number of grid lights for which _accepts holds (it is monotone in the count: the tables only grow), by bisection on the host;
+    accepts: another question of the same signature (tests/unit_sweep_cases.py: a session that collects guides stages less)"""
+    ok = accepts or _accepts
+    assert ok(make_scene(lo), opts, cfg, stage) and not ok(make_scene(hi), opts, cfg, stage)
     while hi - lo > 1:
         mid = (lo + hi) // 2
-        if _accepts(make_scene(mid), opts, cfg, stage):
+        if ok(make_scene(mid), opts, cfg, stage):
             lo = mid
         else:
             hi = mid

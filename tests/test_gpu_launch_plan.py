@@ -4,8 +4,9 @@ environment, kept through a lens, kept with both, and a textured scene with a pe
 guides, of punctual lights and of the light tree: tests/test_gpu_pt_features.py, test_gpu_punct_parity.py, test_gpu_light_tree.py.) Every session renders 32 x 32 at 4 spp; akr_pt_kernel_info's kernel_flags and `specialised` equal what
 akr_host_pt_launch_plan predicts for the same scene, config and options on a host-only scene (tests/test_launch_plan.py holds those
 predictions to the recorded decisions), and the film is the CPU oracle's bit for bit. The sessions through a lens are held bit for bit to the same scene rendered by the
-other kind's lens unit (flattened against kept), as tests/test_gpu_lens.py does; the oracle's own lens holds them in
-tests/test_gpu_punct_parity.py (test_lens, test_lens_kept_scene_kernels)."""
+other kind's lens unit (flattened against kept), as tests/test_gpu_lens.py does, and both to the oracle's lens. This file holds one instantiation
+of each unit; every one of the 432 is swept against the oracle elsewhere: the 240 plain, kept and FEAT kernels in tests/test_gpu_unit_sweep.py,
+the 96 PUNCT kernels in tests/test_gpu_punct_parity.py, the 96 light-tree kernels in tests/test_gpu_light_tree_parity.py."""
 import os
 
 import numpy as np
@@ -91,13 +92,16 @@ def test_textured_per_scene_kernel(ctx, root):
 
 @pytest.mark.parametrize("env", [False, True], ids=["lens", "lens_env"])
 def test_lens_flattened_and_kept(ctx, root, env):
-    """the units plain + LENS / plain + ENV + LENS against kept + LENS / kept + ENV + LENS, and the lens does reach the film"""
+    """the units plain + LENS / plain + ENV + LENS against kept + LENS / kept + ENV + LENS and both against the oracle, and the lens does reach the film"""
     sd, cfg = _two_instances(root, env=env, lens=True), make_config(**CFG)
     flat, fst, fv = _session(ctx, sd, cfg, FLAT)
     kept, kst, kv = _session(ctx, sd, cfg, KEPT)
     assert (fv["inst"], fv["env"], fv["lens"]) == (0, int(env), 1) and (kv["inst"], kv["env"], kv["lens"]) == (1, int(env), 1)
     assert n_bit_diff(flat, kept) == 0, f"{n_bit_diff(flat, kept)} of {flat.size} film floats differ"
     assert all(fst[k] == kst[k] for k in ("n_samples", "n_closest", "n_shadow", "n_shaded"))
+    o, ost = pyoracle.OracleScene(sd).render(cfg)
+    assert_parity(flat, o, sd.camera.width, sd.camera.height, fst, ost)
+    assert_parity(kept, o, sd.camera.width, sd.camera.height, kst, ost)
     sd.lens = None
     pin, _, _ = _session(ctx, sd, cfg, FLAT)
     assert n_bit_diff(pin, flat) > 0
