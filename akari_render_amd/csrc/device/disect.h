@@ -163,7 +163,9 @@ AKR_D bool trace_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmin, float 
 // once after the walk. Operations whose result nothing reads are left out (profiles/walk_unread_ops.md): the closest-hit ray's margin has
 // no tmax - t where no alpha test reads the margin (t < best_t says it), the shadow ray's range term min(t, stmax - t) is computed with
 // its plane solve, not per record, and the best hit is chosen by one test and two selects. Two records per trip on alternating register
-// sets: a one-record software prefetch without the moves that rotating a single set costs.
+// sets: a one-record software prefetch without the moves that rotating a single set costs. In the walk without an alpha test a trip's
+// bookkeeping is shared by its two records (WalkOpt PLANE_LT, PLANE_EXCL below): one comparison per excluded id, and one t < best_t where
+// the records share a plane -- 6 v_cmp and 5 v_cndmask per trip for 10 and 6.
 // Five other forms were measured and retired (records through the scalar cache, both rays packed into v_pk_fma_f32 with and
 // without op_sel broadcast, lockstep pairs of coplanar records); this one was +4.2 % on C2 and +3.3 % on C3 over the next best:
 // HISTORY.md, profiles/r4_ab_walk.txt. The arithmetic (operation order, fma placement) is tri_plane / tri_uv / hit_margin's.
@@ -193,6 +195,10 @@ AKR_D float max3_abs_raw(float a, float b, float c) {
     asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// A truth value per lane as a mask in a scalar register pair, and back: Boolean algebra written on such masks stays on the scalar unit
+// (lanes that are switched off read as 0)
+AKR_D uint64_t lanes_of(bool c) { return __builtin_amdgcn_ballot_w64(c); }
+AKR_D bool in_lanes(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 // tri_plane with the division's range-scaling steps left out (dmath.h div_f_unscaled), and the smallest |numerator| seen so far in `lo`
 AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
     float dz = __builtin_fmaf(r2.x, d.x, __builtin_fmaf(r2.y, d.y, r2.z * d.z));
@@ -206,7 +212,8 @@ AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
     return h;
 }
 
-// A shortcut of the pair walk, bit-neutral, switched per instantiation of the walk (what it buys where: profiles/walk_div_mask_ab.md).
+// The shortcuts of the pair walk, all bit-neutral, switched per instantiation of the walk (what UNSCALED_DIV buys where:
+// profiles/walk_div_mask_ab.md).
 //
 // UNSCALED_DIV -- speculate and validate. The plane solves use div_f_unscaled (8 instructions for the compiler's 12; dmath.h says on which
 // set S of operands it is the contract's quotient). Whether a solve's operands are in S is not tested per solve -- a compare and a branch
@@ -239,9 +246,35 @@ AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
 // accept a record. The callers pass 1e20, -1 or a light sample's distance, which is finite by construction: dpath.h sample_direct.)
 // (Measured with it and retired: the excluded ids as bit masks, v_bfe_i32 + v_or on the margin's bits per ray and record in place of the
 // comparisons below -- the compiler already folds the three comparisons into three v_cmp and one v_cndmask; -1.7 % on C2, same file.)
-template <bool DIV>
+//
+// PLANE_LT, PLANE_EXCL -- the bookkeeping of a two-record trip once per trip, not once per record (profiles/walk_plane_bookkeeping.md;
+// what each buys: profiles/walk_plane_bookkeeping_ab.md). Both apply to the two-record trips of the walk without an alpha test only; the
+// odd last record, the alpha walks and walk_ieee keep the per-record code. The arithmetic -- the solves, (u, v), the margins -- is the
+// per-record code's, operation for operation; only Boolean combinations of its comparisons change, and those are written as lane masks
+// (lanes_of / in_lanes) so that they run on the scalar unit.
+//   PLANE_LT    A trip whose second record takes the plane of its first (plane_share_mask bit k + 1 set): both records see the same T and
+//               the same best_t on entry, b0. With A, B = "margin >= 0 and not excluded" of the first and the second record, the per-record
+//               code computes better_a = A & (T < b0), then better_b = B & (T < b1) with b1 = better_a ? T : b0. Where better_a holds, b1 = T
+//               and T < T is false; elsewhere b1 = b0. So better_b = B & !better_a & (T < b0): one comparison lt = (T < b0) serves both
+//               records, and best_t = ((A | B) & lt) ? T : b0 is one select. (A NaN T makes lt false, as it made both comparisons.) The id is
+//               selected for the second record first and for the first one over it: k wins over k + 1, the lowest-id rule among equal t.
+//               A trip whose second record solves a plane of its own chooses the first record per record, before that solve, and runs the
+//               same text with A = 0 (nothing left to choose for the first record): one more select there, and one text for the compiler.
+//   PLANE_EXCL  Per excluded id e (ex0, sex0, sex1), once per walk: q = e | 1 and the lane mask H = "e is odd". Every trip starts at an even
+//               k (the loop steps by two from 0), so e is k or k + 1 exactly if q == k + 1 -- one comparison E -- and then the first record
+//               is the excluded one where E & !H, the second where E & H. kInvalid | 1 = 0xffffffff equals no k + 1 <= 64. Three comparisons
+//               per trip for six, whether the two records share a plane or not.
+#ifndef AKR_WALK_PLANE_LT
+#define AKR_WALK_PLANE_LT 1  // (0 / 1 from the command line: an A/B build of one part, akari_render_amd/build.py build_variant)
+#endif
+#ifndef AKR_WALK_PLANE_EXCL
+#define AKR_WALK_PLANE_EXCL 1
+#endif
+template <bool DIV, bool LT = DIV && AKR_WALK_PLANE_LT, bool EXCL = DIV && AKR_WALK_PLANE_EXCL>
 struct WalkOpt {
     static constexpr bool unscaled_div = DIV;
+    static constexpr bool plane_lt = LT;
+    static constexpr bool plane_excl = EXCL;
 };
 template <int V>
 struct IntTag {
@@ -268,25 +301,33 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     v2f hx2 = {0.0f, 0.0f}, hy2 = {0.0f, 0.0f}, hz2 = {0.0f, 0.0f};
     float lo = __builtin_inff(), slo = __builtin_inff();  // UNSCALED: the smallest |oz| of the walk, per ray
     // alpha_tag: 0 = no alpha test, 1 = alpha test, 2 = has_alpha decides at run time; div_tag: the plane solves use div_f_unscaled
-    auto record = [&](auto alpha_tag, auto div_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
-        constexpr int ALPHA = decltype(alpha_tag)::value;
+    auto solve = [&](auto div_tag, const v4f& q2) {
         constexpr bool FAST = decltype(div_tag)::value;
-        if (!((sc.plane_share_mask >> k) & 1ull)) {  // wave-uniform: one plane solve per ray per coplanar pair of records
-            const float4 r2 = make_float4(q2.x, q2.y, q2.z, q2.w);
-            const PlaneHit a = FAST ? tri_plane_unscaled(o, d, r2, lo) : tri_plane(o, d, r2), b = FAST ? tri_plane_unscaled(so, sd, r2, slo) : tri_plane(so, sd, r2);
-            T = a.t;
-            srange = min_raw(b.t, stmax - b.t);
-            hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
-        }
+        const float4 r2 = make_float4(q2.x, q2.y, q2.z, q2.w);
+        const PlaneHit a = FAST ? tri_plane_unscaled(o, d, r2, lo) : tri_plane(o, d, r2), b = FAST ? tri_plane_unscaled(so, sd, r2, slo) : tri_plane(so, sd, r2);
+        T = a.t;
+        srange = min_raw(b.t, stmax - b.t);
+        hx2 = (v2f){a.px, b.px}; hy2 = (v2f){a.py, b.py}; hz2 = (v2f){a.pz, b.pz};
+    };
+    // the margins of one record against the current plane's solves, before the exclusions: m the closest-hit ray's, sm the shadow ray's
+    auto margins = [&](auto alpha_tag, const v4f& q0, const v4f& q1, v2f& u2, v2f& v2, float& m, float& sm) {
+        constexpr int ALPHA = decltype(alpha_tag)::value;
         float u, v, su, sv;
         tri_uv(PlaneHit{T, hx2.x, hy2.x, hz2.x}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), u, v);
         tri_uv(PlaneHit{0.0f, hx2.y, hy2.y, hz2.y}, make_float4(q0.x, q0.y, q0.z, q0.w), make_float4(q1.x, q1.y, q1.z, q1.w), su, sv);
-        const v2f u2 = {u, su}, v2 = {v, sv};
+        u2 = (v2f){u, su}; v2 = (v2f){v, sv};
         // hit_margin per ray: min(min(min(u, v), 1 - (u + v)), range), with the range terms described above the WalkOpt struct
         const v2f s2 = {1.0f - (u2.x + v2.x), 1.0f - (u2.y + v2.y)};
         const float range = ALPHA == 0 ? T : min_raw(T, tmax - T);
-        float m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), range);
-        float sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), srange);
+        m = min_raw(min_raw(min_raw(u2.x, v2.x), s2.x), range);
+        sm = min_raw(min_raw(min_raw(u2.y, v2.y), s2.y), srange);
+    };
+    auto record = [&](auto alpha_tag, auto div_tag, uint32_t k, const v4f& q0, const v4f& q1, const v4f& q2) {
+        constexpr int ALPHA = decltype(alpha_tag)::value;
+        if (!((sc.plane_share_mask >> k) & 1ull)) solve(div_tag, q2);  // wave-uniform: one plane solve per ray per coplanar pair of records
+        v2f u2, v2;
+        float m, sm;
+        margins(alpha_tag, q0, q1, u2, v2, m, sm);
         m = (k == ex0) ? -1.0f : m;
         sm = (k == sex0) ? -1.0f : sm;
         sm = (k == sex1) ? -1.0f : sm;
@@ -312,13 +353,71 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
     // cycles of 240 -- to merge the two values of the margins behind the branch.
     auto walk = [&](auto alpha_tag) {
         const BoolTag<UNSCALED> div_tag{};
+        // the plane-wise bookkeeping (WalkOpt PLANE_LT, PLANE_EXCL): only in the walk without an alpha test
+        constexpr bool PLANE_LT = OPT::plane_lt && decltype(alpha_tag)::value == 0, PLANE_EXCL = OPT::plane_excl && decltype(alpha_tag)::value == 0;
         v4f a0 = lrec[0], a1 = lrec[1], a2 = lrec[2], b0, b1, b2;
         uint32_t k = 0;
-        for (; k + 1 < n; k += 2) {
-            b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
-            record(alpha_tag, div_tag, k, a0, a1, a2);
-            a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
-            record(alpha_tag, div_tag, k + 1, b0, b1, b2);
+        if (PLANE_LT || PLANE_EXCL) {
+            // One body for every trip (a second copy of the trip for the pairs alone made the register allocator keep the plane's
+            // solves twice and spill). Truth values are lane masks in scalar registers, written as such (lanes_of / in_lanes): left as
+            // bools, the compiler turns part of the mask algebra into 0 / 1 VGPRs with a select and a comparison each.
+            const uint32_t qex0 = ex0 | 1u, qsex0 = sex0 | 1u, qsex1 = sex1 | 1u;                                           // the trip an excluded id falls into ...
+            const uint64_t hex0 = lanes_of((ex0 & 1u) != 0), hsex0 = lanes_of((sex0 & 1u) != 0), hsex1 = lanes_of((sex1 & 1u) != 0);  // ... and the half of it
+            auto choose = [&](uint64_t acc, uint32_t id) {  // the per-record choice: record()'s
+                const uint64_t better = acc & lanes_of(T < best_t);
+                best_t = in_lanes(better) ? T : best_t;
+                best = in_lanes(better) ? id : best;
+            };
+            for (; k + 1 < n; k += 2) {
+                b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
+                const uint32_t k1 = k + 1;
+                const bool own_b = !((sc.plane_share_mask >> k1) & 1ull);  // wave-uniform: the second record solves a plane of its own
+                uint64_t xa, xb, sxa, sxb;  // the lanes whose closest-hit ray excludes the first / the second record; whose shadow ray does
+                if (PLANE_EXCL) {  // (k is even in every trip, whether the records share a plane or not)
+                    const uint64_t e = lanes_of(qex0 == k1), s0 = lanes_of(qsex0 == k1), s1 = lanes_of(qsex1 == k1);
+                    xa = e & ~hex0; xb = e & hex0;
+                    sxa = (s0 & ~hsex0) | (s1 & ~hsex1); sxb = (s0 & hsex0) | (s1 & hsex1);
+                } else {
+                    xa = lanes_of(k == ex0); xb = lanes_of(k1 == ex0);
+                    sxa = lanes_of(k == sex0) | lanes_of(k == sex1); sxb = lanes_of(k1 == sex0) | lanes_of(k1 == sex1);
+                }
+                v2f u2, v2;
+                float ma, sma, mb, smb;
+                if (!((sc.plane_share_mask >> k) & 1ull)) solve(div_tag, a2);
+                margins(alpha_tag, a0, a1, u2, v2, ma, sma);
+                sma = in_lanes(sxa) ? -1.0f : sma;
+                uint64_t acc_a = lanes_of(ma >= 0.0f) & ~xa;
+                a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
+                if (!PLANE_LT) choose(acc_a, k);
+                if (own_b) {
+                    if (PLANE_LT) {  // the first record is chosen on its own T, before the second one's solve overwrites it, and is settled
+                        choose(acc_a, k);
+                        acc_a = 0;
+                    }
+                    solve(div_tag, b2);
+                }
+                margins(alpha_tag, b0, b1, u2, v2, mb, smb);
+                smb = in_lanes(sxb) ? -1.0f : smb;
+                const uint64_t acc_b = lanes_of(mb >= 0.0f) & ~xb;
+                if (PLANE_LT) {
+                    // both records on one T and one best_t (or the first one settled: acc_a = 0): one comparison, one select of best_t -- the
+                    // identity above the WalkOpt struct. One text for both kinds of trip: two made the compiler carry T < best_t into them as a 0 / 1 VGPR.
+                    const uint64_t lt = lanes_of(T < best_t);
+                    best_t = in_lanes((acc_a | acc_b) & lt) ? T : best_t;
+                    best = in_lanes(acc_b & lt) ? k1 : best;
+                    best = in_lanes(acc_a & lt) ? k : best;
+                } else {
+                    choose(acc_b, k1);
+                }
+                occ_margin = max_raw(max_raw(occ_margin, sma), smb);
+            }
+        } else {
+            for (; k + 1 < n; k += 2) {
+                b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
+                record(alpha_tag, div_tag, k, a0, a1, a2);
+                a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
+                record(alpha_tag, div_tag, k + 1, b0, b1, b2);
+            }
         }
         if (k < n) record(alpha_tag, div_tag, k, a0, a1, a2);
     };

@@ -36,6 +36,8 @@ namespace akr {
 // The pair walk's shortcut (disect.h WalkOpt: division without range scaling) per exhaustive instantiation. On for the kernels of scenes
 // without textures (C2 +0.6 ... +1.4 %, C3 +1.3 ... +2.1 %, the reference's default configuration +3.1 %), off for those with: the textured
 // room's interpreter kernel measured 878 -> 869 Msamples/s with it, three alternating runs, the parent's spread 1.7 (profiles/walk_div_mask_ab.md).
+// The walk's bookkeeping per trip (WalkOpt PLANE_LT, PLANE_EXCL) goes with it: measured on the untextured kernels only
+// (profiles/walk_plane_bookkeeping_ab.md), so the textured ones keep the per-record code.
 template <bool TEX>
 using PairWalkOpt = WalkOpt<!TEX>;
 // (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_layout)
