@@ -426,14 +426,14 @@ AKR_D float pdf_direct(const DScene& sc, const SurfacePoint& si, uint32_t gid, v
 // (PtParams.stage_total != 0); the per-triangle records stay in HBM. Must be called by every thread of the workgroup.
 template <bool BVH, bool TEX = false, bool GGX = false>
 AKR_D void stage_scene_tables(const PtParams& p, uint32_t* lds, PtParams& staged) {
-    const void* src[13] = {p.sc.shade,      p.sc.normals, p.sc.inst,      p.sc.materials, p.sc.light_alias, p.sc.area_alias,
-                           p.sc.lights,     p.sc.light_pdf, p.sc.area_pdf, p.sc.tex.nodes, p.sc.tex.images, p.sc.tex.mat_inputs,
-                           p.sc.ggx_table};
-    uint32_t* dst[13];
+    const void* src[ST_COUNT] = {p.sc.shade,      p.sc.normals, p.sc.inst,      p.sc.materials, p.sc.light_alias, p.sc.area_alias,  // (StageTable's order: kernels.h)
+                                 p.sc.lights,     p.sc.light_pdf, p.sc.area_pdf, p.sc.tex.nodes, p.sc.tex.images, p.sc.tex.mat_inputs,
+                                 p.sc.ggx_table};
+    uint32_t* dst[ST_COUNT];
     uint32_t off = BVH ? p.sc.bvh_stack_depth * 256u : 0u;  // in words, behind the stacks
 #pragma unroll
-    for (int e = BVH ? 2 : 0; e < 13; e++) {
-        if ((e >= 9 && e < 12 && !TEX) || (e == 12 && !GGX)) continue;
+    for (int e = BVH ? ST_INST : ST_SHADE; e < ST_COUNT; e++) {
+        if ((e >= ST_TEX_NODES && e <= ST_MAT_INPUTS && !TEX) || (e == ST_GGX && !GGX)) continue;
         const uint32_t n = p.stage_bytes[e] >> 2;
         const uint32_t* g = (const uint32_t*)src[e];
         uint32_t* l = lds + off;
@@ -443,16 +443,16 @@ AKR_D void stage_scene_tables(const PtParams& p, uint32_t* lds, PtParams& staged
     }
     __syncthreads();
     if (!BVH) {
-        staged.sc.shade = (const float4*)dst[0];
-        staged.sc.normals = (const float4*)dst[1];  // non-null even without normals: only gates reading the flags in shade row 7
+        staged.sc.shade = (const float4*)dst[ST_SHADE];
+        staged.sc.normals = (const float4*)dst[ST_NORMALS];  // non-null even without normals: only gates reading the flags in shade row 7
     }
-    staged.sc.inst = (const float4*)dst[2];
-    staged.sc.materials = (const DMaterial*)dst[3];
-    staged.sc.light_alias = (const AliasPacked*)dst[4];
-    staged.sc.area_alias = (const AliasPacked*)dst[5];
-    staged.sc.lights = (const LightRec*)dst[6];
-    staged.sc.light_pdf = (const float*)dst[7];
-    staged.sc.area_pdf = (const float*)dst[8];
+    staged.sc.inst = (const float4*)dst[ST_INST];
+    staged.sc.materials = (const DMaterial*)dst[ST_MATERIALS];
+    staged.sc.light_alias = (const AliasPacked*)dst[ST_LIGHT_ALIAS];
+    staged.sc.area_alias = (const AliasPacked*)dst[ST_AREA_ALIAS];
+    staged.sc.lights = (const LightRec*)dst[ST_LIGHTS];
+    staged.sc.light_pdf = (const float*)dst[ST_LIGHT_PDF];
+    staged.sc.area_pdf = (const float*)dst[ST_AREA_PDF];
     // Texture-fed materials: a textured hit walks its node list (32 B per node), reads image headers and the raw input record
     // in dependent chains; from LDS each link is a ds_read instead of an L1 / L2 round trip. Texels stay in HBM.
     // The host stages either all of it or nothing (api_pt.cpp fill_params, scene_build.cpp), so a TEX kernel that stages at all
@@ -460,12 +460,12 @@ AKR_D void stage_scene_tables(const PtParams& p, uint32_t* lds, PtParams& staged
     // The 16 KB albedo table of the specular layer / coat (three to five trilinear lookups of 8 gathers each per shaded vertex),
     // for the kernels of scenes with textures, whose L1 is busy with texels: textured room 822 -> 861 Msamples/s. The plain
     // full-graph kernel is better off with the table in L1 (C3: 1887 with, 1851 without L1 -- LDS bank conflicts of the random
-    // gathers). The host leaves stage_bytes[12] at 0 when the workgroup's LDS budget is spent; the table then stays where it is.
-    if (GGX && p.stage_bytes[12] != 0) staged.sc.ggx_table = (const float*)dst[12];
+    // gathers). The host leaves stage_bytes[ST_GGX] at 0 when the workgroup's LDS budget is spent; the table then stays where it is.
+    if (GGX && p.stage_bytes[ST_GGX] != 0) staged.sc.ggx_table = (const float*)dst[ST_GGX];
     if (TEX) {
-        staged.sc.tex.nodes = (const DNode*)dst[9];
-        staged.sc.tex.images = (const DImage*)dst[10];
-        staged.sc.tex.mat_inputs = (const MatInputs*)dst[11];
+        staged.sc.tex.nodes = (const DNode*)dst[ST_TEX_NODES];
+        staged.sc.tex.images = (const DImage*)dst[ST_TEX_IMAGES];
+        staged.sc.tex.mat_inputs = (const MatInputs*)dst[ST_MAT_INPUTS];
     }
 }
 

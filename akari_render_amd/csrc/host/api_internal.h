@@ -103,11 +103,12 @@ struct DevBuf {
         HIP_CHECK(hipMalloc(&p, n));
         bytes = n;
     }
-    template <typename T>
-    void upload(const std::vector<T>& v) {
-        alloc(v.size() * sizeof(T));
-        if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    void upload(const void* src, size_t n) {
+        alloc(n);
+        if (n) HIP_CHECK(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
     }
+    template <typename T>
+    void upload(const std::vector<T>& v) { upload(v.data(), v.size() * sizeof(T)); }
     template <typename T>
     T* as() const { return (T*)p; }
 };
@@ -190,18 +191,23 @@ struct akr_scene {
     akr_context* ctx = nullptr;
     FlatScene flat;
     CompiledScene cs;
-    DevBuf light_alias, area_alias, lights;
-    DevBuf woop, tri_gid, shade, normals, inst, materials, ggx_table, light_entries, light_pdf, light_inst, light_tri_offset,
-        light_n_tris, area_entries, area_pdf, inst_tri_offset, bvh_nodes, tex_nodes, tex_images, tex_texels, tex_mat_inputs;
-    DevBuf in2_tlas_leaves, in2_mesh_tris, in2_mesh_pos, in2_mesh_meta, in2_mesh_normals, in2_inst_mats, in2_share_bits;  // meshes + instances (scene_inst.cpp)
-    DevBuf env_texels, env_marginal, env_conditional, env_rec;  // the environment light (scene_env.cpp; DScene.env points at env_rec)
-    DevBuf punct;  // the punctual lights' records under the default colour pipeline (scene_punct.cpp; DScene.punct)
+    // the device tables: one row of api_scene.cpp kSceneTables per member (what it holds, when it exists, which pointer of DScene finds it) ...
+    DevBuf woop, tri_gid, shade, normals, inst, materials, area_entries, area_pdf, inst_tri_offset, bvh_nodes;
+    DevBuf in2_tlas_leaves, in2_mesh_tris, in2_mesh_pos, in2_mesh_meta, in2_mesh_normals, in2_inst_mats;
+    DevBuf tex_nodes, tex_images, tex_texels, tex_mat_inputs;
+    DevBuf light_entries, light_pdf, light_inst, light_tri_offset, light_n_tris, punct, light_alias, area_alias, lights, env_texels, env_marginal, env_conditional, env_rec;
+    DevBuf ggx_table, in2_share_bits;  // ... but these two, which the device fills (api_scene.cpp ensure_ggx_table, scene_finish)
     std::atomic<int> sessions{0};  // pt / aov / gpt / mcmc_opt sessions that hold the scene (akr_scene_set_environment and the punctual lights' setters are refused meanwhile)
     std::vector<float> ggx_host;
-    // materials / node lists / raw inputs re-compiled for a non-default colour pipeline (akr_pt_config.color), by pipeline
+    // materials / node lists / raw inputs re-compiled for a non-default colour pipeline (akr_pt_config.color), by pipeline (api_pt.cpp color_set makes them)
     struct ColorSet {
         DevBuf materials, tex_nodes, mat_inputs;
         DevBuf punct;  // the punctual lights' records: their colour goes through the pipeline on the host, as an Emission material's
+        void apply(const CompiledScene& cs, DScene& d) const {  // the tables of a parameter block's scene that this pipeline replaces
+            d.materials = materials.as<DMaterial>();
+            if (cs.has_textures) d.tex.nodes = tex_nodes.as<DNode>(), d.tex.mat_inputs = mat_inputs.as<MatInputs>();
+            if (!cs.punct.empty()) d.punct = punct.as<DPunct>();
+        }
     };
     std::map<uint32_t, std::unique_ptr<ColorSet>> color_sets;
     std::mutex color_sets_mutex;  // sessions of several host threads may begin on one scene; entries are never removed before the scene dies
@@ -235,7 +241,7 @@ struct RenderBase {
     DevBuf owned_tiles;        // shard_count > 1: PtParams.owned_tiles
     uint32_t spp_done = 0, n_launches = 0;
     uint32_t pmj_spp = 1;  // the spp the pmj02bn sampler stratifies for (the method's total spp)
-    const akr_scene::ColorSet* color_set = nullptr;  // the scene's tables for cfg.color != 0 (looked up under the scene's lock by base_begin)
+    const akr_scene::ColorSet* color_set = nullptr;  // the scene's tables for cfg.color != 0 (api_pt.cpp color_set, under the scene's lock)
     // the process-wide tuning options as they were when the session began (base_begin; akr_pt_begin_features: before its refusals): the one
     // state every decision of the session's life is made from -- an akr_option_set on another thread cannot give a session two
     TuningOptions opt;
@@ -277,7 +283,7 @@ struct RenderBase {
 struct PtPlan {
     PtVariant v;
     uint32_t simple_scene, defer_metal, defer_flags;  // PtParams' fields of these names
-    uint32_t stage_bytes[13], stage_total, tex_slots;
+    uint32_t stage_bytes[ST_COUNT], stage_total, tex_slots;
     bool cost_order;  // the session's megakernel launches may deal their items by measured pixel cost (PtRoute::record_costs)
 };
 // What kind of session akr_pt_begin / akr_pt_begin_features make of (scene, config, options): the ONE place that decides it (pt_plan.cpp pt_route).

@@ -46,15 +46,7 @@ void akr_api::session_params(RenderBase* se, const PtPlan* pt) {
     p.counters = se->counters.as<uint64_t>();
     p.color = c.color;
     p.sc.tex.color = c.color;
-    if (c.color != 0) {  // the material tables of this pipeline (created by akr_pt_begin)
-        const auto& set = *se->color_set;
-        p.sc.materials = set.materials.as<DMaterial>();
-        if (s->cs.has_textures) {
-            p.sc.tex.nodes = set.tex_nodes.as<DNode>();
-            p.sc.tex.mat_inputs = set.mat_inputs.as<MatInputs>();
-        }
-        if (!s->cs.punct.empty()) p.sc.punct = set.punct.as<DPunct>();
-    }
+    if (c.color != 0) se->color_set->apply(s->cs, p.sc);  // the tables of this pipeline (color_set)
     p.sampler = c.sampler_type;
     if (c.sampler_type == AKR_SAMPLER_PMJ02BN || c.sampler_type == AKR_SAMPLER_SOBOL) {  // Pmj02BnSamplerCreator::new (sampler/mod.rs:376-395)
         p.smp_seed = (uint32_t)c.sampler_seed;
@@ -177,6 +169,35 @@ AKR_API int32_t akr_pt_config_from_json(const char* text, akr_pt_config* cfg, ch
 }
 
 }  // extern "C"
+// The scene's tables under the colour pipeline `color` != 0 (akr_scene::ColorSet), under the scene's lock from the lookup to the answer: made by the first
+// session of that pipeline, the punctual lights' records again after the lights changed (api_scene.cpp punctual_lights_changed drops them). The pointer is
+// stable: the map owns the set through a unique_ptr and never removes it.
+static const akr_scene::ColorSet* color_set(akr_scene* scene, uint32_t color) {
+    std::lock_guard<std::mutex> lock(scene->color_sets_mutex);
+    auto it = scene->color_sets.find(color);
+    if (it == scene->color_sets.end()) {
+        // ColorPipeline other than sRGB / sRGB: the scene's constants were folded for the default pipeline; fold them again
+        // for this one (svm/texture/mod.rs:9-43 at every Rgb / spectral_uplift node)
+        CompiledScene tmp;
+        tmp.images = scene->cs.images;
+        std::vector<akr_material_desc> descs;
+        compile_materials(scene->flat, color, tmp, descs);
+        auto set = std::make_unique<akr_scene::ColorSet>();
+        set->materials.upload(tmp.materials);
+        if (tmp.has_textures) {
+            set->tex_nodes.upload(tmp.tex_nodes);
+            set->mat_inputs.upload(tmp.mat_inputs);
+        }
+        it = scene->color_sets.emplace(color, std::move(set)).first;
+    }
+    akr_scene::ColorSet& set = *it->second;
+    if (!scene->cs.punct.empty() && !set.punct.p) {
+        std::vector<DPunct> recs;
+        for (const akr_punctual_light_desc& d : scene->flat.punct) recs.push_back(fold_punctual(d, color));
+        set.punct.upload(punctual_device_records(recs, scene->cs.punct_tree));  // (the tree's nodes are the same in every set)
+    }
+    return &set;
+}
 // The aov / gpt / mcmc_opt integrators begin here as well, for sampler states, counters and the kernel parameter block, but launch their own
 // kernels, which interpret shader graphs. They hold a RenderBase and not a pt session, so a per-scene kernel's block cannot reach them.
 void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, const akr_pt_config* cfg, akr_film* film, const TuningOptions* opt) {
@@ -191,29 +212,7 @@ void akr_api::base_begin(RenderBase* se, akr_context* ctx, akr_scene* scene, con
     se->scene = scene;
     se->film = film;
     se->cfg = *cfg;
-    std::unique_lock<std::mutex> color_lock(scene->color_sets_mutex);
-    if (cfg->color != 0 && !scene->color_sets.count(cfg->color)) {
-        // ColorPipeline other than sRGB / sRGB: the scene's constants were folded for the default pipeline; fold them again
-        // for this one (svm/texture/mod.rs:9-43 at every Rgb / spectral_uplift node) and keep the tables with the scene
-        CompiledScene tmp;
-        tmp.images = scene->cs.images;
-        std::vector<akr_material_desc> descs;
-        compile_materials(scene->flat, cfg->color, tmp, descs);
-        auto set = std::make_unique<akr_scene::ColorSet>();
-        set->materials.upload(tmp.materials);
-        if (tmp.has_textures) {
-            set->tex_nodes.upload(tmp.tex_nodes);
-            set->mat_inputs.upload(tmp.mat_inputs);
-        }
-        scene->color_sets[cfg->color] = std::move(set);
-    }
-    if (cfg->color != 0 && !scene->cs.punct.empty() && !scene->color_sets.at(cfg->color)->punct.p) {  // (dropped when the lights change: api_scene.cpp)
-        std::vector<DPunct> recs;
-        for (const akr_punctual_light_desc& d : scene->flat.punct) recs.push_back(fold_punctual(d, cfg->color));
-        scene->color_sets.at(cfg->color)->punct.upload(punctual_device_records(recs, scene->cs.punct_tree));  // (the tree's nodes are the same in every set)
-    }
-    if (cfg->color != 0) se->color_set = scene->color_sets.at(cfg->color).get();  // stable: the map owns it through a unique_ptr
-    color_lock.unlock();
+    if (cfg->color != 0) se->color_set = color_set(scene, cfg->color);
     const uint64_t n = (uint64_t)film->width * film->height;
     // init_pcg32_buffer_with_seed (sampler/mod.rs:148-160): host StdRng(seed) u64 per pixel, device new_seq_offset
     if (cfg->sampler_type == AKR_SAMPLER_PMJ02BN || cfg->sampler_type == AKR_SAMPLER_SOBOL) {

@@ -60,80 +60,155 @@ void akr_api::packed_light_tables(const CompiledScene& cs, std::vector<AliasPack
         lr.push_back(LightRec{cs.light_tri_offset[l], cs.light_n_tris[l], cs.inst_tri_offset[cs.light_inst[l]], cs.light_inst[l]});
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------------ a scene's device tables
+// ONE list, kSceneTables: upload, release, both byte counts and akr_scene_get_array walk it, so a new table is one row, plus its
+// field of DScene if a kernel reads it. Beside the list, as code of their own: the GGX table (ensure_ggx_table), the kept scenes' share bits (a kernel
+// fills them: scene_finish) and the walk-bound word in woop's padding.
+struct Bytes { const void* p; size_t n; };
+template <typename T>
+static Bytes bytes_of(const std::vector<T>& v) { return {v.data(), v.size() * sizeof(T)}; }
+// the tables the device reads in a form of its own, packed when a walk's first row asks: the light tables and the environment's so that each level of
+// sampling is ONE gather (device/dgeom.h, dscene.h), the punctual lights' records with the tree's nodes behind them
+struct Packed {
+    bool made = false;
+    std::vector<AliasPacked> light_alias, area_alias, env_marginal, env_conditional;
+    std::vector<LightRec> lights;
+    std::vector<DPunct> punct;
+    DEnv env;
+    Packed& of(const CompiledScene& cs) {
+        if (made) return *this;
+        made = true;
+        packed_light_tables(cs, light_alias, area_alias, lights);
+        punct = punctual_device_records(cs.punct, cs.punct_tree);
+        if (cs.env.on) {
+            pack_alias(cs.env.marginal_entries, cs.env.marginal_pdf, 0, cs.env.h, env_marginal);
+            for (uint32_t y = 0; y < cs.env.h; y++)  // (j is relative to the row)
+                pack_alias(cs.env.conditional_entries, cs.env.conditional_pdf, (size_t)y * cs.env.w, cs.env.w, env_conditional);
+        }
+        return *this;
+    }
+};
+// DScene.env's record: the environment's three tables where the rows before this one put them (null in a host-only scene), and how to read them
+static Bytes env_record(const akr_scene& s, Packed& pk) {
+    const CompiledScene& cs = s.cs;
+    DEnv& rec = pk.env;
+    std::memset(&rec, 0, sizeof rec);
+    rec.texels = s.env_texels.as<float4>();
+    rec.marginal = s.env_marginal.as<AliasPacked>();
+    rec.conditional = s.env_conditional.as<AliasPacked>();
+    for (int k = 0; k < 9; k++) rec.rot[k] = cs.env.rot_t[k];
+    rec.w = cs.env.w;
+    rec.h = cs.env.h;
+    rec.filter = cs.env.filter;
+    rec.light = cs.n_lights - 1;
+    return {&rec, cs.env.on ? sizeof rec : 0u};
+}
+enum When { ALWAYS, TEXTURED, KEPT, ENV };
+static bool exists(When w, const CompiledScene& cs) { return w == ALWAYS || (w == TEXTURED && cs.has_textures) || (w == KEPT && cs.instanced.on) || (w == ENV && cs.env.on); }
+enum Part {
+    GEOM,    // uploaded once, by scene_finish
+    LIGHT,   // a light table: uploaded again when the environment or the punctual lights change (upload_lights)
+    PACKED,  // ... whose bytes are Packed's: they live as long as the walk that asked, so no AKR_ARRAY_* id may show them (akr_scene_get_array skips the row)
+    SHOWN    // no table: host bytes the device reads only inside a packed one -- a row for akr_scene_get_array alone (no buf, `when` and `bind` unread)
+};
+constexpr int NO_ID = -1;
+struct SceneTable {
+    int array;                                     // the AKR_ARRAY_* id that shows the host bytes, or NO_ID
+    Bytes (*src)(const akr_scene& s, Packed& pk);  // the host bytes
+    DevBuf akr_scene::*buf = nullptr;              // owns the table
+    Part part = SHOWN;
+    When when = ALWAYS;                            // it exists
+    void (*bind)(DScene& d, void* p) = nullptr;    // the pointer the kernels find it by; null: no field of DScene
+};
+#define SRC(v) [](const akr_scene& s, Packed& pk) -> Bytes { (void)s, (void)pk; return bytes_of(v); }
+#define TO(field) [](DScene& d, void* p) { d.field = (decltype(d.field))p; }
+static const SceneTable kSceneTables[] = {  // in the order of upload
+    {AKR_ARRAY_WOOP, SRC(s.cs.woop), &akr_scene::woop, GEOM, ALWAYS, TO(woop)},
+    {AKR_ARRAY_TRI_GID, SRC(s.cs.tri_gid), &akr_scene::tri_gid, GEOM, ALWAYS, TO(tri_gid)},
+    {AKR_ARRAY_SHADE, SRC(s.cs.shade), &akr_scene::shade, GEOM, ALWAYS, TO(shade)},
+    {NO_ID, SRC(s.cs.normals), &akr_scene::normals, GEOM, ALWAYS, TO(normals)},
+    {AKR_ARRAY_INSTANCES, SRC(s.cs.inst), &akr_scene::inst, GEOM, ALWAYS, TO(inst)},
+    {AKR_ARRAY_MATERIALS, SRC(s.cs.materials), &akr_scene::materials, GEOM, ALWAYS, TO(materials)},
+    {AKR_ARRAY_AREA_ENTRIES, SRC(s.cs.area_entries), &akr_scene::area_entries, GEOM, ALWAYS, TO(area_entries)},
+    {AKR_ARRAY_AREA_PDF, SRC(s.cs.area_pdf), &akr_scene::area_pdf, GEOM, ALWAYS, TO(area_pdf)},
+    {AKR_ARRAY_INST_TRI_OFFSET, SRC(s.cs.inst_tri_offset), &akr_scene::inst_tri_offset, GEOM, ALWAYS, TO(inst_tri_offset)},
+    // (a kept scene has no flattened tree, a flattened one no instanced vectors: compile_scene returns from compile_instanced_geometry before it builds one)
+    {AKR_ARRAY_BVH_NODES, SRC(s.cs.instanced.on ? s.cs.instanced.nodes : s.cs.bvh_nodes), &akr_scene::bvh_nodes, GEOM, ALWAYS, TO(bvh_nodes)},
+    {AKR_ARRAY_INST_LEAVES, SRC(s.cs.instanced.tlas_leaves), &akr_scene::in2_tlas_leaves, GEOM, KEPT, TO(in2.tlas_leaves)},  // meshes + instances (scene_inst.cpp)
+    {AKR_ARRAY_MESH_TRIS, SRC(s.cs.instanced.mesh_tris), &akr_scene::in2_mesh_tris, GEOM, KEPT, TO(in2.mesh_tris)},
+    {AKR_ARRAY_MESH_POS, SRC(s.cs.instanced.mesh_pos), &akr_scene::in2_mesh_pos, GEOM, KEPT, TO(in2.mesh_pos)},
+    {AKR_ARRAY_MESH_META, SRC(s.cs.instanced.mesh_meta), &akr_scene::in2_mesh_meta, GEOM, KEPT, TO(in2.mesh_meta)},
+    {AKR_ARRAY_MESH_NORMALS, SRC(s.cs.instanced.mesh_normals), &akr_scene::in2_mesh_normals, GEOM, KEPT, TO(in2.mesh_normals)},
+    {NO_ID, SRC(s.cs.instanced.inst_mats), &akr_scene::in2_inst_mats, GEOM, KEPT, TO(in2.inst_mats)},
+    {AKR_ARRAY_TEX_NODES, SRC(s.cs.tex_nodes), &akr_scene::tex_nodes, GEOM, TEXTURED, TO(tex.nodes)},
+    {AKR_ARRAY_TEX_IMAGES, SRC(s.cs.images), &akr_scene::tex_images, GEOM, TEXTURED, TO(tex.images)},
+    {AKR_ARRAY_TEX_TEXELS, SRC(s.cs.texels), &akr_scene::tex_texels, GEOM, TEXTURED, TO(tex.texels)},
+    {AKR_ARRAY_MAT_INPUTS, SRC(s.cs.mat_inputs), &akr_scene::tex_mat_inputs, GEOM, TEXTURED, TO(tex.mat_inputs)},
+    {AKR_ARRAY_LIGHT_ENTRIES, SRC(s.cs.light_entries), &akr_scene::light_entries, LIGHT, ALWAYS, TO(light_entries)},
+    {AKR_ARRAY_LIGHT_PDF, SRC(s.cs.light_pdf), &akr_scene::light_pdf, LIGHT, ALWAYS, TO(light_pdf)},
+    {NO_ID, SRC(s.cs.light_inst), &akr_scene::light_inst, LIGHT, ALWAYS, TO(light_inst)},
+    {NO_ID, SRC(s.cs.light_tri_offset), &akr_scene::light_tri_offset, LIGHT, ALWAYS, TO(light_tri_offset)},
+    {NO_ID, SRC(s.cs.light_n_tris), &akr_scene::light_n_tris, LIGHT, ALWAYS},  // (no reader: DScene.env took its field)
+    {NO_ID, SRC(pk.of(s.cs).punct), &akr_scene::punct, PACKED, ALWAYS, TO(punct)},  // under the default colour pipeline (the others': api_pt.cpp color_set)
+    {NO_ID, SRC(pk.of(s.cs).light_alias), &akr_scene::light_alias, PACKED, ALWAYS, TO(light_alias)},
+    {NO_ID, SRC(pk.of(s.cs).area_alias), &akr_scene::area_alias, PACKED, ALWAYS, TO(area_alias)},
+    {NO_ID, SRC(pk.of(s.cs).lights), &akr_scene::lights, PACKED, ALWAYS, TO(lights)},
+    {AKR_ARRAY_ENV_TEXELS, SRC(s.cs.env.texels), &akr_scene::env_texels, LIGHT, ENV},  // the environment light (scene_env.cpp): found through env_rec
+    {NO_ID, SRC(pk.of(s.cs).env_marginal), &akr_scene::env_marginal, PACKED, ENV},
+    {NO_ID, SRC(pk.of(s.cs).env_conditional), &akr_scene::env_conditional, PACKED, ENV},
+    {NO_ID, env_record, &akr_scene::env_rec, PACKED, ENV, TO(env)},
+    // what the packed tables above were packed from
+    {AKR_ARRAY_ENV_MARGINAL_ENTRIES, SRC(s.cs.env.marginal_entries)},
+    {AKR_ARRAY_ENV_MARGINAL_PDF, SRC(s.cs.env.marginal_pdf)},
+    {AKR_ARRAY_ENV_CONDITIONAL_ENTRIES, SRC(s.cs.env.conditional_entries)},
+    {AKR_ARRAY_ENV_CONDITIONAL_PDF, SRC(s.cs.env.conditional_pdf)},
+    {AKR_ARRAY_PUNCTUAL_LIGHTS, SRC(s.cs.punct)},
+    {AKR_ARRAY_LIGHT_TREE, SRC(s.cs.punct_tree)},
+};
+#undef SRC
+#undef TO
+// the light rows or the others: on the device, their pointers in s->dscene; a table that does not exist (any more) released, its pointer null
+static void upload_tables(akr_scene* s, bool lights) {
+    Packed pk;
+    for (const SceneTable& t : kSceneTables) {
+        if (t.part == SHOWN || (t.part == GEOM) == lights) continue;
+        DevBuf& b = s->*t.buf;
+        const Bytes src = exists(t.when, s->cs) ? t.src(*s, pk) : Bytes{nullptr, 0};
+        b.upload(src.p, src.n);
+        if (t.bind) t.bind(s->dscene, b.p);
+    }
+}
 // the light tables (and the environment's record and tables, and the punctual lights' records) on the device, and their pointers in s->dscene: at scene
 // creation and after akr_scene_set_environment / akr_scene_add_punctual_light / akr_scene_clear_punctual_lights
 static void upload_lights(akr_scene* s) {
     const CompiledScene& cs = s->cs;
-    s->light_entries.upload(cs.light_entries);
-    s->light_pdf.upload(cs.light_pdf);
-    s->light_inst.upload(cs.light_inst);
-    s->light_tri_offset.upload(cs.light_tri_offset);
-    s->light_n_tris.upload(cs.light_n_tris);
-    s->punct.upload(punctual_device_records(cs.punct, cs.punct_tree));
-    {  // the light tables once more, packed so that each level of light sampling is ONE gather (device/dgeom.h, dscene.h)
-        auto pack = pack_alias;
-        std::vector<AliasPacked> la, aa;
-        std::vector<LightRec> lr;
-        packed_light_tables(cs, la, aa, lr);
-        s->light_alias.upload(la);
-        s->area_alias.upload(aa);
-        s->lights.upload(lr);
-        if (cs.env.on) {
-            std::vector<AliasPacked> marg, cond;
-            pack(cs.env.marginal_entries, cs.env.marginal_pdf, 0, cs.env.h, marg);
-            for (uint32_t y = 0; y < cs.env.h; y++) {
-                const size_t first = (size_t)y * cs.env.w;
-                for (uint32_t x = 0; x < cs.env.w; x++) {  // j is relative to the row
-                    const AliasEntry& e = cs.env.conditional_entries[first + x];
-                    cond.push_back(AliasPacked{e.j, e.t, cs.env.conditional_pdf[first + x], cs.env.conditional_pdf[first + e.j]});
-                }
-            }
-            s->env_texels.upload(cs.env.texels);
-            s->env_marginal.upload(marg);
-            s->env_conditional.upload(cond);
-            DEnv rec;
-            std::memset(&rec, 0, sizeof rec);
-            rec.texels = s->env_texels.as<float4>();
-            rec.marginal = s->env_marginal.as<AliasPacked>();
-            rec.conditional = s->env_conditional.as<AliasPacked>();
-            for (int k = 0; k < 9; k++) rec.rot[k] = cs.env.rot_t[k];
-            rec.w = cs.env.w;
-            rec.h = cs.env.h;
-            rec.filter = cs.env.filter;
-            rec.light = cs.n_lights - 1;
-            s->env_rec.alloc(sizeof rec);
-            HIP_CHECK(hipMemcpy(s->env_rec.p, &rec, sizeof rec, hipMemcpyHostToDevice));
-        } else {
-            s->env_texels.release();
-            s->env_marginal.release();
-            s->env_conditional.release();
-            s->env_rec.release();
-        }
-    }
+    upload_tables(s, true);
     DScene& d = s->dscene;
-    d.light_entries = s->light_entries.as<AliasEntry>();
-    d.light_pdf = s->light_pdf.as<float>();
-    d.light_inst = s->light_inst.as<uint32_t>();
-    d.light_tri_offset = s->light_tri_offset.as<uint32_t>();
-    d.light_alias = s->light_alias.as<AliasPacked>();
-    d.area_alias = s->area_alias.as<AliasPacked>();
-    d.lights = s->lights.as<LightRec>();
     d.n_lights = cs.n_lights;
-    d.env = cs.env.on ? s->env_rec.as<DEnv>() : nullptr;
-    d.punct = s->punct.as<DPunct>();
     d.n_punct = (uint32_t)cs.punct.size();
     for (const DPunct& r : cs.punct)  // (the size is not a matter of the colour pipeline: the colour sets' records have it where these do)
         if (r.radius != 0.0f || r.cos_max != 0.0f) d.n_punct |= kPunctSoftBit;
     d.punct_tree = cs.punct_tree.empty() ? 0u : (uint32_t)cs.punct.size();
 }
+static size_t share_bits_bytes(const CompiledScene& cs) { return cs.instanced.on ? std::max<size_t>(((size_t)cs.n_tris + 31u) / 32u, 1u) * 4u : 0u; }  // in2_share_bits (scene_finish)
 static void count_device_bytes(akr_scene* s) {
-    s->device_bytes = 0;
-    for (const DevBuf* b : {&s->woop, &s->tri_gid, &s->shade, &s->normals, &s->inst, &s->materials, &s->ggx_table, &s->light_entries,
-                            &s->light_pdf, &s->light_inst, &s->light_tri_offset, &s->light_n_tris, &s->area_entries, &s->area_pdf,
-                            &s->inst_tri_offset, &s->light_alias, &s->area_alias, &s->lights, &s->bvh_nodes, &s->tex_nodes, &s->tex_images, &s->tex_texels, &s->tex_mat_inputs,
-                            &s->in2_tlas_leaves, &s->in2_mesh_tris, &s->in2_mesh_pos, &s->in2_mesh_meta, &s->in2_mesh_normals, &s->in2_inst_mats, &s->in2_share_bits,
-                            &s->env_texels, &s->env_marginal, &s->env_conditional, &s->env_rec, &s->punct})
-        s->device_bytes += b->bytes;
+    s->device_bytes = s->ggx_table.bytes + s->in2_share_bits.bytes;  // (the walk-bound word lies in woop)
+    for (const SceneTable& t : kSceneTables)
+        if (t.buf) s->device_bytes += (s->*t.buf).bytes;
+}
+// A host-only scene's estimate of the same. As akr_scene_info.device_bytes has always answered: without the GGX table, and every
+// row's bytes whether or not its table would exist -- which differs only by the images of a scene none of whose materials reads one. It used to be
+// written as arithmetic on CompiledScene; the rows give the same because packed_light_tables makes one light_alias entry and one record per light
+// (n_lights = light_entries.size(): build_alias_table) and one area_alias entry per triangle of an area light (their light_n_tris sum to
+// area_entries.size(): compile_scene appends both together), Packed one marginal entry per row and one conditional entry per texel of the environment.
+// It packs those tables to learn their sizes -- O(emissive triangles + environment texels) per akr_scene_get_info of a host-only scene.
+static uint64_t compiled_scene_bytes(const akr_scene* s) {
+    Packed pk;
+    uint64_t n = share_bits_bytes(s->cs);
+    for (const SceneTable& t : kSceneTables)
+        if (t.buf) n += t.src(*s, pk).n;
+    return n;
 }
 
 // The pair walk's origin bound (dscene.h walk_bound_word): the largest power of two B <= 2^40 such that a ray with |o| <= B and |d| <= 2 per component gives, on every plane row
@@ -211,91 +286,30 @@ void akr_api::scene_finish(akr_scene* s, const TuningOptions& opt) {
     ctx->bind();
     if (cs.bvh_nodes.empty() && !cs.instanced.on && cs.woop.size() > walk_bound_word(cs.n_tris))  // exhaustive path: the pair walk's origin bound, in the records' padding
         cs.woop[walk_bound_word(cs.n_tris)] = walk_origin_bound(cs.woop, cs.n_tris);
-    s->woop.upload(cs.woop);
-    s->tri_gid.upload(cs.tri_gid);
-    s->shade.upload(cs.shade);
-    s->normals.upload(cs.normals);
-    s->inst.upload(cs.inst);
-    s->materials.upload(cs.materials);
-    s->area_entries.upload(cs.area_entries);
-    s->area_pdf.upload(cs.area_pdf);
-    s->inst_tri_offset.upload(cs.inst_tri_offset);
-    s->bvh_nodes.upload(cs.instanced.on ? cs.instanced.nodes : cs.bvh_nodes);
-    if (cs.instanced.on) {
-        s->in2_tlas_leaves.upload(cs.instanced.tlas_leaves);
-        s->in2_mesh_tris.upload(cs.instanced.mesh_tris);
-        s->in2_mesh_pos.upload(cs.instanced.mesh_pos);
-        s->in2_mesh_meta.upload(cs.instanced.mesh_meta);
-        s->in2_mesh_normals.upload(cs.instanced.mesh_normals);
-        s->in2_inst_mats.upload(cs.instanced.inst_mats);
-    }
-    if (cs.has_textures) {
-        s->tex_nodes.upload(cs.tex_nodes);
-        s->tex_images.upload(cs.images);
-        s->tex_texels.upload(cs.texels);
-        s->tex_mat_inputs.upload(cs.mat_inputs);
-    }
-    ensure_ggx_table(s);
     DScene& d = s->dscene;
     std::memset(&d, 0, sizeof d);
-    d.woop = s->woop.as<float4>();
-    d.tri_gid = s->tri_gid.as<uint32_t>();
-    d.shade = s->shade.as<float4>();
-    d.normals = s->normals.as<float4>();
-    d.inst = s->inst.as<float4>();
-    d.materials = s->materials.as<DMaterial>();
+    upload_tables(s, false);
+    ensure_ggx_table(s);
     d.ggx_table = s->ggx_table.as<float>();
-    d.area_entries = s->area_entries.as<AliasEntry>();
-    d.area_pdf = s->area_pdf.as<float>();
-    d.inst_tri_offset = s->inst_tri_offset.as<uint32_t>();
     upload_lights(s);  // light tables, environment
-    d.bvh_nodes = s->bvh_nodes.as<uint4>();
     d.n_tris = cs.n_tris;
     d.n_nodes = scene_n_nodes(cs);
     d.has_alpha = cs.has_alpha ? 1u : 0u;
     d.bvh_stack_depth = scene_stack_depth(cs);
-    if (cs.instanced.on) {
-        d.in2.tlas_leaves = s->in2_tlas_leaves.as<uint4>();
-        d.in2.mesh_tris = s->in2_mesh_tris.as<float4>();
-        d.in2.mesh_pos = s->in2_mesh_pos.as<uint32_t>();
-        d.in2.mesh_meta = s->in2_mesh_meta.as<uint32_t>();
-        d.in2.mesh_normals = s->in2_mesh_normals.as<float4>();
-        d.in2.inst_mats = s->in2_inst_mats.as<uint32_t>();
-        d.in2.on = 1u;
-        d.in2.n_instances = (uint32_t)s->flat.instances.size();
-    }
     d.plane_share_mask = 0;
     if (cs.bvh_nodes.empty() && !cs.instanced.on)  // exhaustive path (<= 64 triangles): which records repeat their predecessor's plane row
         for (uint32_t k = 1; k < d.n_tris && k < 64; k++)
             if (std::memcmp(&cs.woop[12ull * k + 8], &cs.woop[12ull * (k - 1) + 8], 16) == 0) d.plane_share_mask |= 1ull << k;
-    if (cs.has_textures) {
-        d.tex.nodes = s->tex_nodes.as<DNode>();
-        d.tex.images = s->tex_images.as<DImage>();
-        d.tex.texels = s->tex_texels.as<uint32_t>();
-        d.tex.mat_inputs = s->tex_mat_inputs.as<MatInputs>();
-    }
     if (cs.instanced.on) {  // which instance-triangles take their even neighbour's plane row: one bit each, decided on the device (dinst_trav.h resolve_pending)
-        const size_t words = ((size_t)cs.n_tris + 31u) / 32u;
-        s->in2_share_bits.alloc(std::max<size_t>(words, 1u) * 4u);
+        d.in2.on = 1u;
+        d.in2.n_instances = (uint32_t)s->flat.instances.size();
+        s->in2_share_bits.alloc(share_bits_bytes(cs));
         HIP_CHECK(hipMemsetAsync(s->in2_share_bits.p, 0, s->in2_share_bits.bytes, ctx->stream));
         HIP_CHECK(launch_inst_share_bits(d, s->in2_share_bits.as<uint32_t>(), s->in2_mesh_tris.as<uint32_t>(), ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         d.in2.share_bits = s->in2_share_bits.as<uint32_t>();
     }
     count_device_bytes(s);
-}
-
-// the arrays scene_finish uploads, in bytes (the packed light tables repeat the alias tables: 16 B per entry)
-static uint64_t compiled_scene_bytes(const CompiledScene& cs) {
-    auto b = [](const auto& v) { return (uint64_t)v.size() * sizeof(v[0]); };
-    uint64_t n = b(cs.woop) + b(cs.tri_gid) + b(cs.shade) + b(cs.normals) + b(cs.inst) + b(cs.materials) + b(cs.light_entries) + b(cs.light_pdf) +
-                 b(cs.light_inst) + b(cs.light_tri_offset) + b(cs.light_n_tris) + b(cs.area_entries) + b(cs.area_pdf) + b(cs.inst_tri_offset) +
-                 16ull * (cs.light_entries.size() + cs.area_entries.size() + cs.n_lights) + b(cs.bvh_nodes) + b(cs.tex_nodes) + b(cs.images) + b(cs.texels) +
-                 b(cs.mat_inputs);
-    n += (uint64_t)punctual_device_records(cs.punct, cs.punct_tree).size() * sizeof(DPunct);
-    n += b(cs.env.texels) + 16ull * (cs.env.marginal_entries.size() + cs.env.conditional_entries.size()) + (cs.env.on ? sizeof(DEnv) : 0u);
-    const CompiledScene::Instanced& is = cs.instanced;
-    return n + b(is.nodes) + b(is.tlas_leaves) + b(is.mesh_tris) + b(is.mesh_pos) + b(is.mesh_meta) + b(is.mesh_normals) + b(is.inst_mats) + (is.on ? std::max<uint64_t>(((uint64_t)cs.n_tris + 31u) / 32u, 1u) * 4u : 0u);
 }
 
 extern "C" {
@@ -360,7 +374,7 @@ AKR_API int32_t akr_scene_get_info(const akr_scene* s, akr_scene_info* info) {
     info->n_lights = s->cs.n_lights;
     info->n_bvh_nodes = (uint32_t)((s->cs.instanced.on ? s->cs.instanced.nodes.size() : s->cs.bvh_nodes.size()) / kBvhNodeWords);
     info->uses_bvh = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 0u : (s->cs.instanced.on ? 2u : 1u);  // 2 = two-level (meshes + instances)
-    info->device_bytes = s->device_bytes ? s->device_bytes : compiled_scene_bytes(s->cs);  // (a host-only scene: what an upload would take)
+    info->device_bytes = s->device_bytes ? s->device_bytes : compiled_scene_bytes(s);  // (a host-only scene)
     info->node_bytes = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 0u : kBvhNodeWords * 4u;   // bytes a traversal reads per node visit
     info->node_stride_bytes = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 0u : kBvhNodeWords * 4u;
     info->tri_bytes = (s->cs.bvh_nodes.empty() && !s->cs.instanced.on) ? 48u : kBvhTriWords * 4u;
@@ -414,7 +428,7 @@ static void punctual_lights_changed(akr_scene* s, std::vector<akr_punctual_light
         upload_lights(s);
         count_device_bytes(s);
         std::lock_guard<std::mutex> lock(s->color_sets_mutex);
-        for (auto& kv : s->color_sets) kv.second->punct.release();  // folded again by the next session of that pipeline (api_pt.cpp base_begin)
+        for (auto& kv : s->color_sets) kv.second->punct.release();  // folded again by the next session of that pipeline (api_pt.cpp color_set)
     }
 }
 AKR_API int32_t akr_scene_add_punctual_light(akr_scene* s, const akr_punctual_light_desc* desc) {
@@ -593,44 +607,19 @@ AKR_API int32_t akr_scene_get_camera(const akr_scene* s, akr_camera_desc* out) {
 
 AKR_API int32_t akr_scene_get_array(const akr_scene* s, int32_t which, const void** ptr, uint64_t* bytes) {
     if (!s || !ptr || !bytes) return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: NULL argument");
-    const CompiledScene& cs = s->cs;
     auto set = [&](const void* p, size_t n) { *ptr = n ? p : nullptr; *bytes = n; };
-    switch (which) {
-        case AKR_ARRAY_WOOP: set(cs.woop.data(), cs.woop.size() * 4); break;
-        case AKR_ARRAY_TRI_GID: set(cs.tri_gid.data(), cs.tri_gid.size() * 4); break;
-        case AKR_ARRAY_SHADE: set(cs.shade.data(), cs.shade.size() * 4); break;
-        case AKR_ARRAY_INSTANCES: set(cs.inst.data(), cs.inst.size() * 4); break;
-        case AKR_ARRAY_MATERIALS: set(cs.materials.data(), cs.materials.size() * sizeof(DMaterial)); break;
-        case AKR_ARRAY_BVH_NODES:
-            if (cs.instanced.on) set(cs.instanced.nodes.data(), cs.instanced.nodes.size() * 4);
-            else set(cs.bvh_nodes.data(), cs.bvh_nodes.size() * 4);
-            break;
-        case AKR_ARRAY_LIGHT_ENTRIES: set(cs.light_entries.data(), cs.light_entries.size() * sizeof(AliasEntry)); break;
-        case AKR_ARRAY_LIGHT_PDF: set(cs.light_pdf.data(), cs.light_pdf.size() * 4); break;
-        case AKR_ARRAY_AREA_ENTRIES: set(cs.area_entries.data(), cs.area_entries.size() * sizeof(AliasEntry)); break;
-        case AKR_ARRAY_AREA_PDF: set(cs.area_pdf.data(), cs.area_pdf.size() * 4); break;
-        case AKR_ARRAY_INST_TRI_OFFSET: set(cs.inst_tri_offset.data(), cs.inst_tri_offset.size() * 4); break;
-        case AKR_ARRAY_R2C: set(s->r2c, 64); break;
-        case AKR_ARRAY_C2W: set(s->c2w, 64); break;
-        case AKR_ARRAY_TEX_NODES: set(cs.tex_nodes.data(), cs.tex_nodes.size() * sizeof(DNode)); break;
-        case AKR_ARRAY_TEX_IMAGES: set(cs.images.data(), cs.images.size() * sizeof(DImage)); break;
-        case AKR_ARRAY_TEX_TEXELS: set(cs.texels.data(), cs.texels.size() * 4); break;
-        case AKR_ARRAY_MAT_INPUTS: set(cs.mat_inputs.data(), cs.mat_inputs.size() * sizeof(MatInputs)); break;
-        case AKR_ARRAY_INST_LEAVES: set(cs.instanced.tlas_leaves.data(), cs.instanced.tlas_leaves.size() * 4); break;
-        case AKR_ARRAY_MESH_TRIS: set(cs.instanced.mesh_tris.data(), cs.instanced.mesh_tris.size() * 4); break;
-        case AKR_ARRAY_MESH_POS: set(cs.instanced.mesh_pos.data(), cs.instanced.mesh_pos.size() * 4); break;
-        case AKR_ARRAY_MESH_META: set(cs.instanced.mesh_meta.data(), cs.instanced.mesh_meta.size() * 4); break;
-        case AKR_ARRAY_MESH_NORMALS: set(cs.instanced.mesh_normals.data(), cs.instanced.mesh_normals.size() * 4); break;
-        case AKR_ARRAY_ENV_MARGINAL_ENTRIES: set(cs.env.marginal_entries.data(), cs.env.marginal_entries.size() * sizeof(AliasEntry)); break;
-        case AKR_ARRAY_ENV_MARGINAL_PDF: set(cs.env.marginal_pdf.data(), cs.env.marginal_pdf.size() * 4); break;
-        case AKR_ARRAY_ENV_CONDITIONAL_ENTRIES: set(cs.env.conditional_entries.data(), cs.env.conditional_entries.size() * sizeof(AliasEntry)); break;
-        case AKR_ARRAY_ENV_CONDITIONAL_PDF: set(cs.env.conditional_pdf.data(), cs.env.conditional_pdf.size() * 4); break;
-        case AKR_ARRAY_ENV_TEXELS: set(cs.env.texels.data(), cs.env.texels.size() * 4); break;
-        case AKR_ARRAY_PUNCTUAL_LIGHTS: set(cs.punct.data(), cs.punct.size() * sizeof(DPunct)); break;
-        case AKR_ARRAY_LIGHT_TREE: set(cs.punct_tree.data(), cs.punct_tree.size() * 4); break;
-        default: return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: unknown array id");
+    if (which == AKR_ARRAY_R2C || which == AKR_ARRAY_C2W) {  // (not tables)
+        set(which == AKR_ARRAY_R2C ? s->r2c : s->c2w, 64);
+        return AKR_OK;
     }
-    return AKR_OK;
+    for (const SceneTable& t : kSceneTables) {
+        if (t.array != which || t.array == NO_ID || t.part == PACKED) continue;  // (a packed table's bytes would not outlive this call)
+        Packed none;
+        const Bytes b = t.src(*s, none);
+        set(b.p, b.n);
+        return AKR_OK;
+    }
+    return fail(AKR_ERR_INVALID_ARGUMENT, "akr_scene_get_array: unknown array id");
 }
 
 AKR_API int32_t akr_scene_spec_source(akr_scene* scene, char* dst, uint64_t capacity, uint64_t* length) {

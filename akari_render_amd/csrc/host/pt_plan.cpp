@@ -63,16 +63,12 @@ PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const Tuning
         // exhaustive path: everything, per-triangle records included (scene_build.cpp guarantees the fit);
         // BVH path: the per-scene tables only, if the launch still fits its share of the CU's LDS with them (kernels.h pt_lds_layout)
         const bool bvh = v.bvh;
-        size_t bytes[13] = {bvh ? 0 : cs.shade.size() * 4, bvh ? 0 : cs.normals.size() * 4, cs.inst.size() * 4, cs.materials.size() * sizeof(DMaterial),
-                            (size_t)cs.n_lights * sizeof(AliasPacked), cs.area_entries.size() * sizeof(AliasPacked), (size_t)cs.n_lights * sizeof(LightRec),
-                            cs.light_pdf.size() * 4, cs.area_pdf.size() * 4, 0, 0, 0, 0};
-        if (cs.has_textures) {  // the node lists have the same size in every colour pipeline
-            bytes[9] = cs.tex_nodes.size() * sizeof(DNode);
-            bytes[10] = cs.images.size() * sizeof(DImage);
-            bytes[11] = cs.mat_inputs.size() * sizeof(MatInputs);
-        }
-        size_t total = 0;
-        for (int i = 0; i < 12; i++) total += (bytes[i] + 15) & ~(size_t)15;
+        size_t bytes[ST_COUNT], total = 0;
+        stage_table_bytes(cs, cs.n_lights, bytes);  // (the node lists have the same size in every colour pipeline)
+        if (bvh) bytes[ST_SHADE] = bytes[ST_NORMALS] = 0;
+        // the one term that is not scene_build.cpp's: image headers no material reads stay in HBM here and count against the exhaustive budget there
+        if (!cs.has_textures) bytes[ST_TEX_IMAGES] = 0;
+        for (size_t b : bytes) total += (b + 15) & ~(size_t)15;
         pl.tex_slots = (cs.has_textures && !spec_active) ? cs.tex_slots : 0;  // a per-scene kernel keeps node values in registers
         // the workgroup's share: a per-scene kernel built for four waves per SIMD has a quarter of the CU's LDS whatever the scene
         const size_t budget = pt_lds_budget(v.tex && !(spec_active && spec_waves >= 4));
@@ -86,14 +82,14 @@ PtPlan akr_api::pt_plan(const akr_scene* s, const akr_pt_config& c, const Tuning
         // workgroups per CU still fit (AKR_PT_MIN_WAVES_TEX = 3: 160 KB / 3)
         const size_t ggx_bytes = 4096 * sizeof(float);
         if (may && !bvh && v.tex && !v.fd && fits(total + ggx_bytes)) {
-            bytes[12] = ggx_bytes;
+            bytes[ST_GGX] = ggx_bytes;
             total += ggx_bytes;
             v.stage = true;
         } else {
             v.stage = may && (!bvh || fits(total));
         }
         if (v.stage) {
-            for (int i = 0; i < 13; i++) pl.stage_bytes[i] = (uint32_t)bytes[i];
+            for (int i = 0; i < ST_COUNT; i++) pl.stage_bytes[i] = (uint32_t)bytes[i];
             pl.stage_total = (uint32_t)std::max<size_t>(total, 16);
         }
     }

@@ -800,12 +800,20 @@ void compile_scene(const FlatScene& flat, const TuningOptions& tune, CompiledSce
     out.woop.resize(out.woop.size() + 32, 0.0f);
 }
 
+void stage_table_bytes(const CompiledScene& out, size_t n_lights, size_t bytes[ST_COUNT]) {
+    bytes[ST_SHADE] = out.shade.size() * 4, bytes[ST_NORMALS] = out.normals.size() * 4, bytes[ST_INST] = out.inst.size() * 4;
+    bytes[ST_MATERIALS] = out.materials.size() * sizeof(DMaterial);
+    // the light list: one packed entry, one record and one pdf per light (n_lights = out.n_lights: light_pdf.size(), build_alias_table), one packed entry per area entry
+    bytes[ST_LIGHT_ALIAS] = n_lights * sizeof(AliasPacked), bytes[ST_LIGHTS] = n_lights * sizeof(LightRec), bytes[ST_LIGHT_PDF] = n_lights * 4;
+    bytes[ST_AREA_ALIAS] = out.area_entries.size() * sizeof(AliasPacked), bytes[ST_AREA_PDF] = out.area_pdf.size() * 4;
+    // node lists and raw inputs are empty without texture-fed materials (compile_materials); the image headers are NOT, if the scene brings images no material reads
+    bytes[ST_TEX_NODES] = out.tex_nodes.size() * sizeof(DNode), bytes[ST_TEX_IMAGES] = out.images.size() * sizeof(DImage), bytes[ST_MAT_INPUTS] = out.mat_inputs.size() * sizeof(MatInputs);
+    bytes[ST_GGX] = 0;  // the launch plan's to grant (pt_plan.cpp)
+}
 size_t exhaustive_stage_bytes(const CompiledScene& out, size_t n_lights) {
-    size_t stage = 0;
-    for (size_t b : {out.shade.size() * 4, out.normals.size() * 4, out.inst.size() * 4, out.materials.size() * sizeof(DMaterial),
-                     n_lights * 32 /* AliasPacked + LightRec */, out.area_entries.size() * 16, n_lights * 4, out.area_pdf.size() * 4,
-                     out.tex_nodes.size() * sizeof(DNode), out.images.size() * sizeof(DImage), out.mat_inputs.size() * sizeof(MatInputs)})
-        stage += (b + 15) & ~(size_t)15;
+    size_t bytes[ST_COUNT], stage = 0;
+    stage_table_bytes(out, n_lights, bytes);
+    for (size_t b : bytes) stage += (b + 15) & ~(size_t)15;
     return stage;
 }
 

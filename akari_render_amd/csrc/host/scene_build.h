@@ -256,9 +256,11 @@ void build_alias_table(const std::vector<float>& weights, std::vector<AliasEntry
 constexpr uint64_t kSpecAutoSamples = 1ull << 31;  // option specialise = -1: a first-use compile (about a second; 20-30 % of the render to win) has to be worth it
 
 void compile_scene(const FlatScene& flat, const TuningOptions& opt, CompiledScene& out);  // opt: the caller's one snapshot of the options
-// What the exhaustive kernels stage in LDS (device/pt_pass.h: STAGE) of a compiled scene whose light list has n_lights entries, in bytes, each table padded to 16:
-// the ONE sum that compile_scene (exhaustive or BVH?), compile_environment and compile_punctual (does the scene still fit with the entry added?) compare
-// with kStageMaxBytes. A table staged in future is added here.
+// The sizes of the tables a pt kernel stages in LDS (kernels.h StageTable; ST_GGX: 0) of a compiled scene whose light list has n_lights entries: the ONE
+// statement of them, which the launch plan (pt_plan.cpp, n_lights = out.n_lights) takes as they are. A table staged in future is added here.
+void stage_table_bytes(const CompiledScene& out, size_t n_lights, size_t bytes[ST_COUNT]);
+// ... and their sum, each table padded to 16: what compile_scene (exhaustive or BVH?), compile_environment and compile_punctual (does the scene still
+// fit with the entry added?) compare with kStageMaxBytes.
 size_t exhaustive_stage_bytes(const CompiledScene& out, size_t n_lights);
 // "point light" / "spot light" / "sun light" of the scene's first punctual light: what a refusal names
 std::string punctual_light_name(const CompiledScene& cs);

@@ -7,6 +7,17 @@
 #include "device/drng.h"
 #include "device/dscene.h"
 
+// The tables a pt kernel stages in LDS, in the order they lie there: the index of PtParams::stage_bytes, of the sizes the host computes
+// (host/scene_build.cpp stage_table_bytes, host/pt_plan.cpp) and of the copy loop (device/dpath.h stage_scene_tables). Outside the namespace
+// like PtVariant below, and for its reason.
+enum StageTable : int {
+    ST_SHADE, ST_NORMALS,  // per triangle: the exhaustive kernels only
+    ST_INST, ST_MATERIALS, ST_LIGHT_ALIAS, ST_AREA_ALIAS, ST_LIGHTS, ST_LIGHT_PDF, ST_AREA_PDF,
+    ST_TEX_NODES, ST_TEX_IMAGES, ST_MAT_INPUTS,  // the TEX kernels only
+    ST_GGX,  // the GGX albedo table: the full-graph exhaustive kernels of textured scenes, where the LDS budget allows
+    ST_COUNT
+};
+
 #if !defined(__HIPCC_RTC__)
 #include <algorithm>
 // Which instantiation of pt_pass_body (device/pt_pass.h) a pt session runs, decided once per session (host/api_pt.cpp pt_plan) and
@@ -211,10 +222,8 @@ struct PtParams {
     uint64_t smp_mod_magic;                 // fastmod_magic(smp_spp): x % spp without a division (drng.h)
     const uint32_t* pmj_sets;               // [5][65536][2] u32 fixed point
     const uint16_t* bluenoise;              // [48][128][128] unorm16
-    // Small scenes (exhaustive path): the tables the shading phase gathers from, staged in LDS by k_pt_pass. Bytes per table
-    // in the order shade, normals, inst, materials, light_alias, area_alias, lights, light_pdf, area_pdf; 0 total = not staged.
-    // ... then the texture tables of a TEX scene: pruned node lists, image headers, raw material inputs (12 entries in all).
-    uint32_t stage_bytes[13];  // [12]: the GGX albedo table (full-graph exhaustive kernels)
+    // The tables the shading phase gathers from, staged in LDS by k_pt_pass: bytes per table, by StageTable (above); 0 total = not staged.
+    uint32_t stage_bytes[ST_COUNT];
     uint32_t stage_total;
     uint32_t simple_scene;   // no coat, no transmission, no normal map, no glass material, no textures: the full-graph kernels without that code
     uint32_t defer_metal;    // iterations with (iteration & defer_metal) != 0 put hits on "expensive" materials off by one iteration (device/pt_pass.h: DEFER)
