@@ -165,7 +165,9 @@ AKR_D bool trace_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmin, float 
 // its plane solve, not per record, and the best hit is chosen by one test and two selects. Two records per trip on alternating register
 // sets: a one-record software prefetch without the moves that rotating a single set costs. In the walk without an alpha test a trip's
 // bookkeeping is shared by its two records (WalkOpt PLANE_LT, PLANE_EXCL below): one comparison per excluded id, and one t < best_t where
-// the records share a plane -- 6 v_cmp and 5 v_cndmask per trip for 10 and 6.
+// the records share a plane -- 6 v_cmp and 5 v_cndmask per trip for 10 and 6. The id of the best hit is kept as the trip's even id and a
+// lane mask for "its second record" (HALF_MASK: one select and one v_mov per trip for two and two), and the trip's six LDS reads take one
+// address register (ONE_ADDR: one v_add per trip for two v_mov).
 // Five other forms were measured and retired (records through the scalar cache, both rays packed into v_pk_fma_f32 with and
 // without op_sel broadcast, lockstep pairs of coplanar records); this one was +4.2 % on C2 and +3.3 % on C3 over the next best:
 // HISTORY.md, profiles/r4_ab_walk.txt. The arithmetic (operation order, fma placement) is tri_plane / tri_uv / hit_margin's.
@@ -264,17 +266,38 @@ AKR_D PlaneHit tri_plane_unscaled(vec3 o, vec3 d, float4 r2, float& lo) {
 //               k (the loop steps by two from 0), so e is k or k + 1 exactly if q == k + 1 -- one comparison E -- and then the first record
 //               is the excluded one where E & !H, the second where E & H. kInvalid | 1 = 0xffffffff equals no k + 1 <= 64. Three comparisons
 //               per trip for six, whether the two records share a plane or not.
+//
+// HALF_MASK, ONE_ADDR -- instructions taken out of the two-record trip of the walk without an alpha test (profiles/walk_half_mask.md; what each
+// buys: profiles/walk_half_mask_ab.md). Neither touches a comparison or a float.
+//   HALF_MASK   (with PLANE_LT) The mask upd = (A | B) & lt that selects best_t already says that the trip wins; only which of its two records
+//               did is new, one bit per lane. So during the loop `best` is the even id k of the winning trip -- one select on upd -- and
+//               the lane mask `half`, in a scalar register pair, holds the bit: half = (half & ~upd) | (B & ~A & lt). A lane in both A and B
+//               takes the first record (k wins over k + 1 at one t: the lowest-id rule), so its bit is clear. A trip whose second record
+//               solves a plane of its own chooses its first record before that solve (choose), which clears `half` for the lanes it updates,
+//               and runs the merged text with A = 0. After the loop best |= half, once: `half` is set under upd only, where `best` is an
+//               even id, so kInvalid stays kInvalid. The tail record and the (u, v) of the hit read the id after that.
+//   ONE_ADDR    The LDS byte address of the trip's first record in one VGPR, advanced by 96 per trip; the trip's six ds_read_b128 (its
+//               second record, and the next trip's first) are immediate offsets 48 .. 128 from it. Left to the compiler the address lives
+//               in an SGPR and is copied into a VGPR twice per trip.
 #ifndef AKR_WALK_PLANE_LT
 #define AKR_WALK_PLANE_LT 1  // (0 / 1 from the command line: an A/B build of one part, akari_render_amd/build.py build_variant)
 #endif
 #ifndef AKR_WALK_PLANE_EXCL
 #define AKR_WALK_PLANE_EXCL 1
 #endif
-template <bool DIV, bool LT = DIV && AKR_WALK_PLANE_LT, bool EXCL = DIV && AKR_WALK_PLANE_EXCL>
+#ifndef AKR_WALK_HALF_MASK
+#define AKR_WALK_HALF_MASK 1  // (0 / 1 from the command line, like the two above)
+#endif
+#ifndef AKR_WALK_ONE_ADDR
+#define AKR_WALK_ONE_ADDR 1
+#endif
+template <bool DIV, bool LT = DIV && AKR_WALK_PLANE_LT, bool EXCL = DIV && AKR_WALK_PLANE_EXCL, bool HALF = LT && AKR_WALK_HALF_MASK, bool ADDR = DIV && AKR_WALK_ONE_ADDR>
 struct WalkOpt {
     static constexpr bool unscaled_div = DIV;
     static constexpr bool plane_lt = LT;
     static constexpr bool plane_excl = EXCL;
+    static constexpr bool half_mask = HALF && LT;
+    static constexpr bool one_addr = ADDR;
 };
 template <int V>
 struct IntTag {
@@ -355,21 +378,34 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
         const BoolTag<UNSCALED> div_tag{};
         // the plane-wise bookkeeping (WalkOpt PLANE_LT, PLANE_EXCL): only in the walk without an alpha test
         constexpr bool PLANE_LT = OPT::plane_lt && decltype(alpha_tag)::value == 0, PLANE_EXCL = OPT::plane_excl && decltype(alpha_tag)::value == 0;
+        constexpr bool HALF = OPT::half_mask && PLANE_LT, ONE_ADDR = OPT::one_addr && decltype(alpha_tag)::value == 0;
         v4f a0 = lrec[0], a1 = lrec[1], a2 = lrec[2], b0, b1, b2;
         uint32_t k = 0;
-        if (PLANE_LT || PLANE_EXCL) {
+        if (PLANE_LT || PLANE_EXCL || ONE_ADDR) {
             // One body for every trip (a second copy of the trip for the pairs alone made the register allocator keep the plane's
             // solves twice and spill). Truth values are lane masks in scalar registers, written as such (lanes_of / in_lanes): left as
             // bools, the compiler turns part of the mask algebra into 0 / 1 VGPRs with a select and a comparison each.
             const uint32_t qex0 = ex0 | 1u, qsex0 = sex0 | 1u, qsex1 = sex1 | 1u;                                           // the trip an excluded id falls into ...
             const uint64_t hex0 = lanes_of((ex0 & 1u) != 0), hsex0 = lanes_of((sex0 & 1u) != 0), hsex1 = lanes_of((sex1 & 1u) != 0);  // ... and the half of it
+            uint64_t half = 0;  // HALF_MASK: the lanes whose best hit is the second record of its trip (`best` holds the trip's even id meanwhile)
             auto choose = [&](uint64_t acc, uint32_t id) {  // the per-record choice: record()'s
                 const uint64_t better = acc & lanes_of(T < best_t);
                 best_t = in_lanes(better) ? T : best_t;
                 best = in_lanes(better) ? id : best;
+                if (HALF) half &= ~better;  // (called with a trip's first record only where HALF is on)
             };
-            for (; k + 1 < n; k += 2) {
-                b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];
+            // ONE_ADDR: the LDS byte address of the trip's first record in a vector register of its own (what a ds_read takes), advanced once
+            // per trip; the trip's six reads are immediate offsets from it. (Opaque to the compiler in every trip: left to itself it keeps the
+            // address on the scalar unit and copies it into a vector register twice per trip; given a vector register that it may rebase, it
+            // counts from the trip's last read backwards -- negative offsets, which a ds_read has not, so one v_add per read.)
+            uint32_t rec_addr = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) v4f*)lrec;
+            auto rec_row = [&](uint32_t k_rec, uint32_t rel, uint32_t row) -> v4f {  // row `row` of record k_rec + rel, k_rec the trip's first
+                if (ONE_ADDR) return *(const __attribute__((address_space(3))) v4f*)(uintptr_t)(rec_addr + 48u * rel + 16u * row);
+                return lrec[3 * (k_rec + rel) + row];
+            };
+            for (; k + 1 < n; k += 2, rec_addr += 96u) {
+                if (ONE_ADDR) asm("" : "+v"(rec_addr));
+                b0 = rec_row(k, 1, 0); b1 = rec_row(k, 1, 1); b2 = rec_row(k, 1, 2);
                 const uint32_t k1 = k + 1;
                 const bool own_b = !((sc.plane_share_mask >> k1) & 1ull);  // wave-uniform: the second record solves a plane of its own
                 uint64_t xa, xb, sxa, sxb;  // the lanes whose closest-hit ray excludes the first / the second record; whose shadow ray does
@@ -387,7 +423,7 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
                 margins(alpha_tag, a0, a1, u2, v2, ma, sma);
                 sma = in_lanes(sxa) ? -1.0f : sma;
                 uint64_t acc_a = lanes_of(ma >= 0.0f) & ~xa;
-                a0 = lrec[3 * (k + 2)]; a1 = lrec[3 * (k + 2) + 1]; a2 = lrec[3 * (k + 2) + 2];
+                a0 = rec_row(k, 2, 0); a1 = rec_row(k, 2, 1); a2 = rec_row(k, 2, 2);
                 if (!PLANE_LT) choose(acc_a, k);
                 if (own_b) {
                     if (PLANE_LT) {  // the first record is chosen on its own T, before the second one's solve overwrites it, and is settled
@@ -403,14 +439,21 @@ AKR_D void trace_pair_exhaustive(const DScene& sc, vec3 o, vec3 d, float tmax, u
                     // both records on one T and one best_t (or the first one settled: acc_a = 0): one comparison, one select of best_t -- the
                     // identity above the WalkOpt struct. One text for both kinds of trip: two made the compiler carry T < best_t into them as a 0 / 1 VGPR.
                     const uint64_t lt = lanes_of(T < best_t);
-                    best_t = in_lanes((acc_a | acc_b) & lt) ? T : best_t;
-                    best = in_lanes(acc_b & lt) ? k1 : best;
-                    best = in_lanes(acc_a & lt) ? k : best;
+                    const uint64_t upd = (acc_a | acc_b) & lt;  // the trip wins ...
+                    best_t = in_lanes(upd) ? T : best_t;
+                    if (HALF) {  // ... and which half of it did is a bit per lane: the second one only where the first did not accept
+                        best = in_lanes(upd) ? k : best;
+                        half = (half & ~upd) | (acc_b & ~acc_a & lt);
+                    } else {
+                        best = in_lanes(acc_b & lt) ? k1 : best;
+                        best = in_lanes(acc_a & lt) ? k : best;
+                    }
                 } else {
                     choose(acc_b, k1);
                 }
                 occ_margin = max_raw(max_raw(occ_margin, sma), smb);
             }
+            if (HALF) best |= in_lanes(half) ? 1u : 0u;  // (kInvalid stays: `half` is set under `upd` only, where `best` is an even id)
         } else {
             for (; k + 1 < n; k += 2) {
                 b0 = lrec[3 * (k + 1)]; b1 = lrec[3 * (k + 1) + 1]; b2 = lrec[3 * (k + 1) + 2];

@@ -37,9 +37,14 @@ namespace akr {
 // without textures (C2 +0.6 ... +1.4 %, C3 +1.3 ... +2.1 %, the reference's default configuration +3.1 %), off for those with: the textured
 // room's interpreter kernel measured 878 -> 869 Msamples/s with it, three alternating runs, the parent's spread 1.7 (profiles/walk_div_mask_ab.md).
 // The walk's bookkeeping per trip (WalkOpt PLANE_LT, PLANE_EXCL) goes with it: measured on the untextured kernels only
-// (profiles/walk_plane_bookkeeping_ab.md), so the textured ones keep the per-record code.
-template <bool TEX>
-using PairWalkOpt = WalkOpt<!TEX>;
+// (profiles/walk_plane_bookkeeping_ab.md), so the textured ones keep the per-record code. PLANE_EXCL can be chosen per kernel family
+// (FD): alone with PLANE_LT it cost the force_diffuse kernels half a percent; with HALF_MASK and ONE_ADDR it gains there too (C2 3 902 against
+// 3 893 Msamples/s without it, profiles/walk_half_mask_ab.md), so it is on in both families.
+#ifndef AKR_WALK_PLANE_EXCL_FD
+#define AKR_WALK_PLANE_EXCL_FD 1  // PLANE_EXCL in the force_diffuse kernels (0 / 1 from the command line, like disect.h's AKR_WALK_*)
+#endif
+template <bool FD, bool TEX>
+using PairWalkOpt = WalkOpt<!TEX, !TEX && AKR_WALK_PLANE_LT, !TEX && AKR_WALK_PLANE_EXCL && (!FD || AKR_WALK_PLANE_EXCL_FD)>;
 // (AKR_PT_STRAGGLERS*: kernels.h -- the host sizes the launch's LDS from them too, pt_lds_layout)
 // ABSENT: lobes the scene cannot have (dbsdf.h AB_*). The precompiled kernels know 0 and AB_SIMPLE (PtParams.simple_scene: scenes without
 // textures); a per-scene kernel gets the mask of its scene.
@@ -200,7 +205,7 @@ AKR_D void pt_pass_body(const PtParams& p) {
                     }
                 }
             } else {
-                trace_pair_exhaustive<TEX, PairWalkOpt<TEX>>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1, hit, found,
+                trace_pair_exhaustive<TEX, PairWalkOpt<FD, TEX>>(sc, r.ro, r.rd, r.has_ray ? 1e20f : -1.0f, r.ray_ex0, r.s_o, r.s_d, r.has_shadow ? r.s_tmax : -1.0f, r.s_ex0, r.s_ex1, hit, found,
                                            occluded, lds_recs);
             }
             if (DEFER) {
