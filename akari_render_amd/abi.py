@@ -76,7 +76,9 @@ class MaterialDesc(C.Structure):
 # shader graphs / textures (akr_node_op, akr_material_input, akr_image_desc)
 NODE_NONE = 0xFFFFFFFF
 (NODE_CONST, NODE_RGB, NODE_TEXCOORDS, NODE_IMAGE, NODE_MAPPING, NODE_CHECKERBOARD, NODE_SPECTRAL_UPLIFT, NODE_SEPARATE_COLOR,
- NODE_EXTRACT, NODE_NORMAL_MAP) = range(10)
+ NODE_EXTRACT, NODE_NORMAL_MAP, NODE_CONST4, NODE_MATH, NODE_NOISE) = range(13)
+MATH_ADD, MATH_SUB, MATH_MUL, MATH_DIV, MATH_POW, MATH_MIN, MATH_MAX = range(7)  # akr_math_op
+MATH_BROADCAST_FIRST, MATH_BROADCAST_SECOND = 1, 2  # akr_math_broadcast: the operand is a scalar, its .x stands for every component
 MAPPING_POINT, MAPPING_TEXTURE = 0, 1
 FIELD_RED, FIELD_GREEN, FIELD_BLUE, FIELD_UV = 0, 1, 2, 3
 INPUT_NAMES = ("base_color", "metallic", "roughness", "ior", "specular_ior_level", "specular_tint", "transmission_weight",
@@ -554,6 +556,21 @@ class NodeData:
     op: int
     args: tuple = ()
     k: tuple = (0.0, 0.0, 0.0)
+
+
+def const4(x, y, z, w):
+    """NODE_CONST4, the format's float4: (x, y, z, w); w travels as its float bit pattern in arg0."""
+    return NodeData(NODE_CONST4, (int(np.float32(w).view(np.uint32)),), (x, y, z))
+
+
+def math(op, a, b, broadcast=0):
+    """NODE_MATH: MATH_* `op` of nodes `a` and `b`; `broadcast` bits mark the operands that are scalars."""
+    return NodeData(NODE_MATH, (a, b, int(op), int(broadcast)))
+
+
+def noise(scale, vector=NODE_NONE, dim=2):
+    """NODE_NOISE: raw signed Perlin noise of dimension 1 or 2 at `vector` (NODE_NONE: si.uv) times the .x of node `scale`."""
+    return NodeData(NODE_NOISE, (vector, scale, int(dim)))
 
 
 @dataclass

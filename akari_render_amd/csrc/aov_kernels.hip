@@ -1,4 +1,5 @@
 // aov_kernels.hip -- the `aov` integrator (crates/akari_integrator/src/aov.rs:57-173) on gfx950: k_aov (aov_kernel.h), LENS = false here.
+#define AKR_NODE_ARM_OUT_OF_LINE 1  // the interpreter's math / noise arm as one call in this unit (device/dtex.h; measured)
 #include "aov_kernel.h"
 
 namespace akr {

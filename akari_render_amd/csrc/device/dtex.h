@@ -149,8 +149,11 @@ AKR_HD float srgb_to_linear1(float s) { return s <= 0.04045f ? s / 12.92f : pow_
 // ---- node list ---------------------------------------------------------------------------------------------------
 enum : uint32_t {
     NODE_CONST = 0, NODE_RGB = 1, NODE_TEXCOORDS = 2, NODE_IMAGE = 3, NODE_MAPPING = 4, NODE_CHECKERBOARD = 5,
-    NODE_SPECTRAL_UPLIFT = 6, NODE_SEPARATE_COLOR = 7, NODE_EXTRACT = 8, NODE_NORMAL_MAP = 9
+    NODE_SPECTRAL_UPLIFT = 6, NODE_SEPARATE_COLOR = 7, NODE_EXTRACT = 8, NODE_NORMAL_MAP = 9,
+    NODE_CONST4 = 10, NODE_MATH = 11, NODE_NOISE = 12  // the format's float4, math and noise: declared by the reference, evaluated only here
 };
+enum : uint32_t { MATH_ADD = 0, MATH_SUB = 1, MATH_MUL = 2, MATH_DIV = 3, MATH_POW = 4, MATH_MIN = 5, MATH_MAX = 6, MATH_COUNT = 7 };  // akr_math_op
+enum : uint32_t { MATH_BC_FIRST = 1, MATH_BC_SECOND = 2 };  // NODE_MATH arg3: the operand is a scalar, its .x stands for every component
 constexpr uint32_t kNodeNone = 0xffffffffu;
 constexpr uint32_t kMaxGraphNodes = 256;  // after pruning to the texture-fed inputs (host/scene_build.cpp); the values live in at most kTexMaxSlots slots, so the length of a list costs LDS staging space only
 // A pruned node list is also register-allocated on the host: every node's value gets one of at most kTexMaxSlots value slots
@@ -218,6 +221,97 @@ AKR_HD TexVal node_normal_map(TexVal a, float s) {
     if (s != 1.0f) { nx = nx * s; ny = ny * s; nz = nz * 1.0f; }
     return tv(nx, ny, nz, 0.0f);
 }
+// float4 (shader.rs:122-123): the fourth component travels as its bit pattern in arg0.
+AKR_HD TexVal node_const4(float k0, float k1, float k2, uint32_t w_bits) { return tv(k0, k1, k2, u2f(w_bits)); }
+// math (shader.rs:38-49, 124-129; the reference's compiler answers it with todo!()). MIN / MAX are the compare-and-select of
+// `b < a ? b : a` / `a < b ? b : a`: a NaN in b yields a.
+AKR_HD float math_apply(uint32_t op, float a, float b) {
+    switch (op) {
+        case MATH_ADD: return a + b;
+        case MATH_SUB: return a - b;
+        case MATH_MUL: return a * b;
+        case MATH_DIV: return a / b;
+        case MATH_POW: return pow_f(a, b);
+        case MATH_MIN: return b < a ? b : a;
+        case MATH_MAX: return a < b ? b : a;
+        default: return 0.0f;
+    }
+}
+// Two scalars give a scalar; otherwise x, y, z component-wise with a scalar operand's .x broadcast, and w from the first operand
+// that is not a scalar: alpha passes through colour arithmetic as it does through uplift and separate.
+AKR_HD TexVal node_math(TexVal a, TexVal b, uint32_t op, uint32_t bc) {
+    const bool sa = (bc & MATH_BC_FIRST) != 0, sb = (bc & MATH_BC_SECOND) != 0;
+    if (sa && sb) return tv(math_apply(op, a.x, b.x), 0.0f, 0.0f, 0.0f);
+    return tv(math_apply(op, a.x, b.x), math_apply(op, sa ? a.x : a.y, sb ? b.x : b.y), math_apply(op, sa ? a.x : a.z, sb ? b.x : b.z), sa ? b.w : a.w);
+}
+// noise: Perlin's gradient noise as svm/texture/noise/perlin.rs states it, over Blender's lookup3 hashes (util/hash.rs:80-155;
+// all integer arithmetic wraps), with the lerp of this file and the cell of tex_floor_to_int (whose clamping of huge and NaN
+// coordinates is part of the definition). The value is the raw signed one: 0 at every lattice point.
+AKR_HD uint32_t noise_rot(uint32_t x, uint32_t k) { return (x << k) | (x >> (32u - k)); }
+AKR_HD uint32_t noise_hash_final(uint32_t a, uint32_t b, uint32_t c) {
+    c ^= b; c -= noise_rot(b, 14);
+    a ^= c; a -= noise_rot(c, 11);
+    b ^= a; b -= noise_rot(a, 25);
+    c ^= b; c -= noise_rot(b, 16);
+    a ^= c; a -= noise_rot(c, 4);
+    b ^= a; b -= noise_rot(a, 14);
+    c ^= b; c -= noise_rot(b, 24);
+    return c;
+}
+AKR_HD uint32_t noise_hash1(uint32_t kx) {
+    const uint32_t init = 0xdeadbeefu + (1u << 2) + 13u;
+    return noise_hash_final(init + kx, init, init);
+}
+AKR_HD uint32_t noise_hash2(uint32_t kx, uint32_t ky) {  // hash_uint2: the y key goes into a, the x key into b
+    const uint32_t init = 0xdeadbeefu + (2u << 2) + 13u;
+    return noise_hash_final(init + ky, init + kx, init);
+}
+AKR_HD float noise_fade(float t) { return t * t * t * (t * (t * 6.0f - 15.0f) + 10.0f); }
+AKR_HD float noise_grad1(uint32_t hash, float x) {
+    const uint32_t h = hash & 15u;
+    const float g = 1.0f + (float)(h & 7u);
+    return ((h & 8u) != 0 ? -g : g) * x;
+}
+AKR_HD float noise_grad2(uint32_t hash, float x, float y) {
+    const uint32_t h = hash & 7u;
+    const float u = h < 4u ? x : y;
+    const float v = 2.0f * (h < 4u ? y : x);
+    return ((h & 1u) != 0 ? -u : u) + ((h & 2u) != 0 ? -v : v);
+}
+AKR_HD float perlin_1d(float x) {
+    float fl;
+    const uint32_t ix = (uint32_t)tex_floor_to_int(x, fl);
+    const float fx = x - fl;  // fl = float(ix) exactly
+    const float u = noise_fade(fx);
+    return tex_lerp(noise_grad1(noise_hash1(ix), fx), noise_grad1(noise_hash1(ix + 1u), fx - 1.0f), u);
+}
+AKR_HD float perlin_2d(float x, float y) {
+    float flx, fly;
+    const uint32_t ix = (uint32_t)tex_floor_to_int(x, flx), iy = (uint32_t)tex_floor_to_int(y, fly);
+    const float fx = x - flx, fy = y - fly;
+    const float u = noise_fade(fx), v = noise_fade(fy);
+    // nd_lerp (util/lerp.rs): corner i at offset (i & 1, i >> 1), in x first and then in y
+    const float c0 = noise_grad2(noise_hash2(ix, iy), fx, fy), c1 = noise_grad2(noise_hash2(ix + 1u, iy), fx - 1.0f, fy);
+    const float c2 = noise_grad2(noise_hash2(ix, iy + 1u), fx, fy - 1.0f), c3 = noise_grad2(noise_hash2(ix + 1u, iy + 1u), fx - 1.0f, fy - 1.0f);
+    return tex_lerp(tex_lerp(c0, c1, u), tex_lerp(c2, c3, u), v);
+}
+AKR_HD TexVal node_noise(vec2 st, float scale, uint32_t dim) {
+    const float n = dim == 1u ? perlin_1d(st.x * scale) : perlin_2d(st.x * scale, st.y * scale);
+    return tv(n, 0.0f, 0.0f, 0.0f);
+}
+// MATH and NOISE as the interpreter reaches them (`a` of a noise node is its coordinate, `b` its scale); the per-scene kernels call node_math /
+// node_noise directly, with the immediates as literals. Inline by default. A translation unit that defines AKR_NODE_ARM_OUT_OF_LINE before it
+// includes this header gets one call instead: inlined, the arm costs two k_aov kernels an occupancy step and the k_gpt_sample kernels scratch,
+// while a call costs the k_pt_pass and k_wf_shade kernels scratch and the textured room 2 % -- both measured, DESIGN.md 4.18.
+#if defined(AKR_NODE_ARM_OUT_OF_LINE)
+#define AKR_NODE_ARM static __host__ __device__ __attribute__((noinline))
+#else
+#define AKR_NODE_ARM AKR_HD
+#endif
+AKR_NODE_ARM TexVal node_procedural(uint32_t op, TexVal a, TexVal b, uint32_t imm2, uint32_t imm3) {
+    if (op == NODE_MATH) return node_math(a, b, imm2, imm3);
+    return node_noise(mk2(a.x, a.y), b.x, imm2);
+}
 // One node of a list. `get(a)` returns the value of argument node / slot `a`.
 template <typename Get>
 AKR_HD TexVal eval_node(const TexScene& ts, const DNode& nd, uint32_t op, vec2 uv, Get get) {
@@ -249,6 +343,13 @@ AKR_HD TexVal eval_node(const TexScene& ts, const DNode& nd, uint32_t op, vec2 u
         case NODE_NORMAL_MAP: {
             TexVal a = get(nd.arg[0]);
             v = node_normal_map(a, get(nd.arg[1]).x);
+            break;
+        }
+        case NODE_CONST4: v = node_const4(nd.k[0], nd.k[1], nd.k[2], nd.arg[0]); break;
+        case NODE_MATH: case NODE_NOISE: {
+            TexVal a = tv(uv.x, uv.y, 0.0f, 0.0f);
+            if (nd.arg[0] != kNodeNone) a = get(nd.arg[0]);  // (a math node always has both operands: host/scene_build.cpp)
+            v = node_procedural(op, a, get(nd.arg[1]), nd.arg[2], nd.arg[3]);
             break;
         }
         default: break;

@@ -8,6 +8,7 @@
 // scratch film into the accumulators (gpt.rs:424-461); the order in which a pixel's own and its neighbours' splats arrive is
 // whatever the hardware does. Here k_gpt_sample writes what a pixel splats onto itself (`own`) and what it splats for each
 // neighbour (`shifted[i]`) to per-pixel slots and k_gpt_update gathers them in a fixed order -- no atomics, reproducible.
+#define AKR_NODE_ARM_OUT_OF_LINE 1  // the interpreter's math / noise arm as one call in this unit (device/dtex.h; measured)
 #include "device/dradiance.h"
 #include "launch.h"
 

@@ -106,6 +106,9 @@ static_assert(sizeof(DNode) == sizeof(akr_shader_node), "DNode mirrors akr_shade
 static uint32_t node_n_args(uint32_t op) {
     switch (op) {
         case AKR_NODE_CONST: case AKR_NODE_RGB: case AKR_NODE_TEXCOORDS: return 0;
+        case AKR_NODE_CONST4: return 0;  // arg0 is the bit pattern of w
+        case AKR_NODE_MATH: return 2;    // arg2 is the operation, arg3 the broadcast bits
+        case AKR_NODE_NOISE: return 2;   // arg0 the optional vector node, arg1 the scale; arg2 is the dimension
         case AKR_NODE_IMAGE: return 2;  // arg0 is an image id, arg1 the optional uv node
         case AKR_NODE_MAPPING: return 3;
         case AKR_NODE_CHECKERBOARD: return 4;
@@ -149,7 +152,11 @@ static bool alpha_is_one(const HostGraph& g, const std::vector<HostImage>& image
         }
         case AKR_NODE_SPECTRAL_UPLIFT: case AKR_NODE_SEPARATE_COLOR: return alpha_is_one(g, images, n.arg[0]);
         case AKR_NODE_CHECKERBOARD: return alpha_is_one(g, images, n.arg[2]) && alpha_is_one(g, images, n.arg[3]);
-        default: return false;  // float / float3 / texcoords / mapping / extract / normal_map values have w = 0
+        case AKR_NODE_CONST4: return n.arg[0] == 0x3f800000u;
+        case AKR_NODE_MATH:  // w comes from the first operand that is not a scalar; two scalars give w = 0 (node_math, device/dtex.h)
+            if ((n.arg[3] & 3u) == 3u) return false;
+            return alpha_is_one(g, images, (n.arg[3] & AKR_MATH_BROADCAST_FIRST) ? n.arg[1] : n.arg[0]);
+        default: return false;  // float / float3 / texcoords / mapping / extract / normal_map / noise values have w = 0
     }
 }
 static void compile_graph(const HostGraph& g, const std::vector<HostImage>& images, uint32_t color, uint32_t material_index, akr_material_desc& desc, DMaterial& dm,
@@ -174,7 +181,17 @@ static void compile_graph(const HostGraph& g, const std::vector<HostImage>& imag
         if (nd.op == AKR_NODE_EXTRACT && nd.arg[1] > AKR_FIELD_UV) throw std::invalid_argument("akr_shader_node: unknown extract field");
         if (nd.op == AKR_NODE_NORMAL_MAP && (nd.arg[0] == AKR_NODE_NONE || nd.arg[1] == AKR_NODE_NONE))
             throw std::invalid_argument("akr_shader_node: normal_map needs normal and strength");
-        bool v = nd.op == AKR_NODE_TEXCOORDS || nd.op == AKR_NODE_IMAGE || (nd.op == AKR_NODE_CHECKERBOARD && nd.arg[0] == AKR_NODE_NONE);
+        if (nd.op == AKR_NODE_MATH) {
+            if (nd.arg[0] == AKR_NODE_NONE || nd.arg[1] == AKR_NODE_NONE) throw std::invalid_argument("akr_shader_node: math needs first and second");
+            if (nd.arg[2] > AKR_MATH_MAX) throw std::invalid_argument("akr_shader_node: unknown math op");
+            if (nd.arg[3] > 3u) throw std::invalid_argument("akr_shader_node: unknown math broadcast bits");
+        }
+        if (nd.op == AKR_NODE_NOISE) {
+            if (nd.arg[1] == AKR_NODE_NONE) throw std::invalid_argument("akr_shader_node: noise needs scale");
+            if (nd.arg[2] == 3u) throw std::runtime_error("unsupported: noise of dimension 3 (a graph has no position input, and the reference has no 3D function)");
+            if (nd.arg[2] != 1u && nd.arg[2] != 2u) throw std::invalid_argument("akr_shader_node: noise dimension must be 1 or 2");
+        }
+        bool v = nd.op == AKR_NODE_TEXCOORDS || nd.op == AKR_NODE_IMAGE || ((nd.op == AKR_NODE_CHECKERBOARD || nd.op == AKR_NODE_NOISE) && nd.arg[0] == AKR_NODE_NONE);
         for (uint32_t r = 0; r < nr; r++) v = v || varying[refs[r]];
         varying[i] = v;
     }
@@ -283,11 +300,13 @@ static void compile_graph(const HostGraph& g, const std::vector<HostImage>& imag
                         sig += (nd.arg[a] == AKR_NODE_NONE ? std::string("-") : std::to_string(nd.arg[a])) + ",";
                     }
                 }
-                // immediates that select code: the Rgb node's colour space, the sRGB decode of an image, mapping type, extract field
+                // immediates that select code: the Rgb node's colour space, the sRGB decode of an image, mapping type, extract field, math op and broadcast, noise dimension
                 if (nd.op == AKR_NODE_RGB) sig += "t" + std::to_string(nd.arg[0] == 1u ? 1 : 0);
                 if (nd.op == AKR_NODE_IMAGE) sig += "s" + std::to_string(nd.arg[2] != 0 ? 1 : 0);
                 if (nd.op == AKR_NODE_MAPPING) sig += "m" + std::to_string(nd.arg[3]);
                 if (nd.op == AKR_NODE_EXTRACT) sig += "f" + std::to_string(nd.arg[1]);
+                if (nd.op == AKR_NODE_MATH) sig += "o" + std::to_string(nd.arg[2]) + "b" + std::to_string(nd.arg[3]);
+                if (nd.op == AKR_NODE_NOISE) sig += "d" + std::to_string(nd.arg[2]);
                 sig += ")" + std::to_string(feeds[i]) + ";";
             }
             uint32_t kind = 0;

@@ -240,6 +240,7 @@ struct GraphBuilder {
     std::map<std::string, uint32_t>& image_index;  // (buffer view + sampler) key -> image
     HostGraph graph;
     std::map<std::string, uint32_t> memo;
+    std::map<std::string, int> scalar_memo;  // node id -> 1 scalar, 0 vector, -1 being decided (is_scalar)
 
     uint32_t push(uint32_t op, uint32_t a0 = AKR_NODE_NONE, uint32_t a1 = AKR_NODE_NONE, uint32_t a2 = AKR_NODE_NONE, uint32_t a3 = AKR_NODE_NONE,
                   float k0 = 0.0f, float k1 = 0.0f, float k2 = 0.0f) {
@@ -308,6 +309,32 @@ struct GraphBuilder {
         image_index[key] = idx;
         return idx;
     }
+    // The static type of a node's value, for the broadcast bits of a math node: a float, one colour channel, a noise value and
+    // the result of scalar arithmetic are scalars; everything else (extract of uv included) is a vector. Decided once per node
+    // (a chain x_i = add(x_{i-1}, x_{i-1}) would otherwise cost 2^depth visits); a node that is its own operand is refused.
+    bool is_scalar(const JsonValue& ref) {
+        const std::string& id = ref.at("id").as_string();
+        auto it = scalar_memo.find(id);
+        if (it != scalar_memo.end()) {
+            if (it->second < 0) throw std::runtime_error("shader graph: math node '" + id + "' is its own operand");
+            return it->second != 0;
+        }
+        const JsonValue& n = nodes.at(id);
+        const std::string& ty = n.at("type").as_string();
+        bool r = false;
+        if (ty == "float" || ty == "noise") {
+            r = true;
+        } else if (ty == "extract") {
+            const std::string& f = n.at("field").as_string();
+            r = f == "Red" || f == "Green" || f == "Blue";
+        } else if (ty == "math") {
+            scalar_memo[id] = -1;  // being decided
+            const bool a = is_scalar(n.at("first")), b = is_scalar(n.at("second"));
+            r = a && b;
+        }
+        scalar_memo[id] = r ? 1 : 0;
+        return r;
+    }
     uint32_t emit(const JsonValue& ref) {
         const std::string& id = ref.at("id").as_string();
         auto it = memo.find(id);
@@ -354,6 +381,27 @@ struct GraphBuilder {
             uint32_t field = f == "Red" ? AKR_FIELD_RED : f == "Green" ? AKR_FIELD_GREEN : f == "Blue" ? AKR_FIELD_BLUE : (f == "uv" || f == "UV") ? AKR_FIELD_UV : 99u;
             if (field == 99u) throw std::runtime_error("unsupported: extract field '" + f + "'");
             r = push(AKR_NODE_EXTRACT, emit(n.at("node")), field);
+        } else if (ty == "float4") {
+            r = push(AKR_NODE_CONST4, f2u(n.at("value").at(3).as_f32()), AKR_NODE_NONE, AKR_NODE_NONE, AKR_NODE_NONE, n.at("value").at(0).as_f32(),
+                     n.at("value").at(1).as_f32(), n.at("value").at(2).as_f32());
+        } else if (ty == "math") {  // shader.rs:38-49, 124-129; min and max are this library's
+            const std::string& o = n.at("op").as_string();
+            const uint32_t op = o == "add" ? AKR_MATH_ADD : o == "sub" ? AKR_MATH_SUB : o == "mul" ? AKR_MATH_MUL : o == "div" ? AKR_MATH_DIV : o == "pow" ? AKR_MATH_POW
+                                : o == "min" ? AKR_MATH_MIN : o == "max" ? AKR_MATH_MAX : 99u;
+            if (op == 99u) throw std::runtime_error("unsupported: math op '" + o + "'");
+            const uint32_t bc = (is_scalar(n.at("first")) ? AKR_MATH_BROADCAST_FIRST : 0u) | (is_scalar(n.at("second")) ? AKR_MATH_BROADCAST_SECOND : 0u);
+            uint32_t a = emit(n.at("first")), b = emit(n.at("second"));
+            r = push(AKR_NODE_MATH, a, b, op, bc);
+        } else if (ty == "noise") {  // shader.rs:141-145; "vector" as the checkerboard has it
+            const double dim = n.at("dim").as_number();
+            if (dim != 1.0 && dim != 2.0) {
+                std::ostringstream what;  // (printed as the number it is: NaN and huge values have no integer to convert to)
+                what << "unsupported: noise of dimension " << dim << " (1 and 2 are evaluated)";
+                throw std::runtime_error(what.str());
+            }
+            uint32_t v = (n.has("vector") && !n.at("vector").is_null()) ? emit(n.at("vector")) : AKR_NODE_NONE;
+            uint32_t sc = emit(n.at("scale"));
+            r = push(AKR_NODE_NOISE, v, sc, (uint32_t)dim);
         } else {
             throw std::runtime_error("unsupported: shader node '" + ty + "'");
         }

@@ -55,6 +55,7 @@ uint32_t n_args(uint32_t op) {
         case NODE_CHECKERBOARD: return 4;
         case NODE_SPECTRAL_UPLIFT: case NODE_SEPARATE_COLOR: case NODE_EXTRACT: return 1;
         case NODE_NORMAL_MAP: return 2;
+        case NODE_MATH: case NODE_NOISE: return 2;  // their arg2 / arg3 are immediates
         default: return 0;
     }
 }
@@ -122,6 +123,15 @@ std::string emit_nodes(const KindView& kv, const std::vector<uint8_t>& need, boo
             case NODE_SEPARATE_COLOR: e = v(0); break;
             case NODE_EXTRACT: e = "node_extract(" + v(0) + fmt(", %uu)", nd.arg[1]); break;
             case NODE_NORMAL_MAP: e = "node_normal_map(" + v(0) + ", " + v(1) + ".x)"; break;
+            case NODE_CONST4:  // w is data, not shape: a literal when every material of the kind agrees
+                e = "node_const4(" + kv.kc(i, 0) + ", " + kv.kc(i, 1) + ", " + kv.kc(i, 2) + ", " + (kv.uniform_arg(i, 0) ? fmt("0x%08xu)", nd.arg[0]) : fmt("nd[%u].arg[0])", i));
+                break;
+            case NODE_MATH: e = "node_math(" + v(0) + ", " + v(1) + fmt(", %uu, %uu)", nd.arg[2], nd.arg[3]); break;  // op and broadcast as literals: the switch folds away
+            case NODE_NOISE: {
+                const std::string st = nd.arg[0] == kNodeNone ? "uv" : "mk2(" + v(0) + ".x, " + v(0) + ".y)";
+                e = "node_noise(" + st + ", " + v(1) + fmt(".x, %uu)", nd.arg[2]);
+                break;
+            }
             default: e = "tv(0, 0, 0, 0)"; break;
         }
         o += fmt("        const TexVal v%u = ", i) + e + ";\n";

@@ -121,8 +121,22 @@ typedef enum {
     AKR_NODE_SPECTRAL_UPLIFT = 6,/* arg0 rgb: rgb_colorspace -> the space of color_repr    eval.rs:155-175 */
     AKR_NODE_SEPARATE_COLOR = 7, /* arg0 colour (carries the value for AKR_NODE_EXTRACT)   eval.rs:241-256 */
     AKR_NODE_EXTRACT = 8,        /* arg0 node, arg1 akr_extract_field                      eval.rs:208-218 */
-    AKR_NODE_NORMAL_MAP = 9      /* arg0 normal, arg1 strength (tangent space)             eval.rs:176-191 */
+    AKR_NODE_NORMAL_MAP = 9,     /* arg0 normal, arg1 strength (tangent space)             eval.rs:176-191 */
+    /* The format declares the next three (akari_scenegraph shader.rs:117-145); the reference's compiler stops at
+       todo!() for them (svm/compiler.rs:136,163), so their definitions are this library's. */
+    AKR_NODE_CONST4 = 10,        /* Float4: (k0,k1,k2,w), w as its float bit pattern in arg0 */
+    AKR_NODE_MATH = 11,          /* arg0 first, arg1 second, arg2 akr_math_op, arg3 akr_math_broadcast bits: two
+                                    scalars give (op(a.x,b.x),0,0,0); otherwise x,y,z component-wise with a scalar's
+                                    .x broadcast and w copied from the first operand that is not a scalar */
+    AKR_NODE_NOISE = 12          /* arg0 vector | NONE (si.uv), arg1 scale (.x), arg2 dimension 1 | 2: (n,0,0,0), n
+                                    the raw signed Perlin value at vector * scale   svm/texture/noise/perlin.rs */
 } akr_node_op;
+/* ADD..POW are the format's (shader.rs:38-49); MIN and MAX are this library's, so that a noise-driven input can be
+ * clamped: MIN is b < a ? b : a, MAX is a < b ? b : a (a NaN in b yields a). POW is the pow of the sRGB decode. */
+typedef enum {
+    AKR_MATH_ADD = 0, AKR_MATH_SUB = 1, AKR_MATH_MUL = 2, AKR_MATH_DIV = 3, AKR_MATH_POW = 4, AKR_MATH_MIN = 5, AKR_MATH_MAX = 6
+} akr_math_op;
+typedef enum { AKR_MATH_BROADCAST_FIRST = 1, AKR_MATH_BROADCAST_SECOND = 2 } akr_math_broadcast;
 typedef enum { AKR_MAPPING_POINT = 0, AKR_MAPPING_TEXTURE = 1 } akr_mapping_type;
 typedef enum { AKR_FIELD_RED = 0, AKR_FIELD_GREEN = 1, AKR_FIELD_BLUE = 2, AKR_FIELD_UV = 3 } akr_extract_field;
 typedef struct {

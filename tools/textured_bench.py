@@ -29,10 +29,34 @@ def constant_room(lobes_of_the_textured_room):
     v.ggx_table = sd.ggx_table
     return v
 
+def procedural_room():
+    """The room with its image and checkerboard inputs replaced by noise and math graphs, 26 nodes in all as in the textured room:
+    floor colour c1 + (c2 - c1) t and roughness t with t = 0.5 noise + 0.5, back wall rgb * (0.25 noise + 0.5), left wall normal (n, n, 1 + n),
+    light strength 2 + noise. No image is read."""
+    v = textured_room(1920, 1080, n_floor=n_floor)
+    N, A = abi.NodeData, abi
+    v.materials[0].graph = abi.GraphData([
+        N(A.NODE_RGB, (), (0.9, 0.85, 0.8)), N(A.NODE_RGB, (), (0.15, 0.2, 0.3)), N(A.NODE_CONST, (), (6.0, 0, 0)), A.noise(2, A.NODE_NONE, 2),
+        N(A.NODE_CONST, (), (0.5, 0, 0)), A.math(A.MATH_MUL, 3, 4, 3), A.math(A.MATH_ADD, 5, 4, 3), A.math(A.MATH_SUB, 1, 0, 0),
+        A.math(A.MATH_MUL, 7, 6, 2), A.math(A.MATH_ADD, 0, 8, 0)], {"base_color": 9, "roughness": 6})
+    v.materials[0].metallic = 0.25
+    v.materials[1].graph = abi.GraphData([
+        N(A.NODE_CONST, (), (8.0, 0, 0)), A.noise(0, A.NODE_NONE, 2), N(A.NODE_CONST, (), (0.25, 0, 0)), A.math(A.MATH_MUL, 1, 2, 3),
+        N(A.NODE_CONST, (), (0.5, 0, 0)), A.math(A.MATH_ADD, 3, 4, 3), N(A.NODE_RGB, (), (0.9, 0.7, 0.5)), A.math(A.MATH_MUL, 6, 5, 2)], {"base_color": 7})
+    v.materials[2].graph = abi.GraphData([
+        N(A.NODE_CONST, (), (5.0, 0, 0)), A.noise(0, A.NODE_NONE, 1), N(A.NODE_CONST, (), (0.0, 0.0, 1.0)), A.math(A.MATH_ADD, 2, 1, 2)], {"normal": 3})
+    v.materials[6].graph = abi.GraphData([
+        N(A.NODE_CONST, (), (3.0, 0, 0)), A.noise(0, A.NODE_NONE, 2), N(A.NODE_CONST, (), (2.0, 0, 0)), A.math(A.MATH_ADD, 1, 2, 3)], {"emission_strength": 3})
+    v.materials[6].emission_color = (3.0, 3.0, 3.0)
+    v.images = []
+    v.ggx_table = sd.ggx_table
+    return v
+
 small = textured_room(1920, 1080, n_floor=n_floor)  # the 16x24 / 8x8 images of the tests: texel gathers hit in cache
 small.ggx_table = sd.ggx_table
 variants = [("textured", sd, None), ("textured, per-scene kernel", sd, None), ("textured, per-scene kernel, 4 waves", sd, None),
             ("textured, conductor deferral off", sd, "0"), ("textured, small images", small, None),
+            ("procedural", procedural_room(), None), ("procedural, per-scene kernel", procedural_room(), None),
             ("same room, constant materials with the lobes the graphs select", constant_room(True), None),
             ("same room, constant materials", constant_room(False), None)]
 only = os.environ.get("TEXBENCH_ONLY")  # substring of the variant's name
